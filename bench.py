@@ -28,11 +28,17 @@ keypoints to rank 0 (north_star: "RCCL over xGMI used only to gather per-frame k
 back to rank 0") is timed too and reported in the `gather` object, incl. and excl. the
 transfer; `value` stays the exchange-free compute rate.
 
-Rank 0 prints ONE JSON line (see the repo's task contract), with extra objects:
-"roofline" (HIP-event launch time of the headline kernel vs HBM peak), "kernels" (the same
-graded figures for every precision of the path, each with its error on the CPU sample),
-"cpu_baseline" (the reference's CPU execution -- four torch Conv1d calls -- timed on this
-box's host cores; reported only) and, for N > 1, "gather".
+Rank 0 prints ONE JSON line (see the repo's task contract).  A plain run does only what `value`
+needs: set up, W warmup steps, K timed steps, the optional output dump, the line.  `--full` adds
+the secondary figures, each measured after `value`: "value_sustained", "roofline" (HIP-event
+launch time of the headline kernel vs HBM peak), "kernels" (the same graded figures for every
+precision of the path, each with its error on the CPU sample), "cpu_baseline" (the reference's
+CPU execution -- four torch Conv1d calls -- timed on this box's host cores; reported only) and,
+for N > 1, "gather".
+
+`--dump-outputs DIR` writes what the timed path computed in its last step: a fixed, seeded
+sample of rank 0's output frames (`output_sample_frames`) as DIR/hand_kpts_sample.npy, float32
+(n, 21, 2).  Inputs and weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -84,7 +90,30 @@ def parse(argv=None):
                     help="seconds the hand-back measurement may take before the line is printed without it")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group even for one rank (smoke test of RCCL on a one-GPU box)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after `value`, also measure value_sustained, roofline, kernels, cpu_baseline and (N > 1) "
+                         "gather; without it the --sustained / --cpu-* / --gather-* options have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's output to DIR/hand_kpts_sample.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_FRAMES = 1 << 17       # 131 072 frames x 21 x 2 fp32 = 22 MB, under the 64 MB the dump may take
+DUMP_SEED = 20240607
+
+
+def output_sample_frames(n_frames):
+    """Sorted indices into the (S*T) output frames that --dump-outputs writes: every frame when they fit,
+    else the first, the last and DUMP_FRAMES - 2 seeded draws (duplicates dropped); a function of
+    n_frames alone, so every build samples the same frames."""
+    import numpy as np
+    if n_frames <= DUMP_FRAMES:
+        return np.arange(n_frames, dtype=np.int64)
+    draws = np.random.default_rng(DUMP_SEED).integers(0, n_frames, DUMP_FRAMES - 2, dtype=np.int64)
+    return np.unique(np.concatenate([np.array([0, n_frames - 1], dtype=np.int64), draws]))
 
 
 def sources_sha256():
@@ -427,6 +456,13 @@ def main():
         return max_over_ranks(time.perf_counter() - t0)
 
     el = timed_steps()
+    if args.dump_outputs and rank == 0:
+        # before anything below launches again into y (the --full figures rewrite it in other precisions)
+        import numpy as np
+        idx = torch.from_numpy(output_sample_frames(S * T)).to(dev)
+        sample = y.view(S * T, 21, 2).index_select(0, idx).cpu().numpy()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "hand_kpts_sample.npy"), sample)     # y is float32
 
     frames_total = S * T * world * args.steps
     value = frames_total / el
@@ -443,7 +479,7 @@ def main():
                    "preconditioning_steps": max(0, args.precondition),
                    "parallelism": f"seq-shard x{world}", "gpus": gpus},
     }
-    if world == 1 and args.sustained > 0:
+    if args.full and world == 1 and args.sustained > 0:
         # the same K steps once more after `--sustained` further untimed launches: the rate of the stream once the
         # clock / power controller has settled (tools/sustain_probe.py: a launch takes 5-15 % longer during the
         # first ~30 ms after an idle gap).  Reported beside `value`, never as it.
@@ -455,7 +491,7 @@ def main():
     if backend is not None:
         out["config"]["backend"] = "rccl" if backend == "nccl" else "gloo (REHEARSAL on shared GPUs, not xGMI)"
 
-    if rank == 0:
+    if args.full and rank == 0:
         # roofline of the dominant (only) kernel: HIP events on the launch stream
         iters = max(5, min(args.steps, 50))
         rf = kernel_roofline(model, x, y, args.precision, iters)
@@ -526,7 +562,7 @@ def main():
                           "bytes_into_rank0": into0}
         return gat
 
-    if world > 1 and not args.no_gather:
+    if args.full and world > 1 and not args.no_gather:
         # `value` and the roofline above are already measured.  The hand-back is a SECONDARY figure: an
         # RCCL error in it, a hung peer or a blown budget must not cost the run its line -- but must show in
         # the exit code: rank 0 prints the line with `gather.error`, then every rank exits with
@@ -538,7 +574,7 @@ def main():
         store = dist.distributed_c10d._get_default_store()
         out["gather"] = SecondaryGuard(store, rank, world, args.gather_budget, emit_failed).run(gather_phase)
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # the same shard through every other precision of the path, graded the same way
         kernels = {args.precision: dict(out["roofline"])}
         for prec, it in (("bf16", 10), ("f16", 10), ("f16x3", 5), ("f32_mfma", 3)):

@@ -13,9 +13,11 @@ data only.  The committed fixtures are what pins the oracle (oracle/) and,
 through it, the HIP path.
 
     python tests/golden/make_golden.py          # rewrites tests/golden/*.npz
+    MKL_CBWR=COMPATIBLE python tests/golden/make_golden.py --mkl-compat   # only adds y_mkl_compat (main() runs it)
 """
 import importlib.util
 import os
+import subprocess
 import sys
 import types
 
@@ -91,6 +93,29 @@ def conv_case(hpm, name, B, T, C, pos_emb, kind, seed, keep=None):
         rec["y_row_sum"] = y.double().sum(dim=(1, 2, 3)).numpy()
     np.savez_compressed(os.path.join(OUT, name + ".npz"), **rec)
     print(f"{name}: x{tuple(x.shape)} -> y{tuple(y.shape)}  |y|max={y.abs().max():.4f}")
+
+
+MKL_COMPAT_CASES = ("cfg1_b1_t200", "cfg1_b1_t1")      # batch 1: torch runs these as im2col + MKL sgemm
+
+
+def mkl_compat_case(hpm, name):
+    """Add `y_mkl_compat` to a stored batch-1 case: the reference's output on its stored input and weights
+    under MKL's vendor-neutral branch (MKL_CBWR=COMPATIBLE, one thread).  MKL's default sgemm picks its
+    code path, and with it the last bits of the sums, by CPU vendor, ISA and thread count; under this
+    branch on one thread it does not (tests/test_oracle.py::test_torch_port_is_bit_exact)."""
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE", "MKL reads MKL_CBWR when it starts: set it for the process"
+    torch.set_num_threads(1)
+    path = os.path.join(OUT, name + ".npz")
+    with np.load(path) as d:
+        rec = {k: d[k] for k in d.files}
+    B, T, C, pe, _ = [int(v) for v in rec["meta"]]
+    assert B == 1 and "y_idx" not in rec, name
+    model = hpm.ConvModel(C, "ReLU", bool(pe)).eval()
+    model.load_state_dict({k.replace("_", ".", 1): torch.from_numpy(rec[k]) for k in rec if k.startswith("conv")})
+    with torch.no_grad():
+        rec["y_mkl_compat"] = model(torch.from_numpy(rec["x"])).contiguous().numpy()
+    np.savez_compressed(path, **rec)
+    print(f"{name}: y_mkl_compat, max |y_mkl_compat - y| = {np.abs(rec['y_mkl_compat'] - rec['y']).max():.3e}")
 
 
 def transform_case(utils, hpm, name, T, n_frames, seed):
@@ -421,7 +446,16 @@ def main():
     validate_case(utils, tt, hpm, "validate_loop", 43)
     # --predict right_index / right_3fingers item builders and writers
     predict_variants_case(utils, "predict_variants", 29)
+    # the batch-1 cases once more under MKL's reproducible branch, in a process started with it
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--mkl-compat"],
+                          env=dict(os.environ, MKL_CBWR="COMPATIBLE"))
 
 
 if __name__ == "__main__":
-    main()
+    if "--mkl-compat" in sys.argv:
+        _stub_fairseq()
+        hpm = _load(os.path.join(REF, "models", "HandPoseModels.py"), "ref_HandPoseModels")
+        for case in MKL_COMPAT_CASES:
+            mkl_compat_case(hpm, case)
+    else:
+        main()

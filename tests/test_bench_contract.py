@@ -1,17 +1,21 @@
 """bench.py's output contract: rank 0 prints exactly ONE JSON line on stdout, with the keys the
-driver reads plus the `roofline`, `kernels` and `cpu_baseline` objects; `--gpus N` from a plain
-shell starts the N ranks itself; no GPU / no RCCL means a non-zero exit and no line."""
+driver reads; with `--full` also the `roofline`, `kernels` and `cpu_baseline` objects, which a
+plain run does not measure; `--dump-outputs` writes the timed step's output; `--gpus N` from a
+plain shell starts the N ranks itself; no GPU / no RCCL means a non-zero exit and no line."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
-REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
-            "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"]
+PLAIN = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+         "scaling", "vs_baseline", "dtype", "data", "config"]
+FULL_ONLY = ["value_sustained", "roofline", "kernels", "value_le_1e-3_any_input", "cpu_baseline", "gather"]
+REQUIRED = PLAIN + ["roofline", "cpu_baseline"]
 # north_star: <= 1e-3 max-abs vs the reference CPU forward.  The bench sample is U[-0.5, 0.5]
 # (normalised keypoints), where the bf16 headline kernel measures 3.7-5.0e-4.
 SAMPLE_TOL = {"bf16": 1e-3, "f16": 2.5e-4, "f16x3": 2e-5, "f32_mfma": 2e-5}
@@ -25,7 +29,7 @@ def _check_roofline(rf):
 
 @pytest.mark.gpu
 def test_one_json_line_with_the_contract_keys(cuda_device):
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "4", "--warmup", "1", "--full",
                         "--seqs", "2048", "--cpu-seconds", "1.0"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
@@ -63,6 +67,59 @@ def test_one_json_line_with_the_contract_keys(cuda_device):
 
 
 @pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_timed_output(tmp_path, cuda_device):
+    """Without --full the line holds only what `value` needs; --dump-outputs writes the sampled output of the
+    last timed step, identical from run to run and equal to the same seeded forward in this process."""
+    import torch
+
+    import hand_pose_sl_amd as hps
+    sys.path.insert(0, ROOT)
+    import bench
+    S, T = 2048, 200
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--seqs", str(S),
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = r.stdout.splitlines()
+        assert len(lines) == 1, r.stdout[:2000]
+        d = json.loads(lines[0])
+        for k in PLAIN:
+            assert k in d, k
+        assert not [k for k in FULL_ONLY if k in d], sorted(d)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["untimed_launches"] == 1 and d["dtype"] == "bf16"
+        assert abs(d["value"] - S * T * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+        assert [p.name for p in (tmp_path / run).iterdir()] == ["hand_kpts_sample.npy"]
+        dumps.append(np.load(tmp_path / run / "hand_kpts_sample.npy"))
+    idx = bench.output_sample_frames(S * T)
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (len(idx), 21, 2) and dumps[0].nbytes <= 64 << 20
+    assert np.array_equal(dumps[0], dumps[1])
+    torch.manual_seed(0)                                  # bench.py's weights and input stream, rank 0
+    m = hps.ConvModel(30, "ReLU", False, precision="bf16").to(cuda_device).eval()
+    g = torch.Generator(device=cuda_device).manual_seed(1234)
+    x = torch.rand((S, T, 12, 2), dtype=torch.float32, device=cuda_device, generator=g).sub_(0.5)
+    with torch.no_grad():
+        y = m(x).view(S * T, 21, 2)[torch.from_numpy(idx).to(cuda_device)].cpu().numpy()
+    assert np.array_equal(dumps[0], y)
+
+
+def test_output_sample_is_fixed_and_bounded():
+    """The dump's frame sample depends on the output size alone and stays within 64 MB at any size; --steps
+    below 1 is refused rather than reported."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert np.array_equal(bench.output_sample_frames(1000), np.arange(1000))
+    n = 262144 * 200
+    a, b = bench.output_sample_frames(n), bench.output_sample_frames(n)
+    assert np.array_equal(a, b) and a[0] == 0 and a[-1] == n - 1 and np.all(np.diff(a) > 0)
+    assert len(a) * 21 * 2 * 4 <= 64 << 20 and len(a) > bench.DUMP_FRAMES // 2
+    args = bench.parse(["--steps", "7", "--dump-outputs", "out"])
+    assert args.steps == 7 and args.dump_outputs == "out" and not args.full
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+@pytest.mark.gpu
 def test_self_launch_two_ranks_rehearsal(cuda_device):
     """`python bench.py --gpus 2` from a plain shell spawns the two ranks itself.  On the one-GPU box
     RCCL cannot serve two ranks on one device, so the default backend must FAIL loudly (no line);
@@ -73,7 +130,7 @@ def test_self_launch_two_ranks_rehearsal(cuda_device):
         r = subprocess.run(base, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode != 0 and r.stdout.strip() == "", (r.returncode, r.stdout[:500])
         assert "RCCL" in r.stderr or "GPU" in r.stderr
-    r = subprocess.run(base + ["--backend", "gloo"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run(base + ["--backend", "gloo", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
     assert len(lines) == 1, r.stdout[:2000]
@@ -90,7 +147,7 @@ def test_self_launch_two_ranks_rehearsal(cuda_device):
     # the hand-back is a secondary figure: if it outlives its budget the line is still printed, with
     # `value` / `roofline` intact and the failure named in the `gather` object
     # ... and the exit code says so too (3 = `value` stands, the hand-back measurement failed)
-    r = subprocess.run(base + ["--backend", "gloo", "--gather-budget", "0.2"], capture_output=True, text=True,
+    r = subprocess.run(base + ["--backend", "gloo", "--full", "--gather-budget", "0.2"], capture_output=True, text=True,
                        timeout=900, cwd=ROOT)
     assert r.returncode == 3, (r.returncode, r.stderr[-3000:])
     lines = r.stdout.splitlines()

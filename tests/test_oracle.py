@@ -1,11 +1,15 @@
 """The oracle (CPU restatement) against the golden vectors produced by the
 reference's own classes (tests/golden/make_golden.py).  CPU only."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 import oracle
-from conftest import CONV_CASES, load_golden
+from conftest import CONV_CASES, ROOT, load_golden
 
 TOL_F32 = 2e-6   # fp32 summation-order noise; measured <= 1.3e-7
 
@@ -25,12 +29,40 @@ def test_c_oracle_matches_reference(name):
         assert abs(np.abs(y.astype(np.float64)).sum() - float(rec["y_abs_sum"])) < 1e-2
 
 
+def _port_outputs(path):
+    """Body of the child process of `port_outputs`: the torch port on every conv case, on one thread."""
+    torch.set_num_threads(1)
+    ys = {}
+    for name in CONV_CASES:
+        rec = load_golden(name)
+        st = {k: torch.from_numpy(v) for k, v in rec["state"].items()}
+        ys[name] = oracle.torch_forward(torch.from_numpy(rec["x"]), st, rec["pos_emb"]).contiguous().numpy()
+    np.savez(path, **ys)
+
+
+@pytest.fixture(scope="module")
+def port_outputs(tmp_path_factory):
+    """torch runs batch-1 convolutions as im2col + MKL sgemm, whose default code path -- and with it the last
+    bits of the sums -- MKL picks by CPU vendor, ISA and thread count.  So the port runs in a child process
+    under MKL's vendor-neutral branch (MKL_CBWR=COMPATIBLE, read when MKL starts) on one thread, the setting
+    in which tests/golden/make_golden.py --mkl-compat ran the reference (`y_mkl_compat`).  Larger batches run
+    on oneDNN, which MKL_CBWR does not touch."""
+    path = tmp_path_factory.mktemp("port") / "y.npz"
+    tests = os.path.dirname(os.path.abspath(__file__))
+    code = (f"import sys; sys.path[:0] = [{ROOT!r}, {tests!r}]; import test_oracle; "
+            f"test_oracle._port_outputs({str(path)!r})")
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MKL_CBWR="COMPATIBLE"),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    with np.load(path) as d:
+        return {k: d[k] for k in d.files}
+
+
 @pytest.mark.parametrize("name", CONV_CASES)
-def test_torch_port_is_bit_exact(name):
+def test_torch_port_is_bit_exact(name, port_outputs):
     rec = load_golden(name)
-    st = {k: torch.from_numpy(v) for k, v in rec["state"].items()}
-    y = oracle.torch_forward(torch.from_numpy(rec["x"]), st, rec["pos_emb"]).numpy()
-    assert np.array_equal(_pick(y, rec), rec["y"])
+    want = rec["y_mkl_compat"] if rec["B"] == 1 else rec["y"]
+    assert np.array_equal(_pick(port_outputs[name], rec), want)
 
 
 def test_acc64_agrees():

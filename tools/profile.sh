@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps ${PROF_STEPS:-50} --warmup 5 --no-cpu-baseline $*"
+ARGS="--steps ${PROF_STEPS:-50} --warmup 5 --full --no-cpu-baseline $*"
 run() { # name, rocprof flags...
   local name=$1; shift
   timeout -k 10 240 rocprofv3 "$@" --output-format csv -d "$OUT/$name" -o "$name" -- python3 "$REPO/bench.py" $ARGS > "$OUT/$name.stdout" 2> "$OUT/$name.stderr"
