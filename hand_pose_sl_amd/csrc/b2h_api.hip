@@ -137,7 +137,8 @@ struct b2h_model {
     int num_cus = 256;
     // Chunk pools of the persistent 16-bit kernel (kernel_mfma16.h, Sched16): one 128-byte slot per stream
     // that has launched on this model, two words each (claim counter, finished workgroups), zero between
-    // launches.  Launches on one stream are ordered, so a slot is never shared by two running kernels.
+    // launches.  Launches on one stream are ordered, so a slot is never shared by two running kernels -- as long
+    // as one handle value names one ordered queue: hipStreamPerThread does not and never gets a slot (launch()).
     DevBuf pools;
     std::mutex pool_mu;
     std::vector<hipStream_t> pool_streams;
@@ -503,12 +504,13 @@ int launch(b2h_model* m, const float* x, float* y, int64_t B, int64_t T, int ker
             if (nch >= 0x7fffffff) return fail(B2H_ERR_SHAPE, "B*T too large for one launch");
             // Work distribution (Sched16): with >= 256 chunks per workgroup the launch is DYNAMIC -- waves claim runs
             // of two consecutive chunks from a device-wide counter, so the chip walks through x and y as one front
-            // (kernel_mfma16.h).  The counter lives in this stream's slot; no slot (more than kPoolSlots streams)
-            // or a stream under capture (a graph may be replayed on any stream, concurrently with this one) means a
-            // STATIC launch.
+            // (kernel_mfma16.h).  The counter lives in this stream's slot; no slot (more than kPoolSlots streams),
+            // a stream under capture (a graph may be replayed on any stream, concurrently with this one) or
+            // hipStreamPerThread (one handle value for a different stream in every host thread, whose launches
+            // would share one counter and skip chunks) means a STATIC launch.
             Sched16 sched{nullptr, 2};
             const int64_t per_wg = nch / grid16;
-            if (per_wg >= kPoolMinChunks && m->pools.p) {
+            if (per_wg >= kPoolMinChunks && m->pools.p && st != hipStreamPerThread) {
                 hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
                 if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
                 if (cap == hipStreamCaptureStatusNone) {

@@ -106,7 +106,15 @@ int b2h_load_weights(b2h_model* m, const float* w1, const float* b1, const float
  *       the reference's non-contiguous view, :60-62)
  * T >= 1; pos_emb models require T == 100 (B2H_ERR_SHAPE, as torch.cat raises
  * in the reference, :78-84).  B == 0 is a no-op.  x and y must be 16-byte aligned and must
- * not overlap (B2H_ERR_INVALID otherwise). */
+ * not overlap (B2H_ERR_INVALID otherwise).
+ * Streams: a BF16_MFMA / F16_MFMA launch of <= 32 channels with >= 256 chunks per CU (e.g. >= 65 536 sequences of
+ * <= 208 frames on 256 CUs) hands out its work dynamically, through a claim counter in device memory that the
+ * model keeps per stream HANDLE VALUE (64 per model).  Launches on further handles, on hipStreamPerThread (one
+ * value for a different stream in every host thread) and on a stream under capture use the static distribution
+ * (same bits, 1-3 % slower).  The counter assumes that one handle value is one ordered queue, so a caller must
+ * not pass one model a handle value that names different streams at the same time (other than
+ * hipStreamPerThread).  Destroying a stream and creating one that reuses its value is safe: ROCm's
+ * hipStreamDestroy waits for the stream's work (tests/test_poisoned_buffers.py pins both). */
 int b2h_forward(b2h_model* m, const float* x, float* y, int64_t B, int64_t T, int kernel,
                 void* stream);
 

@@ -24,6 +24,7 @@ import torch
 import hand_pose_sl_amd as hps
 import oracle
 from conftest import CONV_CASES, load_golden
+from poison import POISON
 
 pytestmark = pytest.mark.gpu
 
@@ -32,6 +33,12 @@ BF16_RANDN_BOUND = 1.1e-3   # bf16 on N(0,1) inputs only (see the docstring): me
 TOL_MODEL = {"bf16": 6e-4, "f16": 8e-5}   # vs the oracle's operand-rounding model
 ORACLE_MODE = {"bf16": "bf16", "f16": "f16"}
 ALL_PREC = ["f32_valu", "f32_mfma", "f16x3", "bf16", "f16"]
+
+
+def _poisoned(like):
+    """An output buffer shaped like `like` whose every word holds the poison NaN pattern (tests/poison.py): unlike a
+    torch.empty, which hands back the previous call's block with its (correct) rows, it shows any row left unwritten."""
+    return torch.full(like.shape, POISON, dtype=torch.int32, device=like.device).view(torch.float32)
 
 
 def _model(rec, prec, dev):
@@ -498,7 +505,7 @@ def test_dynamic_launch_with_chunked_sequences(prec, cuda_device):
         y = m(x)
         y_small = torch.cat([m(x[a:a + 1000]) for a in range(0, S, 1000)])
         assert torch.equal(y, y_small)
-        assert torch.equal(m(x), y)                                      # the counter is back at zero
+        assert torch.equal(m.forward_into(x, _poisoned(y)), y)           # the counter is back at zero: every row written
         idx = [0, 999, 1000, S - 1]
         ref = oracle.forward_from_state(x[idx].cpu().numpy(), rec["state"])
         assert np.abs(y[idx].cpu().numpy() - ref).max() <= TOL[prec]
@@ -611,8 +618,8 @@ def test_claimed_chunks_pool_launches(prec, cuda_device):
         idx = [0, 1, 4000, S - 1]
         ref = oracle.forward_from_state(x[idx].cpu().numpy(), rec["state"])
         assert np.abs(y_pool[idx].cpu().numpy() - ref).max() <= TOL[prec]
-        for _ in range(4):                                                           # the pool words are back at zero
-            assert torch.equal(m(x), y_pool)
+        for _ in range(4):                                   # the pool words are back at zero: every row written again
+            assert torch.equal(m.forward_into(x, _poisoned(y_pool)), y_pool)
         x2 = x.flip(0).contiguous()
         y2 = m(x2)
         assert torch.equal(y2, y_pool.flip(0))
@@ -637,4 +644,4 @@ def test_claimed_chunks_pool_launches(prec, cuda_device):
             graph.replay()
             torch.cuda.synchronize()
             assert torch.equal(ys, want)
-        assert torch.equal(m(x), y_pool)                                             # and a pool launch after the replays
+        assert torch.equal(m.forward_into(x, _poisoned(y_pool)), y_pool)             # and a pool launch after the replays

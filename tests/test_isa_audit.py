@@ -83,3 +83,94 @@ def test_audit_detects_the_pattern(tmp_path):
     assert total(bad.replace("offen\n", "offen\n.LBB0_1:\n")) == 0                              # new basic block
     assert total("\tglobal_store_dwordx4 v[0:1], v[142:145], off\n\tv_mov_b32_e32 v143, v7") == 1
     assert total("\tbuffer_store_dwordx2 v[114:115], v116, s[8:11], 0 offen\n\tv_cndmask_b32_e32 v114, v74, v118, vcc") == 1
+
+
+# ---- the dynamic claim's destination register (kernel_mfma16.h, Sched16) ---------------------------------------
+# The device-wide claim is an inline-asm `global_atomic_add vD, ... sc0` whose answer lands in vD asynchronously; the
+# compiler does not track that write (inline asm is opaque to its wait-count insertion).  The kernel is correct only
+# while nothing reads or writes vD before the `s_waitcnt vmcnt(0)` of pin_loads16: a copy or a live-range split of
+# `pv` there would read a stale claim and skip or repeat chunks.
+_CLAIM_KERNEL = "_ZN3b2h14b2h_fwd_mfma16I"
+
+
+def _vregs(text):
+    """VGPR numbers an operand string names, single registers and v[a:b] ranges."""
+    import re
+    regs = set()
+    for a, b in re.findall(r"\bv\[(\d+):(\d+)\]", text):
+        regs.update(range(int(a), int(b) + 1))
+    regs.update(int(r) for r in re.findall(r"\bv(\d+)\b", text))
+    return regs
+
+
+def claim_register_violations(listing):
+    """(claims, done_counts, violations) over every b2h_fwd_mfma16 instantiation of an assembly listing: each
+    returning global_atomic_add's destination must be untouched until the next s_waitcnt with vmcnt(0)."""
+    import re
+    claims = done = 0
+    bad = []
+    kernel = None
+    lines = listing.splitlines()
+    for i, raw in enumerate(lines):
+        line = raw.split(";", 1)[0].rstrip()
+        label = re.match(r"^(_Z\w+):", line)
+        if label:
+            kernel = label.group(1) if label.group(1).startswith(_CLAIM_KERNEL) else None
+            continue
+        if kernel is None:
+            continue
+        m = re.match(r"^\s*global_atomic_add\s+v(\d+),(.*)\bsc0\b", line)
+        if not m:
+            continue
+        vd = int(m.group(1))
+        if "offset:" in m.group(2):
+            done += 1
+        else:
+            claims += 1
+        for j in range(i + 1, len(lines)):
+            nxt = lines[j].split(";", 1)[0].strip()
+            if re.match(r"^s_waitcnt\b.*\bvmcnt\(0\)", nxt):
+                break
+            if re.match(r"^(_Z\w+:|s_endpgm\b)", nxt):
+                bad.append((kernel, i + 1, "no vmcnt(0) before the end of the kernel"))
+                break
+            if not nxt or nxt.endswith(":") or nxt.startswith("."):
+                continue
+            parts = nxt.split(None, 1)
+            if len(parts) == 2 and vd in _vregs(parts[1]):
+                bad.append((kernel, j + 1, f"v{vd} used before the wait: {nxt}"))
+    return claims, done, bad
+
+
+def test_claim_register_untouched_until_the_wait(compiled):
+    with open(compiled[0]) as f:
+        claims, done, bad = claim_register_violations(f.read())
+    assert claims == 8, claims        # one claim per b2h_fwd_mfma16<PREC, FUSED, STREAM>: the check is not vacuous
+    assert done == 8, done            # and one finished-workgroup count (offset:4) each
+    assert not bad, bad
+
+
+def test_claim_register_audit_detects_uses():
+    """The claim audit on synthetic listings: a copy or an overwrite of the destination before the wait is
+    reported, a read after it is not."""
+    head = "_ZN3b2h14b2h_fwd_mfma16ILi1ELb0ELb1EEEvPKfPfiiilPKviNS_9FusedArgsENS_7Sched16E:\n"
+    atomic = "\tglobal_atomic_add v202, v2, v6, s[10:11] sc0\n\tv_mfma_f32_16x16x32_bf16 v[0:3], v[4:7], v[8:11], v[0:3]\n"
+    wait = "\ts_waitcnt vmcnt(0)\n"
+    tail = "\tv_readfirstlane_b32 s0, v202\n\ts_endpgm\n"
+
+    def audit(body):
+        return claim_register_violations(head + body)
+
+    assert audit(atomic + wait + tail) == (1, 0, [])                                  # read after the wait: fine
+    assert len(audit(atomic + "\tv_mov_b32_e32 v5, v202\n" + wait + tail)[2]) == 1    # copied before the wait
+    assert len(audit(atomic + "\tv_add_u32_e32 v202, 1, v3\n" + wait + tail)[2]) == 1  # overwritten before the wait
+    assert len(audit(atomic + "\tv_pk_mov_b32 v[201:202], v[8:9], v[8:9] op_sel:[0,1]\n" + wait + tail)[2]) == 1
+    assert len(audit(atomic + "\ts_waitcnt vmcnt(3)\n\tv_mov_b32_e32 v5, v202\n" + wait + tail)[2]) == 1
+    assert audit(atomic + "\ts_waitcnt vmcnt(0) lgkmcnt(0)\n" + tail)[2] == []
+    assert audit(atomic + "\tv_mov_b32_e32 v5, v2020\n" + wait + tail)[2] == []
+    # the finished-workgroup count (offset:4) obeys the same rule
+    done = "\tglobal_atomic_add v1, v1, v2, s[10:11] offset:4 sc0\n.LBB13_105:\n\ts_or_b64 exec, exec, s[0:1]\n"
+    assert audit(done + wait + "\tv_readfirstlane_b32 s0, v1\n\ts_endpgm\n") == (0, 1, [])
+    assert len(audit(done + "\tv_mov_b32_e32 v0, v1\n" + wait + "\ts_endpgm\n")[2]) == 1
+    # other kernels are not audited (their atomics are waited for by the compiler)
+    assert claim_register_violations("_Z5otherv:\n" + atomic + "\tv_mov_b32_e32 v5, v202\n" + wait) == (0, 0, [])
