@@ -43,6 +43,12 @@ SYMBOLS = {
                                             ctypes.c_float, _vp]),
     "b2h_masked_l1": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp]),
     "b2h_weighted_l1": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp]),
+    "b2h_train_forward": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp]),
+    "b2h_backward_workspace_bytes": (ctypes.c_size_t, [_vp, ctypes.c_int64, ctypes.c_int64]),
+    "b2h_backward": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.c_int64,
+                                    ctypes.c_int64, _vp, ctypes.c_size_t, _vp]),
+    "b2h_masked_l1_backward": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp]),
+    "b2h_weighted_l1_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp]),
     "b2h_tenc_create": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(_vp)]),
     "b2h_tenc_destroy": (ctypes.c_int, [_vp]),
     "b2h_tenc_set_kernel": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -9,8 +9,12 @@ containers only -- constructing them in the reference's order also makes a
 seeded default init identical to the reference's -- their forward is never
 called: the four layers run fused in one HIP kernel through the C ABI.
 
-Inference only (the north-star path).  Calling the module with autograd enabled
-on parameters that require grad raises, it never silently runs PyTorch ops.
+Training: in training mode with autograd enabled and a parameter or the input requiring
+a gradient, `model(x)` runs `_ConvTrainFn` -- an exact-fp32 HIP forward and a HIP backward
+(b2h_train_forward / b2h_backward) that read the parameters' own storage -- so the reference's
+loop body (steps/traintest.py:87-121) runs unchanged with any torch optimizer.  Every other call
+(eval mode or no_grad) runs the inference kernels selected by `precision`.  No path ever falls
+back to PyTorch ops.
 """
 import ctypes
 
@@ -38,7 +42,10 @@ fp32 CPU forward, measured in tests/test_gpu_parity.py::test_error_vs_input_scal
   "bf16"   bf16 operands, fp32 accumulate: 3.7-5.0e-4 on normalised keypoints (|x| <~ 1), 1.05e-3 at N(0,1) --
            i.e. it meets the <= 1e-3 gate only on inputs scaled like keypoints / 1280; `f16` runs at the SAME
            speed and holds the gate on any such input, so prefer it unless bf16's exponent range is needed
-           (activations beyond 65504)                               18 G frames/s"""
+           (activations beyond 65504)                               18 G frames/s
+training (model.train(), autograd on, a parameter or the input requires grad): always exact fp32 on the
+vector ALU (b2h_train_forward / b2h_backward), whatever `precision` says; gradients as accurate as the
+reference's own fp32 CPU training (tests/test_train_gpu.py)."""
 
 
 class ConvModel(nn.Module):
@@ -81,22 +88,29 @@ class ConvModel(nn.Module):
     def _device(self):
         return self._modules["conv1"]._parameters["weight"].device
 
-    def _ensure_handle(self):
+    def _ensure_created(self):
+        """The native model on the parameters' device, without packed weights (all the training path needs)."""
         dev = self._device()
         if dev.type != "cuda":
             raise RuntimeError("hand_pose_sl_amd.ConvModel runs on an MI355X only: call "
                                "model.to('cuda') first (there is no CPU path in the product)")
         lib = _lib.load()
-        key = (dev.index,) + tuple((p.data_ptr(), p._version) for p in self._params())
-        if self._handle is not None and key == self._packed_key:
-            return lib
-        with torch.cuda.device(dev):
-            if self._handle is None or self._packed_key[0] != dev.index:
-                self._free()
+        if self._handle is None or self.__dict__.get("_handle_dev") != dev.index:
+            self._free()
+            with torch.cuda.device(dev):
                 h = ctypes.c_void_p()
                 _lib.check(lib.b2h_create(self.conv_channels, b"ReLU", int(self.pos_emb is not None),
                                           ctypes.byref(h)))
-                self._handle = h
+            self._handle = h
+            self._handle_dev = dev.index
+        return lib, dev
+
+    def _ensure_handle(self):
+        lib, dev = self._ensure_created()
+        key = (dev.index,) + tuple((p.data_ptr(), p._version) for p in self._params())
+        if key == self._packed_key:
+            return lib
+        with torch.cuda.device(dev):
             ps = [p.detach().to(torch.float32).contiguous() for p in self._params()]
             torch.cuda.current_stream(dev).synchronize()
             _lib.check(lib.b2h_load_weights(self._handle, *[ctypes.c_void_p(p.data_ptr()) for p in ps], 1))
@@ -111,6 +125,7 @@ class ConvModel(nn.Module):
                 pass
             self.__dict__["_handle"] = None
             self.__dict__["_packed_key"] = None
+            self.__dict__["_handle_dev"] = None
 
     def __del__(self):
         self._free()
@@ -120,18 +135,23 @@ class ConvModel(nn.Module):
         lib = self._ensure_handle()
         return lib.b2h_kernel_name(self._handle, _lib.KERNELS[precision or self.precision]).decode()
 
+    def _wants_grad(self, inp):
+        """The training path's condition: training mode, autograd on, a parameter or the input needs a gradient."""
+        return (self.training and torch.is_grad_enabled() and
+                (inp.requires_grad or any(p.requires_grad for p in self._params())))
+
     def _check_input(self, inp):
         if inp.dim() != 4 or inp.shape[2] != 12 or inp.shape[3] != 2:
             raise RuntimeError(f"expected input of shape (B, T, 12, 2), got {tuple(inp.shape)}")
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError("hand_pose_sl_amd.ConvModel is inference-only: call model.eval() and "
-                               "wrap the call in torch.no_grad() as steps/traintest.py:350-351 does")
         dev = self._device()
         # traintest.py:354-358 passes batch["body_kp"], which the loop never moved to the device
         x = inp.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
         return x
 
     def forward(self, inp):
+        if self._wants_grad(inp):
+            x = self._check_input(inp)
+            return _ConvTrainFn.apply(self, x, *self._params())
         lib = self._ensure_handle()
         x = self._check_input(inp)
         B, T = x.shape[0], x.shape[1]
@@ -165,7 +185,10 @@ class ConvModel(nn.Module):
                       mask_tail=False, factor=1280.0):
         """Raw-pixel body keypoints in, pixel-space hand keypoints out, in ONE kernel:
         ChestDifference + /factor (steps/utils.py:180-210) -> four conv layers ->
-        x factor (traintest.py:387-388) -> optional tail mask (utils.py:309-312)."""
+        x factor (traintest.py:387-388) -> optional tail mask (utils.py:309-312).  Inference only."""
+        if self._wants_grad(body):
+            raise RuntimeError("ConvModel.forward_fused is inference-only (no gradient): call model.eval() or wrap the "
+                               "call in torch.no_grad(); train through model(x), which is differentiable")
         lib = self._ensure_handle()
         x = self._check_input(body)
         B, T = x.shape[0], x.shape[1]
@@ -199,6 +222,64 @@ class ConvModel(nn.Module):
                                             _lib.KERNELS[precision or self.precision], int(iters),
                                             ctypes.c_void_p(st), ctypes.byref(ms)))
         return ms.value
+
+
+def _ptrs(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _aligned(t):
+    """The kernels' 16-byte vector accesses: a contiguous slice of a larger batch may start anywhere."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _ConvTrainFn(torch.autograd.Function):
+    """y = ConvModel(x) with its gradient: b2h_train_forward / b2h_backward (exact fp32, kernel_train.h).
+    The parameters go in as themselves (their own data_ptr, saved for backward, so autograd's version check
+    catches an in-place edit between forward and backward); nothing else is saved, the backward recomputes."""
+
+    @staticmethod
+    def forward(ctx, model, x, *params):
+        for p in params:
+            if p.device != x.device or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("training needs contiguous float32 parameters on the input's device")
+        lib, dev = model._ensure_created()
+        x = _aligned(x)
+        B, T = x.shape[0], x.shape[1]
+        y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=x.device)
+        with _lib.on_device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.b2h_train_forward(model._handle, _ptrs(params), ctypes.c_void_p(x.data_ptr()),
+                                             ctypes.c_void_p(y.data_ptr()), B, T, ctypes.c_void_p(st)))
+        ctx.model = model
+        ctx.save_for_backward(x, *params)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, *params = ctx.saved_tensors
+        model = ctx.model
+        need_dx = ctx.needs_input_grad[1]
+        B, T = x.shape[0], x.shape[1]
+        if B == 0:
+            grads = [torch.zeros_like(p) for p in params]
+            dx = torch.zeros_like(x) if need_dx else None
+        else:
+            lib, dev = model._ensure_created()
+            dy = _aligned(dy.to(torch.float32).contiguous())   # autograd may hand over an expanded / CopySlices gradient
+            grads = [torch.empty_like(p) for p in params]
+            dx = torch.empty_like(x) if need_dx else None
+            nbytes = lib.b2h_backward_workspace_bytes(model._handle, B, T)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+            with _lib.on_device(dev):
+                st = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(lib.b2h_backward(model._handle, _ptrs(params), ctypes.c_void_p(x.data_ptr()),
+                                            ctypes.c_void_p(dy.data_ptr()),
+                                            ctypes.c_void_p(dx.data_ptr()) if dx is not None else None,
+                                            _ptrs(grads), B, T, ctypes.c_void_p(ws.data_ptr()), nbytes,
+                                            ctypes.c_void_p(st)))
+        return (None, dx) + tuple(g if ctx.needs_input_grad[2 + i] else None for i, g in enumerate(grads))
 
 
 def target_transform(body, hand, dif_encoding=True, normalize=True, factor=1280.0):

@@ -21,6 +21,7 @@
 #include "kernel_mfma3.h"
 #include "kernel_mfma3w.h"
 #include "kernel_tenc.h"
+#include "kernel_train.h"
 #include "kernel_valu.h"
 
 using namespace b2h;
@@ -886,6 +887,86 @@ int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, 
 
 } // extern "C"
 
+// ---- training (kernel_train.h) ------------------------------------------------------------------------------
+namespace {
+int odd_stride(int n) { return n | 1; }
+
+TrainParams train_params(const b2h_model* m, const float* const* params) {
+    TrainParams p;
+    int off = 0; // < 2^18 floats at 128 channels
+    for (int l = 0; l < 4; ++l) {
+        p.w[l] = params[2 * l];
+        p.b[l] = params[2 * l + 1];
+        p.off[2 * l] = off;
+        off += m->cout[l] * m->cin[l] * kTaps;
+        p.off[2 * l + 1] = off;
+        off += m->cout[l];
+    }
+    p.C = m->C;
+    p.cin0 = m->cin[0];
+    p.pos_emb = m->pos_emb;
+    p.xs = odd_stride(m->cin[0]);
+    p.as = odd_stride(m->C);
+    p.gs = odd_stride(kOutCh);
+    p.slab = (off + 3) / 4 * 4;
+    return p;
+}
+
+int64_t train_param_floats(const TrainParams& p) { return p.off[7] + kOutCh; }
+
+size_t train_lds_bytes(const TrainParams& p, int mode) {
+    const int R = train_rows(mode);
+    return (size_t)R * (p.xs + 3 * p.as + (mode ? p.gs : 0)) * 4;
+}
+
+// Tiles of a backward launch -> slabs: depends on (B, T) and the width only, never on the device.
+int64_t train_tiles(int64_t B, int64_t T, int mode) { return B * ((T + train_tile(mode) - 1) / train_tile(mode)); }
+int train_nslabs(const TrainParams& p, int64_t B, int64_t T) {
+    // at most 2^26 floats (256 MiB) of slabs, at least 64 slabs
+    const int64_t cap = std::max<int64_t>(64, std::min<int64_t>(kTrainMaxSlabs, ((int64_t)1 << 26) / p.slab));
+    return (int)std::min<int64_t>(train_tiles(B, T, 1), cap);
+}
+
+int set_train_kernel_attributes() {
+    static std::mutex mu;
+    static bool done[64] = {};
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (dev >= 0 && dev < 64 && done[dev]) return B2H_OK;
+    int rc;
+    if ((rc = raise_lds_cap(b2h_train_conv<0>)) || (rc = raise_lds_cap(b2h_train_conv<1>)) ||
+        (rc = raise_lds_cap(b2h_train_conv<2>)))
+        return rc;
+    if (dev >= 0 && dev < 64) done[dev] = true;
+    return B2H_OK;
+}
+
+bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
+    const char* x = reinterpret_cast<const char*>(a);
+    const char* y = reinterpret_cast<const char*>(b);
+    return x < y + bn && y < x + an;
+}
+
+bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) & (a - 1); }
+
+// Shared checks of b2h_train_forward / b2h_backward, as launch() makes them for b2h_forward.
+int train_check(const b2h_model* m, const float* const* params, int64_t B, int64_t T) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (B < 0 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0 and T >= 1");
+    if (T > (1 << 24)) return fail(B2H_ERR_SHAPE, "T too large");
+    if (m->pos_emb && T != 100)
+        return fail(B2H_ERR_SHAPE, "pos_emb model requires T == 100 (LinearPositionalEmbedding max_len, "
+                                   "HandPoseModels.py:23,78-84)");
+    if (!params) return fail(B2H_ERR_INVALID, "params is NULL");
+    for (int i = 0; i < 8; ++i) {
+        if (!params[i]) return fail(B2H_ERR_INVALID, "params[" + std::to_string(i) + "] is NULL");
+        if (misaligned(params[i], 4)) return fail(B2H_ERR_INVALID, "params must be 4-byte aligned fp32 tensors");
+    }
+    return B2H_OK;
+}
+} // namespace
+
 extern "C" {
 
 int b2h_version(void) { return B2H_VERSION; }
@@ -927,6 +1008,7 @@ int b2h_create(int conv_channels, const char* activation, int pos_emb, b2h_model
     const int C = conv_channels;
     const int cin[4] = {kInCh + m->pos_emb, C, C, C}, cout[4] = {C, C, C, kOutCh};
     for (int l = 0; l < 4; ++l) { m->cin[l] = cin[l]; m->cout[l] = cout[l]; }
+    if (int rc = set_train_kernel_attributes()) return rc; // before any launch: the training entry points stay capturable
     *out = m.release();
     return B2H_OK;
 }
@@ -1028,6 +1110,135 @@ int b2h_weighted_l1(const float* pred, const float* target, const float* scores,
                     int64_t T, float* per_seq, float* loss, void* stream) {
     if (!scores) return fail(B2H_ERR_INVALID, "scores is NULL");
     return l1_metric(pred, target, scores, n_frames, B, T, per_seq, loss, stream);
+}
+
+
+int b2h_train_forward(b2h_model* m, const float* const* params, const float* x, float* y, int64_t B, int64_t T,
+                      void* stream) {
+    if (int rc = train_check(m, params, B, T)) return rc;
+    if (B == 0) return B2H_OK;
+    if (!x || !y) return fail(B2H_ERR_INVALID, "x / y is NULL");
+    if (int rc = check_device(m->device)) return rc;
+    if (misaligned(x, 16) || misaligned(y, 16))
+        return fail(B2H_ERR_INVALID, "x and y must be 16-byte aligned (hipMalloc / torch allocations are)");
+    const size_t xn = (size_t)B * T * kInCh * 4, yn = (size_t)B * T * kOutCh * 4;
+    if (overlaps(x, xn, y, yn)) return fail(B2H_ERR_INVALID, "x and y overlap");
+    for (int i = 0; i < 8; ++i)
+        if (overlaps(params[i], 4, y, yn)) return fail(B2H_ERR_INVALID, "y overlaps a parameter");
+    const TrainParams p = train_params(m, params);
+    const int64_t tiles = train_tiles(B, T, 0);
+    if (tiles > 0x7fffffff) return fail(B2H_ERR_SHAPE, "B*T too large for one launch");
+    const int tps = (int)((T + kTrainFwdTile - 1) / kTrainFwdTile);
+    hipLaunchKernelGGL(b2h_train_conv<0>, dim3((unsigned)tiles), dim3(256), train_lds_bytes(p, 0), (hipStream_t)stream,
+                       x, nullptr, y, nullptr, p, (int)T, tps, tiles, 0);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+size_t b2h_backward_workspace_bytes(const b2h_model* m, int64_t B, int64_t T) {
+    if (!m || B < 1 || T < 1) return 0;
+    float* dummy[8] = {};
+    const TrainParams p = train_params(m, dummy);
+    return (size_t)train_nslabs(p, B, T) * p.slab * 4;
+}
+
+int b2h_backward(b2h_model* m, const float* const* params, const float* x, const float* dy, float* dx,
+                 float* const* grads, int64_t B, int64_t T, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = train_check(m, params, B, T)) return rc;
+    if (B == 0) return fail(B2H_ERR_SHAPE, "b2h_backward needs B >= 1 (the gradients of an empty batch are not defined here)");
+    if (!x || !dy) return fail(B2H_ERR_INVALID, "x / dy is NULL");
+    if (!grads) return fail(B2H_ERR_INVALID, "grads is NULL");
+    if (int rc = check_device(m->device)) return rc;
+    if (misaligned(x, 16) || misaligned(dy, 16) || (dx && misaligned(dx, 16)) || misaligned(workspace, 16))
+        return fail(B2H_ERR_INVALID, "x, dy, dx and the workspace must be 16-byte aligned");
+    const TrainParams p = train_params(m, params);
+    const int nslabs = train_nslabs(p, B, T);
+    const size_t need = (size_t)nslabs * p.slab * 4;
+    if (!workspace || workspace_bytes < need)
+        return fail(B2H_ERR_INVALID, "workspace smaller than b2h_backward_workspace_bytes (" + std::to_string(need) + " B)");
+    const size_t xn = (size_t)B * T * kInCh * 4, yn = (size_t)B * T * kOutCh * 4;
+    // outputs: dx, the eight gradients, the workspace; none may overlap another operand
+    const void* outs[10];
+    size_t outn[10];
+    int nout = 0;
+    for (int i = 0; i < 8; ++i) {
+        if (!grads[i]) return fail(B2H_ERR_INVALID, "grads[" + std::to_string(i) + "] is NULL");
+        if (misaligned(grads[i], 4)) return fail(B2H_ERR_INVALID, "grads must be 4-byte aligned");
+        outs[nout] = grads[i];
+        outn[nout++] = (size_t)((i + 1 < 8 ? p.off[i + 1] : train_param_floats(p)) - p.off[i]) * 4;
+    }
+    if (dx) { outs[nout] = dx; outn[nout++] = xn; }
+    outs[nout] = workspace;
+    outn[nout++] = need;
+    for (int a = 0; a < nout; ++a) {
+        if (overlaps(outs[a], outn[a], x, xn) || overlaps(outs[a], outn[a], dy, yn))
+            return fail(B2H_ERR_INVALID, "an output overlaps x or dy");
+        for (int i = 0; i < 8; ++i)
+            if (overlaps(outs[a], outn[a], params[i], (size_t)((i + 1 < 8 ? p.off[i + 1] : train_param_floats(p)) - p.off[i]) * 4))
+                return fail(B2H_ERR_INVALID, "an output overlaps a parameter");
+        for (int c = a + 1; c < nout; ++c)
+            if (overlaps(outs[a], outn[a], outs[c], outn[c])) return fail(B2H_ERR_INVALID, "two outputs overlap");
+    }
+    const int64_t tiles = train_tiles(B, T, 1);
+    const int tps = (int)((T + kTrainBwdTile - 1) / kTrainBwdTile);
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = static_cast<float*>(workspace);
+    if (dx)
+        hipLaunchKernelGGL(b2h_train_conv<2>, dim3((unsigned)nslabs), dim3(256), train_lds_bytes(p, 2), st, x, dy, dx, ws,
+                           p, (int)T, tps, tiles, nslabs);
+    else
+        hipLaunchKernelGGL(b2h_train_conv<1>, dim3((unsigned)nslabs), dim3(256), train_lds_bytes(p, 1), st, x, dy,
+                           nullptr, ws, p, (int)T, tps, tiles, nslabs);
+    TrainGrads g;
+    for (int i = 0; i < 8; ++i) {
+        g.g[i] = grads[i];
+        g.off[i] = p.off[i];
+    }
+    g.off[8] = train_param_floats(p);
+    hipLaunchKernelGGL(b2h_train_reduce, dim3((unsigned)((g.off[8] + 63) / 64)), dim3(256), 0, st, ws, p.slab, nslabs, g);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+namespace {
+int l1_backward(const float* pred, const float* target, const float* scores, const int64_t* n_frames, int64_t B,
+                int64_t T, const float* dloss, float* dpred, void* stream) {
+    if (B < 1 || T < 1) return fail(B2H_ERR_SHAPE, "the L1 loss gradients need B >= 1 and T >= 1");
+    if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
+    int rc;
+    if ((rc = check_device_ptr(pred, "pred")) || (rc = check_device_ptr(target, "target")) ||
+        (rc = check_device_ptr(dloss, "dloss")) || (rc = check_device_ptr(dpred, "dpred")) ||
+        (scores && (rc = check_device_ptr(scores, "scores"))) || (n_frames && (rc = check_device_ptr(n_frames, "n_frames"))))
+        return rc;
+    if (misaligned(pred, 16) || misaligned(target, 16) || misaligned(dpred, 16))
+        return fail(B2H_ERR_INVALID, "pred, target and dpred must be 16-byte aligned");
+    const size_t pn = (size_t)B * T * kOutCh * 4;
+    if (overlaps(dpred, pn, pred, pn) || overlaps(dpred, pn, target, pn) || overlaps(dpred, pn, dloss, 4) ||
+        (scores && overlaps(dpred, pn, scores, pn / 2)) || (n_frames && overlaps(dpred, pn, n_frames, (size_t)B * 8)))
+        return fail(B2H_ERR_INVALID, "dpred overlaps an input");
+    const int64_t n = B * T * (kOutCh / 2);
+    const int64_t blocks = std::min<int64_t>((n + 255) / 256, 256 * 16);
+    hipStream_t st = (hipStream_t)stream;
+    if (scores)
+        hipLaunchKernelGGL(b2h_l1_backward_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, pred, target, scores,
+                           n_frames, dloss, dpred, B, (int)T);
+    else
+        hipLaunchKernelGGL(b2h_l1_backward_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, pred, target,
+                           nullptr, n_frames, dloss, dpred, B, (int)T);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+} // namespace
+
+int b2h_masked_l1_backward(const float* pred, const float* target, const int64_t* n_frames, int64_t B, int64_t T,
+                           const float* dloss, float* dpred, void* stream) {
+    return l1_backward(pred, target, nullptr, n_frames, B, T, dloss, dpred, stream);
+}
+
+int b2h_weighted_l1_backward(const float* pred, const float* target, const float* scores, const int64_t* n_frames,
+                             int64_t B, int64_t T, const float* dloss, float* dpred, void* stream) {
+    if (!scores) return fail(B2H_ERR_INVALID, "scores is NULL");
+    return l1_backward(pred, target, scores, n_frames, B, T, dloss, dpred, stream);
 }
 
 int b2h_model_info(const b2h_model* m, int* conv_channels, int* pos_emb, int* has_weights) {

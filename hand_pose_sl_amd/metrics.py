@@ -7,6 +7,10 @@
 target joints' confidences, SUMMED over the batch (the class does not divide).  `l1_to_pixels`
 mirrors `L12Pixels(21, 1280)` (steps/utils.py:291-299), the "pixel distance" the training loop
 prints (traintest.py:27-28,139).
+
+Both losses are differentiable in the prediction (the training loop's `loss.backward()`,
+traintest.py:111-121): when `prediction` requires a gradient and autograd is on, the same forward
+kernels run inside an autograd Function whose backward is a HIP kernel.
 """
 import ctypes
 
@@ -34,17 +38,58 @@ def _l1(prediction, target, lengths, scores, return_per_sequence, what):
         sc = scores.to(device=p.device, dtype=torch.float32).contiguous()   # the reference moves them too (utils.py:439)
         if sc.shape != (B, T, 21):
             raise RuntimeError(f"scores must have shape ({B}, {T}, 21), got {tuple(sc.shape)}")
+    if p.requires_grad and torch.is_grad_enabled():
+        loss, per_seq = _L1Fn.apply(p, t.detach(), nf, None if sc is None else sc.detach())
+    else:
+        loss, per_seq = _l1_forward(p.detach(), t, nf, sc)
+    return (loss, per_seq) if return_per_sequence else loss
+
+
+def _ptr(x):
+    return ctypes.c_void_p(x.data_ptr()) if x is not None else None
+
+
+def _l1_forward(p, t, nf, sc):
+    B, T = p.shape[0], p.shape[1]
     per_seq = torch.empty((B,), dtype=torch.float32, device=p.device)
     loss = torch.empty((), dtype=torch.float32, device=p.device)
     lib = _lib.load()
     with _lib.on_device(p.device):
         st = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None else None
         if sc is None:
-            _lib.check(lib.b2h_masked_l1(ptr(p), ptr(t), ptr(nf), B, T, ptr(per_seq), ptr(loss), st))
+            _lib.check(lib.b2h_masked_l1(_ptr(p), _ptr(t), _ptr(nf), B, T, _ptr(per_seq), _ptr(loss), st))
         else:
-            _lib.check(lib.b2h_weighted_l1(ptr(p), ptr(t), ptr(sc), ptr(nf), B, T, ptr(per_seq), ptr(loss), st))
-    return (loss, per_seq) if return_per_sequence else loss
+            _lib.check(lib.b2h_weighted_l1(_ptr(p), _ptr(t), _ptr(sc), _ptr(nf), B, T, _ptr(per_seq), _ptr(loss), st))
+    return loss, per_seq
+
+
+class _L1Fn(torch.autograd.Function):
+    """The two L1 losses, differentiable in the prediction: the forward kernels above, and
+    b2h_masked_l1_backward / b2h_weighted_l1_backward, which read dL/dloss from device memory (no host read).
+    The per-sequence means are not differentiable."""
+
+    @staticmethod
+    def forward(ctx, p, t, nf, sc):
+        loss, per_seq = _l1_forward(p, t, nf, sc)
+        ctx.mark_non_differentiable(per_seq)
+        ctx.save_for_backward(p, t, nf, sc)
+        return loss, per_seq
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss, _gper):
+        p, t, nf, sc = ctx.saved_tensors
+        B, T = p.shape[0], p.shape[1]
+        g = (gloss if gloss is not None else torch.zeros((), device=p.device)).to(device=p.device, dtype=torch.float32).contiguous()
+        dp = torch.empty_like(p)
+        lib = _lib.load()
+        with _lib.on_device(p.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
+            if sc is None:
+                _lib.check(lib.b2h_masked_l1_backward(_ptr(p), _ptr(t), _ptr(nf), B, T, _ptr(g), _ptr(dp), st))
+            else:
+                _lib.check(lib.b2h_weighted_l1_backward(_ptr(p), _ptr(t), _ptr(sc), _ptr(nf), B, T, _ptr(g), _ptr(dp), st))
+        return dp, None, None, None
 
 
 def masked_pose_l1(prediction, target, lengths=None, return_per_sequence=False):
@@ -69,7 +114,7 @@ def l1_to_pixels(loss, num_joints=21, upsample=1280):
 
 class maskedPoseL1(nn.Module):  # noqa: N801 -- the reference's class name (steps/utils.py:413-428)
     """`criterion = maskedPoseL1()` as traintest.py:36-38 builds it; `criterion(prediction, target, lengths)`
-    runs the HIP reduction.  Inference / evaluation only (no autograd)."""
+    runs the HIP reduction; differentiable in `prediction` when it requires a gradient (training)."""
 
     def forward(self, prediction, target, lengths):
         return masked_pose_l1(prediction, target, lengths)

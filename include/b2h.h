@@ -152,6 +152,51 @@ int b2h_masked_l1(const float* pred, const float* target, const int64_t* n_frame
 int b2h_weighted_l1(const float* pred, const float* target, const float* scores, const int64_t* n_frames,
                     int64_t B, int64_t T, float* per_seq, float* loss, void* stream);
 
+/* Training (ConvModel) ------------------------------------------------------
+ * The reference trains ConvModel with the loop body of steps/traintest.py:111-121:
+ *   prediction = model(body_kp); mask_output(...); loss = criterion(...); loss.backward(); optimizer.step()
+ * These entry points are that forward and backward (HandPoseModels.py:40-64 under autograd) and the
+ * gradients of its two losses (steps/utils.py:413-452).  All arithmetic is exact fp32 (VALU FMA),
+ * whatever kernel the inference path uses.  They read the weights straight from the caller's eight
+ * fp32 tensors, never from the model's packed buffers: b2h_load_weights is not needed (nor called),
+ * and an optimizer may update the tensors in place between launches.
+ *   params: host array of the 8 device fp32 tensors in state_dict order (w1, b1, ..., w4, b4), layouts
+ *           as b2h_load_weights.
+ * Like b2h_forward they are stream-ordered and asynchronous: none synchronises, allocates or reads
+ * device memory on the host, so they can be captured into a HIP graph.  Arguments are checked as
+ * b2h_forward checks them (current device, 16-byte alignment of x / y / dy / dx / workspace, no overlap
+ * of an output with any operand, T == 100 for pos_emb models: B2H_ERR_SHAPE). */
+
+/* y = ConvModel(x), HandPoseModels.py:40-64: x (B, T, 12, 2) -> y (B, T, 21, 2), device fp32.
+ * Saves nothing for the backward pass (b2h_backward recomputes what it needs).  B == 0 is a no-op. */
+int b2h_train_forward(b2h_model* m, const float* const* params, const float* x, float* y, int64_t B,
+                      int64_t T, void* stream);
+/* Bytes of device workspace b2h_backward needs for a (B, T) batch of this model (0 for B < 1). */
+size_t b2h_backward_workspace_bytes(const b2h_model* m, int64_t B, int64_t T);
+/* loss.backward() through ConvModel.forward (HandPoseModels.py:40-64 under autograd), B >= 1:
+ *   dy    : device fp32 (B, T, 21, 2), dL/dy
+ *   dx    : device fp32 (B, T, 12, 2) dL/dx, or NULL; with pos_emb the constant channel 0 gets none
+ *   grads : host array of 8 device fp32 tensors shaped like params, OVERWRITTEN (not accumulated)
+ * Deterministic: the frame tiles and their per-workgroup partial sums in `workspace` depend on (B, T)
+ * and the width only, and a second kernel adds those partials in a fixed order (no atomics), so the
+ * same inputs give the same bits on any device and stream; dx of a sequence does not depend on the
+ * other sequences of the batch.  The workspace's prior contents do not matter. */
+int b2h_backward(b2h_model* m, const float* const* params, const float* x, const float* dy, float* dx,
+                 float* const* grads, int64_t B, int64_t T, void* workspace, size_t workspace_bytes,
+                 void* stream);
+/* dL/dpred of maskedPoseL1 (steps/utils.py:413-428, used at traintest.py:111-121):
+ *   dpred[i, t < n_i] = (g / B) * sign(pred - target) / (n_i * 42),  0 at t >= n_i,
+ * g = *dloss (device fp32 scalar: no host read); n_frames as b2h_masked_l1 (NULL = T, clamped to
+ * [0, T] as slicing does); sign(0) = 0 as torch.nn.L1Loss has it.  A sequence with n_i = 0
+ * contributes no gradient (its forward loss is NaN). */
+int b2h_masked_l1_backward(const float* pred, const float* target, const int64_t* n_frames, int64_t B,
+                           int64_t T, const float* dloss, float* dpred, void* stream);
+/* dL/dpred of poderatedPoseL1 (steps/utils.py:431-452): with s = scores[i, t, joint],
+ *   dpred[i, t < n_i] = g * sign(pred * s - target * s) / (n_i * 42) * s   (no / B: the class sums). */
+int b2h_weighted_l1_backward(const float* pred, const float* target, const float* scores,
+                             const int64_t* n_frames, int64_t B, int64_t T, const float* dloss,
+                             float* dpred, void* stream);
+
 /* TransformerEnc -------------------------------------------
  * The reference's second text-free body->hand model, `TransformerEnc(ninp, nhead, nhid, nout,
  * nlayers, dropout)` (HandPoseModels.py:118-178), as its CLIs build it: ninp = 24, nhead = 4,
