@@ -116,6 +116,67 @@ struct DevBuf {
     }
 };
 
+bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
+    const char* x = reinterpret_cast<const char*>(a);
+    const char* y = reinterpret_cast<const char*>(b);
+    return x < y + bn && y < x + an;
+}
+
+bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) & (a - 1); }
+
+// The current HIP device, which a new model is bound to: it must be a gfx950.
+int probe_device(int& device, int& num_cus) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        return fail(B2H_ERR_NO_DEVICE, "no HIP device visible (libb2h has no CPU path)");
+    HIP_TRY(hipGetDevice(&device));
+    hipDeviceProp_t p;
+    HIP_TRY(hipGetDeviceProperties(&p, device));
+    if (std::strncmp(p.gcnArchName, "gfx950", 6) != 0)
+        return fail(B2H_ERR_NO_DEVICE, std::string("device is ") + p.gcnArchName + ", libb2h is built for gfx950 only");
+    num_cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+    return B2H_OK;
+}
+
+// Flags and factor of the *_forward_fused entry points.
+int check_fused(int flags, float factor) {
+    if (flags & ~(kPreChest | kPreNorm | kPostDenorm | kPostMask)) return fail(B2H_ERR_INVALID, "unknown flag bits");
+    if ((flags & (kPreNorm | kPostDenorm)) && !(factor > 0.f)) return fail(B2H_ERR_INVALID, "factor must be > 0");
+    return B2H_OK;
+}
+
+// Every kernel that may use more than 64 KB of dynamic LDS gets its cap raised ONCE per device, when
+// weights are loaded -- not inside launch(), so that the very first b2h_forward is already free of
+// runtime calls other than the launch itself and can be captured into a HIP graph.
+template <typename K> int raise_lds_cap(K kern, int bytes = 160 * 1024) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return B2H_OK;
+}
+
+// Runs a setter of kernel attributes (which are per device) once for each device.
+struct OncePerDevice {
+    std::mutex mu;
+    bool done[64] = {};
+    template <typename F> int operator()(F set) {
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lock(mu);
+        if (dev >= 0 && dev < 64 && done[dev]) return B2H_OK;
+        if (int rc = set()) return rc;
+        if (dev >= 0 && dev < 64) done[dev] = true;
+        return B2H_OK;
+    }
+};
+
+// Element kinds of the matrix-core weight fragments; also the index of b2h_model::pk.
+enum Elem { EL_BF16, EL_F16, EL_F16X3, EL_F32, kElems };
+
+// The packed weights of one wave-per-chunk kernel variant: per-layer fragments (the bias is b2h_model::bias).
+struct Packed {
+    DevBuf w[4];
+    MfmaParams mp{};
+};
+
 } // namespace
 
 constexpr int kPoolSlots = 64;        // streams per model that get a chunk pool (Sched16); further streams run without
@@ -130,21 +191,18 @@ struct b2h_model {
     int cin[4], cout[4];
     // packed device weights
     DevBuf valu_w[4], valu_b[4];
-    DevBuf mf32_w[4], m_bias[4];  // exact-fp32 MFMA kernel: per-layer fragments + bias fragments
-    DevBuf m3_w[4];               // f16x3 kernel: per-layer hi / lo f16 fragments (bias shared)
-    DevBuf mbf16_all, mf16_all;   // persistent 16-bit kernel: [W L0..L3 | bias L0..L3], kPacked16 bytes
-    DevBuf mwbf_w[4], mwh_w[4], mw_bias[4]; // wide 16-bit kernel (33..64 channels): bf16 / f16 fragments, bias
-    DevBuf mw3_w[4], mw32_w[4];             // wide f16x3 kernel: hi / lo f16 fragments; wide exact-fp32 kernel: fp32 fragments
+    Packed pk[kElems]; // wave-per-chunk matrix-core kernels by element kind (<= 32 channels: F16X3 and F32 only)
+    DevBuf bias[4];    // their bias fragments, one per layer: the out-slot order is the same for every element kind
+    DevBuf img16[2];   // persistent 16-bit kernel, bf16 / f16: [W L0..L3 | bias L0..L3], kPacked16 bytes
     int num_cus = 256;
     // Chunk pools of the persistent 16-bit kernel (kernel_mfma16.h, Sched16): one 128-byte slot per stream
     // that has launched on this model, two words each (claim counter, finished workgroups), zero between
     // launches.  Launches on one stream are ordered, so a slot is never shared by two running kernels -- as long
-    // as one handle value names one ordered queue: hipStreamPerThread does not and never gets a slot (launch()).
+    // as one handle value names one ordered queue: hipStreamPerThread does not and never gets a slot (pool_slot()).
     DevBuf pools;
     std::mutex pool_mu;
     std::vector<hipStream_t> pool_streams;
     ValuParams vp;
-    MfmaParams mp32, mp3, mpw_bf, mpw_h, mpw3, mpw32;
     float w_absmax = 0.f;         // largest |weight| or |bias| (NaN counts as inf): F16X3 needs < 65504
 };
 
@@ -178,72 +236,57 @@ float absmax_of(const std::vector<float>& v, float acc) {
     return acc;
 }
 
-// Wide 16-bit kernel (kernel_mfma16w.h): per layer [mt][tap][ks][lane][8], in-position 32ks + 8q + j
-// (layer 1: the 24|25 inputs, pos_emb moved to slot 24; hidden layers: position = channel), out slot
-// (mt, row) = channel 16(row>>2) + 4mt + (row&3) (head: 16mt + row); bias [mt][q][4] fp32.
-int pack_wide(b2h_model* m, const HostWeights& hw) {
-    for (int l = 0; l < 4; ++l) {
-        const int MT = wide_mt(l), KS = wide_ks(l);
-        auto chan = [&](int mt, int row) { return l == 3 ? last_chan_of(mt, row) : wide_chan_of(mt, row); };
-        std::vector<uint16_t> wb((size_t)MT * kTaps * KS * 64 * 8), wh(wb.size());
-        for (int mt = 0; mt < MT; ++mt)
-            for (int k = 0; k < kTaps; ++k)
-                for (int ks = 0; ks < KS; ++ks)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const float v = hw.at(l, chan(mt, lane & 15), 32 * ks + 8 * (lane >> 4) + j, k, true);
-                            const size_t idx = ((((size_t)mt * kTaps + k) * KS + ks) * 64 + lane) * 8 + j;
-                            wb[idx] = f32_to_bf16(v);
-                            wh[idx] = f32_to_f16(v);
-                        }
-        // f16x3: [mt][tap][ks][hi|lo][lane][8], w = hi + lo with hi = f16(w), lo = f16(w - hi)
-        std::vector<_Float16> w3((size_t)MT * kTaps * KS * 2 * 64 * 8);
-        for (int mt = 0; mt < MT; ++mt)
-            for (int k = 0; k < kTaps; ++k)
-                for (int ks = 0; ks < KS; ++ks)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const float v = hw.at(l, chan(mt, lane & 15), 32 * ks + 8 * (lane >> 4) + j, k, true);
-                            const _Float16 hi = (_Float16)v;
-                            const size_t at = (((((size_t)mt * kTaps + k) * KS + ks) * 2) * 64 + lane) * 8 + j;
-                            w3[at] = hi;
-                            w3[at + 64 * 8] = (_Float16)(v - (float)hi);
-                        }
-        // exact fp32: [mt][tap][g][lane][4], in-position 16g + 4(lane>>4) + j, groups as Geo32<true>
-        const int NG = Geo32<true>::groups(l);
-        std::vector<float> wf((size_t)MT * kTaps * NG * 64 * 4);
-        for (int mt = 0; mt < MT; ++mt)
-            for (int k = 0; k < kTaps; ++k)
-                for (int g = 0; g < NG; ++g)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j)
-                            wf[((((size_t)mt * kTaps + k) * NG + g) * 64 + lane) * 4 + j] =
-                                hw.at(l, chan(mt, lane & 15), 16 * g + 4 * (lane >> 4) + j, k, true);
-        std::vector<float> bf((size_t)MT * 16);
-        for (int mt = 0; mt < MT; ++mt)
-            for (int q = 0; q < 4; ++q)
-                for (int r = 0; r < 4; ++r) bf[(mt * 4 + q) * 4 + r] = hw.bias(l, chan(mt, 4 * q + r));
-        int rc;
-        if ((rc = m->mw32_w[l].upload(wf.data(), wf.size() * 4))) return rc;
-        m->mpw32.w[l] = m->mw32_w[l].p;
-        if ((rc = m->mw3_w[l].upload(w3.data(), w3.size() * 2))) return rc;
-        m->mpw3.w[l] = m->mw3_w[l].p;
-        if ((rc = m->mwbf_w[l].upload(wb.data(), wb.size() * 2))) return rc;
-        if ((rc = m->mwh_w[l].upload(wh.data(), wh.size() * 2))) return rc;
-        if ((rc = m->mw_bias[l].upload(bf.data(), bf.size() * 4))) return rc;
-        m->mpw_bf.w[l] = m->mwbf_w[l].p;
-        m->mpw_h.w[l] = m->mwh_w[l].p;
-        m->mpw_bf.bias[l] = m->mpw_h.bias[l] = m->mpw3.bias[l] = m->mpw32.bias[l] = (const float*)m->mw_bias[l].p;
-    }
-    m->mpw_bf.pos_emb = m->mpw_h.pos_emb = m->mpw3.pos_emb = m->mpw32.pos_emb = m->pos_emb;
-    return B2H_OK;
+// Fragment geometry of layer l in the narrow (<= 32 channels) or wide (33..64) matrix-core kernels: M-tiles,
+// k-steps of 4E inputs (16-bit: k-steps of 32, fp32: k-groups of 16) and out slot (mt, row) -> channel.
+struct FragGeo {
+    int mt, ks;
+    int (*chan)(int mt, int row);
+};
+
+FragGeo frag_geo(bool wide, int l, bool f32) {
+    int (*chan)(int, int) = l == 3 ? last_chan_of : wide ? wide_chan_of : hidden_chan_of;
+    if (wide) return {wide_mt(l), f32 ? Geo32<true>::groups(l) : wide_ks(l), chan};
+    return {Geo32<false>::mt(l), f32 ? Geo32<false>::groups(l) : 1, chan};
 }
 
-// single-parameter aliases of the wide kernel for the launch macro
-template <bool FUSED> constexpr auto b2h_fwd_mfma16w_bf16 = b2h_fwd_mfma16w<PREC_BF16, FUSED>;
-template <bool FUSED> constexpr auto b2h_fwd_mfma16w_f16 = b2h_fwd_mfma16w<PREC_F16, FUSED>;
-template <bool FUSED> constexpr auto b2h_fwd_mfma_f32_narrow = b2h_fwd_mfma_f32<FUSED, false>;
-template <bool FUSED> constexpr auto b2h_fwd_mfma_f32_wide = b2h_fwd_mfma_f32<FUSED, true>;
+// Matrix-core weight fragments of layer l: [mt][tap][ks][lane][E] with E = 8 16-bit or 4 fp32 elements;
+// element j of a lane is the weight of out-channel chan(mt, lane & 15) at in-position 4E ks + E (lane>>4) + j
+// (layer 1: the 24|25 inputs, pos_emb moved to slot 24; hidden layers: position = channel).  F16X3 holds a
+// hi|lo pair per ks block, [ks][hi|lo][lane][8], w = hi + lo with hi = f16(w), lo = f16(w - hi).
+std::vector<char> pack_frags(const HostWeights& hw, int l, const FragGeo& g, Elem el) {
+    const int E = el == EL_F32 ? 4 : 8, parts = el == EL_F16X3 ? 2 : 1;
+    std::vector<char> out((size_t)g.mt * kTaps * g.ks * parts * 64 * E * (el == EL_F32 ? 4 : 2));
+    uint16_t* h = reinterpret_cast<uint16_t*>(out.data());
+    _Float16* h3 = reinterpret_cast<_Float16*>(out.data());
+    float* f = reinterpret_cast<float*>(out.data());
+    for (int mt = 0; mt < g.mt; ++mt)
+        for (int k = 0; k < kTaps; ++k)
+            for (int ks = 0; ks < g.ks; ++ks)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < E; ++j) {
+                        const float v = hw.at(l, g.chan(mt, lane & 15), 4 * E * ks + E * (lane >> 4) + j, k, true);
+                        const size_t at = ((((size_t)mt * kTaps + k) * g.ks + ks) * parts * 64 + lane) * E + j;
+                        switch (el) {
+                            case EL_BF16: h[at] = f32_to_bf16(v); break;
+                            case EL_F16: h[at] = f32_to_f16(v); break;
+                            case EL_F16X3:
+                                h3[at] = (_Float16)v;
+                                h3[at + 64 * 8] = (_Float16)(v - (float)h3[at]);
+                                break;
+                            default: f[at] = v;
+                        }
+                    }
+    return out;
+}
+
+// bias of layer l in the fragments' out-slot order: [mt][q][4] fp32
+std::vector<float> pack_bias(const HostWeights& hw, int l, const FragGeo& g) {
+    std::vector<float> b((size_t)g.mt * 16);
+    for (int mt = 0; mt < g.mt; ++mt)
+        for (int q = 0; q < 4; ++q)
+            for (int r = 0; r < 4; ++r) b[(mt * 4 + q) * 4 + r] = hw.bias(l, g.chan(mt, 4 * q + r));
+    return b;
+}
 
 int pack_all(b2h_model* m, const HostWeights& hw) {
     m->w_absmax = 0.f;
@@ -273,68 +316,37 @@ int pack_all(b2h_model* m, const HostWeights& hw) {
         m->vp.wbuf_floats = wb;
         m->vp.pos_emb = m->pos_emb;
     }
-    if (m->C > kMfmaWideWidth) return B2H_OK;       // 65..128 channels: the VALU kernel only
-    if (m->C > kMfmaWidth) return pack_wide(m, hw); // 33..64 channels: the wide matrix-core kernels
+    if (m->C > kMfmaWideWidth) return B2H_OK; // 65..128 channels: the VALU kernel only
 
-    // ---- MFMA layouts
-    std::vector<unsigned char> ab(kPacked16, 0), ah(kPacked16, 0); // LDS images of the persistent kernel
-    for (int l = 0; l < 4; ++l) {
-        const int MT = (l == 3) ? 3 : 2;
-        auto chan = [&](int mt, int row) { return l == 3 ? last_chan_of(mt, row) : hidden_chan_of(mt, row); };
-        // 16-bit: [mt][tap][lane][8]
-        uint16_t* wb = reinterpret_cast<uint16_t*>(ab.data() + kWLayerOff16[l]);
-        uint16_t* wh = reinterpret_cast<uint16_t*>(ah.data() + kWLayerOff16[l]);
-        for (int mt = 0; mt < MT; ++mt)
-            for (int k = 0; k < kTaps; ++k)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const float v = hw.at(l, chan(mt, lane & 15), 8 * (lane >> 4) + j, k, true);
-                        const size_t idx = (((size_t)mt * kTaps + k) * 64 + lane) * 8 + j;
-                        wb[idx] = f32_to_bf16(v);
-                        wh[idx] = f32_to_f16(v);
-                    }
-        // fp32: [mt][tap][g][lane][4]
-        std::vector<float> wf((size_t)MT * kTaps * 2 * 64 * 4);
-        for (int mt = 0; mt < MT; ++mt)
-            for (int k = 0; k < kTaps; ++k)
-                for (int g = 0; g < 2; ++g)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j)
-                            wf[((((size_t)mt * kTaps + k) * 2 + g) * 64 + lane) * 4 + j] =
-                                hw.at(l, chan(mt, lane & 15), 16 * g + 4 * (lane >> 4) + j, k, true);
-        // bias: [mt][q][4]
-        std::vector<float> bf((size_t)MT * 16);
-        for (int mt = 0; mt < MT; ++mt)
-            for (int q = 0; q < 4; ++q)
-                for (int r = 0; r < 4; ++r) bf[(mt * 4 + q) * 4 + r] = hw.bias(l, chan(mt, 4 * q + r));
-        std::memcpy(ab.data() + kBiasOff16[l], bf.data(), bf.size() * 4);
-        std::memcpy(ah.data() + kBiasOff16[l], bf.data(), bf.size() * 4);
-        // f16x3: [mt][tap][hi|lo][lane][8] halves, w = hi + lo with hi = f16(w), lo = f16(w - hi)
-        std::vector<_Float16> w3((size_t)MT * kTaps * 2 * 64 * 8);
-        for (int mt = 0; mt < MT; ++mt)
-            for (int k = 0; k < kTaps; ++k)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const float v = hw.at(l, chan(mt, lane & 15), 8 * (lane >> 4) + j, k, true);
-                        const _Float16 hi = (_Float16)v;
-                        const size_t at = ((((size_t)mt * kTaps + k) * 2) * 64 + lane) * 8 + j;
-                        w3[at] = hi;
-                        w3[at + 64 * 8] = (_Float16)(v - (float)hi);
-                    }
-        int rc;
-        if ((rc = m->mf32_w[l].upload(wf.data(), wf.size() * 4))) return rc;
-        if ((rc = m->m_bias[l].upload(bf.data(), bf.size() * 4))) return rc;
-        if ((rc = m->m3_w[l].upload(w3.data(), w3.size() * 2))) return rc;
-        m->mp32.w[l] = m->mf32_w[l].p;
-        m->mp32.bias[l] = (const float*)m->m_bias[l].p;
-        m->mp3.w[l] = m->m3_w[l].p;
-        m->mp3.bias[l] = (const float*)m->m_bias[l].p;
-    }
-    m->mp32.pos_emb = m->pos_emb;
-    m->mp3.pos_emb = m->pos_emb;
+    // ---- MFMA layouts: the wave-per-chunk kernels (<= 32 channels: bf16 / f16 run in the persistent kernel)
+    const bool wide = m->C > kMfmaWidth;
     int rc;
-    if ((rc = m->mbf16_all.upload(ab.data(), ab.size()))) return rc;
-    if ((rc = m->mf16_all.upload(ah.data(), ah.size()))) return rc;
+    for (int l = 0; l < 4; ++l) {
+        const std::vector<float> b = pack_bias(hw, l, frag_geo(wide, l, false));
+        if ((rc = m->bias[l].upload(b.data(), b.size() * 4))) return rc;
+    }
+    for (int el = wide ? EL_BF16 : EL_F16X3; el < kElems; ++el) {
+        Packed& P = m->pk[el];
+        for (int l = 0; l < 4; ++l) {
+            const std::vector<char> w = pack_frags(hw, l, frag_geo(wide, l, el == EL_F32), (Elem)el);
+            if ((rc = P.w[l].upload(w.data(), w.size()))) return rc;
+            P.mp.w[l] = P.w[l].p;
+            P.mp.bias[l] = (const float*)m->bias[l].p;
+        }
+        P.mp.pos_emb = m->pos_emb;
+    }
+    if (wide) return B2H_OK;
+    for (int el : {EL_BF16, EL_F16}) { // the persistent kernel's LDS image
+        std::vector<char> img(kPacked16, 0);
+        for (int l = 0; l < 4; ++l) {
+            const FragGeo g = frag_geo(false, l, false);
+            const std::vector<char> w = pack_frags(hw, l, g, (Elem)el);
+            const std::vector<float> b = pack_bias(hw, l, g);
+            std::memcpy(img.data() + kWLayerOff16[l], w.data(), w.size());
+            std::memcpy(img.data() + kBiasOff16[l], b.data(), b.size() * 4);
+        }
+        if ((rc = m->img16[el].upload(img.data(), img.size()))) return rc;
+    }
     if (!m->pools.p) { // once per model: a later weight replacement must not touch the words of a running launch
         const std::vector<char> zeros((size_t)kPoolSlots * kPoolSlotBytes, 0);
         if ((rc = m->pools.upload(zeros.data(), zeros.size()))) return rc;
@@ -365,36 +377,107 @@ bool kernel_ok(const b2h_model* m, int k) {
     }
 }
 
-// Every kernel that may use more than 64 KB of dynamic LDS gets its cap raised ONCE per device, when
-// weights are loaded -- not inside launch(), so that the very first b2h_forward is already free of
-// runtime calls other than the launch itself and can be captured into a HIP graph.
-template <typename K> int raise_lds_cap(K kern) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+// ---- ConvModel dispatch
+// VALU kernel by width: <= 56, 57..104, 105..128 channels (kernel_valu.h: unrolled in-channel loop, three work
+// items per thread)
+using ValuKernel = void (*)(const float*, float*, int, int, ValuParams, FusedArgs);
+constexpr ValuKernel kValuTiers[] = {b2h_fwd_f32_valu<false>, b2h_fwd_f32_valu<true>, b2h_fwd_f32_valu<true, 3>};
+
+// The wave-per-chunk matrix-core kernels, one row per kernel variant and geometry.
+using ChunkKernel = void (*)(const float*, float*, int, int, int, int64_t, MfmaParams, FusedArgs);
+struct ChunkVariant {
+    int kernel;               // B2H_KERNEL_*
+    bool wide;                // 33..64 channels
+    ChunkKernel plain, fused; // the plain instantiation carries no transform code at all
+    int lds;                  // bytes per workgroup
+    Elem packed;              // b2h_model::pk entry it reads
+    int wgs_per_cu;           // workgroups per CU (__launch_bounds__), for the chunk-length rule
+    const char* name;         // b2h_kernel_name
+};
+constexpr ChunkVariant kChunkVariants[] = {
+    {B2H_KERNEL_F32_MFMA, false, b2h_fwd_mfma_f32<false, false>, b2h_fwd_mfma_f32<true, false>,
+     kWavesPerBlock * Geo32<false>::kImg, EL_F32, 2, "b2h_fwd_mfma_f32<false, false>"},
+    {B2H_KERNEL_F32_MFMA, true, b2h_fwd_mfma_f32<false, true>, b2h_fwd_mfma_f32<true, true>,
+     kWavesPerBlock * Geo32<true>::kImg, EL_F32, 1, "b2h_fwd_mfma_f32<false, true>"},
+    {B2H_KERNEL_F16X3_MFMA, false, b2h_fwd_mfma_f16x3<false>, b2h_fwd_mfma_f16x3<true>,
+     kWavesPerBlock * 2 * kImg3, EL_F16X3, 2, "b2h_fwd_mfma_f16x3<false>"}, // hi + lo images = the fp32 image's bytes
+    {B2H_KERNEL_F16X3_MFMA, true, b2h_fwd_mfma_f16x3w<false>, b2h_fwd_mfma_f16x3w<true>,
+     kWavesPerBlock * 2 * kImg3W, EL_F16X3, 1, "b2h_fwd_mfma_f16x3w<false>"},
+    {B2H_KERNEL_BF16_MFMA, true, b2h_fwd_mfma16w<PREC_BF16, false>, b2h_fwd_mfma16w<PREC_BF16, true>,
+     kWavesPerBlock * kImgW, EL_BF16, 2, "b2h_fwd_mfma16w<1, false>"},
+    {B2H_KERNEL_F16_MFMA, true, b2h_fwd_mfma16w<PREC_F16, false>, b2h_fwd_mfma16w<PREC_F16, true>,
+     kWavesPerBlock * kImgW, EL_F16, 2, "b2h_fwd_mfma16w<2, false>"},
+};
+
+// nullptr: the VALU kernel, or the persistent 16-bit kernel (bf16 / f16 at <= 32 channels)
+const ChunkVariant* chunk_variant(int k, bool wide) {
+    for (const ChunkVariant& v : kChunkVariants)
+        if (v.kernel == k && v.wide == wide) return &v;
+    return nullptr;
+}
+
+// The persistent 16-bit kernel (kernel_mfma16.h): [STREAM][f16][FUSED]
+using Kernel16 = void (*)(const float*, float*, int, int, int, int64_t, const void*, int, FusedArgs, Sched16);
+constexpr Kernel16 kFwd16[2][2][2] = {
+    {{b2h_fwd_mfma16<PREC_BF16, false, false>, b2h_fwd_mfma16<PREC_BF16, true, false>},
+     {b2h_fwd_mfma16<PREC_F16, false, false>, b2h_fwd_mfma16<PREC_F16, true, false>}},
+    {{b2h_fwd_mfma16<PREC_BF16, false, true>, b2h_fwd_mfma16<PREC_BF16, true, true>},
+     {b2h_fwd_mfma16<PREC_F16, false, true>, b2h_fwd_mfma16<PREC_F16, true, true>}},
+};
+
+int set_conv_kernel_attributes() {
+    static OncePerDevice once;
+    return once([] {
+        int rc = B2H_OK;
+        for (ValuKernel k : kValuTiers)
+            if ((rc = raise_lds_cap(k))) return rc;
+        for (const ChunkVariant& v : kChunkVariants)
+            if ((rc = raise_lds_cap(v.plain)) || (rc = raise_lds_cap(v.fused))) return rc;
+        for (const auto& by_prec : kFwd16)
+            for (const auto& by_fused : by_prec)
+                for (Kernel16 k : by_fused)
+                    if ((rc = raise_lds_cap(k))) return rc;
+        return rc;
+    });
+}
+
+// Work distribution of the persistent kernel (Sched16): with >= 256 chunks per workgroup the launch is DYNAMIC
+// -- waves claim runs of two consecutive chunks from a device-wide counter, so the chip walks through x and y as
+// one front (kernel_mfma16.h).  The counter lives in this stream's slot; no slot (more than kPoolSlots streams),
+// a stream under capture (a graph may be replayed on any stream, concurrently with this one) or
+// hipStreamPerThread (one handle value for a different stream in every host thread, whose launches would share
+// one counter and skip chunks) means a STATIC launch: nullptr.
+unsigned* pool_slot(b2h_model* m, hipStream_t st) {
+    if (!m->pools.p || st == hipStreamPerThread) return nullptr;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+    if (cap != hipStreamCaptureStatusNone) return nullptr;
+    std::lock_guard<std::mutex> lock(m->pool_mu);
+    size_t slot = 0;
+    while (slot < m->pool_streams.size() && m->pool_streams[slot] != st) ++slot;
+    if (slot == m->pool_streams.size() && slot < (size_t)kPoolSlots) m->pool_streams.push_back(st);
+    if (slot >= (size_t)kPoolSlots) return nullptr;
+    return reinterpret_cast<unsigned*>(static_cast<char*>(m->pools.p) + slot * kPoolSlotBytes);
+}
+
+// ConvModel shape rules, shared by b2h_forward and the training entry points
+int check_shape(const b2h_model* m, int64_t B, int64_t T) {
+    if (B < 0 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0 and T >= 1");
+    if (T > (1 << 24)) return fail(B2H_ERR_SHAPE, "T too large");
+    if (m->pos_emb && T != 100)
+        return fail(B2H_ERR_SHAPE, "pos_emb model requires T == 100 (LinearPositionalEmbedding max_len, "
+                                   "HandPoseModels.py:23,78-84)");
     return B2H_OK;
 }
 
-int set_conv_kernel_attributes() {
-    static std::mutex mu;
-    static bool done[64] = {};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev >= 0 && dev < 64 && done[dev]) return B2H_OK;
-    int rc;
-    if ((rc = raise_lds_cap(b2h_fwd_f32_valu<true>)) || (rc = raise_lds_cap(b2h_fwd_f32_valu<false>)) ||
-        (rc = raise_lds_cap(b2h_fwd_f32_valu<true, 3>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma_f32<false, false>)) || (rc = raise_lds_cap(b2h_fwd_mfma_f32<true, false>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma_f32<false, true>)) || (rc = raise_lds_cap(b2h_fwd_mfma_f32<true, true>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma_f16x3<false>)) || (rc = raise_lds_cap(b2h_fwd_mfma_f16x3<true>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma_f16x3w<false>)) || (rc = raise_lds_cap(b2h_fwd_mfma_f16x3w<true>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma16<PREC_BF16, false, false>)) || (rc = raise_lds_cap(b2h_fwd_mfma16<PREC_BF16, true, false>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma16<PREC_F16, false, false>)) || (rc = raise_lds_cap(b2h_fwd_mfma16<PREC_F16, true, false>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma16<PREC_BF16, false, true>)) || (rc = raise_lds_cap(b2h_fwd_mfma16<PREC_BF16, true, true>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma16<PREC_F16, false, true>)) || (rc = raise_lds_cap(b2h_fwd_mfma16<PREC_F16, true, true>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma16w<PREC_BF16, false>)) || (rc = raise_lds_cap(b2h_fwd_mfma16w<PREC_BF16, true>)) ||
-        (rc = raise_lds_cap(b2h_fwd_mfma16w<PREC_F16, false>)) || (rc = raise_lds_cap(b2h_fwd_mfma16w<PREC_F16, true>)))
-        return rc;
-    if (dev >= 0 && dev < 64) done[dev] = true;
+// x (B, T, 24) and y (B, T, 42) of a ConvModel launch with B >= 1: 16-B vector loads of x rows (96 B each)
+// and 8-B granular stores of y rows (168 B each)
+int check_xy(const b2h_model* m, const float* x, const float* y, int64_t B, int64_t T) {
+    if (!x || !y) return fail(B2H_ERR_INVALID, "x / y is NULL");
+    if (int rc = check_device(m->device)) return rc;
+    if (misaligned(x, 16) || misaligned(y, 16))
+        return fail(B2H_ERR_INVALID, "x and y must be 16-byte aligned (hipMalloc / torch allocations are)");
+    if (overlaps(x, (size_t)B * T * kInCh * 4, y, (size_t)B * T * kOutCh * 4)) return fail(B2H_ERR_INVALID, "x and y overlap");
     return B2H_OK;
 }
 
@@ -402,23 +485,9 @@ int launch(b2h_model* m, const float* x, float* y, int64_t B, int64_t T, int ker
            const FusedArgs& fa, hipStream_t st) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
     if (!m->has_weights) return fail(B2H_ERR_NO_WEIGHTS, "b2h_forward before b2h_load_weights");
-    if (B < 0 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0 and T >= 1");
-    if (T > (1 << 24)) return fail(B2H_ERR_SHAPE, "T too large");
-    if (m->pos_emb && T != 100)
-        return fail(B2H_ERR_SHAPE, "pos_emb model requires T == 100 (LinearPositionalEmbedding max_len, "
-                                   "HandPoseModels.py:23,78-84)");
+    if (int rc = check_shape(m, B, T)) return rc;
     if (B == 0) return B2H_OK;
-    if (!x || !y) return fail(B2H_ERR_INVALID, "x / y is NULL");
-    if (int rc = check_device(m->device)) return rc;
-    // 16-B vector loads of x rows (96 B each) and 8-B granular stores of y rows (168 B each)
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15))
-        return fail(B2H_ERR_INVALID, "x and y must be 16-byte aligned (hipMalloc / torch allocations are)");
-    {
-        const char* xb = reinterpret_cast<const char*>(x);
-        const char* yb = reinterpret_cast<const char*>(y);
-        const size_t xn = (size_t)B * T * kInCh * 4, yn = (size_t)B * T * kOutCh * 4;
-        if (xb < yb + yn && yb < xb + xn) return fail(B2H_ERR_INVALID, "x and y overlap");
-    }
+    if (int rc = check_xy(m, x, y, B, T)) return rc;
     if ((fa.flags & kPostMask) && !fa.n_frames)
         return fail(B2H_ERR_INVALID, "B2H_POST_MASK_TAIL needs n_frames");
     const int k = resolve_kernel(m, kernel);
@@ -429,33 +498,26 @@ int launch(b2h_model* m, const float* x, float* y, int64_t B, int64_t T, int ker
         return fail(B2H_ERR_UNSUPPORTED, "kernel variant does not support conv_channels=" + std::to_string(m->C) +
                                              " (matrix-core kernels: <= 64; exact fp32 VALU kernel: <= 128)");
     }
+    const bool fused = fa.flags != 0;
+    const ChunkVariant* v = chunk_variant(k, m->C > kMfmaWidth);
 
     if (k == B2H_KERNEL_F32_VALU) {
         const int tiles = (int)((T + kValuTile - 1) / kValuTile);
         const int64_t grid = B * tiles;
         if (grid > 0x7fffffff) return fail(B2H_ERR_SHAPE, "B*T too large for one launch");
         const size_t lds = ((size_t)2 * kValuRows * m->vp.act_stride + m->vp.wbuf_floats) * 4;
-        if (m->C > 104) { // three work items per thread (kernel_valu.h)
-            hipLaunchKernelGGL((b2h_fwd_f32_valu<true, 3>), dim3((unsigned)grid), dim3(256), lds, st, x, y, (int)T, tiles, m->vp, fa);
-        } else if (m->C > 56) {
-            hipLaunchKernelGGL(b2h_fwd_f32_valu<true>, dim3((unsigned)grid), dim3(256), lds, st, x, y, (int)T, tiles, m->vp, fa);
-        } else {
-            hipLaunchKernelGGL(b2h_fwd_f32_valu<false>, dim3((unsigned)grid), dim3(256), lds, st, x, y, (int)T, tiles, m->vp, fa);
-        }
-    } else {
+        hipLaunchKernelGGL(kValuTiers[m->C > 104 ? 2 : m->C > 56 ? 1 : 0], dim3((unsigned)grid), dim3(256), lds, st, x,
+                           y, (int)T, tiles, m->vp, fa);
+    } else if (v) {
         // chunk length of the wave-per-chunk kernels: 112 frames (the LDS image's capacity) unless
-        // that leaves most of the chip's wave slots idle (2 workgroups x 4 waves per CU); then 64 or
+        // that leaves most of the chip's wave slots idle (1 or 2 workgroups x 4 waves per CU); then 64 or
         // 32 frames, paying the +-8-frame halo recompute for parallelism.  Any chunking computes
         // bit-identical frames.
-        const bool wide = m->C > kMfmaWidth; // 33..64 channels: wave-per-chunk 16-bit kernel (kernel_mfma16w.h)
         int chunk_len = kChunk;
-        const bool wide3 = wide && (k == B2H_KERNEL_F16X3_MFMA || k == B2H_KERNEL_F32_MFMA); // one 4-wave workgroup per CU
-        if (wide || (k != B2H_KERNEL_BF16_MFMA && k != B2H_KERNEL_F16_MFMA)) {
-            const int64_t slots = (int64_t)m->num_cus * (wide3 ? 1 : 2) * kWavesPerBlock;
-            for (int cand : {64, 32}) {
-                if (B * ((T + chunk_len - 1) / chunk_len) * 2 >= slots) break;
-                chunk_len = cand;
-            }
+        const int64_t slots = (int64_t)m->num_cus * v->wgs_per_cu * kWavesPerBlock;
+        for (int cand : {64, 32}) {
+            if (B * ((T + chunk_len - 1) / chunk_len) * 2 >= slots) break;
+            chunk_len = cand;
         }
         const int cps = (int)((T + chunk_len - 1) / chunk_len);
         // (equal chunks -- T = 200 as 100 + 100 instead of 112 + 88 -- measured 3.9 % SLOWER in f16x3 and 1.6 %
@@ -463,83 +525,32 @@ int launch(b2h_model* m, const float* x, float* y, int64_t B, int64_t T, int ker
         const int64_t nchunks = B * cps;
         const int64_t grid = (nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
         if (grid > 0x7fffffff) return fail(B2H_ERR_SHAPE, "B*T too large for one launch");
-        const dim3 g((unsigned)grid), blk(64 * kWavesPerBlock);
-        const bool fusedc = fa.flags != 0; // the plain instantiations carry no transform code at all
-#define B2H_LAUNCHC(KERN, LDS, MP)                                                                          \
-    do {                                                                                                    \
-        if (fusedc) hipLaunchKernelGGL((KERN<true>), g, blk, LDS, st, x, y, (int)T, cps, chunk_len, nchunks, MP, fa);  \
-        else hipLaunchKernelGGL((KERN<false>), g, blk, LDS, st, x, y, (int)T, cps, chunk_len, nchunks, MP, fa);        \
-    } while (0)
-        if (wide3 && k == B2H_KERNEL_F16X3_MFMA) {
-            const size_t lds = (size_t)kWavesPerBlock * 2 * kImg3W;
-            B2H_LAUNCHC(b2h_fwd_mfma_f16x3w, lds, m->mpw3);
-        } else if (wide3) {
-            const size_t lds = (size_t)kWavesPerBlock * Geo32<true>::kImg;
-            B2H_LAUNCHC(b2h_fwd_mfma_f32_wide, lds, m->mpw32);
-        } else if (wide) {
-            const size_t lds = (size_t)kWavesPerBlock * kImgW;
-            if (k == B2H_KERNEL_BF16_MFMA) B2H_LAUNCHC(b2h_fwd_mfma16w_bf16, lds, m->mpw_bf);
-            else B2H_LAUNCHC(b2h_fwd_mfma16w_f16, lds, m->mpw_h);
-        } else if (k == B2H_KERNEL_F32_MFMA) {
-            const size_t lds = (size_t)kWavesPerBlock * Geo32<false>::kImg;
-            B2H_LAUNCHC(b2h_fwd_mfma_f32_narrow, lds, m->mp32);
-        } else if (k == B2H_KERNEL_F16X3_MFMA) {
-            const size_t lds = (size_t)kWavesPerBlock * 2 * kImg3; // hi + lo images = the fp32 image's bytes
-            B2H_LAUNCHC(b2h_fwd_mfma_f16x3, lds, m->mp3);
-        } else {
-            // persistent kernel: one 512-thread workgroup per CU
-            // Chunk length: whole sequences (<= 208 frames) or 192-frame chunks keep the halo
-            // recompute at zero / 8 %.  When that leaves most of the chip's 2048 wave slots idle
-            // (small batches) shorter chunks trade halo work for parallelism; every chunking
-            // computes bit-identical frames.
-            int TT = (T <= kChunkWhole16) ? kChunkWhole16 : kChunkSplit16;
-            int64_t nch = B * ((T + TT - 1) / TT);
-            const int64_t slots = (int64_t)m->num_cus * kWaves16;
-            for (int cand : {96, 48}) {
-                if (nch * 2 >= slots || T <= cand) break;
-                TT = cand;
-                nch = B * ((T + TT - 1) / TT);
-            }
-            const int cps16 = (int)((T + TT - 1) / TT);
-            const unsigned grid16 = (unsigned)std::min<int64_t>(m->num_cus, nch);
-            if (nch >= 0x7fffffff) return fail(B2H_ERR_SHAPE, "B*T too large for one launch");
-            // Work distribution (Sched16): with >= 256 chunks per workgroup the launch is DYNAMIC -- waves claim runs
-            // of two consecutive chunks from a device-wide counter, so the chip walks through x and y as one front
-            // (kernel_mfma16.h).  The counter lives in this stream's slot; no slot (more than kPoolSlots streams),
-            // a stream under capture (a graph may be replayed on any stream, concurrently with this one) or
-            // hipStreamPerThread (one handle value for a different stream in every host thread, whose launches
-            // would share one counter and skip chunks) means a STATIC launch.
-            Sched16 sched{nullptr, 2};
-            const int64_t per_wg = nch / grid16;
-            if (per_wg >= kPoolMinChunks && m->pools.p && st != hipStreamPerThread) {
-                hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-                if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-                if (cap == hipStreamCaptureStatusNone) {
-                    std::lock_guard<std::mutex> lock(m->pool_mu);
-                    size_t slot = 0;
-                    while (slot < m->pool_streams.size() && m->pool_streams[slot] != st) ++slot;
-                    if (slot == m->pool_streams.size() && slot < (size_t)kPoolSlots) m->pool_streams.push_back(st);
-                    if (slot < (size_t)kPoolSlots)
-                        sched.pool = reinterpret_cast<unsigned*>(static_cast<char*>(m->pools.p) + slot * kPoolSlotBytes);
-                }
-            }
-            const bool fused = fa.flags != 0;
-            const bool bf = (k == B2H_KERNEL_BF16_MFMA);
-            const void* wp = bf ? m->mbf16_all.p : m->mf16_all.p;
-            // streaming cache policy (kernel_mfma.h: kLdStream / kStStream) from 1 MiB of traffic up
-            const bool stream = B * T * (int64_t)((kInCh + kOutCh) * 4) >= (1 << 20);
-#define B2H_LAUNCH16(PR, FU, SM)                                                                          \
-    hipLaunchKernelGGL((b2h_fwd_mfma16<PR, FU, SM>), dim3(grid16), dim3(64 * kWaves16), kLdsAlloc16, st, x, y, \
-                       (int)T, cps16, TT, nch, wp, m->pos_emb, fa, sched)
-#define B2H_LAUNCH16S(PR, FU) do { if (stream) B2H_LAUNCH16(PR, FU, true); else B2H_LAUNCH16(PR, FU, false); } while (0)
-            if (bf && !fused) B2H_LAUNCH16S(PREC_BF16, false);
-            else if (bf) B2H_LAUNCH16S(PREC_BF16, true);
-            else if (!fused) B2H_LAUNCH16S(PREC_F16, false);
-            else B2H_LAUNCH16S(PREC_F16, true);
-#undef B2H_LAUNCH16S
-#undef B2H_LAUNCH16
+        hipLaunchKernelGGL(fused ? v->fused : v->plain, dim3((unsigned)grid), dim3(64 * kWavesPerBlock), v->lds, st, x,
+                           y, (int)T, cps, chunk_len, nchunks, m->pk[v->packed].mp, fa);
+    } else {
+        // persistent kernel: one 512-thread workgroup per CU
+        // Chunk length: whole sequences (<= 208 frames) or 192-frame chunks keep the halo
+        // recompute at zero / 8 %.  When that leaves most of the chip's 2048 wave slots idle
+        // (small batches) shorter chunks trade halo work for parallelism; every chunking
+        // computes bit-identical frames.
+        int TT = (T <= kChunkWhole16) ? kChunkWhole16 : kChunkSplit16;
+        int64_t nch = B * ((T + TT - 1) / TT);
+        const int64_t slots = (int64_t)m->num_cus * kWaves16;
+        for (int cand : {96, 48}) {
+            if (nch * 2 >= slots || T <= cand) break;
+            TT = cand;
+            nch = B * ((T + TT - 1) / TT);
         }
-#undef B2H_LAUNCHC
+        const int cps16 = (int)((T + TT - 1) / TT);
+        const unsigned grid16 = (unsigned)std::min<int64_t>(m->num_cus, nch);
+        if (nch >= 0x7fffffff) return fail(B2H_ERR_SHAPE, "B*T too large for one launch");
+        Sched16 sched{nullptr, 2};
+        if (nch / grid16 >= kPoolMinChunks) sched.pool = pool_slot(m, st);
+        const bool f16 = k == B2H_KERNEL_F16_MFMA;
+        // streaming cache policy (kernel_mfma.h: kLdStream / kStStream) from 1 MiB of traffic up
+        const bool stream = B * T * (int64_t)((kInCh + kOutCh) * 4) >= (1 << 20);
+        hipLaunchKernelGGL(kFwd16[stream][f16][fused], dim3(grid16), dim3(64 * kWaves16), kLdsAlloc16, st, x, y, (int)T,
+                           cps16, TT, nch, m->img16[f16].p, m->pos_emb, fa, sched);
     }
     HIP_TRY(hipGetLastError());
     return B2H_OK;
@@ -628,10 +639,114 @@ int launch_chain(b2h_tenc* m, ChainArgs& a, hipStream_t st) {
     constexpr size_t lds = (size_t)2 * kStageBlobMax * sizeof(float);
     // persistent: one workgroup per CU (134 KB of LDS each) walks over the 128-frame blocks
     const int64_t blocks = std::min<int64_t>((a.n + 16 * kLinWaves - 1) / (16 * kLinWaves), m->num_cus);
-    if (m->kernel == B2H_TENC_F16X3)
-        hipLaunchKernelGGL(b2h_tenc_chain<true>, dim3((unsigned)blocks), dim3(64 * kLinWaves), lds, st, a);
-    else
-        hipLaunchKernelGGL(b2h_tenc_chain<false>, dim3((unsigned)blocks), dim3(64 * kLinWaves), lds, st, a);
+    hipLaunchKernelGGL(m->kernel == B2H_TENC_F16X3 ? b2h_tenc_chain<true> : b2h_tenc_chain<false>, dim3((unsigned)blocks),
+                       dim3(64 * kLinWaves), lds, st, a);
+    return B2H_OK;
+}
+
+// Attention kernels by query tiles, [nt - 1] with nt = ceil(T / 16) <= 8.  f16x3: b2h_attn_qkv_h3 projects Q, K, V
+// itself.  fp32: b2h_attn_mfma_f32 reads them from the chain's QKV rows; b2h_attn_mfma_h3, its f16x3 twin, has not
+// been launched since the projection moved into b2h_attn_qkv_h3, and stays built.
+using AttnQkvKernel = void (*)(AttnQkvArgs);
+constexpr AttnQkvKernel kAttnQkvH3[kAttnMaxTiles] = {b2h_attn_qkv_h3<1>, b2h_attn_qkv_h3<2>, b2h_attn_qkv_h3<3>,
+                                                     b2h_attn_qkv_h3<4>, b2h_attn_qkv_h3<5>, b2h_attn_qkv_h3<6>,
+                                                     b2h_attn_qkv_h3<7>, b2h_attn_qkv_h3<8>};
+using AttnKernel = void (*)(const float*, float*, int);
+constexpr struct { AttnKernel h3, f32; } kAttn[kAttnMaxTiles] = {
+    {b2h_attn_mfma_h3<1>, b2h_attn_mfma_f32<1>}, {b2h_attn_mfma_h3<2>, b2h_attn_mfma_f32<2>},
+    {b2h_attn_mfma_h3<3>, b2h_attn_mfma_f32<3>}, {b2h_attn_mfma_h3<4>, b2h_attn_mfma_f32<4>},
+    {b2h_attn_mfma_h3<5>, b2h_attn_mfma_f32<5>}, {b2h_attn_mfma_h3<6>, b2h_attn_mfma_f32<6>},
+    {b2h_attn_mfma_h3<7>, b2h_attn_mfma_f32<7>}, {b2h_attn_mfma_h3<8>, b2h_attn_mfma_f32<8>},
+};
+
+// Residual stream XA, attention output OC and (fp32 path) the Q, K, V rows of the next attention; QKV is
+// nullptr on the f16x3 path, whose attention kernel projects them itself.
+struct TencWs {
+    float *XA, *OC, *QKV;
+};
+
+void add_qkv(const b2h_tenc* m, ChainArgs& a, int l, float* QKV) {
+    a.st[a.nstages++] = stage_of(m, m->layers[l].q, ST_STORE, QKV, 3 * kTencD);
+    a.st[a.nstages++] = stage_of(m, m->layers[l].k, ST_STORE, QKV + kTencD, 3 * kTencD);
+    a.st[a.nstages++] = stage_of(m, m->layers[l].v, ST_STORE, QKV + 2 * kTencD, 3 * kTencD);
+}
+
+// src + pe -> pose2hidden_projection (HandPoseModels.py:167-169) -> residual stream [+ layer 0's Q, K, V]
+int chain_in(b2h_tenc* m, const float* x, int64_t n, int T, const FusedArgs& fa, const TencWs& ws, hipStream_t st) {
+    ChainArgs a{};
+    a.x = x; a.ldx = kInCh; a.kgroups0 = 2; a.kvalid = kInCh; a.pe = (const float*)m->pe.p; a.T = T;
+    a.res = nullptr; a.n = n; a.nstages = 1;
+    a.flags = fa.flags & (kPreChest | kPreNorm); a.factor = fa.factor; a.Tseq = T;
+    a.st[0] = stage_of(m, m->in_proj, ST_SET, ws.XA, kTencD);
+    if (ws.QKV) add_qkv(m, a, 0, ws.QKV);
+    return launch_chain(m, a, st);
+}
+
+// out_proj +res LN1 -> linear1 ReLU -> linear2 +res LN2 -> residual stream [+ next layer's Q, K, V] | hidden2pose (:171)
+int chain_tail(b2h_tenc* m, int l, float* y, int64_t n, int T, const FusedArgs& fa, const TencWs& ws, hipStream_t st) {
+    ChainArgs a{};
+    a.x = ws.OC; a.ldx = kTencD; a.kgroups0 = 8; a.kvalid = kTencD; a.pe = nullptr; a.T = 1;
+    a.res = ws.XA; a.n = n; a.nstages = 3;
+    a.st[0] = stage_of(m, m->layers[l].attn_out, ST_RESLN_GLOBAL, nullptr, kTencD);
+    a.st[1] = stage_of(m, m->layers[l].ff1, ST_RELU, nullptr, kTencD);
+    if (l + 1 < m->nlayers) {
+        a.st[2] = stage_of(m, m->layers[l].ff2, ST_RESLN_REG, ws.XA, kTencD); // the next layer's input and residual
+        if (ws.QKV) add_qkv(m, a, l + 1, ws.QKV);
+    } else {
+        a.st[2] = stage_of(m, m->layers[l].ff2, ST_RESLN_REG, nullptr, kTencD);
+        a.st[3] = stage_of(m, m->out_proj, ST_STORE, y, kOutCh);
+        a.nstages = 4;
+        a.flags = fa.flags & (kPostDenorm | kPostMask); a.factor = fa.factor; a.n_frames = fa.n_frames;
+    }
+    a.Tseq = T;
+    return launch_chain(m, a, st);
+}
+
+int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, const FusedArgs& fa, void* workspace,
+                size_t workspace_bytes, void* stream) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (!m->has_weights) return fail(B2H_ERR_NO_WEIGHTS, "b2h_tenc_forward before b2h_tenc_load_weights");
+    if (B < 0 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0 and T >= 1");
+    if (T > m->max_len)
+        return fail(B2H_ERR_SHAPE, "TransformerEnc: T exceeds the positional encoding's max_len (src + pe[:T], "
+                                   "HandPoseModels.py:101,167)");
+    if (B == 0) return B2H_OK;
+    const int64_t n = B * T;
+    // grid limits: attention launches B x heads workgroups, the chain n / 128
+    if (B * kTencHeads > 0x7fffffff || n / (16 * kLinWaves) >= 0x7fffffff) return fail(B2H_ERR_SHAPE, "batch too large for one launch");
+    if (!x || !y || !workspace) return fail(B2H_ERR_INVALID, "NULL pointer");
+    if (int rc = check_device(m->device)) return rc;
+    if (m->kernel == B2H_TENC_F16X3 && !(m->w_absmax < kF16Max))
+        return fail(B2H_ERR_UNSUPPORTED, "B2H_TENC_F16X3: a parameter is outside the f16 range (|w| >= 65504 or not "
+                                         "finite); use B2H_TENC_F32");
+    if (misaligned(x, 16) || misaligned(workspace, 16)) return fail(B2H_ERR_INVALID, "x and workspace must be 16-byte aligned");
+    if (workspace_bytes < b2h_tenc_workspace_bytes(m, B, T)) return fail(B2H_ERR_INVALID, "workspace too small");
+    const int nt = (int)((T + 15) / 16);
+    if (nt > kAttnMaxTiles) return fail(B2H_ERR_SHAPE, "TransformerEnc: T > 128");
+    hipStream_t st = (hipStream_t)stream;
+    // f16x3, round 3: the Q, K, V projection runs inside the attention kernel (b2h_attn_qkv_h3), so only the residual
+    // stream and the attention output cross HBM between launches (2.5 KB per frame and layer -> 1.25 KB).
+    const bool h3 = m->kernel == B2H_TENC_F16X3;
+    float* XA = reinterpret_cast<float*>(workspace);
+    const TencWs ws{XA, XA + n * kTencD, h3 ? nullptr : XA + 2 * n * kTencD};
+    int rc;
+    if ((rc = chain_in(m, x, n, (int)T, fa, ws, st))) return rc;
+    for (int l = 0; l < m->nlayers; ++l) { // torch.nn.TransformerEncoderLayer, post-norm, ReLU
+        if (h3) {
+            // persistent: one workgroup per CU, bound to a head (blockIdx = 8 (4 slot + head) + xcd: 32 per sequence slot)
+            const unsigned grid = (unsigned)std::max(32, m->num_cus / 32 * 32);
+            const size_t lds = (size_t)kQkvBlobBytes + 2 * ((size_t)2 * nt * 16 * 48 * 2 + (size_t)2 * kTencHd * kAttnVtRow * 2); // K rows of 48 halves
+            AttnQkvArgs qa{};
+            qa.x = ws.XA; qa.out = ws.OC; qa.T = (int)T; qa.B = B;
+            for (int hd = 0; hd < kTencHeads; ++hd) qa.blob[hd] = (const float*)m->layers[l].qkv_head[hd].buf16.p;
+            hipLaunchKernelGGL(kAttnQkvH3[nt - 1], dim3(grid), dim3(64 * nt), lds, st, qa);
+        } else { // K and V rows padded to kAttnRow floats
+            hipLaunchKernelGGL(kAttn[nt - 1].f32, dim3((unsigned)(B * kTencHeads)), dim3(64 * nt),
+                               (size_t)nt * 16 * kAttnRow * 8, st, ws.QKV, ws.OC, (int)T);
+        }
+        if ((rc = chain_tail(m, l, y, n, (int)T, fa, ws, st))) return rc;
+    }
+    HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
 
@@ -647,18 +762,10 @@ int b2h_tenc_create(int ninp, int nhead, int nhid, int nout, int nlayers, int ma
                                          "(infer_utterance.py:99-101) is implemented");
     if (nlayers < 1 || nlayers > 16 || max_len < 1 || max_len > 128)
         return fail(B2H_ERR_UNSUPPORTED, "TransformerEnc: 1 <= nlayers <= 16 and 1 <= max_len <= 128");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        return fail(B2H_ERR_NO_DEVICE, "no HIP device visible (libb2h has no CPU path)");
     std::unique_ptr<b2h_tenc> m(new b2h_tenc()); // released to the caller only on success
-    HIP_TRY(hipGetDevice(&m->device));
-    hipDeviceProp_t p;
-    HIP_TRY(hipGetDeviceProperties(&p, m->device));
-    if (std::strncmp(p.gcnArchName, "gfx950", 6) != 0)
-        return fail(B2H_ERR_NO_DEVICE, std::string("device is ") + p.gcnArchName + ", libb2h is built for gfx950 only");
+    if (int rc = probe_device(m->device, m->num_cus)) return rc;
     m->nlayers = nlayers;
     m->max_len = max_len;
-    m->num_cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
     m->layers.resize(nlayers);
     *out = m.release();
     return B2H_OK;
@@ -698,14 +805,13 @@ int b2h_tenc_load_weights(b2h_tenc* m, const float* const* tensors, int count, i
     if (int rc0 = check_device(m->device)) return rc0;
     // LDS caps are raised here, not in b2h_tenc_forward: the first forward is already capture-safe
     constexpr int kChainLds = 2 * kStageBlobMax * (int)sizeof(float);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(b2h_tenc_chain<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kChainLds));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(b2h_tenc_chain<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kChainLds));
-#define B2H_AQ_CAP(N) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(b2h_attn_qkv_h3<N>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    B2H_AQ_CAP(1) B2H_AQ_CAP(2) B2H_AQ_CAP(3) B2H_AQ_CAP(4) B2H_AQ_CAP(5) B2H_AQ_CAP(6) B2H_AQ_CAP(7) B2H_AQ_CAP(8)
-#undef B2H_AQ_CAP
+    int rc;
+    if ((rc = raise_lds_cap(b2h_tenc_chain<false>, kChainLds)) || (rc = raise_lds_cap(b2h_tenc_chain<true>, kChainLds)))
+        return rc;
+    for (AttnQkvKernel k : kAttnQkvH3)
+        if ((rc = raise_lds_cap(k))) return rc;
     m->w_absmax = 0.f;
     for (int i = 1; i < count; ++i) m->w_absmax = absmax_of(h[i], m->w_absmax); // h[0] is the pe table (|pe| <= 1)
-    int rc;
     if ((rc = m->pe.upload(h[0].data(), h[0].size() * 4))) return rc;
     if ((rc = pack_blob(m->in_proj, h[1].data(), h[2].data(), 0, D, kInCh, nullptr, nullptr))) return rc;
     for (int l = 0; l < m->nlayers; ++l) {
@@ -738,138 +844,6 @@ size_t b2h_tenc_workspace_bytes(const b2h_tenc* m, int64_t B, int64_t T) {
     return (size_t)B * T * (5 * kTencD) * sizeof(float); // residual stream XA, attention output OC (128 each) + QKV (384)
 }
 
-} // extern "C"
-
-namespace {
-int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, const FusedArgs& fa, void* workspace,
-                size_t workspace_bytes, void* stream) {
-    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
-    if (!m->has_weights) return fail(B2H_ERR_NO_WEIGHTS, "b2h_tenc_forward before b2h_tenc_load_weights");
-    if (B < 0 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0 and T >= 1");
-    if (T > m->max_len)
-        return fail(B2H_ERR_SHAPE, "TransformerEnc: T exceeds the positional encoding's max_len (src + pe[:T], "
-                                   "HandPoseModels.py:101,167)");
-    if (B == 0) return B2H_OK;
-    const int64_t n = B * T;
-    // grid limits: attention launches B x heads workgroups, the chain n / 128
-    if (B * kTencHeads > 0x7fffffff || n / (16 * kLinWaves) >= 0x7fffffff) return fail(B2H_ERR_SHAPE, "batch too large for one launch");
-    if (!x || !y || !workspace) return fail(B2H_ERR_INVALID, "NULL pointer");
-    if (int rc = check_device(m->device)) return rc;
-    if (m->kernel == B2H_TENC_F16X3 && !(m->w_absmax < kF16Max))
-        return fail(B2H_ERR_UNSUPPORTED, "B2H_TENC_F16X3: a parameter is outside the f16 range (|w| >= 65504 or not "
-                                         "finite); use B2H_TENC_F32");
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return fail(B2H_ERR_INVALID, "x and workspace must be 16-byte aligned");
-    if (workspace_bytes < b2h_tenc_workspace_bytes(m, B, T)) return fail(B2H_ERR_INVALID, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float* XA = reinterpret_cast<float*>(workspace);
-    float* OC = XA + n * kTencD;
-    float* QKV = OC + n * kTencD;
-    int rc;
-    const bool h3 = m->kernel == B2H_TENC_F16X3;
-    if (h3) {
-        // Round 3: the Q, K, V projection runs inside the attention kernel (b2h_attn_qkv_h3), so only the residual
-        // stream and the attention output cross HBM between launches (2.5 KB per frame and layer -> 1.25 KB).
-        {   // src + pe -> pose2hidden_projection (HandPoseModels.py:167-169) -> residual stream
-            ChainArgs a{};
-            a.x = x; a.ldx = kInCh; a.kgroups0 = 2; a.kvalid = kInCh; a.pe = (const float*)m->pe.p; a.T = (int)T;
-            a.res = nullptr; a.n = n; a.nstages = 1;
-            a.flags = fa.flags & (kPreChest | kPreNorm); a.factor = fa.factor; a.Tseq = (int)T;
-            a.st[0] = stage_of(m, m->in_proj, ST_SET, XA, kTencD);
-            if ((rc = launch_chain(m, a, st))) return rc;
-        }
-        const int nt = (int)((T + 15) / 16);
-        // persistent: one workgroup per CU, bound to a head (blockIdx = 8 (4 slot + head) + xcd: 32 per sequence slot)
-        const unsigned grid = (unsigned)std::max(32, m->num_cus / 32 * 32);
-        const size_t qlds = (size_t)kQkvBlobBytes + 2 * ((size_t)2 * nt * 16 * 48 * 2 + (size_t)2 * kTencHd * kAttnVtRow * 2); // K rows of 48 halves
-        for (int l = 0; l < m->nlayers; ++l) { // torch.nn.TransformerEncoderLayer, post-norm, ReLU
-            auto& L = m->layers[l];
-            AttnQkvArgs qa{};
-            qa.x = XA; qa.out = OC; qa.T = (int)T; qa.B = B;
-            for (int hd = 0; hd < kTencHeads; ++hd) qa.blob[hd] = (const float*)L.qkv_head[hd].buf16.p;
-            switch (nt) {
-#define B2H_AQ(N) case N: hipLaunchKernelGGL(b2h_attn_qkv_h3<N>, dim3(grid), dim3(64 * N), qlds, st, qa); break;
-                B2H_AQ(1) B2H_AQ(2) B2H_AQ(3) B2H_AQ(4) B2H_AQ(5) B2H_AQ(6) B2H_AQ(7) B2H_AQ(8)
-#undef B2H_AQ
-                default: return fail(B2H_ERR_SHAPE, "TransformerEnc: T > 128");
-            }
-            // out_proj +res LN1 -> linear1 ReLU -> linear2 +res LN2 -> residual stream | hidden2pose (:171)
-            ChainArgs a{};
-            a.x = OC; a.ldx = kTencD; a.kgroups0 = 8; a.kvalid = kTencD; a.pe = nullptr; a.T = 1;
-            a.res = XA; a.n = n;
-            a.st[0] = stage_of(m, L.attn_out, ST_RESLN_GLOBAL, nullptr, kTencD);
-            a.st[1] = stage_of(m, L.ff1, ST_RELU, nullptr, kTencD);
-            if (l + 1 < m->nlayers) {
-                a.st[2] = stage_of(m, L.ff2, ST_RESLN_REG, XA, kTencD); // the next layer's input and residual
-                a.nstages = 3;
-            } else {
-                a.st[2] = stage_of(m, L.ff2, ST_RESLN_REG, nullptr, kTencD);
-                a.st[3] = stage_of(m, m->out_proj, ST_STORE, y, kOutCh);
-                a.nstages = 4;
-                a.flags = fa.flags & (kPostDenorm | kPostMask); a.factor = fa.factor; a.n_frames = fa.n_frames;
-            }
-            a.Tseq = (int)T;
-            if ((rc = launch_chain(m, a, st))) return rc;
-        }
-        HIP_TRY(hipGetLastError());
-        return B2H_OK;
-    }
-    {   // src + pe -> pose2hidden_projection (HandPoseModels.py:167-169) -> layer 0's Q, K, V
-        ChainArgs a{};
-        a.x = x; a.ldx = kInCh; a.kgroups0 = 2; a.kvalid = kInCh; a.pe = (const float*)m->pe.p; a.T = (int)T;
-        a.res = nullptr; a.n = n; a.nstages = 4;
-        a.flags = fa.flags & (kPreChest | kPreNorm); a.factor = fa.factor; a.Tseq = (int)T;
-        a.st[0] = stage_of(m, m->in_proj, ST_SET, XA, kTencD);
-        a.st[1] = stage_of(m, m->layers[0].q, ST_STORE, QKV, 3 * kTencD);
-        a.st[2] = stage_of(m, m->layers[0].k, ST_STORE, QKV + kTencD, 3 * kTencD);
-        a.st[3] = stage_of(m, m->layers[0].v, ST_STORE, QKV + 2 * kTencD, 3 * kTencD);
-        if ((rc = launch_chain(m, a, st))) return rc;
-    }
-    for (int l = 0; l < m->nlayers; ++l) { // torch.nn.TransformerEncoderLayer, post-norm, ReLU
-        auto& L = m->layers[l];
-        const int nt = (int)((T + 15) / 16);
-        const dim3 ag((unsigned)(B * kTencHeads)), ab(64 * nt);
-        // fp32: K and V rows padded to kAttnRow floats; f16x3: K hi/lo [keys][32] + V^T hi/lo [32][kAttnVtRow]
-        const size_t alds = h3 ? ((size_t)2 * nt * 16 * kTencHd + (size_t)2 * kTencHd * kAttnVtRow) * 2
-                               : (size_t)nt * 16 * kAttnRow * 8;
-        switch (nt) {
-#define B2H_ATTN(N)                                                                                   \
-    case N:                                                                                           \
-        if (h3) hipLaunchKernelGGL(b2h_attn_mfma_h3<N>, ag, ab, alds, st, QKV, OC, (int)T);            \
-        else hipLaunchKernelGGL(b2h_attn_mfma_f32<N>, ag, ab, alds, st, QKV, OC, (int)T);              \
-        break;
-            B2H_ATTN(1) B2H_ATTN(2) B2H_ATTN(3) B2H_ATTN(4) B2H_ATTN(5) B2H_ATTN(6) B2H_ATTN(7) B2H_ATTN(8)
-#undef B2H_ATTN
-            default: return fail(B2H_ERR_SHAPE, "TransformerEnc: T > 128");
-        }
-        // out_proj +res LN1 -> linear1 ReLU -> linear2 +res LN2 -> next layer's Q,K,V | hidden2pose (:171)
-        ChainArgs a{};
-        a.x = OC; a.ldx = kTencD; a.kgroups0 = 8; a.kvalid = kTencD; a.pe = nullptr; a.T = 1;
-        a.res = XA; a.n = n;
-        a.st[0] = stage_of(m, L.attn_out, ST_RESLN_GLOBAL, nullptr, kTencD);
-        a.st[1] = stage_of(m, L.ff1, ST_RELU, nullptr, kTencD);
-        if (l + 1 < m->nlayers) {
-            a.st[2] = stage_of(m, L.ff2, ST_RESLN_REG, XA, kTencD); // the next layer's residual
-            a.st[3] = stage_of(m, m->layers[l + 1].q, ST_STORE, QKV, 3 * kTencD);
-            a.st[4] = stage_of(m, m->layers[l + 1].k, ST_STORE, QKV + kTencD, 3 * kTencD);
-            a.st[5] = stage_of(m, m->layers[l + 1].v, ST_STORE, QKV + 2 * kTencD, 3 * kTencD);
-            a.nstages = 6;
-        } else {
-            a.st[2] = stage_of(m, L.ff2, ST_RESLN_REG, nullptr, kTencD);
-            a.st[3] = stage_of(m, m->out_proj, ST_STORE, y, kOutCh);
-            a.nstages = 4;
-            a.flags = fa.flags & (kPostDenorm | kPostMask); a.factor = fa.factor; a.n_frames = fa.n_frames;
-        }
-        a.Tseq = (int)T;
-        if ((rc = launch_chain(m, a, st))) return rc;
-    }
-    HIP_TRY(hipGetLastError());
-    return B2H_OK;
-}
-} // namespace
-
-extern "C" {
-
 int b2h_tenc_forward(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, void* workspace,
                      size_t workspace_bytes, void* stream) {
     FusedArgs fa{0, 1.0f, nullptr};
@@ -878,8 +852,7 @@ int b2h_tenc_forward(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T
 
 int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, int64_t T, int flags, float factor,
                            const int64_t* n_frames, void* workspace, size_t workspace_bytes, void* stream) {
-    if (flags & ~(kPreChest | kPreNorm | kPostDenorm | kPostMask)) return fail(B2H_ERR_INVALID, "unknown flag bits");
-    if ((flags & (kPreNorm | kPostDenorm)) && !(factor > 0.f)) return fail(B2H_ERR_INVALID, "factor must be > 0");
+    if (int rc = check_fused(flags, factor)) return rc;
     if ((flags & kPostMask) && !n_frames) return fail(B2H_ERR_INVALID, "B2H_POST_MASK_TAIL needs n_frames");
     FusedArgs fa{flags, factor, n_frames};
     return tenc_launch(m, body, y, B, T, fa, workspace, workspace_bytes, stream);
@@ -928,41 +901,70 @@ int train_nslabs(const TrainParams& p, int64_t B, int64_t T) {
 }
 
 int set_train_kernel_attributes() {
-    static std::mutex mu;
-    static bool done[64] = {};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev >= 0 && dev < 64 && done[dev]) return B2H_OK;
-    int rc;
-    if ((rc = raise_lds_cap(b2h_train_conv<0>)) || (rc = raise_lds_cap(b2h_train_conv<1>)) ||
-        (rc = raise_lds_cap(b2h_train_conv<2>)))
-        return rc;
-    if (dev >= 0 && dev < 64) done[dev] = true;
-    return B2H_OK;
+    static OncePerDevice once;
+    return once([]() -> int {
+        int rc;
+        if ((rc = raise_lds_cap(b2h_train_conv<0>)) || (rc = raise_lds_cap(b2h_train_conv<1>)) ||
+            (rc = raise_lds_cap(b2h_train_conv<2>)))
+            return rc;
+        return B2H_OK;
+    });
 }
-
-bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
-    const char* x = reinterpret_cast<const char*>(a);
-    const char* y = reinterpret_cast<const char*>(b);
-    return x < y + bn && y < x + an;
-}
-
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) & (a - 1); }
 
 // Shared checks of b2h_train_forward / b2h_backward, as launch() makes them for b2h_forward.
 int train_check(const b2h_model* m, const float* const* params, int64_t B, int64_t T) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
-    if (B < 0 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0 and T >= 1");
-    if (T > (1 << 24)) return fail(B2H_ERR_SHAPE, "T too large");
-    if (m->pos_emb && T != 100)
-        return fail(B2H_ERR_SHAPE, "pos_emb model requires T == 100 (LinearPositionalEmbedding max_len, "
-                                   "HandPoseModels.py:23,78-84)");
+    if (int rc = check_shape(m, B, T)) return rc;
     if (!params) return fail(B2H_ERR_INVALID, "params is NULL");
     for (int i = 0; i < 8; ++i) {
         if (!params[i]) return fail(B2H_ERR_INVALID, "params[" + std::to_string(i) + "] is NULL");
         if (misaligned(params[i], 4)) return fail(B2H_ERR_INVALID, "params must be 4-byte aligned fp32 tensors");
     }
+    return B2H_OK;
+}
+
+// Shape and device-pointer checks of the L1 metrics (grad = false: outputs a, b = per_seq, loss) and of their
+// gradients (grad = true: a, b = dloss, dpred).
+int l1_check(bool grad, const float* pred, const float* target, const float* scores, const int64_t* n_frames,
+             int64_t B, int64_t T, const float* a, const char* a_name, const float* b, const char* b_name) {
+    if (B < 1 || T < 1)
+        return grad ? fail(B2H_ERR_SHAPE, "the L1 loss gradients need B >= 1 and T >= 1")
+                    : fail(B2H_ERR_SHAPE, "the L1 metrics need B >= 1 and T >= 1");
+    if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
+    int rc;
+    if ((rc = check_device_ptr(pred, "pred")) || (rc = check_device_ptr(target, "target")) ||
+        (rc = check_device_ptr(a, a_name)) || (rc = check_device_ptr(b, b_name)) ||
+        (scores && (rc = check_device_ptr(scores, "scores"))) || (n_frames && (rc = check_device_ptr(n_frames, "n_frames"))))
+        return rc;
+    return B2H_OK;
+}
+
+int l1_metric(const float* pred, const float* target, const float* scores, const int64_t* n_frames, int64_t B,
+              int64_t T, float* per_seq, float* loss, void* stream) {
+    if (int rc = l1_check(false, pred, target, scores, n_frames, B, T, per_seq, "per_seq", loss, "loss")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(scores ? b2h_masked_l1_seq_kernel<true> : b2h_masked_l1_seq_kernel<false>, dim3((unsigned)B),
+                       dim3(256), 0, st, pred, target, scores, n_frames, per_seq, (int)T);
+    hipLaunchKernelGGL(b2h_mean_kernel, dim3(1), dim3(256), 0, st, per_seq, loss, B, scores ? 0 : 1);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+int l1_backward(const float* pred, const float* target, const float* scores, const int64_t* n_frames, int64_t B,
+                int64_t T, const float* dloss, float* dpred, void* stream) {
+    if (int rc = l1_check(true, pred, target, scores, n_frames, B, T, dloss, "dloss", dpred, "dpred")) return rc;
+    if (misaligned(pred, 16) || misaligned(target, 16) || misaligned(dpred, 16))
+        return fail(B2H_ERR_INVALID, "pred, target and dpred must be 16-byte aligned");
+    const size_t pn = (size_t)B * T * kOutCh * 4;
+    if (overlaps(dpred, pn, pred, pn) || overlaps(dpred, pn, target, pn) || overlaps(dpred, pn, dloss, 4) ||
+        (scores && overlaps(dpred, pn, scores, pn / 2)) || (n_frames && overlaps(dpred, pn, n_frames, (size_t)B * 8)))
+        return fail(B2H_ERR_INVALID, "dpred overlaps an input");
+    const int64_t n = B * T * (kOutCh / 2);
+    const int64_t blocks = std::min<int64_t>((n + 255) / 256, 256 * 16);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(scores ? b2h_l1_backward_kernel<true> : b2h_l1_backward_kernel<false>, dim3((unsigned)blocks),
+                       dim3(256), 0, st, pred, target, scores, n_frames, dloss, dpred, B, (int)T);
+    HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
 } // namespace
@@ -993,16 +995,8 @@ int b2h_create(int conv_channels, const char* activation, int pos_emb, b2h_model
         return fail(B2H_ERR_INVALID, "activation must be \"ReLU\" (HandPoseModels.py:34-37)");
     if (conv_channels < 1 || conv_channels > kMaxWidth)
         return fail(B2H_ERR_INVALID, "conv_channels must be in [1, 128]");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        return fail(B2H_ERR_NO_DEVICE, "no HIP device visible (libb2h has no CPU path)");
     std::unique_ptr<b2h_model> m(new b2h_model()); // released to the caller only on success
-    HIP_TRY(hipGetDevice(&m->device));
-    hipDeviceProp_t p;
-    HIP_TRY(hipGetDeviceProperties(&p, m->device));
-    if (std::strncmp(p.gcnArchName, "gfx950", 6) != 0)
-        return fail(B2H_ERR_NO_DEVICE, std::string("device is ") + p.gcnArchName + ", libb2h is built for gfx950 only");
-    m->num_cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+    if (int rc = probe_device(m->device, m->num_cus)) return rc;
     m->C = conv_channels;
     m->pos_emb = pos_emb ? 1 : 0;
     const int C = conv_channels;
@@ -1053,8 +1047,7 @@ int b2h_forward(b2h_model* m, const float* x, float* y, int64_t B, int64_t T, in
 
 int b2h_forward_fused(b2h_model* m, const float* body, float* y, int64_t B, int64_t T, int flags, float factor,
                       const int64_t* n_frames, int kernel, void* stream) {
-    if (flags & ~(kPreChest | kPreNorm | kPostDenorm | kPostMask)) return fail(B2H_ERR_INVALID, "unknown flag bits");
-    if ((flags & (kPreNorm | kPostDenorm)) && !(factor > 0.f)) return fail(B2H_ERR_INVALID, "factor must be > 0");
+    if (int rc = check_fused(flags, factor)) return rc;
     FusedArgs fa{flags, factor, n_frames};
     return launch(m, body, y, B, T, kernel, fa, (hipStream_t)stream);
 }
@@ -1078,29 +1071,6 @@ int b2h_target_transform(const float* body, const float* hand, float* hand_out, 
     return B2H_OK;
 }
 
-namespace {
-int l1_metric(const float* pred, const float* target, const float* scores, const int64_t* n_frames, int64_t B,
-              int64_t T, float* per_seq, float* loss, void* stream) {
-    if (B < 1 || T < 1) return fail(B2H_ERR_SHAPE, "the L1 metrics need B >= 1 and T >= 1");
-    if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
-    int rc;
-    if ((rc = check_device_ptr(pred, "pred")) || (rc = check_device_ptr(target, "target")) ||
-        (rc = check_device_ptr(per_seq, "per_seq")) || (rc = check_device_ptr(loss, "loss")) ||
-        (scores && (rc = check_device_ptr(scores, "scores"))) || (n_frames && (rc = check_device_ptr(n_frames, "n_frames"))))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (scores)
-        hipLaunchKernelGGL(b2h_masked_l1_seq_kernel<true>, dim3((unsigned)B), dim3(256), 0, st, pred, target, scores,
-                           n_frames, per_seq, (int)T);
-    else
-        hipLaunchKernelGGL(b2h_masked_l1_seq_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, pred, target, scores,
-                           n_frames, per_seq, (int)T);
-    hipLaunchKernelGGL(b2h_mean_kernel, dim3(1), dim3(256), 0, st, per_seq, loss, B, scores ? 0 : 1);
-    HIP_TRY(hipGetLastError());
-    return B2H_OK;
-}
-} // namespace
-
 int b2h_masked_l1(const float* pred, const float* target, const int64_t* n_frames, int64_t B, int64_t T,
                   float* per_seq, float* loss, void* stream) {
     return l1_metric(pred, target, nullptr, n_frames, B, T, per_seq, loss, stream);
@@ -1112,17 +1082,12 @@ int b2h_weighted_l1(const float* pred, const float* target, const float* scores,
     return l1_metric(pred, target, scores, n_frames, B, T, per_seq, loss, stream);
 }
 
-
 int b2h_train_forward(b2h_model* m, const float* const* params, const float* x, float* y, int64_t B, int64_t T,
                       void* stream) {
     if (int rc = train_check(m, params, B, T)) return rc;
     if (B == 0) return B2H_OK;
-    if (!x || !y) return fail(B2H_ERR_INVALID, "x / y is NULL");
-    if (int rc = check_device(m->device)) return rc;
-    if (misaligned(x, 16) || misaligned(y, 16))
-        return fail(B2H_ERR_INVALID, "x and y must be 16-byte aligned (hipMalloc / torch allocations are)");
-    const size_t xn = (size_t)B * T * kInCh * 4, yn = (size_t)B * T * kOutCh * 4;
-    if (overlaps(x, xn, y, yn)) return fail(B2H_ERR_INVALID, "x and y overlap");
+    if (int rc = check_xy(m, x, y, B, T)) return rc;
+    const size_t yn = (size_t)B * T * kOutCh * 4;
     for (int i = 0; i < 8; ++i)
         if (overlaps(params[i], 4, y, yn)) return fail(B2H_ERR_INVALID, "y overlaps a parameter");
     const TrainParams p = train_params(m, params);
@@ -1157,6 +1122,7 @@ int b2h_backward(b2h_model* m, const float* const* params, const float* x, const
     if (!workspace || workspace_bytes < need)
         return fail(B2H_ERR_INVALID, "workspace smaller than b2h_backward_workspace_bytes (" + std::to_string(need) + " B)");
     const size_t xn = (size_t)B * T * kInCh * 4, yn = (size_t)B * T * kOutCh * 4;
+    auto param_bytes = [&](int i) { return (size_t)((i + 1 < 8 ? p.off[i + 1] : train_param_floats(p)) - p.off[i]) * 4; };
     // outputs: dx, the eight gradients, the workspace; none may overlap another operand
     const void* outs[10];
     size_t outn[10];
@@ -1165,7 +1131,7 @@ int b2h_backward(b2h_model* m, const float* const* params, const float* x, const
         if (!grads[i]) return fail(B2H_ERR_INVALID, "grads[" + std::to_string(i) + "] is NULL");
         if (misaligned(grads[i], 4)) return fail(B2H_ERR_INVALID, "grads must be 4-byte aligned");
         outs[nout] = grads[i];
-        outn[nout++] = (size_t)((i + 1 < 8 ? p.off[i + 1] : train_param_floats(p)) - p.off[i]) * 4;
+        outn[nout++] = param_bytes(i);
     }
     if (dx) { outs[nout] = dx; outn[nout++] = xn; }
     outs[nout] = workspace;
@@ -1174,7 +1140,7 @@ int b2h_backward(b2h_model* m, const float* const* params, const float* x, const
         if (overlaps(outs[a], outn[a], x, xn) || overlaps(outs[a], outn[a], dy, yn))
             return fail(B2H_ERR_INVALID, "an output overlaps x or dy");
         for (int i = 0; i < 8; ++i)
-            if (overlaps(outs[a], outn[a], params[i], (size_t)((i + 1 < 8 ? p.off[i + 1] : train_param_floats(p)) - p.off[i]) * 4))
+            if (overlaps(outs[a], outn[a], params[i], param_bytes(i)))
                 return fail(B2H_ERR_INVALID, "an output overlaps a parameter");
         for (int c = a + 1; c < nout; ++c)
             if (overlaps(outs[a], outn[a], outs[c], outn[c])) return fail(B2H_ERR_INVALID, "two outputs overlap");
@@ -1183,12 +1149,8 @@ int b2h_backward(b2h_model* m, const float* const* params, const float* x, const
     const int tps = (int)((T + kTrainBwdTile - 1) / kTrainBwdTile);
     hipStream_t st = (hipStream_t)stream;
     float* ws = static_cast<float*>(workspace);
-    if (dx)
-        hipLaunchKernelGGL(b2h_train_conv<2>, dim3((unsigned)nslabs), dim3(256), train_lds_bytes(p, 2), st, x, dy, dx, ws,
-                           p, (int)T, tps, tiles, nslabs);
-    else
-        hipLaunchKernelGGL(b2h_train_conv<1>, dim3((unsigned)nslabs), dim3(256), train_lds_bytes(p, 1), st, x, dy,
-                           nullptr, ws, p, (int)T, tps, tiles, nslabs);
+    hipLaunchKernelGGL(dx ? b2h_train_conv<2> : b2h_train_conv<1>, dim3((unsigned)nslabs), dim3(256),
+                       train_lds_bytes(p, dx ? 2 : 1), st, x, dy, dx, ws, p, (int)T, tps, tiles, nslabs);
     TrainGrads g;
     for (int i = 0; i < 8; ++i) {
         g.g[i] = grads[i];
@@ -1199,36 +1161,6 @@ int b2h_backward(b2h_model* m, const float* const* params, const float* x, const
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
-
-namespace {
-int l1_backward(const float* pred, const float* target, const float* scores, const int64_t* n_frames, int64_t B,
-                int64_t T, const float* dloss, float* dpred, void* stream) {
-    if (B < 1 || T < 1) return fail(B2H_ERR_SHAPE, "the L1 loss gradients need B >= 1 and T >= 1");
-    if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
-    int rc;
-    if ((rc = check_device_ptr(pred, "pred")) || (rc = check_device_ptr(target, "target")) ||
-        (rc = check_device_ptr(dloss, "dloss")) || (rc = check_device_ptr(dpred, "dpred")) ||
-        (scores && (rc = check_device_ptr(scores, "scores"))) || (n_frames && (rc = check_device_ptr(n_frames, "n_frames"))))
-        return rc;
-    if (misaligned(pred, 16) || misaligned(target, 16) || misaligned(dpred, 16))
-        return fail(B2H_ERR_INVALID, "pred, target and dpred must be 16-byte aligned");
-    const size_t pn = (size_t)B * T * kOutCh * 4;
-    if (overlaps(dpred, pn, pred, pn) || overlaps(dpred, pn, target, pn) || overlaps(dpred, pn, dloss, 4) ||
-        (scores && overlaps(dpred, pn, scores, pn / 2)) || (n_frames && overlaps(dpred, pn, n_frames, (size_t)B * 8)))
-        return fail(B2H_ERR_INVALID, "dpred overlaps an input");
-    const int64_t n = B * T * (kOutCh / 2);
-    const int64_t blocks = std::min<int64_t>((n + 255) / 256, 256 * 16);
-    hipStream_t st = (hipStream_t)stream;
-    if (scores)
-        hipLaunchKernelGGL(b2h_l1_backward_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, pred, target, scores,
-                           n_frames, dloss, dpred, B, (int)T);
-    else
-        hipLaunchKernelGGL(b2h_l1_backward_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, pred, target,
-                           nullptr, n_frames, dloss, dpred, B, (int)T);
-    HIP_TRY(hipGetLastError());
-    return B2H_OK;
-}
-} // namespace
 
 int b2h_masked_l1_backward(const float* pred, const float* target, const int64_t* n_frames, int64_t B, int64_t T,
                            const float* dloss, float* dpred, void* stream) {
@@ -1256,12 +1188,12 @@ int b2h_kernel_supported(const b2h_model* m, int kernel) {
 
 const char* b2h_kernel_name(const b2h_model* m, int kernel) {
     if (!m) return "";
-    switch (resolve_kernel(m, kernel)) {
+    const int k = resolve_kernel(m, kernel);
+    if (const ChunkVariant* v = chunk_variant(k, m->C > kMfmaWidth)) return v->name;
+    switch (k) { // the persistent kernel is named by its streaming instantiation
         case B2H_KERNEL_F32_VALU: return "b2h_fwd_f32_valu";
-        case B2H_KERNEL_F32_MFMA: return m->C > kMfmaWidth ? "b2h_fwd_mfma_f32<false, true>" : "b2h_fwd_mfma_f32<false, false>";
-        case B2H_KERNEL_BF16_MFMA: return m->C > kMfmaWidth ? "b2h_fwd_mfma16w<1, false>" : "b2h_fwd_mfma16<1, false, true>";
-        case B2H_KERNEL_F16_MFMA: return m->C > kMfmaWidth ? "b2h_fwd_mfma16w<2, false>" : "b2h_fwd_mfma16<2, false, true>";
-        case B2H_KERNEL_F16X3_MFMA: return m->C > kMfmaWidth ? "b2h_fwd_mfma_f16x3w<false>" : "b2h_fwd_mfma_f16x3<false>";
+        case B2H_KERNEL_BF16_MFMA: return "b2h_fwd_mfma16<1, false, true>";
+        case B2H_KERNEL_F16_MFMA: return "b2h_fwd_mfma16<2, false, true>";
         default: return "";
     }
 }

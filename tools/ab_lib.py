@@ -1,21 +1,22 @@
 #!/usr/bin/env python3
 """GPU box: same-process A/B of two (or more) builds of libb2h.so on the bench shape, interleaved
 rounds (cdna_hip_programming.md rule 24).  Each library is loaded under its own ctypes handle.
-    python tools/ab_lib.py <libA.so> <libB.so> [...] [precision=bf16] [seqs=65536] [T=200]"""
+    python tools/ab_lib.py <libA.so> <libB.so> [...] [precision=bf16] [seqs=65536] [T=200] [C=<conv_channels, 30>]"""
 import ctypes, os, sys, statistics
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hand_pose_sl_amd import _lib
 
 paths = [a for a in sys.argv[1:] if a.endswith(".so")]
-rest = [a for a in sys.argv[1:] if not a.endswith(".so")]
+rest = [a for a in sys.argv[1:] if not a.endswith(".so") and not a.startswith("C=")]
+C = int(next((a[2:] for a in sys.argv[1:] if a.startswith("C=")), 30))
 prec = rest[0] if len(rest) > 0 else "bf16"
 S = int(rest[1]) if len(rest) > 1 else 65536
 T = int(rest[2]) if len(rest) > 2 else 200
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
 import torch.nn as nn
-convs = [nn.Conv1d(24, 30, 5, padding=2), nn.Conv1d(30, 30, 5, padding=2), nn.Conv1d(30, 30, 5, padding=2), nn.Conv1d(30, 42, 5, padding=2)]
+convs = [nn.Conv1d(24, C, 5, padding=2), nn.Conv1d(C, C, 5, padding=2), nn.Conv1d(C, C, 5, padding=2), nn.Conv1d(C, 42, 5, padding=2)]
 ps = [p.detach().to(dev).contiguous() for c in convs for p in (c.weight, c.bias)]
 x = torch.rand((S, T, 12, 2), device=dev) - 0.5
 ys = []
@@ -27,7 +28,7 @@ for p in paths:
             getattr(lib, name).restype = res
             getattr(lib, name).argtypes = args
     h = ctypes.c_void_p()
-    assert lib.b2h_create(30, b"ReLU", 0, ctypes.byref(h)) == 0
+    assert lib.b2h_create(C, b"ReLU", 0, ctypes.byref(h)) == 0
     assert lib.b2h_load_weights(h, *[ctypes.c_void_p(t.data_ptr()) for t in ps], 1) == 0
     libs.append((lib, h, None))
 k = _lib.KERNELS[prec]
