@@ -90,14 +90,15 @@ class TransformerEnc(nn.Module):
                                "first (there is no CPU path in the product)")
         lib = _lib.load()
         tensors = self._tensors()
-        key = (dev.index,) + tuple((p.data_ptr(), p._version) for p in tensors)
+        # the handle is made for one device and one max_len (b2h_tenc_load_weights reads max_len rows of pe)
+        key = (dev.index, int(tensors[0].shape[0])) + tuple((p.data_ptr(), p._version) for p in tensors)
         if self._handle is not None and key == self._packed_key:
             return lib
         with torch.cuda.device(dev):
-            if self._handle is None or self._packed_key[0] != dev.index:
+            if self._handle is None or self._packed_key is None or self._packed_key[:2] != key[:2]:
                 self._free()
                 h = ctypes.c_void_p()
-                _lib.check(lib.b2h_tenc_create(*self._geom, int(self.pos_encoder.pe.shape[0]), ctypes.byref(h)))
+                _lib.check(lib.b2h_tenc_create(*self._geom, key[1], ctypes.byref(h)))
                 self.__dict__["_handle"] = h
             ps = [p.detach().to(torch.float32).contiguous() for p in tensors]
             torch.cuda.current_stream(dev).synchronize()

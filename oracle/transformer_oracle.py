@@ -25,8 +25,9 @@ def _ln(x, g, b, eps=1e-5):
     return (x - mu) / np.sqrt(var + eps) * g + b
 
 
-def transformer_forward(x, state, nhead=4, dtype=np.float32):
-    """x (B,T,12,2) -> (B,T,21,2).  `state`: the reference's state_dict as numpy arrays."""
+def transformer_forward(x, state, nhead=4, dtype=np.float32, out_dtype=np.float32):
+    """x (B,T,12,2) -> (B,T,21,2).  `state`: the reference's state_dict as numpy arrays.  Computes in `dtype`;
+    the result is rounded to `out_dtype`."""
     st = {k: np.asarray(v, dtype=dtype) for k, v in state.items()}
     x = np.asarray(x, dtype=dtype)
     B, T = x.shape[:2]
@@ -57,4 +58,4 @@ def transformer_forward(x, state, nhead=4, dtype=np.float32):
         f = f @ st[p + "linear2.weight"].T + st[p + "linear2.bias"]
         h = _ln(h + f, st[p + "norm2.weight"], st[p + "norm2.bias"])
     y = h @ st["hidden2pose_projection.weight"].T + st["hidden2pose_projection.bias"]
-    return y.reshape(B, T, 21, 2).astype(np.float32)
+    return y.reshape(B, T, 21, 2).astype(out_dtype)

@@ -14,6 +14,7 @@ through it, the HIP path.
 
     python tests/golden/make_golden.py          # rewrites tests/golden/*.npz
     MKL_CBWR=COMPATIBLE python tests/golden/make_golden.py --mkl-compat   # only adds y_mkl_compat (main() runs it)
+    python tests/golden/make_golden.py --tenc-params    # only (re)writes tenc_params.npz
 """
 import importlib.util
 import os
@@ -280,6 +281,104 @@ def tenc_cases(hpm):
     print("tenc params", sum(v.numel() for v in model.parameters()))
 
 
+def _tenc_logits(model, x, layer):
+    """Per-head attention logits (B, H, T, T) of encoder layer `layer` of the reference model on input x."""
+    with torch.no_grad():
+        h = model.pose2hidden_projection(model.pos_encoder.pe[:x.shape[1]] + x.reshape(x.shape[0], x.shape[1], 24).permute(1, 0, 2))
+        for lyr in model.transformer_encoder.layers[:layer]:
+            h = lyr(h)
+        sa = model.transformer_encoder.layers[layer].self_attn
+        q, k, _ = (h @ sa.in_proj_weight.T + sa.in_proj_bias).chunk(3, dim=-1)
+        T, B = h.shape[:2]
+        q = q.reshape(T, B, 4, 32).permute(1, 2, 0, 3) * 32 ** -0.5
+        k = k.reshape(T, B, 4, 32).permute(1, 2, 0, 3)
+        return q @ k.transpose(-1, -2)
+
+
+TENC_PARAMS_CASES = (("b2_t1", 2, 1, "randn", 61), ("b3_t17", 3, 17, "u55", 62), ("b2_t33", 2, 33, "randn", 63),
+                     ("b2_t100", 2, 100, "u55", 64))
+
+
+def tenc_params_case(hpm):
+    """TransformerEnc(24, 4, 128, 42, nlayers=2) with EVERY parameter away from its default init (which has
+    LayerNorm gamma = 1, beta = 0 and zero attention biases, so that packer or epilogue bugs on them multiply by 1
+    or add 0): norm gammas in +-[0.3, 2.5] with negative ones, norm betas and both attention biases +-[0.3, 1].
+    Layer 1 gets peaked attention: the Q and K rows of heads 0 and 1 scaled until their logits reach ~30
+    (near-one-hot softmax), and head 3's Q and K biases pointing in opposite directions so that all its real-key
+    logits are <= -20 (softmax does not mind; an unmasked zero key would take all the weight).
+    `lnvar__*` overrides layer 0's norm1 (gamma 1e-3, beta 30) and scales its linear2 by 2^-13, so that norm2
+    sees rows of mean ~30 and variance below eps: a one-pass E[x^2] - E[x]^2 variance fails there."""
+    torch.manual_seed(53)
+    model = hpm.TransformerEnc(ninp=24, nhead=4, nhid=128, nout=42, nlayers=2, dropout=0.5).eval()
+    gen = torch.Generator().manual_seed(54)
+
+    def mag(shape, lo, hi):
+        return lo + (hi - lo) * torch.rand(shape, generator=gen)
+
+    def sign(shape, p_neg):
+        return torch.where(torch.rand(shape, generator=gen) < p_neg, -1.0, 1.0)
+
+    inputs = {name: _inputs(kind, (B, T, 12, 2), torch.Generator().manual_seed(seed))
+              for name, B, T, kind, seed in TENC_PARAMS_CASES}
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if name.endswith(("norm1.weight", "norm2.weight")):
+                p.copy_(mag(p.shape, 0.3, 2.5) * sign(p.shape, 0.25))
+            elif name.endswith(("norm1.bias", "norm2.bias", "in_proj_bias", "out_proj.bias")):
+                p.copy_(mag(p.shape, 0.3, 1.0) * sign(p.shape, 0.5))
+        sa = model.transformer_encoder.layers[1].self_attn
+        W, b = sa.in_proj_weight, sa.in_proj_bias
+        # head 3: q.k gets -|c|^2 / sqrt(32) from the biases; its weight rows shrink so that term dominates
+        u = torch.randn(32, generator=gen)
+        u = u / u.norm()
+        for part in (0, 1):
+            W[part * 128 + 96:part * 128 + 128] *= 0.25
+        b[96:128], b[128 + 96:256] = 12.0 * u, -12.0 * u
+        # heads 0 and 1: Q and K rows scaled by s, the weight part of the logits by s^2, up to ~30 on the
+        # fixture inputs (twice: the bias part does not scale)
+        s = 1.0
+        for _ in range(2):
+            top = max(float(_tenc_logits(model, x, 1)[:, :2].abs().max()) for x in inputs.values())
+            for part in (0, 1):
+                W[part * 128:part * 128 + 64] *= (30.0 / top) ** 0.5
+            s *= (30.0 / top) ** 0.5
+        lg = [_tenc_logits(model, x, 1) for x in inputs.values()]
+        peak = max(float(l[:, :2].abs().max()) for l in lg)
+        worst3 = max(float(l[:, 3].max()) for l in lg)
+        assert 20.0 <= peak <= 40.0 and worst3 <= -20.0, (peak, worst3)
+        print(f"tenc_params: layer 1 Q/K rows of heads 0, 1 x{s:.3f}: max |logit| {peak:.1f}; head 3 max logit {worst3:.1f}")
+    rec = {"sd__" + k: v.numpy().copy() for k, v in model.state_dict().items()}   # the lnvar edits below are in place
+    for name, x in inputs.items():
+        with torch.no_grad():
+            y = model(x).contiguous()
+        rec["x_" + name], rec["y_" + name] = x.numpy(), y.numpy()
+        print(f"tenc_params {name}: x{tuple(x.shape)} -> y{tuple(y.shape)} |y|max={y.abs().max():.4f}")
+    # the near-eps LayerNorm variant, on the b2_t33 input
+    lyr = model.transformer_encoder.layers[0]
+    with torch.no_grad():
+        lyr.norm1.weight.copy_(1e-3 * mag(lyr.norm1.weight.shape, 0.5, 1.5) * sign(lyr.norm1.weight.shape, 0.25))
+        lyr.norm1.bias.fill_(30.0)
+        lyr.linear2.weight.mul_(2.0 ** -13)
+        lyr.linear2.bias.mul_(2.0 ** -13)
+        over = ("norm1.weight", "norm1.bias", "linear2.weight", "linear2.bias")
+        params = dict(lyr.named_parameters())
+        for k in over:
+            rec["lnvar__transformer_encoder.layers.0." + k] = params[k].numpy().copy()
+        h = model.pose2hidden_projection(model.pos_encoder.pe[:33] + inputs["b2_t33"].reshape(2, 33, 24).permute(1, 0, 2))
+        h1 = lyr.norm1(h + lyr._sa_block(h, None, None))
+        z = h1 + lyr._ff_block(h1)
+        var, mean = z.var(-1, unbiased=False), z.mean(-1)
+        print(f"tenc_params lnvar: norm2 input mean {float(mean.abs().min()):.1f}..{float(mean.abs().max()):.1f}, "
+              f"variance {float(var.min()):.2e}..{float(var.max()):.2e} (eps 1e-5)")
+        assert float(mean.abs().min()) > 20.0 and float(var.max()) < 1e-5
+        y = model(inputs["b2_t33"]).contiguous()
+    rec["y_lnvar_b2_t33"] = y.numpy()
+    print(f"tenc_params lnvar b2_t33: |y|max={y.abs().max():.4f}")
+    path = os.path.join(OUT, "tenc_params.npz")
+    np.savez_compressed(path, **rec)
+    print(f"{path}: {os.path.getsize(path)} bytes")
+
+
 def tenc_transform_case(utils, hpm, name, T, n_frames, seed):
     """The item transforms around TransformerEnc exactly as run.py:83-107 / infer_utterance.py order
     them for `--model TransformerEnc --dif-encoding`: WristDifference, ChestDifference,
@@ -431,6 +530,7 @@ def main():
     # TransformerEnc
     tenc_cases(hpm)
     tenc_transform_case(utils, hpm, "tenc_transforms_b6_t40", 40, [40, 1, 17, 39, 25, 8], 13)
+    tenc_params_case(hpm)
     # evaluation metric
     metric_case(utils, "metric_b5_t60", 5, 60, [60, 1, 33, 59, 17], 31)
     weighted_metric_case(utils, "metric_conf_b5_t60", 5, 60, [60, 1, 33, 59, 17], 37)
@@ -457,5 +557,8 @@ if __name__ == "__main__":
         hpm = _load(os.path.join(REF, "models", "HandPoseModels.py"), "ref_HandPoseModels")
         for case in MKL_COMPAT_CASES:
             mkl_compat_case(hpm, case)
+    elif "--tenc-params" in sys.argv:
+        _stub_fairseq()
+        tenc_params_case(_load(os.path.join(REF, "models", "HandPoseModels.py"), "ref_HandPoseModels"))
     else:
         main()

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """GPU box: randomized sweep of the TransformerEnc path against the numpy oracle -- random batch,
-length (1..100), layer count, weight scale, kernel (fp32 / f16x3) and, for a third of the cases, the
-fused item transforms with random flags and ragged tail masks; plus the masked-L1 metric
-and the target transform (bit-exact) on random shapes.    python tools/stress_tenc.py [seconds=120] [seed=0]"""
+length (1..100), layer count, weight scale, LayerNorm gammas and betas, all biases (attention ones
+included), kernel (fp32 / f16x3) and, for a third of the cases, the fused item transforms with
+random flags and ragged tail masks; plus the masked-L1 metric and the target transform (bit-exact)
+on random shapes.    python tools/stress_tenc.py [seconds=120] [seed=0]"""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,10 +23,16 @@ while time.time() < t_end:
     if key not in models:
         torch.manual_seed(int(rng.integers(1 << 30)))
         m = hps.TransformerEnc(24, 4, 128, 42, L, precision=prec)
-        with torch.no_grad():
+        with torch.no_grad():   # every tensor away from its default: norm gammas and betas, both attention biases too
             for name, p in m.named_parameters():
-                if "norm" not in name:
-                    p.mul_(float(rng.uniform(0.6, 1.8)))
+                shape = tuple(p.shape)
+                if name.endswith(("norm1.weight", "norm2.weight")):      # +-[0.3, 2.5], a quarter negative
+                    v = rng.uniform(0.3, 2.5, shape) * np.where(rng.random(shape) < 0.25, -1.0, 1.0)
+                elif name.endswith("bias"):                               # +-[0.3, 1]
+                    v = rng.uniform(0.3, 1.0, shape) * np.where(rng.random(shape) < 0.5, -1.0, 1.0)
+                else:
+                    v = p.numpy() * float(rng.uniform(0.6, 1.8))
+                p.copy_(torch.from_numpy(np.asarray(v, np.float32)))
         models = {key: (m.to(dev).eval(), {k: v.detach().cpu().numpy() for k, v in m.state_dict().items()})}
     m, state = models[key]
     T = int(rng.integers(1, 101))
