@@ -636,28 +636,23 @@ ChainStage stage_of(const b2h_tenc* m, const TencBlob& B, int type, float* out, 
 }
 
 int launch_chain(b2h_tenc* m, ChainArgs& a, hipStream_t st) {
-    constexpr size_t lds = (size_t)2 * kStageBlobMax * sizeof(float);
     // persistent: one workgroup per CU (134 KB of LDS each) walks over the 128-frame blocks
     const int64_t blocks = std::min<int64_t>((a.n + 16 * kLinWaves - 1) / (16 * kLinWaves), m->num_cus);
     hipLaunchKernelGGL(m->kernel == B2H_TENC_F16X3 ? b2h_tenc_chain<true> : b2h_tenc_chain<false>, dim3((unsigned)blocks),
-                       dim3(64 * kLinWaves), lds, st, a);
+                       dim3(64 * kLinWaves), (size_t)kChainLdsBytes, st, a);
     return B2H_OK;
 }
 
 // Attention kernels by query tiles, [nt - 1] with nt = ceil(T / 16) <= 8.  f16x3: b2h_attn_qkv_h3 projects Q, K, V
-// itself.  fp32: b2h_attn_mfma_f32 reads them from the chain's QKV rows; b2h_attn_mfma_h3, its f16x3 twin, has not
-// been launched since the projection moved into b2h_attn_qkv_h3, and stays built.
+// itself.  fp32: b2h_attn_mfma_f32 reads them from the chain's QKV rows.
 using AttnQkvKernel = void (*)(AttnQkvArgs);
 constexpr AttnQkvKernel kAttnQkvH3[kAttnMaxTiles] = {b2h_attn_qkv_h3<1>, b2h_attn_qkv_h3<2>, b2h_attn_qkv_h3<3>,
                                                      b2h_attn_qkv_h3<4>, b2h_attn_qkv_h3<5>, b2h_attn_qkv_h3<6>,
                                                      b2h_attn_qkv_h3<7>, b2h_attn_qkv_h3<8>};
 using AttnKernel = void (*)(const float*, float*, int);
-constexpr struct { AttnKernel h3, f32; } kAttn[kAttnMaxTiles] = {
-    {b2h_attn_mfma_h3<1>, b2h_attn_mfma_f32<1>}, {b2h_attn_mfma_h3<2>, b2h_attn_mfma_f32<2>},
-    {b2h_attn_mfma_h3<3>, b2h_attn_mfma_f32<3>}, {b2h_attn_mfma_h3<4>, b2h_attn_mfma_f32<4>},
-    {b2h_attn_mfma_h3<5>, b2h_attn_mfma_f32<5>}, {b2h_attn_mfma_h3<6>, b2h_attn_mfma_f32<6>},
-    {b2h_attn_mfma_h3<7>, b2h_attn_mfma_f32<7>}, {b2h_attn_mfma_h3<8>, b2h_attn_mfma_f32<8>},
-};
+constexpr AttnKernel kAttn[kAttnMaxTiles] = {b2h_attn_mfma_f32<1>, b2h_attn_mfma_f32<2>, b2h_attn_mfma_f32<3>,
+                                             b2h_attn_mfma_f32<4>, b2h_attn_mfma_f32<5>, b2h_attn_mfma_f32<6>,
+                                             b2h_attn_mfma_f32<7>, b2h_attn_mfma_f32<8>};
 
 // Residual stream XA, attention output OC and (fp32 path) the Q, K, V rows of the next attention; QKV is
 // nullptr on the f16x3 path, whose attention kernel projects them itself.
@@ -735,14 +730,13 @@ int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, con
         if (h3) {
             // persistent: one workgroup per CU, bound to a head (blockIdx = 8 (4 slot + head) + xcd: 32 per sequence slot)
             const unsigned grid = (unsigned)std::max(32, m->num_cus / 32 * 32);
-            const size_t lds = (size_t)kQkvBlobBytes + 2 * ((size_t)2 * nt * 16 * 48 * 2 + (size_t)2 * kTencHd * kAttnVtRow * 2); // K rows of 48 halves
             AttnQkvArgs qa{};
             qa.x = ws.XA; qa.out = ws.OC; qa.T = (int)T; qa.B = B;
             for (int hd = 0; hd < kTencHeads; ++hd) qa.blob[hd] = (const float*)m->layers[l].qkv_head[hd].buf16.p;
-            hipLaunchKernelGGL(kAttnQkvH3[nt - 1], dim3(grid), dim3(64 * nt), lds, st, qa);
-        } else { // K and V rows padded to kAttnRow floats
-            hipLaunchKernelGGL(kAttn[nt - 1].f32, dim3((unsigned)(B * kTencHeads)), dim3(64 * nt),
-                               (size_t)nt * 16 * kAttnRow * 8, st, ws.QKV, ws.OC, (int)T);
+            hipLaunchKernelGGL(kAttnQkvH3[nt - 1], dim3(grid), dim3(64 * nt), (size_t)attn_qkv_lds_bytes(nt), st, qa);
+        } else {
+            hipLaunchKernelGGL(kAttn[nt - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nt),
+                               (size_t)attn_f32_lds_bytes(nt), st, ws.QKV, ws.OC, (int)T);
         }
         if ((rc = chain_tail(m, l, y, n, (int)T, fa, ws, st))) return rc;
     }
@@ -804,12 +798,11 @@ int b2h_tenc_load_weights(b2h_tenc* m, const float* const* tensors, int count, i
     HIP_TRY(hipDeviceSynchronize());
     if (int rc0 = check_device(m->device)) return rc0;
     // LDS caps are raised here, not in b2h_tenc_forward: the first forward is already capture-safe
-    constexpr int kChainLds = 2 * kStageBlobMax * (int)sizeof(float);
     int rc;
-    if ((rc = raise_lds_cap(b2h_tenc_chain<false>, kChainLds)) || (rc = raise_lds_cap(b2h_tenc_chain<true>, kChainLds)))
+    if ((rc = raise_lds_cap(b2h_tenc_chain<false>, kChainLdsBytes)) || (rc = raise_lds_cap(b2h_tenc_chain<true>, kChainLdsBytes)))
         return rc;
-    for (AttnQkvKernel k : kAttnQkvH3)
-        if ((rc = raise_lds_cap(k))) return rc;
+    for (int nt = 1; nt <= kAttnMaxTiles; ++nt)
+        if ((rc = raise_lds_cap(kAttnQkvH3[nt - 1], attn_qkv_lds_bytes(nt)))) return rc;
     m->w_absmax = 0.f;
     for (int i = 1; i < count; ++i) m->w_absmax = absmax_of(h[i], m->w_absmax); // h[0] is the pe table (|pe| <= 1)
     if ((rc = m->pe.upload(h[0].data(), h[0].size() * 4))) return rc;

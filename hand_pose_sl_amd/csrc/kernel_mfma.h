@@ -23,15 +23,14 @@
 // with the swizzle, x2 / x4 without).
 #pragma once
 #include "b2h_common.h"
+#include "f16_split.h"   // f16x2 / f16x4 / f16x8
 #include "dev/b2h_dev.h" // B2H_ABLATE hooks: constant-false in the shipped build
 
 namespace b2h {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kChunk = 112;            // output frames per wave-chunk: 18 KB of LDS per wave, so two
                                        // 4-wave workgroups share a CU (2 waves/SIMD); T=200 -> 112 + 88

@@ -46,7 +46,6 @@ constexpr int kInRegs = 20;                        // ceil(208 * 6 / 64) float4 
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 template <int PREC> struct Pack2;
 template <> struct Pack2<PREC_BF16> { using v2 = bf16x2; };
 template <> struct Pack2<PREC_F16> { using v2 = f16x2; };

@@ -17,32 +17,13 @@
 // consecutive channels of its own 16-byte chunk, so the write-back is one ds_write_b128 per image.
 #pragma once
 #include "kernel_mfma.h"
-#include "kernel_mfma16.h" // relu_bits
-#include "dev/b2h_dev.h"  // B2H_STAMP3: empty in the shipped build
+#include "kernel_mfma16.h"  // relu_bits
+#include "kernel_mfma16w.h" // lds_offw, kWideRowB: the input stager below serves kernel_mfma3w.h too
+#include "dev/b2h_dev.h"   // B2H_STAMP3: empty in the shipped build
 
 namespace b2h {
 
 constexpr int kImg3 = kRows * 64; // bytes of one image (hi or lo) of a wave
-
-
-// hi = f16(v) packed two per instruction (v_cvt_pk_f16_f32), residual v - hi as ONE mixed-precision
-// FMA per value (v_fma_mix_f32 reads the f16 half straight out of the packed register; written as
-// asm because hipcc otherwise converts hi back with v_cvt_f32_f16 and subtracts), lo = f16(residual)
-// packed: 16 VALU for 8 values.
-__device__ __forceinline__ void split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f16x2 h = f16x2{(_Float16)v[2 * i], (_Float16)v[2 * i + 1]};
-        const uint32_t hb = __builtin_bit_cast(uint32_t, h);
-        float r0, r1;
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hb), "v"(v[2 * i]));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hb), "v"(v[2 * i + 1]));
-        const f16x2 l = f16x2{(_Float16)r0, (_Float16)r1};
-        hi[2 * i] = h[0]; hi[2 * i + 1] = h[1];
-        lo[2 * i] = l[0]; lo[2 * i + 1] = l[1];
-    }
-}
 
 // One layer over this wave's chunk.  Software pipeline over 16-frame tiles, two deep: fragments are
 // read two tiles ahead (ping-pong B0/B1), a tile's epilogue runs one tile late (ping-pong accA/accB)
@@ -188,23 +169,29 @@ __device__ __forceinline__ void layer3(const ChunkCtx& cx, const MfmaParams& mp)
 }
 
 // ---- input staging: (T,24) fp32 rows -> hi / lo images of layer-1 input ------------------------
+// For both geometries of the images: ROWB = 64 (this file: 4 chunks per row, swizzle lds_off<64>) and
+// ROWB = kWideRowB (kernel_mfma3w.h: 8 chunks per row, swizzle lds_offw; layer 1 reads chunks 0..3 only).
+template <int ROWB> __device__ __forceinline__ int img3_off(int P, int c) {
+    if constexpr (ROWB == kWideRowB) return lds_offw(P, c);
+    else return lds_off<ROWB>(P, c);
+}
+
 __device__ __forceinline__ void split4(const float4& w, f16x4& hi, f16x4& lo) {
     const float e[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const _Float16 a = (_Float16)e[j];
-        hi[j] = a;
-        lo[j] = (_Float16)(e[j] - (float)a);
-    }
+    for (int j = 0; j < 4; ++j) split1(e[j], hi, lo, j);
 }
 
+template <int ROWB>
 __device__ __forceinline__ void stage_input3(const ChunkCtx& cx, const float* __restrict__ xs, int pos_emb) {
+    static_assert(ROWB == 64 || ROWB == kWideRowB, "16-bit image geometries: 64-B or 128-B rows");
+    constexpr int CPR = ROWB / 16, LC = (CPR == 4) ? 2 : 3; // chunks per row, and its log2
     char* img_h = cx.lds;
-    char* img_l = cx.lds + kImg3;
+    char* img_l = cx.lds + kRows * ROWB;
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    const StagedRows st = stage_rows<64>(
+    const StagedRows st = stage_rows<ROWB>(
         cx, xs, pos_emb, // channels 4c4 .. 4c4+3: half (c4 & 1) of 16-B chunk c4 >> 1
-        [&](int P, int c4) { return lds_off<64>(P, c4 >> 1) + (c4 & 1) * 8; },
+        [&](int P, int c4) { return img3_off<ROWB>(P, c4 >> 1) + (c4 & 1) * 8; },
         [&](int off, float4 w) {
             f16x4 wh, wl;
             split4(w, wh, wl);
@@ -212,24 +199,27 @@ __device__ __forceinline__ void stage_input3(const ChunkCtx& cx, const float* __
             *reinterpret_cast<f16x4*>(img_l + off) = wl;
         },
         [&](int P, float pe) { // channel padding 24..31 = chunk 3
-            const _Float16 ph = (_Float16)pe;
             f16x8 zh, zl;
 #pragma unroll
             for (int j = 0; j < 8; ++j) { zh[j] = (_Float16)0.f; zl[j] = (_Float16)0.f; }
-            zh[0] = ph;
-            zl[0] = (_Float16)(pe - (float)ph);
-            *reinterpret_cast<f16x8*>(img_h + lds_off<64>(P, 3)) = zh;
-            *reinterpret_cast<f16x8*>(img_l + lds_off<64>(P, 3)) = zl;
+            split1(pe, zh, zl, 0);
+            *reinterpret_cast<f16x8*>(img_h + img3_off<ROWB>(P, 3)) = zh;
+            *reinterpret_cast<f16x8*>(img_l + img3_off<ROWB>(P, 3)) = zl;
         });
-    // zero rows: t in [-8,0) at the sequence start (all layers' low padding) and t = T, T+1 at its end;
-    // 4 chunks per row per image
-    if (cx.s == 0) { // 8 rows x 4 chunks x 2 images
-        const int i = cx.lane;
-        *reinterpret_cast<f32x4*>((i < 32 ? img_h : img_l) + lds_off<64>((i & 31) >> 2, i & 3)) = z4;
+    // zero rows (every chunk of both images): t in [-8,0) at the sequence start (all layers' low padding)
+    // and t = T, T+1 at its end
+    if (cx.s == 0) { // 8 rows x CPR chunks x 2 images: the lanes cover both images of 4-chunk rows, one of 8-chunk rows
+        if constexpr (CPR == 4) {
+            *reinterpret_cast<f32x4*>((cx.lane < 32 ? img_h : img_l) + img3_off<ROWB>((cx.lane & 31) >> 2, cx.lane & 3)) = z4;
+        } else {
+            *reinterpret_cast<f32x4*>(img_h + img3_off<ROWB>(cx.lane >> 3, cx.lane & 7)) = z4;
+            *reinterpret_cast<f32x4*>(img_l + img3_off<ROWB>(cx.lane >> 3, cx.lane & 7)) = z4;
+        }
     }
-    if (st.at_end && cx.lane < 16) { // 2 rows x 4 chunks x 2 images
+    if (st.at_end && cx.lane < 4 * CPR) { // 2 rows x CPR chunks x 2 images
         const int i = cx.lane;
-        *reinterpret_cast<f32x4*>((i < 8 ? img_h : img_l) + lds_off<64>(st.P0 + st.nrows + ((i & 7) >> 2), i & 3)) = z4;
+        *reinterpret_cast<f32x4*>((i < 2 * CPR ? img_h : img_l) +
+                                  img3_off<ROWB>(st.P0 + st.nrows + ((i >> LC) & 1), i & (CPR - 1))) = z4;
     }
     wave_lds_sync();
 }
@@ -244,7 +234,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void b2h_fwd_mfma_f16x3(
     ChunkCtx cx;
     if (!chunk_ctx(cx, smem_mfma3, 2 * kImg3, y, T, chunks_per_seq, chunk_len, nchunks, fa)) return;
     B2H_STAMP3(cx, 0);
-    stage_input3(cx, x + cx.seq * (int64_t)T * kInCh, mp.pos_emb);
+    stage_input3<64>(cx, x + cx.seq * (int64_t)T * kInCh, mp.pos_emb);
     B2H_STAMP3(cx, 1); // input staged
     layer3<0, FUSED>(cx, mp); layer3<1, FUSED>(cx, mp); layer3<2, FUSED>(cx, mp); layer3<3, FUSED>(cx, mp);
 }

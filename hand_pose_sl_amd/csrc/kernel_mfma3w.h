@@ -17,7 +17,7 @@
 // was the only fp32-grade path for these widths.
 #pragma once
 #include "kernel_mfma16w.h" // lds_offw, wide_chan_of, wide_mt, wide_ks
-#include "kernel_mfma3.h"   // split8
+#include "kernel_mfma3.h"   // stage_input3
 
 namespace b2h {
 
@@ -118,41 +118,6 @@ __device__ __forceinline__ void layer3w(const ChunkCtx& cx, const MfmaParams& mp
     }
 }
 
-// ---- input staging: (T,24) fp32 rows -> hi / lo images of the layer-1 input (chunks 0..3) ---------
-__device__ __forceinline__ void stage_input3w(const ChunkCtx& cx, const float* __restrict__ xs, int pos_emb) {
-    char* img_h = cx.lds;
-    char* img_l = cx.lds + kImg3W;
-    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    const StagedRows st = stage_rows<kWideRowB>(
-        cx, xs, pos_emb, // channels 4c4 .. 4c4+3: half (c4 & 1) of 16-B chunk c4 >> 1
-        [&](int P, int c4) { return lds_offw(P, c4 >> 1) + (c4 & 1) * 8; },
-        [&](int off, float4 w) {
-            f16x4 wh, wl;
-            split4(w, wh, wl);
-            *reinterpret_cast<f16x4*>(img_h + off) = wh;
-            *reinterpret_cast<f16x4*>(img_l + off) = wl;
-        },
-        [&](int P, float pe) { // in-positions 24..31 = chunk 3; layer 1 reads chunks 0..3 only
-            const _Float16 ph = (_Float16)pe;
-            f16x8 zh, zl;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { zh[j] = (_Float16)0.f; zl[j] = (_Float16)0.f; }
-            zh[0] = ph;
-            zl[0] = (_Float16)(pe - (float)ph);
-            *reinterpret_cast<f16x8*>(img_h + lds_offw(P, 3)) = zh;
-            *reinterpret_cast<f16x8*>(img_l + lds_offw(P, 3)) = zl;
-        });
-    // zero rows (all 8 chunks of both images): t in [-8,0) at the sequence start (every layer's low
-    // padding) and t = T, T+1 at the sequence end
-    if (cx.s == 0) {
-        *reinterpret_cast<f32x4*>(img_h + lds_offw(cx.lane >> 3, cx.lane & 7)) = z4;
-        *reinterpret_cast<f32x4*>(img_l + lds_offw(cx.lane >> 3, cx.lane & 7)) = z4;
-    }
-    if (st.at_end && cx.lane < 32) // 2 rows x 8 chunks x 2 images
-        *reinterpret_cast<f32x4*>((cx.lane < 16 ? img_h : img_l) + lds_offw(st.P0 + st.nrows + ((cx.lane >> 3) & 1), cx.lane & 7)) = z4;
-    wave_lds_sync();
-}
-
 // One wave per (sequence, chunk); no workgroup barrier anywhere.  One 4-wave workgroup per CU.
 template <bool FUSED>
 __global__ __launch_bounds__(64 * kWavesPerBlock, 1) void b2h_fwd_mfma_f16x3w(
@@ -161,7 +126,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 1) void b2h_fwd_mfma_f16x3w(
     extern __shared__ __attribute__((aligned(16))) char smem_mfma3w[];
     ChunkCtx cx;
     if (!chunk_ctx(cx, smem_mfma3w, 2 * kImg3W, y, T, chunks_per_seq, chunk_len, nchunks, fa)) return;
-    stage_input3w(cx, x + cx.seq * (int64_t)T * kInCh, mp.pos_emb);
+    stage_input3<kWideRowB>(cx, x + cx.seq * (int64_t)T * kInCh, mp.pos_emb);
     layer3w<0, FUSED>(cx, mp); layer3w<1, FUSED>(cx, mp); layer3w<2, FUSED>(cx, mp); layer3w<3, FUSED>(cx, mp);
 }
 

@@ -1,23 +1,27 @@
 // TransformerEnc (body2hand/src/models/HandPoseModels.py:118-178) on gfx950.
 // Two kernels per precision:
 //
-//   b2h_attn_mfma_f32 / b2h_attn_mfma_h3
-//                       self-attention, workgroup = (sequence, head), wave = 16 query frames:
-//                       scores and P.V on the matrix cores, softmax in registers over all T keys
-//                       (the reference passes no mask, HandPoseModels.py:170).
+//   b2h_attn_mfma_f32 / b2h_attn_qkv_h3
+//                       self-attention, wave = 16 query frames of one (sequence, head): scores and
+//                       P.V on the matrix cores, softmax in registers over all T keys (the
+//                       reference passes no mask, HandPoseModels.py:170).  The fp32 kernel reads
+//                       Q, K, V rows; the f16x3 kernel projects them itself from the residual stream.
 //   b2h_tenc_chain<H3>  everything between two attention calls, which is all per-frame: a wave
 //                       carries 16 frames through a chain of Linear layers in registers (the
 //                       accumulator layout IS the next GEMM's operand layout), with bias, ReLU,
 //                       residual + LayerNorm fused between them; weights double-buffered in LDS.
 //
 // B2H_TENC_F32 computes every product in fp32 (v_mfma_f32_16x16x4_f32); B2H_TENC_F16X3 (the _h3 /
-// <true> instantiations) splits every operand into f16 hi + lo and uses three
+// <true> instantiations) splits every operand into f16 hi + lo (f16_split.h) and uses three
 // v_mfma_f32_16x16x32_f16 per product with fp32 accumulation: fp32-grade results at 3/16 of the
 // matrix cycles.  Softmax, LayerNorm, bias and residual arithmetic is fp32 in both.
 //
-// Per forward: 1 front chain (src + pe -> pose2hidden -> Q,K,V) and per layer 1 attention + 1
-// chain launch; only the residual stream, the attention output and Q,K,V cross HBM (2.5 KB per
-// frame of caller-provided workspace).
+// Per forward: 1 front chain (src + pe -> pose2hidden [-> Q,K,V, fp32 only]) and per layer 1
+// attention + 1 chain launch; only the residual stream, the attention output and (fp32) Q,K,V cross
+// HBM (2.5 KB per frame of caller-provided workspace).
+//
+// Each kernel's dynamic LDS size is a constexpr next to it (attn_f32_lds_bytes, attn_qkv_lds_bytes,
+// kChainLdsBytes), used by the kernel's own pointer arithmetic and by the host's launches.
 //
 // All kernels address global memory with buffer instructions over per-workgroup descriptors:
 // the hardware range check replaces lane predicates, which keeps every s_waitcnt a counted one.
@@ -26,13 +30,12 @@
 #pragma once
 #include <utility>
 #include "b2h_common.h"
+#include "f16_split.h"     // f16x8, split2, split8
 #include "kernel_mfma.h"   // f32x4
 #include "kernel_mfma16.h" // pack helpers
 #include "dev/b2h_dev.h"   // B2H_ABLATE / B2H_STAMP hooks: constant-false / empty in the shipped build
 
 namespace b2h {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kTencD = 128;      // nhid (d_model and feed-forward width in the reference's CLIs)
 constexpr int kTencHeads = 4;
@@ -77,13 +80,14 @@ __device__ __forceinline__ float quad_max(float s) {
 // workgroup are in flight together.
 constexpr int kAttnMaxTiles = 8; // T <= 128
 constexpr int kAttnRow = 36;
+constexpr int attn_f32_lds_bytes(int nt) { return 2 * nt * 16 * kAttnRow * (int)sizeof(float); } // K, then V
 
 template <int NT> // number of 16-frame tiles = ceil(T / 16): compile-time so that the loops are branch-free
 __global__ __launch_bounds__(64 * NT) void b2h_attn_mfma_f32(const float* __restrict__ qkv,
                                                           float* __restrict__ out, int T) {
     extern __shared__ __attribute__((aligned(16))) char smem_attn2[];
     float* Ks = reinterpret_cast<float*>(smem_attn2);
-    float* Vs = Ks + NT * 16 * kAttnRow;
+    float* Vs = reinterpret_cast<float*>(smem_attn2 + attn_f32_lds_bytes(NT) / 2);
     const int b = blockIdx.x / kTencHeads, h = blockIdx.x % kTencHeads;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(qkv + (int64_t)b * T * (3 * kTencD), T * 3 * kTencD * 4);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -158,141 +162,6 @@ __global__ __launch_bounds__(64 * NT) void b2h_attn_mfma_f32(const float* __rest
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
 }
 
-// Self-attention with 3 x f16 split operands (B2H_TENC_F16X3; the split itself: see the chain's
-// f16x3 section below).  Same workgroup / wave mapping and softmax as b2h_attn_mfma_f32; both
-// products run on v_mfma_f32_16x16x32_f16 as hi.hi + hi.lo + lo.hi with fp32 accumulation:
-//   S^T tile = K[16 keys][32 dims] . Q^T           one k-step (k = dims): A from LDS rows of K
-//              (f16 hi / lo, 64 B per key), B = this lane's query dims 8q .. 8q+7
-//   O^T      = V^T[32 dims][keys] . P^T            k = keys, 32 per step: the lane's score
-//              registers of key tiles 2s (j < 4) and 2s+1 (j >= 4) ARE the B operand when k-slot
-//              (s, q, j) means key 32s + 16(j>>2) + 4q + (j&3); V^T is stored in LDS with its keys
-//              in that slot order, so an A fragment is one 16-byte read.
-constexpr int kAttnVtRow = 136; // halves per V^T row: 128 key slots + 8 (rows 4 banks apart)
-
-template <int NT>
-__global__ __launch_bounds__(64 * NT) void b2h_attn_mfma_h3(const float* __restrict__ qkv, float* __restrict__ out, int T) {
-    extern __shared__ __attribute__((aligned(16))) char smem_attn3[];
-    constexpr int KS = (NT + 1) / 2;                       // k-steps of 32 keys
-    _Float16* Kh = reinterpret_cast<_Float16*>(smem_attn3); // [NT*16 keys][32 dims]
-    _Float16* Kl = Kh + NT * 16 * kTencHd;
-    _Float16* Vh = Kl + NT * 16 * kTencHd;                  // [32 dims][kAttnVtRow key slots]
-    _Float16* Vl = Vh + kTencHd * kAttnVtRow;
-    const int b = blockIdx.x / kTencHeads, h = blockIdx.x % kTencHeads;
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(qkv + (int64_t)b * T * (3 * kTencD), T * 3 * kTencD * 4);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
-    const int tq = wave * 16 + col;
-    // K, V of the head: each thread takes dims 4c .. 4c+3 of the key PAIR (2u, 2u+1) -- adjacent
-    // slots of V^T, so a dim's two keys go out as one 32-bit LDS write
-    const int vc = threadIdx.x & 7, vu = threadIdx.x >> 3;
-    f32x4 k4[2], v4[2], q4[2];
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int off = ((2 * vu + it) * 3 * kTencD + h * kTencHd + 4 * vc) * 4;
-        k4[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, kTencD * 4, 0));
-        v4[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 2 * kTencD * 4, 0));
-    }
-#pragma unroll
-    for (int g = 0; g < 2; ++g) // this lane's query, dims 8q + 4g .. +3
-        q4[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            rs, (tq * 3 * kTencD + h * kTencHd + 8 * q + 4 * g) * 4, 0, 0));
-    if (KS * 32 > NT * 16) { // odd NT: the last k-step's upper 16 key slots have no writer
-        for (int i = threadIdx.x; i < kTencHd * 16; i += 64 * NT) {
-            const int d = i >> 4, p = (KS - 1) * 32 + 8 * ((i >> 2) & 3) + 4 + (i & 3);
-            Vh[d * kAttnVtRow + p] = (_Float16)0.f;
-            Vl[d * kAttnVtRow + p] = (_Float16)0.f;
-        }
-    }
-    {
-        typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-        const int t0 = 2 * vu;
-        // key t -> slot: k-step t>>5, then 8*((t>>2)&3) + 4*((t>>4)&1) + (t&3); t0 is even: t0+1 -> p+1
-        const int p = (t0 & ~31) + 8 * ((t0 >> 2) & 3) + 4 * ((t0 >> 4) & 1) + (t0 & 3);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            f16x4 kh, kl;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const _Float16 a = (_Float16)k4[it][e];
-                kh[e] = a;
-                kl[e] = (_Float16)(k4[it][e] - (float)a);
-            }
-            *reinterpret_cast<f16x4*>(Kh + (t0 + it) * kTencHd + 4 * vc) = kh;
-            *reinterpret_cast<f16x4*>(Kl + (t0 + it) * kTencHd + 4 * vc) = kl;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const _Float16 a0 = (_Float16)v4[0][e], a1 = (_Float16)v4[1][e];
-            *reinterpret_cast<f16x2*>(Vh + (4 * vc + e) * kAttnVtRow + p) = f16x2{a0, a1};
-            *reinterpret_cast<f16x2*>(Vl + (4 * vc + e) * kAttnVtRow + p) =
-                f16x2{(_Float16)(v4[0][e] - (float)a0), (_Float16)(v4[1][e] - (float)a1)};
-        }
-    }
-    f16x8 qh, ql; // B operand of S^T, pre-scaled (torch scales q, not the scores)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = q4[j >> 2][j & 3] * 0.17677669529663687f;
-        const _Float16 a = (_Float16)x;
-        qh[j] = a;
-        ql[j] = (_Float16)(x - (float)a);
-    }
-    __syncthreads();
-    f32x4 sc[2 * KS];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-        const f16x8 ah = *reinterpret_cast<const f16x8*>(Kh + (kt * 16 + col) * kTencHd + 8 * q);
-        const f16x8 al = *reinterpret_cast<const f16x8*>(Kl + (kt * 16 + col) * kTencHd + 8 * q);
-        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, qh, a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, ql, a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, qh, a, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { // D row 4q + r = key index within the tile
-            if (kt * 16 + 4 * q + r >= T) a[r] = -INFINITY;
-            mx = fmaxf(mx, a[r]);
-        }
-        sc[kt] = a;
-    }
-    if (2 * KS > NT) sc[2 * KS - 1] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    mx = quad_max(mx);
-    float l = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 2 * KS; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            sc[kt][r] = __expf(sc[kt][r] - mx); // v_exp_f32 (1 ulp); masked keys: exp(-inf) = 0
-            l += sc[kt][r];
-        }
-    l = quad_sum(l);
-    f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        f16x8 ph, pl;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float x = sc[2 * s + (j >> 2)][j & 3];
-            const _Float16 a = (_Float16)x;
-            ph[j] = a;
-            pl[j] = (_Float16)(x - (float)a);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) { // A: V^T row d = 16mt + col, key slots 32s + 8q .. +7
-            const f16x8 vh = *reinterpret_cast<const f16x8*>(Vh + (16 * mt + col) * kAttnVtRow + 32 * s + 8 * q);
-            const f16x8 vl = *reinterpret_cast<const f16x8*>(Vl + (16 * mt + col) * kAttnVtRow + 32 * s + 8 * q);
-            o[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl, ph, o[mt], 0, 0, 0);
-            o[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, pl, o[mt], 0, 0, 0);
-            o[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, ph, o[mt], 0, 0, 0);
-        }
-    }
-    const float inv = 1.0f / l;
-    const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + (int64_t)b * T * kTencD, T * kTencD * 4);
-    const int ooff = (tq * kTencD + h * kTencHd + 4 * q) * 4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0] * inv), ors, ooff, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
-}
-
 // ---- per-frame chain ---------------------------------------------------------------------
 // Between two attention calls every operation of the model is per-frame.  For
 // v_mfma_f32_16x16x4_f32 the accumulator tile of one GEMM (lane = frame, register r of M-tile
@@ -307,6 +176,7 @@ enum { ST_SET = 0, ST_RELU = 1, ST_RESLN_GLOBAL = 2, ST_RESLN_REG = 3, ST_STORE 
 constexpr int kChainMaxStages = 8;
 constexpr int kStageParams = 3 * kTencD;                                   // bias, gamma, beta
 constexpr int kStageBlobMax = kLinChunkMT * 8 * 64 * 4 + kStageParams;    // floats: 16384 + 384
+constexpr int kChainLdsBytes = 2 * kStageBlobMax * (int)sizeof(float);    // the two blob buffers: 134 KB
 
 struct ChainStage {
     const float* blob;   // [wf4 x 16 B of weight fragments][bias 128][gamma 128][beta 128]
@@ -355,27 +225,20 @@ __device__ __forceinline__ void chain_gemm(const f32x4* __restrict__ wl, int lan
 }
 
 // ---- 3 x f16 split operands (B2H_TENC_F16X3) ---------------------------------------------------
-// x = hi + lo with hi = f16(x), lo = f16(x - hi) carries 22 significant bits, and
-//     W.x  ~=  Whi.xhi + Whi.xlo + Wlo.xhi          (the dropped Wlo.xlo term is ~2^-22 relative)
-// is three v_mfma_f32_16x16x32_f16 (fp32 accumulate) at 16x the fp32 matrix rate each: fp32-grade
-// results (max error of the golden model vs fp64: 1.2e-6, the same as the fp32 kernel) for 3/16 of
-// the matrix cycles, valid while |activation| < 65504 (f16 range).
+// With the split of f16_split.h, W.x ~= Wlo.xhi + Whi.xlo + Whi.xhi is three v_mfma_f32_16x16x32_f16
+// (fp32 accumulate) at 16x the fp32 matrix rate each: fp32-grade results (max error of the golden
+// model vs fp64: 1.2e-6, the same as the fp32 kernel) for 3/16 of the matrix cycles, valid while
+// |activation| < 65504 (f16 range).
 // The accumulator -> operand identity of the fp32 chain carries over: k-slot (g, q, j) of the
 // 32-wide k-group g holds feature 32g + 16(j>>2) + 4q + (j&3), i.e. lane (frame, q) packs its own
 // accumulator tiles 2g (j < 4) and 2g+1 (j >= 4); the host packs the weights in the same slot order.
 __device__ __forceinline__ void chain_split(const f32x4 (&v)[8], f16x8 (&bh)[4], f16x8 (&bl)[4]) {
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
-        for (int j = 0; j < 8; j += 2) { // two values per packed convert; residual = one v_fma_mix_f32 each
-            const float x0 = v[2 * g + (j >> 2)][j & 3], x1 = v[2 * g + (j >> 2)][(j & 3) + 1];
-            const f16x2 h = f16x2{(_Float16)x0, (_Float16)x1};
-            const uint32_t hb = __builtin_bit_cast(uint32_t, h);
-            float r0, r1; // x - hi, exact in fp32 (asm: hipcc otherwise converts hi back and subtracts)
-            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hb), "v"(x0));
-            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hb), "v"(x1));
-            const f16x2 l = f16x2{(_Float16)r0, (_Float16)r1};
+        for (int j = 0; j < 8; j += 2) {
+            f16x2 h, l;
+            split2(v[2 * g + (j >> 2)][j & 3], v[2 * g + (j >> 2)][(j & 3) + 1], h, l);
             bh[g][j] = h[0]; bh[g][j + 1] = h[1];
             bl[g][j] = l[0]; bl[g][j + 1] = l[1];
         }
@@ -471,38 +334,28 @@ __device__ __forceinline__ f32x4 chain_ld(__amdgpu_buffer_rsrc_t rs, uint32_t of
 
 
 // ---- Q, K, V projection + self-attention in one kernel (B2H_TENC_F16X3) ---------------------------
-// Round 3.  In the two-kernel form above the chain wrote Q, K, V (1 536 B per frame and layer) for the
-// attention kernel to read back: 60 % of the path's HBM traffic, on kernels that sit on their HBM floor.
+// Round 3.  In the two-kernel form of the fp32 path the chain writes Q, K, V (1 536 B per frame and layer) for
+// the attention kernel to read back: 60 % of the path's HBM traffic, on kernels that sit on their HBM floor.
 // Here the projection lives where its result is used: a workgroup is bound to one HEAD for the whole
 // launch -- its 96 x 128 slice of in_proj_weight (rows of Q_h, K_h, V_h; f16 hi + lo fragments, 48 KB)
 // is copied into LDS once -- and walks over sequences: wave w owns frames 16w .. 16w+15 of the sequence,
 //     x rows (residual stream, 512 B per frame)  --split-->  [Q_h | K_h | V_h] = W_h . x + b_h     (72 MFMAs)
 //     Q_h stays in registers: with the chain's k-slot order (slot (q, j) = dim 16(j>>2) + 4q + (j&3)) a lane's
 //         eight accumulators ARE its query fragment; K_h goes to LDS as the lane's one 16-byte chunk of its
-//         key row in the same slot order, V_h as V^T[dim][key slot] like b2h_attn_mfma_h3 stores it
-//     barrier, then scores / softmax / P.V exactly as in b2h_attn_mfma_h3.
+//         key row in the same slot order, V_h as V^T[dim][key slot]
+//     barrier, then the same wave mapping and softmax as b2h_attn_mfma_f32, both products on
+//     v_mfma_f32_16x16x32_f16 as lo.hi + hi.lo + hi.hi with fp32 accumulation:
+//       S^T tile = K[16 keys][32 dims] . Q^T     one k-step (k = dims): A from the LDS rows of K (f16 hi / lo),
+//                  B = this lane's query fragment
+//       O^T      = V^T[32 dims][keys] . P^T      k = keys, 32 per step: the lane's score registers of key tiles
+//                  2s (j < 4) and 2s+1 (j >= 4) ARE the B operand when k-slot (s, q, j) means key
+//                  32s + 16(j>>2) + 4q + (j&3); V^T is stored in LDS with its keys in that slot order
+//                  (vt_slot), so an A fragment is one 16-byte read.
 // K and V are double-buffered (sequence i + 1 is projected while slower waves still attend to sequence i:
 // one barrier per sequence), the next sequence's x rows are requested before this one's MFMAs.  Only the
 // residual stream (read) and the attention output (written) cross HBM: 1 KB per frame and layer instead of
 // 2 KB here + 1.5 KB of Q, K, V stores in the chain.  The four head-workgroups of a sequence list sit on
 // one XCD (blockIdx = 8 * (4 * slot + head) + xcd), so three of their four reads of a row are L2 hits.
-// hi = f16(v) packed two per instruction, residual v - hi as one mixed-precision FMA per value, lo = f16(residual):
-// 16 vector instructions for 8 values (the scalar casts cost twice that; see split8 in kernel_mfma3.h)
-__device__ __forceinline__ void tenc_split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f16x2 h = f16x2{(_Float16)v[2 * i], (_Float16)v[2 * i + 1]};
-        const uint32_t hb = __builtin_bit_cast(uint32_t, h);
-        float r0, r1;
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hb), "v"(v[2 * i]));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hb), "v"(v[2 * i + 1]));
-        const f16x2 l = f16x2{(_Float16)r0, (_Float16)r1};
-        hi[2 * i] = h[0]; hi[2 * i + 1] = h[1];
-        lo[2 * i] = l[0]; lo[2 * i + 1] = l[1];
-    }
-}
-
 struct AttnQkvArgs {
     const float* x;        // (B*T, 128) residual stream entering the layer
     float* out;            // (B*T, 128) attention output, head h -> columns 32h ..
@@ -512,17 +365,22 @@ struct AttnQkvArgs {
 };
 constexpr int kQkvMT = 6;                                       // M-tiles of a head's projection: Q 0-1, K 2-3, V 4-5
 constexpr int kQkvBlobBytes = 2 * kQkvMT * 4 * 64 * 16 + kStageParams * 4; // 49 152 + 1 536
+constexpr int kKRow = 48;       // halves per K row: 32 dims + 16 of padding -- with 64-B rows four keys of a
+                                // ds_read_b128 lane group share a bank quad (30 % of this kernel's LDS cycles
+                                // were conflicts); 96 B: none
+constexpr int kAttnVtRow = 136; // halves per V^T row: 128 key slots + 8 (rows 4 banks apart)
+constexpr int kAttnVtBytes = kTencHd * kAttnVtRow * 2;                                      // one V^T image (hi or lo)
+constexpr int attn_k_bytes(int nt) { return nt * 16 * kKRow * 2; }                           // one K image (hi or lo)
+constexpr int attn_kv_bytes(int nt) { return 2 * attn_k_bytes(nt) + 2 * kAttnVtBytes; }      // K hi, K lo, V^T hi, V^T lo
+constexpr int attn_qkv_lds_bytes(int nt) { return kQkvBlobBytes + 2 * attn_kv_bytes(nt); }   // weights + two K, V buffers
+// key 16 tile + k (k < 16) -> its slot in a V^T row: k-step tile >> 1, then (q, j) = (k >> 2, 4 (tile & 1) + (k & 3))
+__device__ __forceinline__ int vt_slot(int tile, int k) { return 32 * (tile >> 1) + 8 * (k >> 2) + 4 * (tile & 1) + (k & 3); }
 
 template <int NT>
 __global__ __launch_bounds__(64 * NT) void b2h_attn_qkv_h3(AttnQkvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_aq[];
     constexpr int KS = (NT + 1) / 2;                          // k-steps of 32 keys
-    constexpr int kKRow = 48;                                 // halves per K row: 32 dims + 16 of padding -- with 64-B rows
-                                                              // four keys of a ds_read_b128 lane group share a bank quad
-                                                              // (30 % of this kernel's LDS cycles were conflicts); 96 B: none
-    constexpr int kKBytes = NT * 16 * kKRow * 2;              // one K image (hi or lo)
-    constexpr int kVBytes = kTencHd * kAttnVtRow * 2;         // one V^T image
-    constexpr int kKV = 2 * kKBytes + 2 * kVBytes;            // K hi, K lo, V^T hi, V^T lo
+    constexpr int kKBytes = attn_k_bytes(NT), kKV = attn_kv_bytes(NT);
     const f32x4* wl = reinterpret_cast<const f32x4*>(smem_aq);
     const float* prm = reinterpret_cast<const float*>(smem_aq + 2 * kQkvMT * 4 * 64 * 16);
     char* kvbase = smem_aq + kQkvBlobBytes;
@@ -549,15 +407,14 @@ __global__ __launch_bounds__(64 * NT) void b2h_attn_qkv_h3(AttnQkvArgs a) {
     if (KS * 32 > NT * 16) { // odd NT: the last k-step's upper 16 key slots of V^T have no writer (both buffers)
         for (int i = threadIdx.x; i < 2 * kTencHd * 16; i += 64 * NT) {
             const int bufi = i / (kTencHd * 16), r = i % (kTencHd * 16);
-            const int d = r >> 4, p = (KS - 1) * 32 + 8 * ((r >> 2) & 3) + 4 + (r & 3);
+            const int d = r >> 4, p = (KS - 1) * 32 + 8 * ((r >> 2) & 3) + 4 + (r & 3); // = vt_slot(NT, r & 15): tile NT's keys
             _Float16* Vh = reinterpret_cast<_Float16*>(kvbase + bufi * kKV + 2 * kKBytes);
             Vh[d * kAttnVtRow + p] = (_Float16)0.f;
             (Vh + kTencHd * kAttnVtRow)[d * kAttnVtRow + p] = (_Float16)0.f;
         }
     }
     __syncthreads(); // weights (and the V^T padding) in LDS
-    // key t -> V^T slot: k-step t>>5, then 8*((t>>2)&3) + 4*((t>>4)&1) + (t&3)
-    const int vslot = (tq & ~31) + 8 * ((tq >> 2) & 3) + 4 * ((tq >> 4) & 1) + (tq & 3);
+    const int vslot = vt_slot(tq >> 4, tq & 15);
     int buf = 0;
 #pragma unroll 1
     for (; b < a.B; b += stride, buf ^= 1) {
@@ -583,9 +440,9 @@ __global__ __launch_bounds__(64 * NT) void b2h_attn_qkv_h3(AttnQkvArgs a) {
                 vv[j] = acc[4 + (j >> 2)][j & 3];
             }
             f16x8 kh, kl, vh, vl;
-            tenc_split8(vq, qh, ql);
-            tenc_split8(vk, kh, kl);
-            tenc_split8(vv, vh, vl);
+            split8(vq, qh, ql);
+            split8(vk, kh, kl);
+            split8(vv, vh, vl);
             *reinterpret_cast<f16x8*>(Kh + tq * kKRow + 8 * q) = kh;
             *reinterpret_cast<f16x8*>(Kl + tq * kKRow + 8 * q) = kl;
 #pragma unroll
@@ -631,7 +488,7 @@ __global__ __launch_bounds__(64 * NT) void b2h_attn_qkv_h3(AttnQkvArgs a) {
             float pv[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) pv[j] = sc[2 * s + (j >> 2)][j & 3];
-            tenc_split8(pv, ph, pl);
+            split8(pv, ph, pl);
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) { // A: V^T row d = 16mt + col, key slots 32s + 8q .. +7
                 const f16x8 vh = *reinterpret_cast<const f16x8*>(Vh + (16 * mt + col) * kAttnVtRow + 32 * s + 8 * q);
@@ -655,7 +512,7 @@ __global__ __launch_bounds__(64 * kLinWaves, 2) void b2h_tenc_chain(ChainArgs a)
     (void)nstamp;
     extern __shared__ __attribute__((aligned(16))) char smem_chain[];
     f32x4* buf0 = reinterpret_cast<f32x4*>(smem_chain);
-    f32x4* buf1 = buf0 + kStageBlobMax / 4;
+    f32x4* buf1 = reinterpret_cast<f32x4*>(smem_chain + kChainLdsBytes / 2);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, tcol = lane & 15, q0 = lane >> 4;
     constexpr int kFrames = 16 * kLinWaves, kThreads = 64 * kLinWaves;
