@@ -21,6 +21,7 @@
 #include "kernel_mfma3.h"
 #include "kernel_mfma3w.h"
 #include "kernel_tenc.h"
+#include "kernel_tenc_train.h"
 #include "kernel_train.h"
 #include "kernel_valu.h"
 
@@ -744,6 +745,8 @@ int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, con
     return B2H_OK;
 }
 
+int set_tt_kernel_attributes(); // the training kernels' LDS caps, below
+
 } // namespace
 
 extern "C" {
@@ -758,6 +761,7 @@ int b2h_tenc_create(int ninp, int nhead, int nhid, int nout, int nlayers, int ma
         return fail(B2H_ERR_UNSUPPORTED, "TransformerEnc: 1 <= nlayers <= 16 and 1 <= max_len <= 128");
     std::unique_ptr<b2h_tenc> m(new b2h_tenc()); // released to the caller only on success
     if (int rc = probe_device(m->device, m->num_cus)) return rc;
+    if (int rc = set_tt_kernel_attributes()) return rc; // here, not in a launch: b2h_tenc_train_forward is capture-safe
     m->nlayers = nlayers;
     m->max_len = max_len;
     m->layers.resize(nlayers);
@@ -849,6 +853,256 @@ int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, 
     if ((flags & kPostMask) && !n_frames) return fail(B2H_ERR_INVALID, "B2H_POST_MASK_TAIL needs n_frames");
     FusedArgs fa{flags, factor, n_frames};
     return tenc_launch(m, body, y, B, T, fa, workspace, workspace_bytes, stream);
+}
+
+} // extern "C"
+
+// ---- TransformerEnc training (kernel_tenc_train.h) ------------------------------------------------------------
+namespace {
+
+constexpr int64_t kTtSavedFrame = kInCh + kTtD;                  // X0, H0: floats per frame
+constexpr int64_t kTtSavedLayer = 3 * kTtD + 6 * kTtD + 4;       // QKV, O, R1, H1, F1, R2, H2, {mean, rstd} x 2
+constexpr int64_t kTtScratchFrame = 4 * kTtD + 3 * kTtD;         // gA, gB, gBm, gC, gQ
+constexpr int64_t kTtSlab = (int64_t)3 * kTtD * kTtD + 3 * kTtD; // the largest Linear: in_proj weight + bias
+
+// Saved activations of one layer (floats, N = B * T rows each).
+struct TtLayer {
+    float *QKV, *O, *R1, *H1, *F1, *R2, *H2, *ST;
+};
+TtLayer tt_layer(float* saved, int64_t N, int l) {
+    float* p = saved + N * kTtSavedFrame + (int64_t)l * N * kTtSavedLayer;
+    return TtLayer{p, p + N * 384, p + N * 512, p + N * 640, p + N * 768, p + N * 896, p + N * 1024, p + N * 1152};
+}
+
+size_t tt_saved_bytes(int nlayers, int64_t N) { return (size_t)N * (kTtSavedFrame + nlayers * kTtSavedLayer) * 4; }
+size_t tt_scratch_bytes(int64_t N) { return ((size_t)N * kTtScratchFrame + (size_t)tt_nslabs(N) * kTtSlab) * 4; }
+
+int set_tt_kernel_attributes() {
+    static OncePerDevice once;
+    return once([]() -> int {
+        int rc;
+        if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd))) return rc;
+        return B2H_OK;
+    });
+}
+
+// Floats of parameter i (order of b2h_tenc_load_weights, pe first).
+size_t tt_param_floats(const b2h_tenc* m, int i) {
+    const size_t D = kTtD;
+    if (i == 0) return (size_t)m->max_len * kInCh;
+    if (i == 1) return D * kInCh;
+    if (i == 2) return D;
+    const int last = 3 + 12 * m->nlayers;
+    if (i == last) return (size_t)kOutCh * D;
+    if (i == last + 1) return kOutCh;
+    static const size_t per[12] = {3 * D * D, 3 * D, D * D, D, D * D, D, D * D, D, D, D, D, D};
+    return per[(i - 3) % 12];
+}
+
+// Checks shared by b2h_tenc_train_forward / b2h_tenc_backward, as tenc_launch makes them.
+int tt_check(const b2h_tenc* m, const float* const* params, const uint8_t* const* masks, float p, int64_t B, int64_t T) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (!params) return fail(B2H_ERR_INVALID, "params is NULL");
+    if (!(p >= 0.f && p <= 1.f)) return fail(B2H_ERR_INVALID, "dropout p must be in [0, 1]");
+    if ((p > 0.f) != (masks != nullptr)) return fail(B2H_ERR_INVALID, "masks must be given exactly when p > 0");
+    if (B < 0 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0 and T >= 1");
+    if (T > m->max_len || T > 128)
+        return fail(B2H_ERR_SHAPE, "TransformerEnc: T exceeds the positional encoding's max_len (src + pe[:T], "
+                                   "HandPoseModels.py:101,167)");
+    // grid limits: attention launches B x heads workgroups, LayerNorm N / 4 (the largest row grid), the Linears N / 16
+    if (B * kTtHeads > 0x7fffffff || B * T / 4 >= 0x7fffffff) return fail(B2H_ERR_SHAPE, "batch too large for one launch");
+    for (int i = 0; i < 5 + 12 * m->nlayers; ++i) {
+        if (!params[i]) return fail(B2H_ERR_INVALID, "params[" + std::to_string(i) + "] is NULL");
+        if (misaligned(params[i], 4)) return fail(B2H_ERR_INVALID, "params must be 4-byte aligned fp32 tensors");
+    }
+    if (masks)
+        for (int i = 0; i < 1 + 4 * m->nlayers; ++i)
+            if (!masks[i]) return fail(B2H_ERR_INVALID, "masks[" + std::to_string(i) + "] is NULL");
+    return B2H_OK;
+}
+
+struct TtOut {
+    const void* p;
+    size_t n;
+};
+
+// No output may overlap a parameter, a mask, another output or one of the plain inputs.
+int tt_check_overlap(const b2h_tenc* m, const float* const* params, const uint8_t* const* masks, int64_t N, int64_t T,
+                     const std::vector<TtOut>& outs, const std::vector<TtOut>& ins) {
+    for (size_t a = 0; a < outs.size(); ++a) {
+        for (const TtOut& in : ins)
+            if (overlaps(outs[a].p, outs[a].n, in.p, in.n)) return fail(B2H_ERR_INVALID, "an output overlaps an input");
+        for (int i = 0; i < 5 + 12 * m->nlayers; ++i)
+            if (overlaps(outs[a].p, outs[a].n, params[i], tt_param_floats(m, i) * 4))
+                return fail(B2H_ERR_INVALID, "an output overlaps a parameter");
+        if (masks)
+            for (int i = 0; i < 1 + 4 * m->nlayers; ++i) {
+                const int kind = i == 0 ? -1 : (i - 1) % 4;
+                const size_t n = kind < 0 ? (size_t)N * kInCh : (kind == 0 ? (size_t)N * kTtHeads * T : (size_t)N * kTtD);
+                if (overlaps(outs[a].p, outs[a].n, masks[i], n)) return fail(B2H_ERR_INVALID, "an output overlaps a mask");
+            }
+        for (size_t c = a + 1; c < outs.size(); ++c)
+            if (overlaps(outs[a].p, outs[a].n, outs[c].p, outs[c].n)) return fail(B2H_ERR_INVALID, "two outputs overlap");
+    }
+    return B2H_OK;
+}
+
+unsigned tt_row_blocks(int64_t N, int rows) { return (unsigned)((N + rows - 1) / rows); }
+
+void tt_linear(hipStream_t st, const float* X, const float* W, const float* b, float* Y, int64_t N, int K, int M,
+               int relu, const uint8_t* mask, float scale, const float* res) {
+    hipLaunchKernelGGL(b2h_tt_linear, dim3(tt_row_blocks(N, kTtRows)), dim3(128), 0, st, X, W, b, Y, N, K, M, relu, mask,
+                       scale, res);
+}
+
+void tt_linear_dx(hipStream_t st, const float* dY, const float* W, float* dX, int64_t N, int K, int M, const float* gate,
+                  const uint8_t* mask, float scale, const float* add) {
+    hipLaunchKernelGGL(b2h_tt_linear_dx, dim3(tt_row_blocks(N, kTtRows)), dim3(128), 0, st, dY, W, dX, N, K, M, gate,
+                       mask, scale, add);
+}
+
+// dW, db of one Linear: slab partials, then the fixed-order sum into the gradient tensors.
+void tt_linear_dw(hipStream_t st, const float* dY, const float* X, float* slabs, int64_t N, int K, int M, float* gW,
+                  float* gb) {
+    const int S = tt_nslabs(N);
+    hipLaunchKernelGGL(b2h_tt_linear_dw, dim3(S, (M + kTtDwM - 1) / kTtDwM), dim3(256), 0, st, dY, X, slabs, kTtSlab, N,
+                       K, M);
+    hipLaunchKernelGGL(b2h_tt_reduce, dim3((M * K + M + 255) / 256), dim3(256), 0, st, slabs, kTtSlab, S, gW, M * K, gb, M);
+}
+
+void tt_layernorm_bwd(hipStream_t st, const float* dY, const float* X, const float* stats, const float* gamma, float* dX,
+                      float* dXm, const uint8_t* mask, float scale, float* slabs, int64_t N, float* ggamma, float* gbeta) {
+    const int S = tt_nslabs(N);
+    hipLaunchKernelGGL(b2h_tt_layernorm_bwd, dim3(S), dim3(256), 0, st, dY, X, stats, 4, gamma, dX, dXm, mask, scale,
+                       slabs, kTtSlab, N);
+    hipLaunchKernelGGL(b2h_tt_reduce, dim3(1), dim3(256), 0, st, slabs, kTtSlab, S, ggamma, kTtD, gbeta, kTtD);
+}
+
+float tt_scale(float p) { return p < 1.f ? 1.f / (1.f - p) : 0.f; }
+
+} // namespace
+
+extern "C" {
+
+size_t b2h_tenc_train_bytes(const b2h_tenc* m, int64_t B, int64_t T, int which) {
+    if (!m || B < 1 || T < 1 || (which != 0 && which != 1)) return 0;
+    return which == 0 ? tt_saved_bytes(m->nlayers, B * T) : tt_scratch_bytes(B * T);
+}
+
+int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float* x, const uint8_t* const* masks, float p,
+                           float* y, void* saved, size_t saved_bytes, int64_t B, int64_t T, void* stream) {
+    if (int rc = tt_check(m, params, masks, p, B, T)) return rc;
+    if (B == 0) return B2H_OK;
+    if (!x || !y || !saved) return fail(B2H_ERR_INVALID, "NULL pointer");
+    if (int rc = check_device(m->device)) return rc;
+    if (misaligned(x, 16) || misaligned(y, 16) || misaligned(saved, 16))
+        return fail(B2H_ERR_INVALID, "x, y and the saved buffer must be 16-byte aligned");
+    const int64_t N = B * T;
+    const size_t need = tt_saved_bytes(m->nlayers, N);
+    if (saved_bytes < need)
+        return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tenc_train_bytes (" + std::to_string(need) + " B)");
+    if (int rc = tt_check_overlap(m, params, masks, N, T, {{y, (size_t)N * kOutCh * 4}, {saved, need}},
+                                  {{x, (size_t)N * kInCh * 4}}))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const float sc = tt_scale(p);
+    auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
+    float* S = static_cast<float*>(saved);
+    float* X0 = S;
+    float* H = S + N * kInCh;
+    hipLaunchKernelGGL(b2h_tt_posenc, dim3((unsigned)std::min<int64_t>((N * kInCh + 255) / 256, 4096)), dim3(256), 0, st, x,
+                       params[0], mk(0), sc, X0, N, (int)T);
+    tt_linear(st, X0, params[1], params[2], H, N, kInCh, kTtD, 0, nullptr, 1.f, nullptr);
+    for (int l = 0; l < m->nlayers; ++l) { // torch.nn.TransformerEncoderLayer, post-norm, ReLU
+        const float* const* w = params + 3 + 12 * l;
+        const TtLayer L = tt_layer(S, N, l);
+        tt_linear(st, H, w[0], w[1], L.QKV, N, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
+        hipLaunchKernelGGL(b2h_tt_sdpa, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes((int)T, false), st,
+                           L.QKV, mk(1 + 4 * l), sc, L.O, (int)T);
+        tt_linear(st, L.O, w[2], w[3], L.R1, N, kTtD, kTtD, 0, mk(2 + 4 * l), sc, H);
+        hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R1, w[8], w[9], L.H1, L.ST, 4, N);
+        tt_linear(st, L.H1, w[4], w[5], L.F1, N, kTtD, kTtD, 1, mk(3 + 4 * l), sc, nullptr);
+        tt_linear(st, L.F1, w[6], w[7], L.R2, N, kTtD, kTtD, 0, mk(4 + 4 * l), sc, L.H1);
+        hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R2, w[10], w[11], L.H2, L.ST + 2,
+                           4, N);
+        H = L.H2;
+    }
+    const float* const* wh = params + 3 + 12 * m->nlayers;
+    tt_linear(st, H, wh[0], wh[1], y, N, kTtD, kOutCh, 0, nullptr, 1.f, nullptr);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* const* masks, float p, const float* dy,
+                      const void* saved, size_t saved_bytes, float* dx, float* const* grads, void* scratch,
+                      size_t scratch_bytes, int64_t B, int64_t T, void* stream) {
+    if (int rc = tt_check(m, params, masks, p, B, T)) return rc;
+    if (B == 0) return fail(B2H_ERR_SHAPE, "b2h_tenc_backward needs B >= 1 (the gradients of an empty batch are not defined here)");
+    if (!dy || !saved || !scratch) return fail(B2H_ERR_INVALID, "dy / saved / scratch is NULL");
+    if (!grads) return fail(B2H_ERR_INVALID, "grads is NULL");
+    if (int rc = check_device(m->device)) return rc;
+    if (misaligned(dy, 16) || misaligned(saved, 16) || misaligned(scratch, 16) || (dx && misaligned(dx, 16)))
+        return fail(B2H_ERR_INVALID, "dy, dx, the saved buffer and the scratch must be 16-byte aligned");
+    const int64_t N = B * T;
+    const size_t need_saved = tt_saved_bytes(m->nlayers, N), need = tt_scratch_bytes(N);
+    if (saved_bytes < need_saved) return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tenc_train_bytes");
+    if (scratch_bytes < need)
+        return fail(B2H_ERR_INVALID, "scratch smaller than b2h_tenc_train_bytes (" + std::to_string(need) + " B)");
+    const int ng = 4 + 12 * m->nlayers;
+    std::vector<TtOut> outs;
+    for (int i = 0; i < ng; ++i) {
+        if (!grads[i]) return fail(B2H_ERR_INVALID, "grads[" + std::to_string(i) + "] is NULL");
+        if (misaligned(grads[i], 4)) return fail(B2H_ERR_INVALID, "grads must be 4-byte aligned");
+        outs.push_back({grads[i], tt_param_floats(m, i + 1) * 4});
+    }
+    if (dx) outs.push_back({dx, (size_t)N * kInCh * 4});
+    outs.push_back({scratch, need});
+    if (int rc = tt_check_overlap(m, params, masks, N, T, outs, {{dy, (size_t)N * kOutCh * 4}, {saved, need_saved}})) return rc;
+
+    hipStream_t st = (hipStream_t)stream;
+    const float sc = tt_scale(p);
+    auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
+    float* S = const_cast<float*>(static_cast<const float*>(saved)); // read only
+    float* gA = static_cast<float*>(scratch);
+    float* gB = gA + N * kTtD;
+    float* gBm = gB + N * kTtD;
+    float* gC = gBm + N * kTtD;
+    float* gQ = gC + N * kTtD;
+    float* slabs = gQ + N * 3 * kTtD;
+    const float* X0 = S;
+    const float* H0 = S + N * kInCh;
+    // hidden2pose_projection (HandPoseModels.py:173)
+    const int oh = 3 + 12 * m->nlayers;
+    const float* Hlast = tt_layer(S, N, m->nlayers - 1).H2;
+    tt_linear_dw(st, dy, Hlast, slabs, N, kTtD, kOutCh, grads[oh - 1], grads[oh]);
+    tt_linear_dx(st, dy, params[oh], gA, N, kTtD, kOutCh, nullptr, nullptr, 1.f, nullptr);
+    for (int l = m->nlayers - 1; l >= 0; --l) {
+        const float* const* w = params + 3 + 12 * l;
+        float* const* g = grads + 2 + 12 * l;
+        const TtLayer L = tt_layer(S, N, l);
+        const float* Hin = l ? tt_layer(S, N, l - 1).H2 : H0;
+        // norm2: gA = dH2 -> gB = dR2 (also dH1 through the residual), gBm = dR2 through drop2
+        tt_layernorm_bwd(st, gA, L.R2, L.ST + 2, w[10], gB, gBm, mk(4 + 4 * l), sc, slabs, N, g[10], g[11]);
+        const float* dF = masks ? gBm : gB;
+        tt_linear_dw(st, dF, L.F1, slabs, N, kTtD, kTtD, g[6], g[7]);
+        tt_linear_dx(st, dF, w[6], gC, N, kTtD, kTtD, L.F1, nullptr, masks ? sc : 1.f, nullptr); // through drop_ff and ReLU
+        tt_linear_dw(st, gC, L.H1, slabs, N, kTtD, kTtD, g[4], g[5]);
+        tt_linear_dx(st, gC, w[4], gA, N, kTtD, kTtD, nullptr, nullptr, 1.f, gB);                // gA = dH1
+        // norm1: gA -> gB = dR1 (also dH_in through the residual), gBm through drop1
+        tt_layernorm_bwd(st, gA, L.R1, L.ST, w[8], gB, gBm, mk(2 + 4 * l), sc, slabs, N, g[8], g[9]);
+        const float* dA = masks ? gBm : gB;
+        tt_linear_dw(st, dA, L.O, slabs, N, kTtD, kTtD, g[2], g[3]);
+        tt_linear_dx(st, dA, w[2], gC, N, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);           // gC = dO
+        hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes((int)T, true), st,
+                           L.QKV, gC, mk(1 + 4 * l), sc, gQ, (int)T);
+        tt_linear_dw(st, gQ, Hin, slabs, N, kTtD, 3 * kTtD, g[0], g[1]);
+        tt_linear_dx(st, gQ, w[0], gA, N, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, gB);            // gA = dH_in
+    }
+    // pose2hidden_projection (:171) and the positional encoding's dropout (:101-103)
+    tt_linear_dw(st, gA, X0, slabs, N, kInCh, kTtD, grads[0], grads[1]);
+    if (dx) tt_linear_dx(st, gA, params[1], dx, N, kInCh, kTtD, nullptr, mk(0), sc, nullptr);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
 }
 
 } // extern "C"

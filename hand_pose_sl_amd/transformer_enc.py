@@ -5,8 +5,16 @@ Same constructor `TransformerEnc(ninp, nhead, nhid, nout, nlayers, dropout=0.5)`
 `state_dict` (the torch.nn containers are built in the reference's order, so a seeded default
 init is identical and its checkpoints load as they are); `model(src)` with src float32
 (B, T, 12, 2) -> float32 (B, T, 21, 2).  The torch containers only hold parameters: the forward
-runs through the C ABI (`b2h_tenc_forward`).  Inference only; only the geometry the reference's
-CLIs construct (ninp=24, nhead=4, nhid=128, nout=42; infer_utterance.py:99-101) is implemented.
+runs through the C ABI (`b2h_tenc_forward`).  Only the geometry the reference's CLIs construct
+(ninp=24, nhead=4, nhid=128, nout=42; infer_utterance.py:99-101) is implemented.
+
+Training: in training mode with autograd enabled and a parameter or the input requiring a gradient,
+`model(src)` runs `_TencTrainFn` -- an exact-fp32 HIP forward and backward (b2h_tenc_train_forward /
+b2h_tenc_backward, kernel_tenc_train.h) that read the parameters' own storage -- so the reference's loop
+body (steps/traintest.py:87-121) runs unchanged with any torch optimizer.  The dropout keep-masks are
+drawn by torch on the model's device (`_draw_dropout_masks`; they follow torch.manual_seed) and handed
+to the kernels.  Every other call (eval mode or no_grad) runs the inference kernels selected by
+`precision`.  No path ever falls back to PyTorch ops.
 """
 import ctypes
 import math
@@ -42,7 +50,11 @@ class TransformerEnc(nn.Module):
     """`precision` (not in the reference; keyword only): "fp32" = fp32 operands on the matrix cores
     (default); "f16x3" = every Linear operand split into f16 hi + lo, three f16 MFMAs per product
     with fp32 accumulation: fp32-grade error at 3/16 of the matrix cycles, for activations and
-    weights inside the f16 range (|x| < 65504)."""
+    weights inside the f16 range (|x| < 65504).
+
+    Training (model.train(), autograd on, a parameter or the input requires grad): always exact fp32 on the
+    vector ALU, whatever `precision` says, with dropout probability `pos_encoder.dropout.p` everywhere as in the
+    reference; gradients as accurate as the reference's own fp32 CPU training (tests/test_tenc_train_gpu.py)."""
 
     def __init__(self, ninp, nhead, nhid, nout, nlayers, dropout=0.5, *, precision="fp32"):
         super().__init__()
@@ -83,23 +95,35 @@ class TransformerEnc(nn.Module):
         t.append(h2p["bias"])
         return t
 
-    def _ensure_handle(self):
-        dev = self._modules["pose2hidden_projection"]._parameters["weight"].device
+    def _device(self):
+        return self._modules["pose2hidden_projection"]._parameters["weight"].device
+
+    def _ensure_created(self):
+        """The native model on the parameters' device and for the pe table's max_len, without packed weights
+        (all the training path needs)."""
+        dev = self._device()
         if dev.type != "cuda":
             raise RuntimeError("hand_pose_sl_amd.TransformerEnc runs on an MI355X only: call model.to('cuda') "
                                "first (there is no CPU path in the product)")
         lib = _lib.load()
-        tensors = self._tensors()
         # the handle is made for one device and one max_len (b2h_tenc_load_weights reads max_len rows of pe)
-        key = (dev.index, int(tensors[0].shape[0])) + tuple((p.data_ptr(), p._version) for p in tensors)
-        if self._handle is not None and key == self._packed_key:
+        made = (dev.index, int(self._modules["pos_encoder"]._buffers["pe"].shape[0]))
+        if self._handle is None or self.__dict__.get("_handle_key") != made:
+            self._free()
+            with torch.cuda.device(dev):
+                h = ctypes.c_void_p()
+                _lib.check(lib.b2h_tenc_create(*self._geom, made[1], ctypes.byref(h)))
+            self.__dict__["_handle"] = h
+            self.__dict__["_handle_key"] = made
+        return lib, dev
+
+    def _ensure_handle(self):
+        lib, dev = self._ensure_created()
+        tensors = self._tensors()
+        key = self.__dict__["_handle_key"] + tuple((p.data_ptr(), p._version) for p in tensors)
+        if key == self._packed_key:
             return lib
         with torch.cuda.device(dev):
-            if self._handle is None or self._packed_key is None or self._packed_key[:2] != key[:2]:
-                self._free()
-                h = ctypes.c_void_p()
-                _lib.check(lib.b2h_tenc_create(*self._geom, key[1], ctypes.byref(h)))
-                self.__dict__["_handle"] = h
             ps = [p.detach().to(torch.float32).contiguous() for p in tensors]
             torch.cuda.current_stream(dev).synchronize()
             arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
@@ -115,17 +139,66 @@ class TransformerEnc(nn.Module):
                 pass
             self.__dict__["_handle"] = None
             self.__dict__["_packed_key"] = None
+            self.__dict__["_handle_key"] = None
 
     def __del__(self):
         self._free()
+
+    def _wants_grad(self, src):
+        """The training path's condition: training mode, autograd on, a parameter or the input needs a gradient."""
+        return (self.training and torch.is_grad_enabled() and
+                (src.requires_grad or any(p.requires_grad for p in self._tensors()[1:])))
+
+    def _check_input(self, src):
+        if src.dim() != 4 or src.shape[2] * src.shape[3] != self.ninp:
+            raise RuntimeError(f"expected input of shape (B, T, {self.ninp // 2}, 2), got {tuple(src.shape)}")
+        return src.to(device=self._device(), dtype=torch.float32, non_blocking=True).contiguous()
+
+    def _draw_dropout_masks(self, B, T):
+        """The keep-masks of one training forward: uint8, 1 = keep with probability 1 - p, drawn on the model's
+        device with torch's generator (so they follow torch.manual_seed) in this fixed order: `pos` (B, T, 24);
+        then layer by layer `attn` (B, 4, T, T), `drop1`, `ff`, `drop2` (B, T, 128 each), keyed (layer, name).
+        An empty dict at p = 0."""
+        p = float(self._modules["pos_encoder"]._modules["dropout"].p)
+        if p == 0.0:
+            return {}
+        dev = self._device()
+
+        def draw(*shape):
+            return (torch.rand(shape, device=dev) >= p).to(torch.uint8)
+
+        masks = {"pos": draw(B, T, self.ninp)}
+        nhead, nhid = self._geom[1], self._geom[2]
+        for l in range(self._geom[4]):
+            masks[(l, "attn")] = draw(B, nhead, T, T)
+            for name in ("drop1", "ff", "drop2"):
+                masks[(l, name)] = draw(B, T, nhid)
+        return masks
+
+    def _forward_train(self, src, masks):
+        """The differentiable forward (`_TencTrainFn`) with the given keep-masks (`_draw_dropout_masks`)."""
+        x = self._check_input(src)
+        p = float(self._modules["pos_encoder"]._modules["dropout"].p)
+        if (p > 0.0) != bool(masks):
+            raise ValueError("masks must be given exactly when the dropout probability is > 0")
+        order = []
+        if masks:
+            B, T = x.shape[0], x.shape[1]
+            order = [("pos", (B, T, self.ninp))]
+            for l in range(self._geom[4]):
+                order.append(((l, "attn"), (B, self._geom[1], T, T)))
+                order += [((l, name), (B, T, self._geom[2])) for name in ("drop1", "ff", "drop2")]
+            for key, shape in order:
+                m = masks[key]
+                if m.shape != shape or m.dtype != torch.uint8 or m.device != x.device or not m.is_contiguous():
+                    raise RuntimeError(f"mask {key}: expected a contiguous uint8 tensor of shape {shape} on {x.device}")
+        tensors = self._tensors()
+        return _TencTrainFn.apply(self, p, [masks[k] for k, _ in order], x, tensors[0], *tensors[1:])
 
     def _run(self, src, flags, factor, n_frames):
         lib = self._ensure_handle()
         if src.dim() != 4 or src.shape[2] * src.shape[3] != self.ninp:
             raise RuntimeError(f"expected input of shape (B, T, {self.ninp // 2}, 2), got {tuple(src.shape)}")
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError("hand_pose_sl_amd.TransformerEnc is inference-only: call model.eval() and wrap "
-                               "the call in torch.no_grad()")
         dev = self._modules["pose2hidden_projection"]._parameters["weight"].device
         x = src.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
         B, T = x.shape[0], x.shape[1]
@@ -156,6 +229,9 @@ class TransformerEnc(nn.Module):
         return y
 
     def forward(self, src):
+        if self._wants_grad(src):
+            x = self._check_input(src)
+            return self._forward_train(x, self._draw_dropout_masks(x.shape[0], x.shape[1]))
         return self._run(src, 0, 1.0, None)
 
     def forward_fused(self, body, n_frames=None, dif_encoding=True, normalize=True, denormalize=True,
@@ -164,7 +240,74 @@ class TransformerEnc(nn.Module):
         the model's own first and last kernel: ChestDifference + /factor (steps/utils.py:180-210) on the
         rows as they enter (before the positional encoding, HandPoseModels.py:167) -> the encoder ->
         x factor (traintest.py:270-271) and the optional tail mask (utils.py:309-312) in the store of
-        hidden2pose_projection's output.  Same flags as ConvModel.forward_fused."""
+        hidden2pose_projection's output.  Same flags as ConvModel.forward_fused.  Inference only."""
+        if self._wants_grad(body):
+            raise RuntimeError("TransformerEnc.forward_fused is inference-only (no gradient): call model.eval() or wrap "
+                               "the call in torch.no_grad(); train through model(x), which is differentiable")
         flags = ((_lib.PRE_CHEST_DIFF if dif_encoding else 0) | (_lib.PRE_NORMALIZE if normalize else 0) |
                  (_lib.POST_DENORMALIZE if denormalize else 0) | (_lib.POST_MASK_TAIL if mask_tail else 0))
         return self._run(body, flags, factor, n_frames)
+
+
+def _ptrs(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _aligned(t):
+    """The kernels' 16-byte vector accesses: a contiguous slice of a larger batch may start anywhere."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _TencTrainFn(torch.autograd.Function):
+    """y = TransformerEnc(x) in training mode with its gradient: b2h_tenc_train_forward / b2h_tenc_backward
+    (exact fp32, kernel_tenc_train.h).  The parameters go in as themselves (their own data_ptr, saved for
+    backward, so autograd's version check catches an in-place edit between forward and backward).  The context
+    keeps the saved-activation buffer and the masks alive; the backward needs neither x nor y (the reference's
+    loop overwrites the prediction's tail in place before the loss)."""
+
+    @staticmethod
+    def forward(ctx, model, p, masks, x, pe, *params):
+        for t in (pe,) + params:
+            if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("training needs contiguous float32 parameters on the input's device")
+        lib, dev = model._ensure_created()
+        x = _aligned(x)
+        B, T = x.shape[0], x.shape[1]
+        y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=x.device)
+        nbytes = lib.b2h_tenc_train_bytes(model._handle, B, T, 0)
+        saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
+        with _lib.on_device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.b2h_tenc_train_forward(model._handle, _ptrs((pe,) + params), ctypes.c_void_p(x.data_ptr()),
+                                                  _ptrs(masks) if masks else None, p, ctypes.c_void_p(y.data_ptr()),
+                                                  ctypes.c_void_p(saved.data_ptr()), nbytes, B, T, ctypes.c_void_p(st)))
+        ctx.model, ctx.p, ctx.masks, ctx.shape = model, p, masks, (B, T)
+        ctx.save_for_backward(saved, pe, *params)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        saved, pe, *params = ctx.saved_tensors
+        model, masks = ctx.model, ctx.masks
+        need_dx = ctx.needs_input_grad[3]
+        B, T = ctx.shape
+        dev = saved.device
+        if B == 0:
+            grads = [torch.zeros_like(t) for t in params]
+            dx = torch.zeros((B, T, 12, 2), dtype=torch.float32, device=dev) if need_dx else None
+        else:
+            lib, dev = model._ensure_created()
+            dy = _aligned(dy.to(torch.float32).contiguous())   # autograd may hand over an expanded / CopySlices gradient
+            grads = [torch.empty_like(t) for t in params]
+            dx = torch.empty((B, T, 12, 2), dtype=torch.float32, device=dev) if need_dx else None
+            nbytes = lib.b2h_tenc_train_bytes(model._handle, B, T, 1)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            with _lib.on_device(dev):
+                st = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(lib.b2h_tenc_backward(model._handle, _ptrs([pe] + params), _ptrs(masks) if masks else None,
+                                                 ctx.p, ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(saved.data_ptr()),
+                                                 saved.numel(), ctypes.c_void_p(dx.data_ptr()) if dx is not None else None,
+                                                 _ptrs(grads), ctypes.c_void_p(ws.data_ptr()), nbytes, B, T,
+                                                 ctypes.c_void_p(st)))
+        return (None, None, None, dx, None) + tuple(g if ctx.needs_input_grad[5 + i] else None for i, g in enumerate(grads))

@@ -200,7 +200,8 @@ int b2h_weighted_l1_backward(const float* pred, const float* target, const float
 /* TransformerEnc -------------------------------------------
  * The reference's second text-free body->hand model, `TransformerEnc(ninp, nhead, nhid, nout,
  * nlayers, dropout)` (HandPoseModels.py:118-178), as its CLIs build it: ninp = 24, nhead = 4,
- * nhid = 128, nout = 42 (infer_utterance.py:99-101).  Inference only (dropout = identity).
+ * nhid = 128, nout = 42 (infer_utterance.py:99-101).  The entry points of this block are the inference path
+ * (dropout = identity); training is b2h_tenc_train_forward / b2h_tenc_backward below.
  * b2h_tenc_create accepts exactly that geometry, 1 <= nlayers <= 16, 1 <= max_len <= 128
  * (100 in the reference, :125) and returns B2H_ERR_UNSUPPORTED for anything else. */
 typedef struct b2h_tenc b2h_tenc;
@@ -242,6 +243,55 @@ int b2h_tenc_forward(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T
 int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, int64_t T, int flags,
                            float factor, const int64_t* n_frames, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* Training (TransformerEnc) ----------------------------------------------------
+ * The reference trains TransformerEnc with the same loop body as ConvModel (steps/traintest.py:87-121), the
+ * model built with dropout = --transformer-dropout.  These entry points are its forward in .train() mode and
+ * its backward (HandPoseModels.py:154-178 under autograd: PositionalEncoding :101-103 with its dropout,
+ * pose2hidden_projection, torch's post-norm nn.TransformerEncoderLayer with ReLU, hidden2pose_projection).
+ * All arithmetic is exact fp32 on the vector ALU, whatever b2h_tenc_set_kernel selected.  The parameters are
+ * read straight from the caller's tensors (b2h_tenc_load_weights is neither needed nor called), so an
+ * optimizer may update them in place between launches.
+ *   params: host array of the 5 + 12*nlayers device fp32 tensors in the order of b2h_tenc_load_weights
+ *           (pos_encoder.pe first), 4-byte aligned.
+ *   p     : the dropout probability (the reference passes one value everywhere), 0 <= p <= 1.
+ *   masks : NULL when p == 0 (nothing is dropped or scaled); else a host array of 1 + 4*nlayers device
+ *           uint8 keep-masks (1 = keep; kept values are scaled by 1 / (1 - p), everything is dropped at
+ *           p == 1), drawn by the caller:
+ *             pos (B, T, 24); then per layer: attn (B, 4, T, T) on the softmax probabilities,
+ *             drop1 (B, T, 128) on out_proj's output, ff (B, T, 128) after linear1's ReLU,
+ *             drop2 (B, T, 128) on linear2's output.
+ * Like b2h_tenc_forward they are stream-ordered and asynchronous: none synchronises, allocates or reads
+ * device memory on the host, so they can be captured into a HIP graph.  1 <= T <= max_len; x, y, dy, dx, the
+ * saved buffer and the scratch must be 16-byte aligned and no output may overlap another operand
+ * (B2H_ERR_INVALID). */
+
+/* Sizes of what autograd keeps for the reference between `prediction = model(body_kp)` and `loss.backward()`
+ * (steps/traintest.py:94,119: the activations of HandPoseModels.py:154-178), which the caller owns here.
+ * Bytes a (B, T) batch needs: which = 0, the saved-activation buffer b2h_tenc_train_forward fills for
+ * b2h_tenc_backward (608 + 4624*nlayers bytes per frame); which = 1, the scratch of b2h_tenc_backward.
+ * 0 for a NULL model, B < 1, T < 1 or another `which`. */
+size_t b2h_tenc_train_bytes(const b2h_tenc* m, int64_t B, int64_t T, int which);
+/* y = TransformerEnc(x) in .train() mode with the given dropout masks, HandPoseModels.py:154-178:
+ * x (B, T, 12, 2) -> y (B, T, 21, 2), device fp32; fills `saved` (device, >= b2h_tenc_train_bytes(m, B, T, 0)).
+ * B == 0 is a no-op. */
+int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float* x, const uint8_t* const* masks,
+                           float p, float* y, void* saved, size_t saved_bytes, int64_t B, int64_t T, void* stream);
+/* loss.backward() through TransformerEnc.forward (HandPoseModels.py:154-178 under autograd,
+ * traintest.py:111-121), B >= 1.  Needs neither x nor y: the loop overwrites the prediction's tail in place
+ * (mask_output, steps/utils.py:309-312) before the loss.
+ *   masks, p: the same as in the forward;  dy: device fp32 (B, T, 21, 2), dL/dy
+ *   saved   : what b2h_tenc_train_forward wrote for this batch (read only)
+ *   dx      : device fp32 (B, T, 12, 2) dL/dx, or NULL
+ *   grads   : host array of 4 + 12*nlayers device fp32 tensors shaped like params without pe (a buffer: no
+ *             gradient), OVERWRITTEN (not accumulated)
+ *   scratch : device, >= b2h_tenc_train_bytes(m, B, T, 1); its prior contents do not matter.
+ * Deterministic: the per-workgroup partial sums of the parameter gradients depend on (B, T) only and are
+ * added in a fixed order by a second kernel (no atomics), so the same inputs give the same bits on any
+ * device and stream; dx of a sequence does not depend on the other sequences of the batch. */
+int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* const* masks, float p,
+                      const float* dy, const void* saved, size_t saved_bytes, float* dx, float* const* grads,
+                      void* scratch, size_t scratch_bytes, int64_t B, int64_t T, void* stream);
 
 /* Introspection / measurement -------------------------------------------- */
 
