@@ -22,6 +22,7 @@
 #include "kernel_mfma3w.h"
 #include "kernel_tenc.h"
 #include "kernel_tenc_train.h"
+#include "kernel_tpt.h"
 #include "kernel_train.h"
 #include "kernel_valu.h"
 
@@ -587,7 +588,7 @@ namespace {
 // rows [r0, r0 + nout) of W (*, k) row-major fp32 -> [mt][g][lane][4] with
 // W[r0 + 16mt + (lane&15)][16g + 4(lane>>4) + j], followed by bias, gamma, beta (128 each)
 int pack_blob(TencBlob& B, const float* w, const float* b, int r0, int nout, int k, const float* gamma,
-              const float* beta) {
+              const float* beta, bool with_f16 = true) {
     B.kgroups = (k + 15) / 16;
     B.mtiles = (nout + 15) / 16;
     B.nout = nout;
@@ -605,7 +606,7 @@ int pack_blob(TencBlob& B, const float* w, const float* b, int r0, int nout, int
     if (gamma) std::memcpy(blob.data() + nw + kTencD, gamma, kTencD * 4);
     if (beta) std::memcpy(blob.data() + nw + 2 * kTencD, beta, kTencD * 4);
     int rc = B.buf.upload(blob.data(), blob.size() * 4);
-    if (rc) return rc;
+    if (rc || !with_f16) return rc; // (TextPoseTransformer is fp32 only)
     // f16 hi/lo fragments for v_mfma_f32_16x16x32_f16: [part][mt][g][lane][8] with k-slot (g, q, j)
     // = input feature 32g + 16(j>>2) + 4q + (j&3) (kernel_tenc.h), then the same fp32 parameters
     B.kgroups32 = (k + 31) / 32;
@@ -853,6 +854,293 @@ int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, 
     if ((flags & kPostMask) && !n_frames) return fail(B2H_ERR_INVALID, "B2H_POST_MASK_TAIL needs n_frames");
     FusedArgs fa{flags, factor, n_frames};
     return tenc_launch(m, body, y, B, T, fa, workspace, workspace_bytes, stream);
+}
+
+} // extern "C"
+
+// ---- TextPoseTransformer (kernel_tpt.h) -----------------------------------------------------------------------
+// torch.nn.Transformer(128, 4, n_enc, n_dec, 128) between a token embedding and the two pose projections
+// (HandPoseModels.py:181-230), inference, exact fp32.  Per-frame work is b2h_tenc_chain<false> by descriptors.
+struct b2h_tpt {
+    int n_tokens = 0, n_enc = 0, n_dec = 0, device = 0, num_cus = 256;
+    bool has_weights = false;
+    DevBuf table;               // token_embedding.weight (n_tokens, 128)
+    DevBuf enc_norm, dec_norm;  // encoder.norm / decoder.norm: gamma (128), beta (128)
+    TencBlob in_proj, out_proj; // pose2hidden_projection, hidden2pose_projection
+    struct EncLayer {
+        TencBlob q, k, v, attn_out, ff1, ff2;
+    };
+    struct DecLayer {
+        TencBlob q, k, v, self_out;       // self_attn; out_proj carries norm1
+        TencBlob cq, ck, cv, cross_out;   // multihead_attn on the encoder memory; out_proj carries norm2
+        TencBlob ff1, ff2;                // linear2 carries norm3
+    };
+    std::vector<EncLayer> enc;
+    std::vector<DecLayer> dec;
+};
+
+namespace {
+
+constexpr int kTptMaxLen = 16 * kAttnMaxTiles; // tokens and frames per sequence: one workgroup holds all keys
+
+// Workspace (floats; Ns = B*S token rows, Nt = B*T frame rows).  Every region is written before it is read:
+//   MEM  Ns x 128  encoder residual stream, at the end the memory (after encoder.norm)
+//   OCs  Ns x 128  encoder attention output          QKVs Ns x 384  encoder Q | K | V
+//   MKV  n_dec x (Ns x 256)  K | V of the memory for each decoder layer's multihead_attn
+//   XT   Nt x 128  decoder residual stream           X1   Nt x 128  norm1 output (residual of the cross block)
+//   OCt  Nt x 128  attention output (self, cross)    QC   Nt x 128  cross-attention query
+//   QKVt Nt x 384  decoder self-attention Q | K | V
+constexpr int64_t kTptTokenFloats = 5 * kTencD, kTptTokenLayerFloats = 2 * kTencD, kTptFrameFloats = 7 * kTencD;
+struct TptWs {
+    float *MEM, *OCs, *QKVs, *MKV, *XT, *X1, *OCt, *QC, *QKVt;
+};
+TptWs tpt_ws(void* workspace, int64_t Ns, int64_t Nt, int n_dec) {
+    TptWs w;
+    w.MEM = reinterpret_cast<float*>(workspace);
+    w.OCs = w.MEM + Ns * kTencD;
+    w.QKVs = w.OCs + Ns * kTencD;
+    w.MKV = w.QKVs + Ns * 3 * kTencD;
+    w.XT = w.MKV + Ns * kTptTokenLayerFloats * n_dec;
+    w.X1 = w.XT + Nt * kTencD;
+    w.OCt = w.X1 + Nt * kTencD;
+    w.QC = w.OCt + Nt * kTencD;
+    w.QKVt = w.QC + Nt * kTencD;
+    return w;
+}
+
+using AttnCrossKernel = void (*)(const float*, int, int, const float*, int, int, int, float*, int, int);
+constexpr AttnCrossKernel kAttnCross[kAttnMaxTiles] = {b2h_attn_cross_f32<1>, b2h_attn_cross_f32<2>, b2h_attn_cross_f32<3>,
+                                                       b2h_attn_cross_f32<4>, b2h_attn_cross_f32<5>, b2h_attn_cross_f32<6>,
+                                                       b2h_attn_cross_f32<7>, b2h_attn_cross_f32<8>};
+
+ChainStage tpt_stage(const TencBlob& B, int type, float* out, int ldo) {
+    return ChainStage{(const float*)B.buf.p, out, type, B.mtiles, B.kgroups, ldo, B.nout, B.mtiles * B.kgroups * 64};
+}
+
+// (n, ldx) rows entering a chain, with the (n, 128) residual rows of a leading ST_RESLN_GLOBAL stage
+ChainArgs tpt_rows(const float* x, int ldx, const float* res, int64_t n) {
+    ChainArgs a{};
+    a.x = x; a.ldx = ldx; a.kgroups0 = (ldx + 15) / 16; a.kvalid = ldx; a.T = 1; a.Tseq = 1;
+    a.res = res; a.n = n; a.factor = 1.0f;
+    return a;
+}
+
+void tpt_add(ChainArgs& a, const TencBlob& B, int type, float* out, int ldo = kTencD) {
+    a.st[a.nstages++] = tpt_stage(B, type, out, ldo);
+}
+
+void tpt_add_qkv(ChainArgs& a, const TencBlob& q, const TencBlob& k, const TencBlob& v, float* QKV) {
+    tpt_add(a, q, ST_STORE, QKV, 3 * kTencD);
+    tpt_add(a, k, ST_STORE, QKV + kTencD, 3 * kTencD);
+    tpt_add(a, v, ST_STORE, QKV + 2 * kTencD, 3 * kTencD);
+}
+
+void tpt_chain(const b2h_tpt* m, const ChainArgs& a, hipStream_t st) {
+    // persistent: one workgroup per CU walks over the 128-row blocks (launch_chain)
+    const int64_t blocks = std::min<int64_t>((a.n + 16 * kLinWaves - 1) / (16 * kLinWaves), m->num_cus);
+    hipLaunchKernelGGL(b2h_tenc_chain<false>, dim3((unsigned)blocks), dim3(64 * kLinWaves), (size_t)kChainLdsBytes, st, a);
+}
+
+void tpt_layernorm(const DevBuf& gb, float* x, int64_t n, hipStream_t st) {
+    const float* g = (const float*)gb.p;
+    hipLaunchKernelGGL(b2h_tpt_layernorm, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, st, x, g, g + kTencD, x, n);
+}
+
+void tpt_self_attn(const float* QKV, float* OC, int64_t B, int T, hipStream_t st) {
+    const int nt = (T + 15) / 16;
+    hipLaunchKernelGGL(kAttn[nt - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nt), (size_t)attn_f32_lds_bytes(nt), st,
+                       QKV, OC, T);
+}
+
+} // namespace
+
+extern "C" {
+
+int b2h_tpt_create(int n_tokens, int ninp, int nhead, int nhid, int nout, int n_enc_layers, int n_dec_layers,
+                   b2h_tpt** out) {
+    if (!out) return fail(B2H_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (ninp != kInCh || nhead != kTencHeads || nhid != kTencD || nout != kOutCh)
+        return fail(B2H_ERR_UNSUPPORTED, "TextPoseTransformer: only n_joints*joints_dim=24, nhead=4, nhid=128, nout=42 "
+                                         "(run.py:148-151) is implemented");
+    if (n_enc_layers < 1 || n_enc_layers > 16 || n_dec_layers < 1 || n_dec_layers > 16 || n_tokens < 1)
+        return fail(B2H_ERR_UNSUPPORTED, "TextPoseTransformer: 1 <= n_enc_layers, n_dec_layers <= 16 and n_tokens >= 1");
+    std::unique_ptr<b2h_tpt> m(new b2h_tpt()); // released to the caller only on success
+    if (int rc = probe_device(m->device, m->num_cus)) return rc;
+    m->n_tokens = n_tokens;
+    m->n_enc = n_enc_layers;
+    m->n_dec = n_dec_layers;
+    m->enc.resize(n_enc_layers);
+    m->dec.resize(n_dec_layers);
+    *out = m.release();
+    return B2H_OK;
+}
+
+int b2h_tpt_destroy(b2h_tpt* m) {
+    delete m;
+    return B2H_OK;
+}
+
+int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int on_device) {
+    if (!m || !tensors) return fail(B2H_ERR_INVALID, "NULL argument");
+    if (count != 9 + 12 * m->n_enc + 18 * m->n_dec)
+        return fail(B2H_ERR_INVALID, "expected 9 + 12*n_enc_layers + 18*n_dec_layers tensors");
+    const size_t D = kTencD;
+    std::vector<size_t> sizes;
+    const auto attn = [&] { for (size_t s : {3 * D * D, 3 * D, D * D, D}) sizes.push_back(s); };
+    const auto tail = [&](int norms) { // linear1, linear2, then the layer's LayerNorms
+        for (size_t s : {D * D, D, D * D, D}) sizes.push_back(s);
+        sizes.insert(sizes.end(), 2 * norms, D);
+    };
+    for (int l = 0; l < m->n_enc; ++l) { attn(); tail(2); }
+    sizes.insert(sizes.end(), 2, D);
+    for (int l = 0; l < m->n_dec; ++l) { attn(); attn(); tail(3); }
+    sizes.insert(sizes.end(), 2, D);
+    for (size_t s : {(size_t)m->n_tokens * D, (size_t)kOutCh * D, (size_t)kOutCh, D * kInCh, D}) sizes.push_back(s);
+    std::vector<std::vector<float>> h(count);
+    for (int i = 0; i < count; ++i) {
+        if (!tensors[i]) return fail(B2H_ERR_INVALID, "tensor pointer is NULL");
+        h[i].resize(sizes[i]);
+        if (on_device) HIP_TRY(hipMemcpy(h[i].data(), tensors[i], sizes[i] * 4, hipMemcpyDeviceToHost));
+        else std::memcpy(h[i].data(), tensors[i], sizes[i] * 4);
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc0 = check_device(m->device)) return rc0;
+    int rc;
+    // the LDS cap is raised here, not in b2h_tpt_forward: the first forward is already capture-safe
+    if ((rc = raise_lds_cap(b2h_tenc_chain<false>, kChainLdsBytes))) return rc;
+    const int Di = kTencD;
+    // one Linear of 128 inputs: rows [r0, r0 + 128) of tensor i with bias i + 1, and the LayerNorm that follows it
+    const auto lin = [&](TencBlob& blob, int i, int r0, int norm) {
+        return pack_blob(blob, h[i].data(), h[i + 1].data(), r0, Di, Di, norm >= 0 ? h[norm].data() : nullptr,
+                         norm >= 0 ? h[norm + 1].data() : nullptr, false);
+    };
+    const auto norm = [&](DevBuf& buf, int i) {
+        std::vector<float> gb(h[i]);
+        gb.insert(gb.end(), h[i + 1].begin(), h[i + 1].end());
+        return buf.upload(gb.data(), gb.size() * 4);
+    };
+    for (int l = 0; l < m->n_enc; ++l) {
+        auto& L = m->enc[l];
+        const int o = 12 * l;
+        if ((rc = lin(L.q, o, 0, -1)) || (rc = lin(L.k, o, Di, -1)) || (rc = lin(L.v, o, 2 * Di, -1)) ||
+            (rc = lin(L.attn_out, o + 2, 0, o + 8)) || (rc = lin(L.ff1, o + 4, 0, -1)) || (rc = lin(L.ff2, o + 6, 0, o + 10)))
+            return rc;
+    }
+    int o = 12 * m->n_enc;
+    if ((rc = norm(m->enc_norm, o))) return rc;
+    o += 2;
+    for (int l = 0; l < m->n_dec; ++l, o += 18) {
+        auto& L = m->dec[l];
+        if ((rc = lin(L.q, o, 0, -1)) || (rc = lin(L.k, o, Di, -1)) || (rc = lin(L.v, o, 2 * Di, -1)) ||
+            (rc = lin(L.self_out, o + 2, 0, o + 12)) || (rc = lin(L.cq, o + 4, 0, -1)) || (rc = lin(L.ck, o + 4, Di, -1)) ||
+            (rc = lin(L.cv, o + 4, 2 * Di, -1)) || (rc = lin(L.cross_out, o + 6, 0, o + 14)) ||
+            (rc = lin(L.ff1, o + 8, 0, -1)) || (rc = lin(L.ff2, o + 10, 0, o + 16)))
+            return rc;
+    }
+    if ((rc = norm(m->dec_norm, o))) return rc;
+    o += 2;
+    if ((rc = m->table.upload(h[o].data(), h[o].size() * 4))) return rc;
+    if ((rc = pack_blob(m->out_proj, h[o + 1].data(), h[o + 2].data(), 0, kOutCh, Di, nullptr, nullptr, false))) return rc;
+    if ((rc = pack_blob(m->in_proj, h[o + 3].data(), h[o + 4].data(), 0, Di, kInCh, nullptr, nullptr, false))) return rc;
+    m->has_weights = true;
+    return B2H_OK;
+}
+
+size_t b2h_tpt_workspace_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T) {
+    if (!m || B < 0 || S < 0 || T < 0) return 0;
+    return ((size_t)B * S * (kTptTokenFloats + kTptTokenLayerFloats * m->n_dec) + (size_t)B * T * kTptFrameFloats) * sizeof(float);
+}
+
+
+int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y, int64_t B, int64_t S, int64_t T,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (!m->has_weights) return fail(B2H_ERR_NO_WEIGHTS, "b2h_tpt_forward before b2h_tpt_load_weights");
+    if (B < 0 || S < 1 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0, S >= 1 and T >= 1");
+    if (S > kTptMaxLen || T > kTptMaxLen)
+        return fail(B2H_ERR_SHAPE, "TextPoseTransformer: S and T are limited to 128 (the reference's datasets feed 40 "
+                                   "tokens and 100 frames, text_pose_dataset.py:467-470)");
+    if (B == 0) return B2H_OK;
+    if (!tokens || !x || !y || !workspace) return fail(B2H_ERR_INVALID, "NULL pointer");
+    if (misaligned(tokens, 8) || misaligned(x, 16) || misaligned(y, 8) || misaligned(workspace, 16))
+        return fail(B2H_ERR_INVALID, "x and workspace must be 16-byte aligned, tokens and y 8-byte aligned");
+    if (workspace_bytes < b2h_tpt_workspace_bytes(m, B, S, T)) return fail(B2H_ERR_INVALID, "workspace too small");
+    const int64_t Ns = B * S, Nt = B * T;
+    // grid limits: attention launches B x heads workgroups, the row kernels 8 rows per workgroup
+    if (B * kTencHeads > 0x7fffffff || std::max(Ns, Nt) / 8 >= 0x7fffffff)
+        return fail(B2H_ERR_SHAPE, "batch too large for one launch");
+    if (int rc = check_device(m->device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const TptWs ws = tpt_ws(workspace, Ns, Nt, m->n_dec);
+
+    // encoder (torch.nn.TransformerEncoder, post-norm, ReLU): token_embedding -> layers -> encoder.norm
+    hipLaunchKernelGGL(b2h_tpt_embed, dim3((unsigned)((Ns * 32 + 255) / 256)), dim3(256), 0, st, tokens,
+                       (const float*)m->table.p, ws.MEM, Ns, m->n_tokens);
+    {
+        ChainArgs a = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
+        tpt_add_qkv(a, m->enc[0].q, m->enc[0].k, m->enc[0].v, ws.QKVs);
+        tpt_chain(m, a, st);
+    }
+    for (int l = 0; l < m->n_enc; ++l) {
+        const auto& L = m->enc[l];
+        tpt_self_attn(ws.QKVs, ws.OCs, B, (int)S, st);
+        ChainArgs a = tpt_rows(ws.OCs, kTencD, ws.MEM, Ns); // exactly TransformerEnc's chain_tail
+        tpt_add(a, L.attn_out, ST_RESLN_GLOBAL, nullptr);
+        tpt_add(a, L.ff1, ST_RELU, nullptr);
+        tpt_add(a, L.ff2, ST_RESLN_REG, ws.MEM);
+        if (l + 1 < m->n_enc) tpt_add_qkv(a, m->enc[l + 1].q, m->enc[l + 1].k, m->enc[l + 1].v, ws.QKVs);
+        tpt_chain(m, a, st);
+    }
+    tpt_layernorm(m->enc_norm, ws.MEM, Ns, st);
+    // K and V of the memory for every decoder layer: two ST_STORE stages per layer, four layers per launch
+    for (int l0 = 0; l0 < m->n_dec; l0 += kChainMaxStages / 2) {
+        ChainArgs a = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
+        for (int l = l0; l < std::min(m->n_dec, l0 + kChainMaxStages / 2); ++l) {
+            float* kv = ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats;
+            tpt_add(a, m->dec[l].ck, ST_STORE, kv, 2 * kTencD);
+            tpt_add(a, m->dec[l].cv, ST_STORE, kv + kTencD, 2 * kTencD);
+        }
+        tpt_chain(m, a, st);
+    }
+
+    // decoder (torch.nn.TransformerDecoder): pose2hidden_projection -> layers -> decoder.norm -> hidden2pose_projection
+    {
+        ChainArgs a = tpt_rows(x, kInCh, nullptr, Nt);
+        tpt_add(a, m->in_proj, ST_SET, ws.XT);
+        tpt_add_qkv(a, m->dec[0].q, m->dec[0].k, m->dec[0].v, ws.QKVt);
+        tpt_chain(m, a, st);
+    }
+    const int nk = (int)((S + 15) / 16), nq = (int)((T + 15) / 16);
+    for (int l = 0; l < m->n_dec; ++l) {
+        const auto& L = m->dec[l];
+        tpt_self_attn(ws.QKVt, ws.OCt, B, (int)T, st);
+        {   // self out_proj + x -> norm1 -> X1; the cross-attention query of X1
+            ChainArgs a = tpt_rows(ws.OCt, kTencD, ws.XT, Nt);
+            tpt_add(a, L.self_out, ST_RESLN_GLOBAL, ws.X1);
+            tpt_add(a, L.cq, ST_STORE, ws.QC);
+            tpt_chain(m, a, st);
+        }
+        hipLaunchKernelGGL(kAttnCross[nk - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nq), (size_t)attn_f32_lds_bytes(nk),
+                           st, ws.QC, kTencD, 0, ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats, 2 * kTencD, 0, kTencD,
+                           ws.OCt, (int)T, (int)S);
+        {   // cross out_proj + X1 -> norm2 -> linear1 ReLU -> linear2 + res -> norm3 -> XT [+ the next layer's Q, K, V]
+            ChainArgs a = tpt_rows(ws.OCt, kTencD, ws.X1, Nt);
+            tpt_add(a, L.cross_out, ST_RESLN_GLOBAL, nullptr);
+            tpt_add(a, L.ff1, ST_RELU, nullptr);
+            tpt_add(a, L.ff2, ST_RESLN_REG, ws.XT);
+            if (l + 1 < m->n_dec) tpt_add_qkv(a, m->dec[l + 1].q, m->dec[l + 1].k, m->dec[l + 1].v, ws.QKVt);
+            tpt_chain(m, a, st);
+        }
+    }
+    tpt_layernorm(m->dec_norm, ws.XT, Nt, st);
+    {
+        ChainArgs a = tpt_rows(ws.XT, kTencD, nullptr, Nt);
+        tpt_add(a, m->out_proj, ST_STORE, y, kOutCh);
+        tpt_chain(m, a, st);
+    }
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
 }
 
 } // extern "C"

@@ -293,6 +293,55 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
                       const float* dy, const void* saved, size_t saved_bytes, float* dx, float* const* grads,
                       void* scratch, size_t scratch_bytes, int64_t B, int64_t T, void* stream);
 
+/* TextPoseTransformer --------------------------------------------------------
+ * The reference's text-conditioned model and the default of its CLIs (`--model TextPoseTransformer`,
+ * run.py:32-36,148-151; infer_utterance.py:27-28,102-103): `TextPoseTransformer(n_tokens, n_joints, joints_dim,
+ * nhead, nhid, nout, n_enc_layers, n_dec_layers, dropout)` (HandPoseModels.py:181-230) = a token embedding (not
+ * scaled), pose2hidden_projection, torch.nn.Transformer(nhid, nhead, n_enc_layers, n_dec_layers, nhid) with the
+ * token embeddings as source and the projected pose as target, hidden2pose_projection.  Post-norm layers, ReLU,
+ * eps 1e-5, both stacks end with their LayerNorm; the reference passes no mask of any kind (:211), so padded
+ * token id 0 is attended like any other, and never applies its two positional encodings.  Inference only
+ * (dropout = identity), exact fp32 on the matrix cores.  Tokenisation stays with the caller: the model's boundary
+ * is integer ids (:201, traintest.py:105-107). */
+typedef struct b2h_tpt b2h_tpt;
+/* Replaces TextPoseTransformer.__init__ (HandPoseModels.py:181-230) as run.py:148-151 calls it.  `ninp` is
+ * n_joints * joints_dim.  Accepts ninp = 24, nhead = 4, nhid = 128, nout = 42, 1 <= n_enc_layers, n_dec_layers
+ * <= 16 and n_tokens >= 1; B2H_ERR_UNSUPPORTED for anything else.  Bound to the current HIP device. */
+int b2h_tpt_create(int n_tokens, int ninp, int nhead, int nhid, int nout, int n_enc_layers, int n_dec_layers,
+                   b2h_tpt** out);
+int b2h_tpt_destroy(b2h_tpt* m);
+/* Replaces load_state_dict for this model (HandPoseModels.py:181-230; traintest.py:62).  `tensors`:
+ * 9 + 12*n_enc_layers + 18*n_dec_layers fp32 contiguous arrays in state_dict order WITHOUT the two `pe` buffers
+ * (token_pos_encoder.pe, pose_pos_encoder.pe: constructed at :187-190, never applied):
+ *   per encoder layer i, transformer.encoder.layers.i.: self_attn.in_proj_weight (384,128), .in_proj_bias (384),
+ *     self_attn.out_proj.weight (128,128), .bias, linear1.weight (128,128), .bias, linear2.weight (128,128), .bias,
+ *     norm1.weight, .bias, norm2.weight, .bias (128 each);
+ *   transformer.encoder.norm.weight, .bias;
+ *   per decoder layer i, transformer.decoder.layers.i.: self_attn.* (4 tensors as above), multihead_attn.* (the same
+ *     4 shapes), linear1.*, linear2.*, norm1.*, norm2.*, norm3.*;
+ *   transformer.decoder.norm.weight, .bias;
+ *   token_embedding.weight (n_tokens,128); hidden2pose_projection.weight (42,128), .bias (42);
+ *   pose2hidden_projection.weight (128,24), .bias (128).
+ * `on_device` as for b2h_load_weights; synchronous; may be called again to replace the weights. */
+int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int on_device);
+/* Bytes of device scratch b2h_tpt_forward needs: a function of (B, S, T) and the layer counts only --
+ * 2560 + 1024*n_dec_layers per token and 3584 per frame.  0 for a NULL model or a negative size. */
+size_t b2h_tpt_workspace_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T);
+/* Replaces TextPoseTransformer.forward(input_tokens, input_pose) (HandPoseModels.py:181-230, :201-222; called at
+ * traintest.py:105-107 and through run.py:148-151):
+ *   tokens : device int64 (B, S) token ids  -- read only.  An id outside [0, n_tokens) never reads outside the
+ *            embedding table: the whole output of ITS sequence becomes NaN, no other sequence is touched
+ *            (nn.Embedding raises on the host; this entry point does not synchronise)
+ *   x      : device fp32 (B, T, 12, 2)      -- read only
+ *   y      : device fp32 (B, T, 21, 2)      -- written
+ * 1 <= S <= 128 and 1 <= T <= 128 (B2H_ERR_SHAPE; the reference's datasets feed S = 40, T = 100:
+ * text_pose_dataset.py:467-470).  B == 0 is a no-op.  x and the workspace must be 16-byte aligned, tokens and y
+ * 8-byte aligned.  `workspace`: device memory of at least b2h_tpt_workspace_bytes(m, B, S, T); its prior contents
+ * do not matter.  Stream-ordered and asynchronous, no atomics: the same inputs give the same bits on any stream,
+ * and a sequence's output does not depend on the rest of the batch. */
+int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y, int64_t B, int64_t S,
+                    int64_t T, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Introspection / measurement -------------------------------------------- */
 
 /* conv_channels, pos_emb and whether weights are loaded. */
