@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import NativeModule, _aligned, _ptrs
 
 
 class LinearPositionalEmbedding(nn.Module):
@@ -48,7 +49,7 @@ vector ALU (b2h_train_forward / b2h_backward), whatever `precision` says; gradie
 reference's own fp32 CPU training (tests/test_train_gpu.py)."""
 
 
-class ConvModel(nn.Module):
+class ConvModel(NativeModule, nn.Module):
     __doc__ = """ConvModel(conv_channels, activation, pos_emb, precision="fp32") -- the reference's constructor
     (HandPoseModels.py:18-37) plus the kernel choice.\n\n""" + PRECISION_NOTES
 
@@ -70,10 +71,9 @@ class ConvModel(nn.Module):
         self.precision = precision
         if precision not in _lib.KERNELS:
             raise ValueError(f"precision must be one of {sorted(_lib.KERNELS)}")
-        self._handle = None
-        self._packed_key = None
+    # ---- native handle (NativeModule) -----------------------------------------------------
+    _NAME, _CREATE, _LOAD, _DESTROY = "ConvModel", "b2h_create", "b2h_load_weights", "b2h_destroy"
 
-    # ---- native handle -----------------------------------------------------
     def _params(self):
         # through the module dictionaries: nn.Module.__getattr__ costs ~0.4 us per hop, and this
         # runs on every forward (weight-replacement check) -- 8 us of a 15 us small-batch call
@@ -85,50 +85,16 @@ class ConvModel(nn.Module):
             out.append(p["bias"])
         return out
 
+    _tensors = _params
+
     def _device(self):
         return self._modules["conv1"]._parameters["weight"].device
 
-    def _ensure_created(self):
-        """The native model on the parameters' device, without packed weights (all the training path needs)."""
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("hand_pose_sl_amd.ConvModel runs on an MI355X only: call "
-                               "model.to('cuda') first (there is no CPU path in the product)")
-        lib = _lib.load()
-        if self._handle is None or self.__dict__.get("_handle_dev") != dev.index:
-            self._free()
-            with torch.cuda.device(dev):
-                h = ctypes.c_void_p()
-                _lib.check(lib.b2h_create(self.conv_channels, b"ReLU", int(self.pos_emb is not None),
-                                          ctypes.byref(h)))
-            self._handle = h
-            self._handle_dev = dev.index
-        return lib, dev
+    def _create_args(self):
+        return self.conv_channels, b"ReLU", int(self.pos_emb is not None)
 
-    def _ensure_handle(self):
-        lib, dev = self._ensure_created()
-        key = (dev.index,) + tuple((p.data_ptr(), p._version) for p in self._params())
-        if key == self._packed_key:
-            return lib
-        with torch.cuda.device(dev):
-            ps = [p.detach().to(torch.float32).contiguous() for p in self._params()]
-            torch.cuda.current_stream(dev).synchronize()
-            _lib.check(lib.b2h_load_weights(self._handle, *[ctypes.c_void_p(p.data_ptr()) for p in ps], 1))
-        self._packed_key = key
-        return lib
-
-    def _free(self):
-        if self.__dict__.get("_handle") is not None:
-            try:
-                _lib.load().b2h_destroy(self._handle)
-            except Exception:
-                pass
-            self.__dict__["_handle"] = None
-            self.__dict__["_packed_key"] = None
-            self.__dict__["_handle_dev"] = None
-
-    def __del__(self):
-        self._free()
+    def _load_args(self, ps):
+        return [ctypes.c_void_p(p.data_ptr()) for p in ps] + [1]
 
     # ---- forward -------------------------------------------------------------
     def kernel_name(self, precision=None):
@@ -222,15 +188,6 @@ class ConvModel(nn.Module):
                                             _lib.KERNELS[precision or self.precision], int(iters),
                                             ctypes.c_void_p(st), ctypes.byref(ms)))
         return ms.value
-
-
-def _ptrs(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _aligned(t):
-    """The kernels' 16-byte vector accesses: a contiguous slice of a larger batch may start anywhere."""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 class _ConvTrainFn(torch.autograd.Function):

@@ -126,6 +126,38 @@ bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
 
 bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) & (a - 1); }
 
+// An operand of a training entry point: n bytes at p.  `what` names a read-only one in check_overlap's message.
+struct Span {
+    const void* p;
+    size_t n;
+    const char* what = nullptr;
+};
+
+// No output may overlap a read-only operand (an input, a parameter, a mask) or another output.
+int check_overlap(const std::vector<Span>& outs, const std::vector<Span>& read_only) {
+    for (size_t a = 0; a < outs.size(); ++a) {
+        for (const Span& r : read_only)
+            if (overlaps(outs[a].p, outs[a].n, r.p, r.n)) return fail(B2H_ERR_INVALID, std::string("an output overlaps ") + r.what);
+        for (size_t c = a + 1; c < outs.size(); ++c)
+            if (overlaps(outs[a].p, outs[a].n, outs[c].p, outs[c].n)) return fail(B2H_ERR_INVALID, "two outputs overlap");
+    }
+    return B2H_OK;
+}
+
+// Host copies of a model's fp32 tensors (non-NULL; host memory, or memory of the current device) of the given
+// sizes in floats.  Returns after the device is idle: no launch may still read the old packed buffers.
+int fetch_tensors(const float* const* tensors, const std::vector<size_t>& sizes, int on_device,
+                  std::vector<std::vector<float>>& out) {
+    out.resize(sizes.size());
+    for (size_t i = 0; i < sizes.size(); ++i) {
+        out[i].resize(sizes[i]);
+        if (on_device) HIP_TRY(hipMemcpy(out[i].data(), tensors[i], sizes[i] * 4, hipMemcpyDeviceToHost));
+        else std::memcpy(out[i].data(), tensors[i], sizes[i] * 4);
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return B2H_OK;
+}
+
 // The current HIP device, which a new model is bound to: it must be a gfx950.
 int probe_device(int& device, int& num_cus) {
     int n = 0;
@@ -147,9 +179,9 @@ int check_fused(int flags, float factor) {
     return B2H_OK;
 }
 
-// Every kernel that may use more than 64 KB of dynamic LDS gets its cap raised ONCE per device, when
-// weights are loaded -- not inside launch(), so that the very first b2h_forward is already free of
-// runtime calls other than the launch itself and can be captured into a HIP graph.
+// Every kernel that may use more than 64 KB of dynamic LDS gets its cap raised ONCE per device (OncePerDevice),
+// when a model is created or its weights are loaded -- not inside a launch, so that the very first forward is
+// already free of runtime calls other than the launches themselves and can be captured into a HIP graph.
 template <typename K> int raise_lds_cap(K kern, int bytes = 160 * 1024) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     return B2H_OK;
@@ -568,15 +600,27 @@ struct TencBlob {
     int mtiles = 0, kgroups = 0, kgroups32 = 0, nout = 0;
 };
 
+// One torch.nn.TransformerEncoderLayer (post-norm, ReLU): attn_out carries norm1, ff2 carries norm2.
+struct EncLayer {
+    TencBlob q, k, v, attn_out, ff1, ff2;
+};
+
+// Floats of its twelve tensors in state_dict order: self_attn in_proj weight, bias; out_proj; linear1; linear2;
+// norm1; norm2 (d_model = dim_feedforward = 128).  A decoder layer is made of the same pieces.
+constexpr size_t kDD = (size_t)kTencD * kTencD;
+constexpr size_t kEncLayerFloats[12] = {3 * kDD, 3 * kTencD, kDD, kTencD, kDD, kTencD, kDD, kTencD, kTencD, kTencD, kTencD, kTencD};
+
 struct b2h_tenc {
     int nlayers = 0, max_len = 0, device = 0;
     bool has_weights = false;
     int kernel = B2H_TENC_F32;
     float w_absmax = 0.f; // largest |parameter| (NaN counts as inf): B2H_TENC_F16X3 needs < 65504
+    // floats of the 5 + 12*nlayers tensors in the order of b2h_tenc_load_weights: pe, pose2hidden_projection, the
+    // layers, hidden2pose_projection
+    std::vector<size_t> sizes;
     DevBuf pe;
     TencBlob in_proj, out_proj;
-    struct Layer {
-        TencBlob q, k, v, attn_out, ff1, ff2;
+    struct Layer : EncLayer {
         TencBlob qkv_head[kTencHeads]; // rows of Q_h, K_h, V_h of in_proj_weight: the projection inside b2h_attn_qkv_h3
     };
     int num_cus = 256;
@@ -631,19 +675,41 @@ int pack_blob(TencBlob& B, const float* w, const float* b, int r0, int nout, int
     return B.buf16.upload(blob16.data(), blob16.size());
 }
 
-ChainStage stage_of(const b2h_tenc* m, const TencBlob& B, int type, float* out, int ldo) {
-    if (m->kernel == B2H_TENC_F16X3)
-        return ChainStage{(const float*)B.buf16.p, out, type, B.mtiles, B.kgroups32, ldo, B.nout, 2 * B.mtiles * B.kgroups32 * 64};
-    return ChainStage{(const float*)B.buf.p, out, type, B.mtiles, B.kgroups, ldo, B.nout, B.mtiles * B.kgroups * 64};
-}
-
-int launch_chain(b2h_tenc* m, ChainArgs& a, hipStream_t st) {
-    // persistent: one workgroup per CU (134 KB of LDS each) walks over the 128-frame blocks
-    const int64_t blocks = std::min<int64_t>((a.n + 16 * kLinWaves - 1) / (16 * kLinWaves), m->num_cus);
-    hipLaunchKernelGGL(m->kernel == B2H_TENC_F16X3 ? b2h_tenc_chain<true> : b2h_tenc_chain<false>, dim3((unsigned)blocks),
-                       dim3(64 * kLinWaves), (size_t)kChainLdsBytes, st, a);
-    return B2H_OK;
-}
+// One launch of the chain kernel under construction: the rows that enter, then the stages in order.  h3 selects the
+// f16 hi + lo fragments (k-groups of 32) and b2h_tenc_chain<true>, otherwise the fp32 ones (k-groups of 16).
+struct Chain {
+    bool h3 = false;
+    ChainArgs a{};
+    // (n, ldx) rows entering the chain, with the (n, 128) residual rows of a leading ST_RESLN_GLOBAL stage
+    void rows(const float* x, int ldx, const float* res, int64_t n) {
+        a.x = x; a.ldx = ldx; a.kgroups0 = (ldx + 15) / 16; a.kvalid = ldx; a.T = 1;
+        a.res = res; a.n = n;
+    }
+    void add(const TencBlob& B, int type, float* out, int ldo = kTencD) {
+        a.st[a.nstages++] = h3 ? ChainStage{(const float*)B.buf16.p, out, type, B.mtiles, B.kgroups32, ldo, B.nout, 2 * B.mtiles * B.kgroups32 * 64}
+                               : ChainStage{(const float*)B.buf.p, out, type, B.mtiles, B.kgroups, ldo, B.nout, B.mtiles * B.kgroups * 64};
+    }
+    void add_qkv(const TencBlob& q, const TencBlob& k, const TencBlob& v, float* QKV) {
+        add(q, ST_STORE, QKV, 3 * kTencD);
+        add(k, ST_STORE, QKV + kTencD, 3 * kTencD);
+        add(v, ST_STORE, QKV + 2 * kTencD, 3 * kTencD);
+    }
+    // out_proj +res LN1 -> linear1 ReLU -> linear2 +res LN2 -> residual stream `xs` (or nullptr: the rows stay in
+    // registers for the stages that follow) [+ the Q, K, V rows of the layer `next`]
+    void add_layer_tail(const TencBlob& out_proj, const TencBlob& ff1, const TencBlob& ff2, float* xs, const EncLayer* next,
+                        float* QKV) {
+        add(out_proj, ST_RESLN_GLOBAL, nullptr);
+        add(ff1, ST_RELU, nullptr);
+        add(ff2, ST_RESLN_REG, xs);
+        if (next) add_qkv(next->q, next->k, next->v, QKV);
+    }
+    void launch(int num_cus, hipStream_t st) const {
+        // persistent: one workgroup per CU (134 KB of LDS each) walks over the 128-row blocks
+        const int64_t blocks = std::min<int64_t>((a.n + 16 * kLinWaves - 1) / (16 * kLinWaves), num_cus);
+        hipLaunchKernelGGL(h3 ? b2h_tenc_chain<true> : b2h_tenc_chain<false>, dim3((unsigned)blocks), dim3(64 * kLinWaves),
+                           (size_t)kChainLdsBytes, st, a);
+    }
+};
 
 // Attention kernels by query tiles, [nt - 1] with nt = ceil(T / 16) <= 8.  f16x3: b2h_attn_qkv_h3 projects Q, K, V
 // itself.  fp32: b2h_attn_mfma_f32 reads them from the chain's QKV rows.
@@ -656,47 +722,59 @@ constexpr AttnKernel kAttn[kAttnMaxTiles] = {b2h_attn_mfma_f32<1>, b2h_attn_mfma
                                              b2h_attn_mfma_f32<4>, b2h_attn_mfma_f32<5>, b2h_attn_mfma_f32<6>,
                                              b2h_attn_mfma_f32<7>, b2h_attn_mfma_f32<8>};
 
+// The LDS caps of the transformer kernels (inference and training), raised when a TransformerEnc or a
+// TextPoseTransformer is created: here, not in a launch, so that every forward is capture-safe from the first one.
+int set_tenc_kernel_attributes() {
+    static OncePerDevice once;
+    return once([]() -> int {
+        int rc;
+        if ((rc = raise_lds_cap(b2h_tenc_chain<false>, kChainLdsBytes)) || (rc = raise_lds_cap(b2h_tenc_chain<true>, kChainLdsBytes)))
+            return rc;
+        for (int nt = 1; nt <= kAttnMaxTiles; ++nt)
+            if ((rc = raise_lds_cap(kAttnQkvH3[nt - 1], attn_qkv_lds_bytes(nt)))) return rc;
+        if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd))) return rc;
+        return B2H_OK;
+    });
+}
+
+// fp32 self-attention of B sequences of T <= 128 rows: Q | K | V rows (B*T, 384) -> OC (B*T, 128)
+void self_attn_f32(const float* QKV, float* OC, int64_t B, int T, hipStream_t st) {
+    const int nt = (T + 15) / 16;
+    hipLaunchKernelGGL(kAttn[nt - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nt), (size_t)attn_f32_lds_bytes(nt), st,
+                       QKV, OC, T);
+}
+
 // Residual stream XA, attention output OC and (fp32 path) the Q, K, V rows of the next attention; QKV is
 // nullptr on the f16x3 path, whose attention kernel projects them itself.
 struct TencWs {
     float *XA, *OC, *QKV;
 };
 
-void add_qkv(const b2h_tenc* m, ChainArgs& a, int l, float* QKV) {
-    a.st[a.nstages++] = stage_of(m, m->layers[l].q, ST_STORE, QKV, 3 * kTencD);
-    a.st[a.nstages++] = stage_of(m, m->layers[l].k, ST_STORE, QKV + kTencD, 3 * kTencD);
-    a.st[a.nstages++] = stage_of(m, m->layers[l].v, ST_STORE, QKV + 2 * kTencD, 3 * kTencD);
-}
-
 // src + pe -> pose2hidden_projection (HandPoseModels.py:167-169) -> residual stream [+ layer 0's Q, K, V]
-int chain_in(b2h_tenc* m, const float* x, int64_t n, int T, const FusedArgs& fa, const TencWs& ws, hipStream_t st) {
-    ChainArgs a{};
-    a.x = x; a.ldx = kInCh; a.kgroups0 = 2; a.kvalid = kInCh; a.pe = (const float*)m->pe.p; a.T = T;
-    a.res = nullptr; a.n = n; a.nstages = 1;
-    a.flags = fa.flags & (kPreChest | kPreNorm); a.factor = fa.factor; a.Tseq = T;
-    a.st[0] = stage_of(m, m->in_proj, ST_SET, ws.XA, kTencD);
-    if (ws.QKV) add_qkv(m, a, 0, ws.QKV);
-    return launch_chain(m, a, st);
+void chain_in(b2h_tenc* m, const float* x, int64_t n, int T, const FusedArgs& fa, const TencWs& ws, hipStream_t st) {
+    Chain c{m->kernel == B2H_TENC_F16X3};
+    c.rows(x, kInCh, nullptr, n);
+    c.a.pe = (const float*)m->pe.p; c.a.T = T;
+    c.a.flags = fa.flags & (kPreChest | kPreNorm); c.a.factor = fa.factor; c.a.Tseq = T;
+    c.add(m->in_proj, ST_SET, ws.XA);
+    if (ws.QKV) c.add_qkv(m->layers[0].q, m->layers[0].k, m->layers[0].v, ws.QKV);
+    c.launch(m->num_cus, st);
 }
 
-// out_proj +res LN1 -> linear1 ReLU -> linear2 +res LN2 -> residual stream [+ next layer's Q, K, V] | hidden2pose (:171)
-int chain_tail(b2h_tenc* m, int l, float* y, int64_t n, int T, const FusedArgs& fa, const TencWs& ws, hipStream_t st) {
-    ChainArgs a{};
-    a.x = ws.OC; a.ldx = kTencD; a.kgroups0 = 8; a.kvalid = kTencD; a.pe = nullptr; a.T = 1;
-    a.res = ws.XA; a.n = n; a.nstages = 3;
-    a.st[0] = stage_of(m, m->layers[l].attn_out, ST_RESLN_GLOBAL, nullptr, kTencD);
-    a.st[1] = stage_of(m, m->layers[l].ff1, ST_RELU, nullptr, kTencD);
-    if (l + 1 < m->nlayers) {
-        a.st[2] = stage_of(m, m->layers[l].ff2, ST_RESLN_REG, ws.XA, kTencD); // the next layer's input and residual
-        if (ws.QKV) add_qkv(m, a, l + 1, ws.QKV);
-    } else {
-        a.st[2] = stage_of(m, m->layers[l].ff2, ST_RESLN_REG, nullptr, kTencD);
-        a.st[3] = stage_of(m, m->out_proj, ST_STORE, y, kOutCh);
-        a.nstages = 4;
-        a.flags = fa.flags & (kPostDenorm | kPostMask); a.factor = fa.factor; a.n_frames = fa.n_frames;
+// the layer's tail -> residual stream [+ next layer's Q, K, V] | hidden2pose (:171)
+void chain_tail(b2h_tenc* m, int l, float* y, int64_t n, int T, const FusedArgs& fa, const TencWs& ws, hipStream_t st) {
+    const EncLayer& L = m->layers[l];
+    const bool last = l + 1 == m->nlayers;
+    Chain c{m->kernel == B2H_TENC_F16X3};
+    c.rows(ws.OC, kTencD, ws.XA, n);
+    c.a.Tseq = T;
+    // XA: the next layer's input and residual
+    c.add_layer_tail(L.attn_out, L.ff1, L.ff2, last ? nullptr : ws.XA, !last && ws.QKV ? &m->layers[l + 1] : nullptr, ws.QKV);
+    if (last) {
+        c.add(m->out_proj, ST_STORE, y, kOutCh);
+        c.a.flags = fa.flags & (kPostDenorm | kPostMask); c.a.factor = fa.factor; c.a.n_frames = fa.n_frames;
     }
-    a.Tseq = T;
-    return launch_chain(m, a, st);
+    c.launch(m->num_cus, st);
 }
 
 int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, const FusedArgs& fa, void* workspace,
@@ -726,8 +804,7 @@ int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, con
     const bool h3 = m->kernel == B2H_TENC_F16X3;
     float* XA = reinterpret_cast<float*>(workspace);
     const TencWs ws{XA, XA + n * kTencD, h3 ? nullptr : XA + 2 * n * kTencD};
-    int rc;
-    if ((rc = chain_in(m, x, n, (int)T, fa, ws, st))) return rc;
+    chain_in(m, x, n, (int)T, fa, ws, st);
     for (int l = 0; l < m->nlayers; ++l) { // torch.nn.TransformerEncoderLayer, post-norm, ReLU
         if (h3) {
             // persistent: one workgroup per CU, bound to a head (blockIdx = 8 (4 slot + head) + xcd: 32 per sequence slot)
@@ -737,16 +814,13 @@ int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, con
             for (int hd = 0; hd < kTencHeads; ++hd) qa.blob[hd] = (const float*)m->layers[l].qkv_head[hd].buf16.p;
             hipLaunchKernelGGL(kAttnQkvH3[nt - 1], dim3(grid), dim3(64 * nt), (size_t)attn_qkv_lds_bytes(nt), st, qa);
         } else {
-            hipLaunchKernelGGL(kAttn[nt - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nt),
-                               (size_t)attn_f32_lds_bytes(nt), st, ws.QKV, ws.OC, (int)T);
+            self_attn_f32(ws.QKV, ws.OC, B, (int)T, st);
         }
-        if ((rc = chain_tail(m, l, y, n, (int)T, fa, ws, st))) return rc;
+        chain_tail(m, l, y, n, (int)T, fa, ws, st);
     }
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
-
-int set_tt_kernel_attributes(); // the training kernels' LDS caps, below
 
 } // namespace
 
@@ -762,9 +836,12 @@ int b2h_tenc_create(int ninp, int nhead, int nhid, int nout, int nlayers, int ma
         return fail(B2H_ERR_UNSUPPORTED, "TransformerEnc: 1 <= nlayers <= 16 and 1 <= max_len <= 128");
     std::unique_ptr<b2h_tenc> m(new b2h_tenc()); // released to the caller only on success
     if (int rc = probe_device(m->device, m->num_cus)) return rc;
-    if (int rc = set_tt_kernel_attributes()) return rc; // here, not in a launch: b2h_tenc_train_forward is capture-safe
+    if (int rc = set_tenc_kernel_attributes()) return rc;
     m->nlayers = nlayers;
     m->max_len = max_len;
+    m->sizes = {(size_t)max_len * kInCh, (size_t)kTencD * kInCh, (size_t)kTencD};
+    for (int l = 0; l < nlayers; ++l) m->sizes.insert(m->sizes.end(), kEncLayerFloats, kEncLayerFloats + 12);
+    m->sizes.insert(m->sizes.end(), {(size_t)kOutCh * kTencD, (size_t)kOutCh});
     m->layers.resize(nlayers);
     *out = m.release();
     return B2H_OK;
@@ -784,30 +861,13 @@ int b2h_tenc_set_kernel(b2h_tenc* m, int kernel) {
 
 int b2h_tenc_load_weights(b2h_tenc* m, const float* const* tensors, int count, int on_device) {
     if (!m || !tensors) return fail(B2H_ERR_INVALID, "NULL argument");
-    if (count != 5 + 12 * m->nlayers) return fail(B2H_ERR_INVALID, "expected 5 + 12*nlayers tensors");
-    const int D = kTencD;
-    std::vector<size_t> sizes = {(size_t)m->max_len * kInCh, (size_t)D * kInCh, (size_t)D};
-    for (int l = 0; l < m->nlayers; ++l)
-        for (size_t s : {(size_t)3 * D * D, (size_t)3 * D, (size_t)D * D, (size_t)D, (size_t)D * D, (size_t)D,
-                         (size_t)D * D, (size_t)D, (size_t)D, (size_t)D, (size_t)D, (size_t)D})
-            sizes.push_back(s);
-    sizes.push_back((size_t)kOutCh * D);
-    sizes.push_back((size_t)kOutCh);
-    std::vector<std::vector<float>> h(count);
-    for (int i = 0; i < count; ++i) {
+    if (count != (int)m->sizes.size()) return fail(B2H_ERR_INVALID, "expected 5 + 12*nlayers tensors");
+    for (int i = 0; i < count; ++i)
         if (!tensors[i]) return fail(B2H_ERR_INVALID, "tensor pointer is NULL");
-        h[i].resize(sizes[i]);
-        if (on_device) HIP_TRY(hipMemcpy(h[i].data(), tensors[i], sizes[i] * 4, hipMemcpyDeviceToHost));
-        else std::memcpy(h[i].data(), tensors[i], sizes[i] * 4);
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    if (int rc0 = check_device(m->device)) return rc0;
-    // LDS caps are raised here, not in b2h_tenc_forward: the first forward is already capture-safe
+    const int D = kTencD;
+    std::vector<std::vector<float>> h;
     int rc;
-    if ((rc = raise_lds_cap(b2h_tenc_chain<false>, kChainLdsBytes)) || (rc = raise_lds_cap(b2h_tenc_chain<true>, kChainLdsBytes)))
-        return rc;
-    for (int nt = 1; nt <= kAttnMaxTiles; ++nt)
-        if ((rc = raise_lds_cap(kAttnQkvH3[nt - 1], attn_qkv_lds_bytes(nt)))) return rc;
+    if ((rc = fetch_tensors(tensors, m->sizes, on_device, h)) || (rc = check_device(m->device))) return rc;
     m->w_absmax = 0.f;
     for (int i = 1; i < count; ++i) m->w_absmax = absmax_of(h[i], m->w_absmax); // h[0] is the pe table (|pe| <= 1)
     if ((rc = m->pe.upload(h[0].data(), h[0].size() * 4))) return rc;
@@ -867,13 +927,8 @@ struct b2h_tpt {
     DevBuf table;               // token_embedding.weight (n_tokens, 128)
     DevBuf enc_norm, dec_norm;  // encoder.norm / decoder.norm: gamma (128), beta (128)
     TencBlob in_proj, out_proj; // pose2hidden_projection, hidden2pose_projection
-    struct EncLayer {
-        TencBlob q, k, v, attn_out, ff1, ff2;
-    };
-    struct DecLayer {
-        TencBlob q, k, v, self_out;       // self_attn; out_proj carries norm1
+    struct DecLayer : EncLayer {          // q, k, v, attn_out: self_attn, its out_proj carries norm1; ff2 carries norm3
         TencBlob cq, ck, cv, cross_out;   // multihead_attn on the encoder memory; out_proj carries norm2
-        TencBlob ff1, ff2;                // linear2 carries norm3
     };
     std::vector<EncLayer> enc;
     std::vector<DecLayer> dec;
@@ -913,43 +968,17 @@ constexpr AttnCrossKernel kAttnCross[kAttnMaxTiles] = {b2h_attn_cross_f32<1>, b2
                                                        b2h_attn_cross_f32<4>, b2h_attn_cross_f32<5>, b2h_attn_cross_f32<6>,
                                                        b2h_attn_cross_f32<7>, b2h_attn_cross_f32<8>};
 
-ChainStage tpt_stage(const TencBlob& B, int type, float* out, int ldo) {
-    return ChainStage{(const float*)B.buf.p, out, type, B.mtiles, B.kgroups, ldo, B.nout, B.mtiles * B.kgroups * 64};
-}
-
-// (n, ldx) rows entering a chain, with the (n, 128) residual rows of a leading ST_RESLN_GLOBAL stage
-ChainArgs tpt_rows(const float* x, int ldx, const float* res, int64_t n) {
-    ChainArgs a{};
-    a.x = x; a.ldx = ldx; a.kgroups0 = (ldx + 15) / 16; a.kvalid = ldx; a.T = 1; a.Tseq = 1;
-    a.res = res; a.n = n; a.factor = 1.0f;
-    return a;
-}
-
-void tpt_add(ChainArgs& a, const TencBlob& B, int type, float* out, int ldo = kTencD) {
-    a.st[a.nstages++] = tpt_stage(B, type, out, ldo);
-}
-
-void tpt_add_qkv(ChainArgs& a, const TencBlob& q, const TencBlob& k, const TencBlob& v, float* QKV) {
-    tpt_add(a, q, ST_STORE, QKV, 3 * kTencD);
-    tpt_add(a, k, ST_STORE, QKV + kTencD, 3 * kTencD);
-    tpt_add(a, v, ST_STORE, QKV + 2 * kTencD, 3 * kTencD);
-}
-
-void tpt_chain(const b2h_tpt* m, const ChainArgs& a, hipStream_t st) {
-    // persistent: one workgroup per CU walks over the 128-row blocks (launch_chain)
-    const int64_t blocks = std::min<int64_t>((a.n + 16 * kLinWaves - 1) / (16 * kLinWaves), m->num_cus);
-    hipLaunchKernelGGL(b2h_tenc_chain<false>, dim3((unsigned)blocks), dim3(64 * kLinWaves), (size_t)kChainLdsBytes, st, a);
+// A chain of b2h_tenc_chain<false> without the item transforms: (n, ldx) rows, optional (n, 128) residual rows
+Chain tpt_rows(const float* x, int ldx, const float* res, int64_t n) {
+    Chain c;
+    c.rows(x, ldx, res, n);
+    c.a.Tseq = 1; c.a.factor = 1.0f;
+    return c;
 }
 
 void tpt_layernorm(const DevBuf& gb, float* x, int64_t n, hipStream_t st) {
     const float* g = (const float*)gb.p;
     hipLaunchKernelGGL(b2h_tpt_layernorm, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, st, x, g, g + kTencD, x, n);
-}
-
-void tpt_self_attn(const float* QKV, float* OC, int64_t B, int T, hipStream_t st) {
-    const int nt = (T + 15) / 16;
-    hipLaunchKernelGGL(kAttn[nt - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nt), (size_t)attn_f32_lds_bytes(nt), st,
-                       QKV, OC, T);
 }
 
 } // namespace
@@ -967,6 +996,7 @@ int b2h_tpt_create(int n_tokens, int ninp, int nhead, int nhid, int nout, int n_
         return fail(B2H_ERR_UNSUPPORTED, "TextPoseTransformer: 1 <= n_enc_layers, n_dec_layers <= 16 and n_tokens >= 1");
     std::unique_ptr<b2h_tpt> m(new b2h_tpt()); // released to the caller only on success
     if (int rc = probe_device(m->device, m->num_cus)) return rc;
+    if (int rc = set_tenc_kernel_attributes()) return rc;
     m->n_tokens = n_tokens;
     m->n_enc = n_enc_layers;
     m->n_dec = n_dec_layers;
@@ -985,30 +1015,23 @@ int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int
     if (!m || !tensors) return fail(B2H_ERR_INVALID, "NULL argument");
     if (count != 9 + 12 * m->n_enc + 18 * m->n_dec)
         return fail(B2H_ERR_INVALID, "expected 9 + 12*n_enc_layers + 18*n_dec_layers tensors");
-    const size_t D = kTencD;
-    std::vector<size_t> sizes;
-    const auto attn = [&] { for (size_t s : {3 * D * D, 3 * D, D * D, D}) sizes.push_back(s); };
-    const auto tail = [&](int norms) { // linear1, linear2, then the layer's LayerNorms
-        for (size_t s : {D * D, D, D * D, D}) sizes.push_back(s);
-        sizes.insert(sizes.end(), 2 * norms, D);
-    };
-    for (int l = 0; l < m->n_enc; ++l) { attn(); tail(2); }
-    sizes.insert(sizes.end(), 2, D);
-    for (int l = 0; l < m->n_dec; ++l) { attn(); attn(); tail(3); }
-    sizes.insert(sizes.end(), 2, D);
-    for (size_t s : {(size_t)m->n_tokens * D, (size_t)kOutCh * D, (size_t)kOutCh, D * kInCh, D}) sizes.push_back(s);
-    std::vector<std::vector<float>> h(count);
-    for (int i = 0; i < count; ++i) {
+    for (int i = 0; i < count; ++i)
         if (!tensors[i]) return fail(B2H_ERR_INVALID, "tensor pointer is NULL");
-        h[i].resize(sizes[i]);
-        if (on_device) HIP_TRY(hipMemcpy(h[i].data(), tensors[i], sizes[i] * 4, hipMemcpyDeviceToHost));
-        else std::memcpy(h[i].data(), tensors[i], sizes[i] * 4);
+    const size_t D = kTencD;
+    const size_t* E = kEncLayerFloats; // a decoder layer: two attention blocks, linear1 and linear2, three LayerNorms
+    std::vector<size_t> sizes;
+    for (int l = 0; l < m->n_enc; ++l) sizes.insert(sizes.end(), E, E + 12);
+    sizes.insert(sizes.end(), 2, D);
+    for (int l = 0; l < m->n_dec; ++l) {
+        sizes.insert(sizes.end(), E, E + 4);
+        sizes.insert(sizes.end(), E, E + 8);
+        sizes.insert(sizes.end(), 6, D);
     }
-    HIP_TRY(hipDeviceSynchronize());
-    if (int rc0 = check_device(m->device)) return rc0;
+    sizes.insert(sizes.end(), 2, D);
+    sizes.insert(sizes.end(), {(size_t)m->n_tokens * D, (size_t)kOutCh * D, (size_t)kOutCh, D * kInCh, D});
+    std::vector<std::vector<float>> h;
     int rc;
-    // the LDS cap is raised here, not in b2h_tpt_forward: the first forward is already capture-safe
-    if ((rc = raise_lds_cap(b2h_tenc_chain<false>, kChainLdsBytes))) return rc;
+    if ((rc = fetch_tensors(tensors, sizes, on_device, h)) || (rc = check_device(m->device))) return rc;
     const int Di = kTencD;
     // one Linear of 128 inputs: rows [r0, r0 + 128) of tensor i with bias i + 1, and the LayerNorm that follows it
     const auto lin = [&](TencBlob& blob, int i, int r0, int norm) {
@@ -1033,7 +1056,7 @@ int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int
     for (int l = 0; l < m->n_dec; ++l, o += 18) {
         auto& L = m->dec[l];
         if ((rc = lin(L.q, o, 0, -1)) || (rc = lin(L.k, o, Di, -1)) || (rc = lin(L.v, o, 2 * Di, -1)) ||
-            (rc = lin(L.self_out, o + 2, 0, o + 12)) || (rc = lin(L.cq, o + 4, 0, -1)) || (rc = lin(L.ck, o + 4, Di, -1)) ||
+            (rc = lin(L.attn_out, o + 2, 0, o + 12)) || (rc = lin(L.cq, o + 4, 0, -1)) || (rc = lin(L.ck, o + 4, Di, -1)) ||
             (rc = lin(L.cv, o + 4, 2 * Di, -1)) || (rc = lin(L.cross_out, o + 6, 0, o + 14)) ||
             (rc = lin(L.ff1, o + 8, 0, -1)) || (rc = lin(L.ff2, o + 10, 0, o + 16)))
             return rc;
@@ -1077,67 +1100,61 @@ int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y,
     // encoder (torch.nn.TransformerEncoder, post-norm, ReLU): token_embedding -> layers -> encoder.norm
     hipLaunchKernelGGL(b2h_tpt_embed, dim3((unsigned)((Ns * 32 + 255) / 256)), dim3(256), 0, st, tokens,
                        (const float*)m->table.p, ws.MEM, Ns, m->n_tokens);
+    const auto qkv = [](Chain& c, const EncLayer& L, float* QKV) { c.add_qkv(L.q, L.k, L.v, QKV); };
     {
-        ChainArgs a = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
-        tpt_add_qkv(a, m->enc[0].q, m->enc[0].k, m->enc[0].v, ws.QKVs);
-        tpt_chain(m, a, st);
+        Chain c = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
+        qkv(c, m->enc[0], ws.QKVs);
+        c.launch(m->num_cus, st);
     }
     for (int l = 0; l < m->n_enc; ++l) {
-        const auto& L = m->enc[l];
-        tpt_self_attn(ws.QKVs, ws.OCs, B, (int)S, st);
-        ChainArgs a = tpt_rows(ws.OCs, kTencD, ws.MEM, Ns); // exactly TransformerEnc's chain_tail
-        tpt_add(a, L.attn_out, ST_RESLN_GLOBAL, nullptr);
-        tpt_add(a, L.ff1, ST_RELU, nullptr);
-        tpt_add(a, L.ff2, ST_RESLN_REG, ws.MEM);
-        if (l + 1 < m->n_enc) tpt_add_qkv(a, m->enc[l + 1].q, m->enc[l + 1].k, m->enc[l + 1].v, ws.QKVs);
-        tpt_chain(m, a, st);
+        const EncLayer& L = m->enc[l];
+        self_attn_f32(ws.QKVs, ws.OCs, B, (int)S, st);
+        Chain c = tpt_rows(ws.OCs, kTencD, ws.MEM, Ns);
+        c.add_layer_tail(L.attn_out, L.ff1, L.ff2, ws.MEM, l + 1 < m->n_enc ? &m->enc[l + 1] : nullptr, ws.QKVs);
+        c.launch(m->num_cus, st);
     }
     tpt_layernorm(m->enc_norm, ws.MEM, Ns, st);
     // K and V of the memory for every decoder layer: two ST_STORE stages per layer, four layers per launch
     for (int l0 = 0; l0 < m->n_dec; l0 += kChainMaxStages / 2) {
-        ChainArgs a = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
+        Chain c = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
         for (int l = l0; l < std::min(m->n_dec, l0 + kChainMaxStages / 2); ++l) {
             float* kv = ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats;
-            tpt_add(a, m->dec[l].ck, ST_STORE, kv, 2 * kTencD);
-            tpt_add(a, m->dec[l].cv, ST_STORE, kv + kTencD, 2 * kTencD);
+            c.add(m->dec[l].ck, ST_STORE, kv, 2 * kTencD);
+            c.add(m->dec[l].cv, ST_STORE, kv + kTencD, 2 * kTencD);
         }
-        tpt_chain(m, a, st);
+        c.launch(m->num_cus, st);
     }
 
     // decoder (torch.nn.TransformerDecoder): pose2hidden_projection -> layers -> decoder.norm -> hidden2pose_projection
     {
-        ChainArgs a = tpt_rows(x, kInCh, nullptr, Nt);
-        tpt_add(a, m->in_proj, ST_SET, ws.XT);
-        tpt_add_qkv(a, m->dec[0].q, m->dec[0].k, m->dec[0].v, ws.QKVt);
-        tpt_chain(m, a, st);
+        Chain c = tpt_rows(x, kInCh, nullptr, Nt);
+        c.add(m->in_proj, ST_SET, ws.XT);
+        qkv(c, m->dec[0], ws.QKVt);
+        c.launch(m->num_cus, st);
     }
     const int nk = (int)((S + 15) / 16), nq = (int)((T + 15) / 16);
     for (int l = 0; l < m->n_dec; ++l) {
         const auto& L = m->dec[l];
-        tpt_self_attn(ws.QKVt, ws.OCt, B, (int)T, st);
+        self_attn_f32(ws.QKVt, ws.OCt, B, (int)T, st);
         {   // self out_proj + x -> norm1 -> X1; the cross-attention query of X1
-            ChainArgs a = tpt_rows(ws.OCt, kTencD, ws.XT, Nt);
-            tpt_add(a, L.self_out, ST_RESLN_GLOBAL, ws.X1);
-            tpt_add(a, L.cq, ST_STORE, ws.QC);
-            tpt_chain(m, a, st);
+            Chain c = tpt_rows(ws.OCt, kTencD, ws.XT, Nt);
+            c.add(L.attn_out, ST_RESLN_GLOBAL, ws.X1);
+            c.add(L.cq, ST_STORE, ws.QC);
+            c.launch(m->num_cus, st);
         }
         hipLaunchKernelGGL(kAttnCross[nk - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nq), (size_t)attn_f32_lds_bytes(nk),
                            st, ws.QC, kTencD, 0, ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats, 2 * kTencD, 0, kTencD,
                            ws.OCt, (int)T, (int)S);
-        {   // cross out_proj + X1 -> norm2 -> linear1 ReLU -> linear2 + res -> norm3 -> XT [+ the next layer's Q, K, V]
-            ChainArgs a = tpt_rows(ws.OCt, kTencD, ws.X1, Nt);
-            tpt_add(a, L.cross_out, ST_RESLN_GLOBAL, nullptr);
-            tpt_add(a, L.ff1, ST_RELU, nullptr);
-            tpt_add(a, L.ff2, ST_RESLN_REG, ws.XT);
-            if (l + 1 < m->n_dec) tpt_add_qkv(a, m->dec[l + 1].q, m->dec[l + 1].k, m->dec[l + 1].v, ws.QKVt);
-            tpt_chain(m, a, st);
-        }
+        // cross out_proj + X1 -> norm2 -> linear1 ReLU -> linear2 + res -> norm3 -> XT [+ the next layer's Q, K, V]
+        Chain c = tpt_rows(ws.OCt, kTencD, ws.X1, Nt);
+        c.add_layer_tail(L.cross_out, L.ff1, L.ff2, ws.XT, l + 1 < m->n_dec ? &m->dec[l + 1] : nullptr, ws.QKVt);
+        c.launch(m->num_cus, st);
     }
     tpt_layernorm(m->dec_norm, ws.XT, Nt, st);
     {
-        ChainArgs a = tpt_rows(ws.XT, kTencD, nullptr, Nt);
-        tpt_add(a, m->out_proj, ST_STORE, y, kOutCh);
-        tpt_chain(m, a, st);
+        Chain c = tpt_rows(ws.XT, kTencD, nullptr, Nt);
+        c.add(m->out_proj, ST_STORE, y, kOutCh);
+        c.launch(m->num_cus, st);
     }
     HIP_TRY(hipGetLastError());
     return B2H_OK;
@@ -1165,28 +1182,6 @@ TtLayer tt_layer(float* saved, int64_t N, int l) {
 size_t tt_saved_bytes(int nlayers, int64_t N) { return (size_t)N * (kTtSavedFrame + nlayers * kTtSavedLayer) * 4; }
 size_t tt_scratch_bytes(int64_t N) { return ((size_t)N * kTtScratchFrame + (size_t)tt_nslabs(N) * kTtSlab) * 4; }
 
-int set_tt_kernel_attributes() {
-    static OncePerDevice once;
-    return once([]() -> int {
-        int rc;
-        if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd))) return rc;
-        return B2H_OK;
-    });
-}
-
-// Floats of parameter i (order of b2h_tenc_load_weights, pe first).
-size_t tt_param_floats(const b2h_tenc* m, int i) {
-    const size_t D = kTtD;
-    if (i == 0) return (size_t)m->max_len * kInCh;
-    if (i == 1) return D * kInCh;
-    if (i == 2) return D;
-    const int last = 3 + 12 * m->nlayers;
-    if (i == last) return (size_t)kOutCh * D;
-    if (i == last + 1) return kOutCh;
-    static const size_t per[12] = {3 * D * D, 3 * D, D * D, D, D * D, D, D * D, D, D, D, D, D};
-    return per[(i - 3) % 12];
-}
-
 // Checks shared by b2h_tenc_train_forward / b2h_tenc_backward, as tenc_launch makes them.
 int tt_check(const b2h_tenc* m, const float* const* params, const uint8_t* const* masks, float p, int64_t B, int64_t T) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
@@ -1199,7 +1194,7 @@ int tt_check(const b2h_tenc* m, const float* const* params, const uint8_t* const
                                    "HandPoseModels.py:101,167)");
     // grid limits: attention launches B x heads workgroups, LayerNorm N / 4 (the largest row grid), the Linears N / 16
     if (B * kTtHeads > 0x7fffffff || B * T / 4 >= 0x7fffffff) return fail(B2H_ERR_SHAPE, "batch too large for one launch");
-    for (int i = 0; i < 5 + 12 * m->nlayers; ++i) {
+    for (size_t i = 0; i < m->sizes.size(); ++i) {
         if (!params[i]) return fail(B2H_ERR_INVALID, "params[" + std::to_string(i) + "] is NULL");
         if (misaligned(params[i], 4)) return fail(B2H_ERR_INVALID, "params must be 4-byte aligned fp32 tensors");
     }
@@ -1209,30 +1204,18 @@ int tt_check(const b2h_tenc* m, const float* const* params, const uint8_t* const
     return B2H_OK;
 }
 
-struct TtOut {
-    const void* p;
-    size_t n;
-};
-
-// No output may overlap a parameter, a mask, another output or one of the plain inputs.
-int tt_check_overlap(const b2h_tenc* m, const float* const* params, const uint8_t* const* masks, int64_t N, int64_t T,
-                     const std::vector<TtOut>& outs, const std::vector<TtOut>& ins) {
-    for (size_t a = 0; a < outs.size(); ++a) {
-        for (const TtOut& in : ins)
-            if (overlaps(outs[a].p, outs[a].n, in.p, in.n)) return fail(B2H_ERR_INVALID, "an output overlaps an input");
-        for (int i = 0; i < 5 + 12 * m->nlayers; ++i)
-            if (overlaps(outs[a].p, outs[a].n, params[i], tt_param_floats(m, i) * 4))
-                return fail(B2H_ERR_INVALID, "an output overlaps a parameter");
-        if (masks)
-            for (int i = 0; i < 1 + 4 * m->nlayers; ++i) {
-                const int kind = i == 0 ? -1 : (i - 1) % 4;
-                const size_t n = kind < 0 ? (size_t)N * kInCh : (kind == 0 ? (size_t)N * kTtHeads * T : (size_t)N * kTtD);
-                if (overlaps(outs[a].p, outs[a].n, masks[i], n)) return fail(B2H_ERR_INVALID, "an output overlaps a mask");
-            }
-        for (size_t c = a + 1; c < outs.size(); ++c)
-            if (overlaps(outs[a].p, outs[a].n, outs[c].p, outs[c].n)) return fail(B2H_ERR_INVALID, "two outputs overlap");
-    }
-    return B2H_OK;
+// The read-only operands of a training call for check_overlap: its plain inputs, the parameters and the masks.
+std::vector<Span> tt_read_only(const b2h_tenc* m, const float* const* params, const uint8_t* const* masks, int64_t N,
+                               int64_t T, std::vector<Span> ins) {
+    for (Span& in : ins) in.what = "an input";
+    for (size_t i = 0; i < m->sizes.size(); ++i) ins.push_back({params[i], m->sizes[i] * 4, "a parameter"});
+    if (masks)
+        for (int i = 0; i < 1 + 4 * m->nlayers; ++i) {
+            const int kind = i == 0 ? -1 : (i - 1) % 4;
+            const size_t n = kind < 0 ? (size_t)N * kInCh : (kind == 0 ? (size_t)N * kTtHeads * T : (size_t)N * kTtD);
+            ins.push_back({masks[i], n, "a mask"});
+        }
+    return ins;
 }
 
 unsigned tt_row_blocks(int64_t N, int rows) { return (unsigned)((N + rows - 1) / rows); }
@@ -1289,8 +1272,8 @@ int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float*
     const size_t need = tt_saved_bytes(m->nlayers, N);
     if (saved_bytes < need)
         return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tenc_train_bytes (" + std::to_string(need) + " B)");
-    if (int rc = tt_check_overlap(m, params, masks, N, T, {{y, (size_t)N * kOutCh * 4}, {saved, need}},
-                                  {{x, (size_t)N * kInCh * 4}}))
+    if (int rc = check_overlap({{y, (size_t)N * kOutCh * 4}, {saved, need}},
+                               tt_read_only(m, params, masks, N, T, {{x, (size_t)N * kInCh * 4}})))
         return rc;
     hipStream_t st = (hipStream_t)stream;
     const float sc = tt_scale(p);
@@ -1337,15 +1320,16 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
     if (scratch_bytes < need)
         return fail(B2H_ERR_INVALID, "scratch smaller than b2h_tenc_train_bytes (" + std::to_string(need) + " B)");
     const int ng = 4 + 12 * m->nlayers;
-    std::vector<TtOut> outs;
+    std::vector<Span> outs;
     for (int i = 0; i < ng; ++i) {
         if (!grads[i]) return fail(B2H_ERR_INVALID, "grads[" + std::to_string(i) + "] is NULL");
         if (misaligned(grads[i], 4)) return fail(B2H_ERR_INVALID, "grads must be 4-byte aligned");
-        outs.push_back({grads[i], tt_param_floats(m, i + 1) * 4});
+        outs.push_back({grads[i], m->sizes[i + 1] * 4});
     }
     if (dx) outs.push_back({dx, (size_t)N * kInCh * 4});
     outs.push_back({scratch, need});
-    if (int rc = tt_check_overlap(m, params, masks, N, T, outs, {{dy, (size_t)N * kOutCh * 4}, {saved, need_saved}})) return rc;
+    if (int rc = check_overlap(outs, tt_read_only(m, params, masks, N, T, {{dy, (size_t)N * kOutCh * 4}, {saved, need_saved}})))
+        return rc;
 
     hipStream_t st = (hipStream_t)stream;
     const float sc = tt_scale(p);
@@ -1550,25 +1534,22 @@ int b2h_destroy(b2h_model* m) {
 int b2h_load_weights(b2h_model* m, const float* w1, const float* b1, const float* w2, const float* b2,
                      const float* w3, const float* b3, const float* w4, const float* b4, int on_device) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
-    const float* ws[4] = {w1, w2, w3, w4};
-    const float* bs[4] = {b1, b2, b3, b4};
+    const float* tensors[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
+    std::vector<size_t> sizes;
+    for (int l = 0; l < 4; ++l) {
+        if (!tensors[2 * l] || !tensors[2 * l + 1]) return fail(B2H_ERR_INVALID, "weight pointer is NULL");
+        sizes.push_back((size_t)m->cout[l] * m->cin[l] * kTaps);
+        sizes.push_back(m->cout[l]);
+    }
+    std::vector<std::vector<float>> h;
+    int rc;
+    if ((rc = fetch_tensors(tensors, sizes, on_device, h)) || (rc = check_device(m->device))) return rc;
     HostWeights hw;
     hw.m = m;
     for (int l = 0; l < 4; ++l) {
-        if (!ws[l] || !bs[l]) return fail(B2H_ERR_INVALID, "weight pointer is NULL");
-        hw.w[l].resize((size_t)m->cout[l] * m->cin[l] * kTaps);
-        hw.b[l].resize(m->cout[l]);
-        if (on_device) {
-            HIP_TRY(hipMemcpy(hw.w[l].data(), ws[l], hw.w[l].size() * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(hw.b[l].data(), bs[l], hw.b[l].size() * 4, hipMemcpyDeviceToHost));
-        } else {
-            std::memcpy(hw.w[l].data(), ws[l], hw.w[l].size() * 4);
-            std::memcpy(hw.b[l].data(), bs[l], hw.b[l].size() * 4);
-        }
+        hw.w[l] = std::move(h[2 * l]);
+        hw.b[l] = std::move(h[2 * l + 1]);
     }
-    HIP_TRY(hipDeviceSynchronize()); // no launch may still read the old packed buffers
-    int rc = check_device(m->device);
-    if (rc) return rc;
     if ((rc = set_conv_kernel_attributes())) return rc;
     if ((rc = pack_all(m, hw))) return rc;
     m->has_weights = true;
@@ -1658,28 +1639,17 @@ int b2h_backward(b2h_model* m, const float* const* params, const float* x, const
         return fail(B2H_ERR_INVALID, "workspace smaller than b2h_backward_workspace_bytes (" + std::to_string(need) + " B)");
     const size_t xn = (size_t)B * T * kInCh * 4, yn = (size_t)B * T * kOutCh * 4;
     auto param_bytes = [&](int i) { return (size_t)((i + 1 < 8 ? p.off[i + 1] : train_param_floats(p)) - p.off[i]) * 4; };
-    // outputs: dx, the eight gradients, the workspace; none may overlap another operand
-    const void* outs[10];
-    size_t outn[10];
-    int nout = 0;
+    // outputs: the eight gradients, dx, the workspace; none may overlap another operand
+    std::vector<Span> outs, read_only = {{x, xn, "x or dy"}, {dy, yn, "x or dy"}};
     for (int i = 0; i < 8; ++i) {
         if (!grads[i]) return fail(B2H_ERR_INVALID, "grads[" + std::to_string(i) + "] is NULL");
         if (misaligned(grads[i], 4)) return fail(B2H_ERR_INVALID, "grads must be 4-byte aligned");
-        outs[nout] = grads[i];
-        outn[nout++] = param_bytes(i);
+        outs.push_back({grads[i], param_bytes(i)});
+        read_only.push_back({params[i], param_bytes(i), "a parameter"});
     }
-    if (dx) { outs[nout] = dx; outn[nout++] = xn; }
-    outs[nout] = workspace;
-    outn[nout++] = need;
-    for (int a = 0; a < nout; ++a) {
-        if (overlaps(outs[a], outn[a], x, xn) || overlaps(outs[a], outn[a], dy, yn))
-            return fail(B2H_ERR_INVALID, "an output overlaps x or dy");
-        for (int i = 0; i < 8; ++i)
-            if (overlaps(outs[a], outn[a], params[i], param_bytes(i)))
-                return fail(B2H_ERR_INVALID, "an output overlaps a parameter");
-        for (int c = a + 1; c < nout; ++c)
-            if (overlaps(outs[a], outn[a], outs[c], outn[c])) return fail(B2H_ERR_INVALID, "two outputs overlap");
-    }
+    if (dx) outs.push_back({dx, xn});
+    outs.push_back({workspace, need});
+    if (int rc = check_overlap(outs, read_only)) return rc;
     const int64_t tiles = train_tiles(B, T, 1);
     const int tps = (int)((T + kTrainBwdTile - 1) / kTrainBwdTile);
     hipStream_t st = (hipStream_t)stream;

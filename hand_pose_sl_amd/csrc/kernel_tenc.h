@@ -62,6 +62,65 @@ __device__ __forceinline__ float quad_max(float s) {
     return s;
 }
 
+constexpr int kAttnMaxTiles = 8; // T <= 128
+constexpr int kAttnRow = 36;
+constexpr int attn_f32_lds_bytes(int nt) { return 2 * nt * 16 * kAttnRow * (int)sizeof(float); } // K, then V
+
+// The core of both exact-fp32 attention kernels (b2h_attn_mfma_f32 here, b2h_attn_cross_f32 in kernel_tpt.h), from
+// the staged operands to the output stores: score tiles S^T = K . Q^T, the mask of keys >= Tk, softmax over the keys
+// inside the lane quartet, O^T = V^T . P^T, the normalisation and the two stores of query row tq.  Ks / Vs hold the
+// head's 16 NK key / value rows at the kAttnRow pitch (rows >= Tk zero), qb this lane's pre-scaled query fragments
+// (d = 16g + 4q + j); out is (B*Tq, 128).  The kernels differ only in where they load Ks, Vs and qb from.
+template <int NK>
+__device__ __forceinline__ void attn_core_f32(const float* Ks, const float* Vs, const f32x4 (&qb)[2], int Tk,
+                                              float* __restrict__ out, int Tq, int b, int h, int tq, int col, int q) {
+    f32x4 sc[NK];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NK; ++kt) {
+        sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            // A operand: key row kt*16 + col, d = 16g + 4q + j
+            const f32x4 ka = *reinterpret_cast<const f32x4*>(Ks + (kt * 16 + col) * kAttnRow + 16 * g + 4 * q);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[j], qb[g][j], sc[kt], 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { // D row 4q + r = key index within the tile
+            if (kt * 16 + 4 * q + r >= Tk) sc[kt][r] = -INFINITY;
+            mx = fmaxf(mx, sc[kt][r]);
+        }
+    }
+    mx = quad_max(mx); // finite: key 0 exists (Tk >= 1)
+    float l = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NK; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            sc[kt][r] = expf(sc[kt][r] - mx); // masked keys: exp(-inf) = 0
+            l += sc[kt][r];
+        }
+    l = quad_sum(l);
+    // O^T[d][query]: for step (kt, r) lane q supplies P^T[kt*16 + 4q + r][query] = sc[kt][r];
+    // the A operand is V[kt*16 + 4q + r][16mt + col]
+    f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int kt = 0; kt < NK; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float* vrow = Vs + (kt * 16 + 4 * q + r) * kAttnRow + col;
+            o[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[0], sc[kt][r], o[0], 0, 0, 0);
+            o[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[16], sc[kt][r], o[1], 0, 0, 0);
+        }
+    // D rows 16mt + 4q + r = d; queries >= Tq fall outside the descriptor
+    const float inv = 1.0f / l;
+    const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + (int64_t)b * Tq * kTencD, Tq * kTencD * 4);
+    const int ooff = (tq * kTencD + h * kTencHd + 4 * q) * 4;
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0] * inv), ors, ooff, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
+}
+
 // Self-attention on the matrix cores, exact fp32 (v_mfma_f32_16x16x4_f32): softmax(q k^T) v with
 // q pre-scaled by head_dim^-0.5 (torch.nn.MultiheadAttention).
 //   qkv : (B*T, 384) = [q | k | v] x 128, head h = columns h*32 .. h*32+31 of each third
@@ -78,10 +137,6 @@ __device__ __forceinline__ float quad_max(float s) {
 // are zero: every global access is a buffer instruction over the sequence's rows, whose range
 // check returns 0 past T and drops stores, so nothing is predicated and all loads of the
 // workgroup are in flight together.
-constexpr int kAttnMaxTiles = 8; // T <= 128
-constexpr int kAttnRow = 36;
-constexpr int attn_f32_lds_bytes(int nt) { return 2 * nt * 16 * kAttnRow * (int)sizeof(float); } // K, then V
-
 template <int NT> // number of 16-frame tiles = ceil(T / 16): compile-time so that the loops are branch-free
 __global__ __launch_bounds__(64 * NT) void b2h_attn_mfma_f32(const float* __restrict__ qkv,
                                                           float* __restrict__ out, int T) {
@@ -115,51 +170,7 @@ __global__ __launch_bounds__(64 * NT) void b2h_attn_mfma_f32(const float* __rest
     qb[0] *= 0.17677669529663687f; // pre-scaled query (torch scales q, not the scores)
     qb[1] *= 0.17677669529663687f;
     __syncthreads();
-    f32x4 sc[NT];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-        sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            // A operand: key row kt*16 + col, d = 16g + 4q + j
-            const f32x4 ka = *reinterpret_cast<const f32x4*>(Ks + (kt * 16 + col) * kAttnRow + 16 * g + 4 * q);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) sc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[j], qb[g][j], sc[kt], 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { // D row 4q + r = key index within the tile
-            if (kt * 16 + 4 * q + r >= T) sc[kt][r] = -INFINITY;
-            mx = fmaxf(mx, sc[kt][r]);
-        }
-    }
-    mx = quad_max(mx);
-    float l = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            sc[kt][r] = expf(sc[kt][r] - mx); // masked keys: exp(-inf) = 0
-            l += sc[kt][r];
-        }
-    l = quad_sum(l);
-    // O^T[d][query]: for step (kt, r) lane q supplies P^T[kt*16 + 4q + r][query] = sc[kt][r];
-    // the A operand is V[kt*16 + 4q + r][16mt + col]
-    f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* vrow = Vs + (kt * 16 + 4 * q + r) * kAttnRow + col;
-            o[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[0], sc[kt][r], o[0], 0, 0, 0);
-            o[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[16], sc[kt][r], o[1], 0, 0, 0);
-        }
-    // D rows 16mt + 4q + r = d; queries >= T fall outside the descriptor
-    const float inv = 1.0f / l;
-    const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + (int64_t)b * T * kTencD, T * kTencD * 4);
-    const int ooff = (tq * kTencD + h * kTencHd + 4 * q) * 4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0] * inv), ors, ooff, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
+    attn_core_f32<NT>(Ks, Vs, qb, T, out, T, b, h, tq, col, q);
 }
 
 // ---- per-frame chain ---------------------------------------------------------------------

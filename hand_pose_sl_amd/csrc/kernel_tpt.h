@@ -9,7 +9,7 @@
 //   b2h_tpt_layernorm    encoder.norm / decoder.norm, the LayerNorm that ends each stack of torch.nn.Transformer.
 //
 // Everything else of the model is per-frame and runs as descriptors of b2h_tenc_chain<false>; the decoder's
-// self-attention is b2h_attn_mfma_f32 (b2h_api.hip: tpt_launch has the launch list).
+// self-attention is b2h_attn_mfma_f32 (b2h_api.hip: b2h_tpt_forward has the launch list).
 #pragma once
 #include "kernel_tenc.h"
 
@@ -54,10 +54,9 @@ __global__ __launch_bounds__(256) void b2h_tpt_layernorm(const float* X, const f
         make_float4(dx * rstd * g.x + b.x, dy * rstd * g.y + b.y, dz * rstd * g.z + b.z, dw * rstd * g.w + b.w);
 }
 
-// Cross-attention on the matrix cores, exact fp32 (v_mfma_f32_16x16x4_f32).  The arithmetic and the register
-// layouts are b2h_attn_mfma_f32's (kernel_tenc.h): q pre-scaled by 32^-0.5, S^T = K . Q^T per 16 x 16 tile,
-// softmax over the keys inside the lane quartet, the score accumulator as the B operand of O^T = V^T . P^T,
-// K and V rows in LDS at the 36-float pitch.  What differs is where the operands come from:
+// Cross-attention on the matrix cores, exact fp32 (v_mfma_f32_16x16x4_f32).  Everything after the operands are
+// staged is attn_core_f32 (kernel_tenc.h), which b2h_attn_mfma_f32 runs too: q pre-scaled by 32^-0.5, K and V rows
+// in LDS at the 36-float pitch.  What differs is where the operands come from:
 //   q   : (B*Tq, ldq)  rows, the head's 32 columns start at colq + 32 h
 //   kv  : (B*Tk, ldkv) rows of ANOTHER row set, K at colk + 32 h and V at colv + 32 h
 //   out : (B*Tq, 128), head h -> columns 32 h ..
@@ -110,51 +109,7 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_cross_f32(const f
     qb[0] *= 0.17677669529663687f; // pre-scaled query (torch scales q, not the scores)
     qb[1] *= 0.17677669529663687f;
     __syncthreads();
-    f32x4 sc[NK];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NK; ++kt) {
-        sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            // A operand: key row kt*16 + col, d = 16g + 4q + j
-            const f32x4 ka = *reinterpret_cast<const f32x4*>(Ks + (kt * 16 + col) * kAttnRow + 16 * g + 4 * q);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) sc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[j], qb[g][j], sc[kt], 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { // D row 4q + r = key index within the tile
-            if (kt * 16 + 4 * q + r >= Tk) sc[kt][r] = -INFINITY;
-            mx = fmaxf(mx, sc[kt][r]);
-        }
-    }
-    mx = quad_max(mx); // finite: key 0 exists (Tk >= 1)
-    float l = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            sc[kt][r] = expf(sc[kt][r] - mx); // masked keys: exp(-inf) = 0
-            l += sc[kt][r];
-        }
-    l = quad_sum(l);
-    // O^T[d][query]: for step (kt, r) lane q supplies P^T[kt*16 + 4q + r][query] = sc[kt][r];
-    // the A operand is V[kt*16 + 4q + r][16mt + col]
-    f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* vrow = Vs + (kt * 16 + 4 * q + r) * kAttnRow + col;
-            o[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[0], sc[kt][r], o[0], 0, 0, 0);
-            o[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[16], sc[kt][r], o[1], 0, 0, 0);
-        }
-    // D rows 16mt + 4q + r = d; queries >= Tq fall outside the descriptor
-    const float inv = 1.0f / l;
-    const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + (int64_t)b * Tq * kTencD, Tq * kTencD * 4);
-    const int ooff = (tq * kTencD + h * kTencHd + 4 * q) * 4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0] * inv), ors, ooff, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
+    attn_core_f32<NK>(Ks, Vs, qb, Tk, out, Tq, b, h, tq, col, q);
 }
 
 } // namespace b2h

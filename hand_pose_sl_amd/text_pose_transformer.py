@@ -19,10 +19,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import NativeModule
 from .transformer_enc import PositionalEncoding
 
 
-class TextPoseTransformer(nn.Module):
+class TextPoseTransformer(NativeModule, nn.Module):
     """`precision` (not in the reference; keyword only): only "fp32" = fp32 operands on the matrix cores."""
 
     def __init__(self, n_tokens, n_joints, joints_dim, nhead, nhid, nout, n_enc_layers, n_dec_layers, dropout=0.5, *,
@@ -45,10 +46,8 @@ class TextPoseTransformer(nn.Module):
         self.ninp = int(n_joints * joints_dim)
         self._dropout_p = float(dropout)
         self._geom = (self.n_tokens, self.ninp, int(nhead), int(nhid), int(nout), int(n_enc_layers), int(n_dec_layers))
-        self._handle = None
-        self._handle_key = None
-        self._packed_key = None
-        self._workspace = None
+
+    _NAME, _CREATE, _LOAD, _DESTROY = "TextPoseTransformer", "b2h_tpt_create", "b2h_tpt_load_weights", "b2h_tpt_destroy"
 
     def _tensors(self):
         """The parameters in state_dict order, i.e. the order of b2h_tpt_load_weights (the two pe buffers, which the
@@ -58,42 +57,12 @@ class TextPoseTransformer(nn.Module):
     def _device(self):
         return self._modules["pose2hidden_projection"]._parameters["weight"].device
 
+    def _create_args(self):
+        return self._geom
+
     def _ensure_handle(self):
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("hand_pose_sl_amd.TextPoseTransformer runs on an MI355X only: call model.to('cuda') "
-                               "first (there is no CPU path in the product)")
-        lib = _lib.load()
-        if self._handle is None or self._handle_key != dev.index:  # the handle is made for one device
-            self._free()
-            with torch.cuda.device(dev):
-                h = ctypes.c_void_p()
-                _lib.check(lib.b2h_tpt_create(*self._geom, ctypes.byref(h)))
-            self.__dict__["_handle"] = h
-            self.__dict__["_handle_key"] = dev.index
-        tensors = self._tensors()
-        key = (dev.index,) + tuple((p.data_ptr(), p._version) for p in tensors)
-        if key != self._packed_key:
-            with torch.cuda.device(dev):
-                ps = [p.detach().to(torch.float32).contiguous() for p in tensors]
-                torch.cuda.current_stream(dev).synchronize()
-                arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-                _lib.check(lib.b2h_tpt_load_weights(self._handle, arr, len(ps), 1))
-            self.__dict__["_packed_key"] = key
-        return lib, dev
-
-    def _free(self):
-        if self.__dict__.get("_handle") is not None:
-            try:
-                _lib.load().b2h_tpt_destroy(self._handle)
-            except Exception:
-                pass
-            self.__dict__["_handle"] = None
-            self.__dict__["_packed_key"] = None
-            self.__dict__["_handle_key"] = None
-
-    def __del__(self):
-        self._free()
+        """(library, device): this model's callers have always unpacked the pair."""
+        return super()._ensure_handle(), self._device()
 
     def forward(self, input_tokens, input_pose):
         if self.training and self._dropout_p > 0.0:
@@ -119,10 +88,7 @@ class TextPoseTransformer(nn.Module):
         B, S, T = tok.shape[0], tok.shape[1], x.shape[1]
         y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=dev)
         need = lib.b2h_tpt_workspace_bytes(self._handle, B, S, T)
-        ws = self.__dict__.get("_workspace")
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-            self.__dict__["_workspace"] = ws
+        ws = self._grown_workspace(need, dev)
         with _lib.on_device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.b2h_tpt_forward(self._handle, ctypes.c_void_p(tok.data_ptr()), ctypes.c_void_p(x.data_ptr()),

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import NativeModule, _aligned, _ptrs
 
 
 class PositionalEncoding(nn.Module):
@@ -46,7 +47,7 @@ class PositionalEncoding(nn.Module):
 TENC_KERNELS = {"fp32": 0, "f16x3": 1}   # b2h_tenc_kernel (include/b2h.h)
 
 
-class TransformerEnc(nn.Module):
+class TransformerEnc(NativeModule, nn.Module):
     """`precision` (not in the reference; keyword only): "fp32" = fp32 operands on the matrix cores
     (default); "f16x3" = every Linear operand split into f16 hi + lo, three f16 MFMAs per product
     with fp32 accumulation: fp32-grade error at 3/16 of the matrix cycles, for activations and
@@ -72,9 +73,8 @@ class TransformerEnc(nn.Module):
         self.hidden2pose_projection = nn.Linear(nhid, nout)
         self.pose2hidden_projection = nn.Linear(ninp, nhid)
         self._geom = (int(ninp), int(nhead), int(nhid), int(nout), int(nlayers))
-        self._handle = None
-        self._packed_key = None
-        self._workspace = None
+
+    _NAME, _CREATE, _LOAD, _DESTROY = "TransformerEnc", "b2h_tenc_create", "b2h_tenc_load_weights", "b2h_tenc_destroy"
 
     def _tensors(self):
         # through the module dictionaries (53 tensors; nn.Module.__getattr__ would cost ~50 us per forward)
@@ -98,51 +98,12 @@ class TransformerEnc(nn.Module):
     def _device(self):
         return self._modules["pose2hidden_projection"]._parameters["weight"].device
 
-    def _ensure_created(self):
-        """The native model on the parameters' device and for the pe table's max_len, without packed weights
-        (all the training path needs)."""
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("hand_pose_sl_amd.TransformerEnc runs on an MI355X only: call model.to('cuda') "
-                               "first (there is no CPU path in the product)")
-        lib = _lib.load()
+    def _handle_key(self, dev):
         # the handle is made for one device and one max_len (b2h_tenc_load_weights reads max_len rows of pe)
-        made = (dev.index, int(self._modules["pos_encoder"]._buffers["pe"].shape[0]))
-        if self._handle is None or self.__dict__.get("_handle_key") != made:
-            self._free()
-            with torch.cuda.device(dev):
-                h = ctypes.c_void_p()
-                _lib.check(lib.b2h_tenc_create(*self._geom, made[1], ctypes.byref(h)))
-            self.__dict__["_handle"] = h
-            self.__dict__["_handle_key"] = made
-        return lib, dev
+        return dev.index, int(self._modules["pos_encoder"]._buffers["pe"].shape[0])
 
-    def _ensure_handle(self):
-        lib, dev = self._ensure_created()
-        tensors = self._tensors()
-        key = self.__dict__["_handle_key"] + tuple((p.data_ptr(), p._version) for p in tensors)
-        if key == self._packed_key:
-            return lib
-        with torch.cuda.device(dev):
-            ps = [p.detach().to(torch.float32).contiguous() for p in tensors]
-            torch.cuda.current_stream(dev).synchronize()
-            arr = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
-            _lib.check(lib.b2h_tenc_load_weights(self._handle, arr, len(ps), 1))
-        self.__dict__["_packed_key"] = key
-        return lib
-
-    def _free(self):
-        if self.__dict__.get("_handle") is not None:
-            try:
-                _lib.load().b2h_tenc_destroy(self._handle)
-            except Exception:
-                pass
-            self.__dict__["_handle"] = None
-            self.__dict__["_packed_key"] = None
-            self.__dict__["_handle_key"] = None
-
-    def __del__(self):
-        self._free()
+    def _create_args(self):
+        return self._geom + (int(self._modules["pos_encoder"]._buffers["pe"].shape[0]),)
 
     def _wants_grad(self, src):
         """The training path's condition: training mode, autograd on, a parameter or the input needs a gradient."""
@@ -211,10 +172,7 @@ class TransformerEnc(nn.Module):
                 raise RuntimeError(f"n_frames must have shape ({B},)")
         y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=dev)
         need = lib.b2h_tenc_workspace_bytes(self._handle, B, T)
-        ws = self.__dict__.get("_workspace")
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-            self.__dict__["_workspace"] = ws
+        ws = self._grown_workspace(need, dev)
         with _lib.on_device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.b2h_tenc_set_kernel(self._handle, TENC_KERNELS[self.precision]))
@@ -247,15 +205,6 @@ class TransformerEnc(nn.Module):
         flags = ((_lib.PRE_CHEST_DIFF if dif_encoding else 0) | (_lib.PRE_NORMALIZE if normalize else 0) |
                  (_lib.POST_DENORMALIZE if denormalize else 0) | (_lib.POST_MASK_TAIL if mask_tail else 0))
         return self._run(body, flags, factor, n_frames)
-
-
-def _ptrs(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _aligned(t):
-    """The kernels' 16-byte vector accesses: a contiguous slice of a larger batch may start anywhere."""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 class _TencTrainFn(torch.autograd.Function):
