@@ -23,6 +23,7 @@
 #include "kernel_tenc.h"
 #include "kernel_tenc_train.h"
 #include "kernel_tpt.h"
+#include "kernel_tpt_train.h"
 #include "kernel_train.h"
 #include "kernel_valu.h"
 
@@ -732,7 +733,9 @@ int set_tenc_kernel_attributes() {
             return rc;
         for (int nt = 1; nt <= kAttnMaxTiles; ++nt)
             if ((rc = raise_lds_cap(kAttnQkvH3[nt - 1], attn_qkv_lds_bytes(nt)))) return rc;
-        if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd))) return rc;
+        if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd)) ||
+            (rc = raise_lds_cap(b2h_tptt_xsdpa)) || (rc = raise_lds_cap(b2h_tptt_xsdpa_bwd)))
+            return rc;
         return B2H_OK;
     });
 }
@@ -976,6 +979,24 @@ Chain tpt_rows(const float* x, int ldx, const float* res, int64_t n) {
     return c;
 }
 
+// Floats of the 9 + 12*n_enc + 18*n_dec parameters in the order of b2h_tpt_load_weights.  A decoder layer: two
+// attention blocks, linear1 and linear2, three LayerNorms.
+std::vector<size_t> tpt_param_floats(const b2h_tpt* m) {
+    const size_t D = kTencD;
+    const size_t* E = kEncLayerFloats;
+    std::vector<size_t> sizes;
+    for (int l = 0; l < m->n_enc; ++l) sizes.insert(sizes.end(), E, E + 12);
+    sizes.insert(sizes.end(), 2, D);
+    for (int l = 0; l < m->n_dec; ++l) {
+        sizes.insert(sizes.end(), E, E + 4);
+        sizes.insert(sizes.end(), E, E + 8);
+        sizes.insert(sizes.end(), 6, D);
+    }
+    sizes.insert(sizes.end(), 2, D);
+    sizes.insert(sizes.end(), {(size_t)m->n_tokens * D, (size_t)kOutCh * D, (size_t)kOutCh, D * kInCh, D});
+    return sizes;
+}
+
 void tpt_layernorm(const DevBuf& gb, float* x, int64_t n, hipStream_t st) {
     const float* g = (const float*)gb.p;
     hipLaunchKernelGGL(b2h_tpt_layernorm, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, st, x, g, g + kTencD, x, n);
@@ -1017,18 +1038,7 @@ int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int
         return fail(B2H_ERR_INVALID, "expected 9 + 12*n_enc_layers + 18*n_dec_layers tensors");
     for (int i = 0; i < count; ++i)
         if (!tensors[i]) return fail(B2H_ERR_INVALID, "tensor pointer is NULL");
-    const size_t D = kTencD;
-    const size_t* E = kEncLayerFloats; // a decoder layer: two attention blocks, linear1 and linear2, three LayerNorms
-    std::vector<size_t> sizes;
-    for (int l = 0; l < m->n_enc; ++l) sizes.insert(sizes.end(), E, E + 12);
-    sizes.insert(sizes.end(), 2, D);
-    for (int l = 0; l < m->n_dec; ++l) {
-        sizes.insert(sizes.end(), E, E + 4);
-        sizes.insert(sizes.end(), E, E + 8);
-        sizes.insert(sizes.end(), 6, D);
-    }
-    sizes.insert(sizes.end(), 2, D);
-    sizes.insert(sizes.end(), {(size_t)m->n_tokens * D, (size_t)kOutCh * D, (size_t)kOutCh, D * kInCh, D});
+    const std::vector<size_t> sizes = tpt_param_floats(m);
     std::vector<std::vector<float>> h;
     int rc;
     if ((rc = fetch_tensors(tensors, sizes, on_device, h)) || (rc = check_device(m->device))) return rc;
@@ -1174,8 +1184,8 @@ constexpr int64_t kTtSlab = (int64_t)3 * kTtD * kTtD + 3 * kTtD; // the largest 
 struct TtLayer {
     float *QKV, *O, *R1, *H1, *F1, *R2, *H2, *ST;
 };
-TtLayer tt_layer(float* saved, int64_t N, int l) {
-    float* p = saved + N * kTtSavedFrame + (int64_t)l * N * kTtSavedLayer;
+TtLayer tt_layer(float* layers, int64_t N, int l) { // layers: where layer 0 starts
+    float* p = layers + (int64_t)l * N * kTtSavedLayer;
     return TtLayer{p, p + N * 384, p + N * 512, p + N * 640, p + N * 768, p + N * 896, p + N * 1024, p + N * 1152};
 }
 
@@ -1251,6 +1261,54 @@ void tt_layernorm_bwd(hipStream_t st, const float* dY, const float* X, const flo
 
 float tt_scale(float p) { return p < 1.f ? 1.f / (1.f - p) : 0.f; }
 
+// One torch.nn.TransformerEncoderLayer (post-norm, ReLU) over N = B * T rows in training mode: H -> L.H2.
+// w: its twelve tensors in state_dict order; mk: its four keep-masks attn, drop1, ff, drop2, or nullptr.
+void tt_enc_layer_forward(hipStream_t st, const float* const* w, const TtLayer& L, const float* H, int64_t B, int T,
+                          const uint8_t* const* mk, float sc) {
+    const int64_t N = B * T;
+    const auto mask = [&](int i) { return mk ? mk[i] : nullptr; };
+    tt_linear(st, H, w[0], w[1], L.QKV, N, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
+    hipLaunchKernelGGL(b2h_tt_sdpa, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes(T, false), st, L.QKV,
+                       mask(0), sc, L.O, T);
+    tt_linear(st, L.O, w[2], w[3], L.R1, N, kTtD, kTtD, 0, mask(1), sc, H);
+    hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R1, w[8], w[9], L.H1, L.ST, 4, N);
+    tt_linear(st, L.H1, w[4], w[5], L.F1, N, kTtD, kTtD, 1, mask(2), sc, nullptr);
+    tt_linear(st, L.F1, w[6], w[7], L.R2, N, kTtD, kTtD, 0, mask(3), sc, L.H1);
+    hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R2, w[10], w[11], L.H2, L.ST + 2, 4, N);
+}
+
+// The gradient rows of a backward pass (N rows each): four 128-wide, one 384-wide, then the slabs.
+struct TtGrad {
+    float *gA, *gB, *gBm, *gC, *gQ, *slabs;
+};
+TtGrad tt_grad(float* scratch, int64_t N) {
+    return TtGrad{scratch, scratch + N * kTtD, scratch + N * 2 * kTtD, scratch + N * 3 * kTtD, scratch + N * 4 * kTtD,
+                  scratch + N * kTtScratchFrame};
+}
+
+// Backward of tt_enc_layer_forward: G.gA = dH2 on entry, = dH_in on return; g: the layer's twelve gradients.
+void tt_enc_layer_backward(hipStream_t st, const float* const* w, float* const* g, const TtLayer& L, const float* Hin,
+                           const TtGrad& G, int64_t B, int T, const uint8_t* const* mk, float sc) {
+    const int64_t N = B * T;
+    const auto mask = [&](int i) { return mk ? mk[i] : nullptr; };
+    // norm2: gA = dH2 -> gB = dR2 (also dH1 through the residual), gBm = dR2 through drop2
+    tt_layernorm_bwd(st, G.gA, L.R2, L.ST + 2, w[10], G.gB, G.gBm, mask(3), sc, G.slabs, N, g[10], g[11]);
+    const float* dF = mk ? G.gBm : G.gB;
+    tt_linear_dw(st, dF, L.F1, G.slabs, N, kTtD, kTtD, g[6], g[7]);
+    tt_linear_dx(st, dF, w[6], G.gC, N, kTtD, kTtD, L.F1, nullptr, mk ? sc : 1.f, nullptr); // through drop_ff and ReLU
+    tt_linear_dw(st, G.gC, L.H1, G.slabs, N, kTtD, kTtD, g[4], g[5]);
+    tt_linear_dx(st, G.gC, w[4], G.gA, N, kTtD, kTtD, nullptr, nullptr, 1.f, G.gB);              // gA = dH1
+    // norm1: gA -> gB = dR1 (also dH_in through the residual), gBm through drop1
+    tt_layernorm_bwd(st, G.gA, L.R1, L.ST, w[8], G.gB, G.gBm, mask(1), sc, G.slabs, N, g[8], g[9]);
+    const float* dA = mk ? G.gBm : G.gB;
+    tt_linear_dw(st, dA, L.O, G.slabs, N, kTtD, kTtD, g[2], g[3]);
+    tt_linear_dx(st, dA, w[2], G.gC, N, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);             // gC = dO
+    hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes(T, true), st, L.QKV,
+                       G.gC, mask(0), sc, G.gQ, T);
+    tt_linear_dw(st, G.gQ, Hin, G.slabs, N, kTtD, 3 * kTtD, g[0], g[1]);
+    tt_linear_dx(st, G.gQ, w[0], G.gA, N, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);          // gA = dH_in
+}
+
 } // namespace
 
 extern "C" {
@@ -1281,21 +1339,13 @@ int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float*
     float* S = static_cast<float*>(saved);
     float* X0 = S;
     float* H = S + N * kInCh;
+    float* Ls = S + N * kTtSavedFrame;
     hipLaunchKernelGGL(b2h_tt_posenc, dim3((unsigned)std::min<int64_t>((N * kInCh + 255) / 256, 4096)), dim3(256), 0, st, x,
                        params[0], mk(0), sc, X0, N, (int)T);
     tt_linear(st, X0, params[1], params[2], H, N, kInCh, kTtD, 0, nullptr, 1.f, nullptr);
-    for (int l = 0; l < m->nlayers; ++l) { // torch.nn.TransformerEncoderLayer, post-norm, ReLU
-        const float* const* w = params + 3 + 12 * l;
-        const TtLayer L = tt_layer(S, N, l);
-        tt_linear(st, H, w[0], w[1], L.QKV, N, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
-        hipLaunchKernelGGL(b2h_tt_sdpa, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes((int)T, false), st,
-                           L.QKV, mk(1 + 4 * l), sc, L.O, (int)T);
-        tt_linear(st, L.O, w[2], w[3], L.R1, N, kTtD, kTtD, 0, mk(2 + 4 * l), sc, H);
-        hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R1, w[8], w[9], L.H1, L.ST, 4, N);
-        tt_linear(st, L.H1, w[4], w[5], L.F1, N, kTtD, kTtD, 1, mk(3 + 4 * l), sc, nullptr);
-        tt_linear(st, L.F1, w[6], w[7], L.R2, N, kTtD, kTtD, 0, mk(4 + 4 * l), sc, L.H1);
-        hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R2, w[10], w[11], L.H2, L.ST + 2,
-                           4, N);
+    for (int l = 0; l < m->nlayers; ++l) {
+        const TtLayer L = tt_layer(Ls, N, l);
+        tt_enc_layer_forward(st, params + 3 + 12 * l, L, H, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
         H = L.H2;
     }
     const float* const* wh = params + 3 + 12 * m->nlayers;
@@ -1335,44 +1385,312 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
     const float sc = tt_scale(p);
     auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
     float* S = const_cast<float*>(static_cast<const float*>(saved)); // read only
-    float* gA = static_cast<float*>(scratch);
-    float* gB = gA + N * kTtD;
-    float* gBm = gB + N * kTtD;
-    float* gC = gBm + N * kTtD;
-    float* gQ = gC + N * kTtD;
-    float* slabs = gQ + N * 3 * kTtD;
+    const TtGrad G = tt_grad(static_cast<float*>(scratch), N);
     const float* X0 = S;
     const float* H0 = S + N * kInCh;
+    float* Ls = S + N * kTtSavedFrame;
     // hidden2pose_projection (HandPoseModels.py:173)
     const int oh = 3 + 12 * m->nlayers;
-    const float* Hlast = tt_layer(S, N, m->nlayers - 1).H2;
-    tt_linear_dw(st, dy, Hlast, slabs, N, kTtD, kOutCh, grads[oh - 1], grads[oh]);
-    tt_linear_dx(st, dy, params[oh], gA, N, kTtD, kOutCh, nullptr, nullptr, 1.f, nullptr);
-    for (int l = m->nlayers - 1; l >= 0; --l) {
-        const float* const* w = params + 3 + 12 * l;
-        float* const* g = grads + 2 + 12 * l;
-        const TtLayer L = tt_layer(S, N, l);
-        const float* Hin = l ? tt_layer(S, N, l - 1).H2 : H0;
-        // norm2: gA = dH2 -> gB = dR2 (also dH1 through the residual), gBm = dR2 through drop2
-        tt_layernorm_bwd(st, gA, L.R2, L.ST + 2, w[10], gB, gBm, mk(4 + 4 * l), sc, slabs, N, g[10], g[11]);
-        const float* dF = masks ? gBm : gB;
-        tt_linear_dw(st, dF, L.F1, slabs, N, kTtD, kTtD, g[6], g[7]);
-        tt_linear_dx(st, dF, w[6], gC, N, kTtD, kTtD, L.F1, nullptr, masks ? sc : 1.f, nullptr); // through drop_ff and ReLU
-        tt_linear_dw(st, gC, L.H1, slabs, N, kTtD, kTtD, g[4], g[5]);
-        tt_linear_dx(st, gC, w[4], gA, N, kTtD, kTtD, nullptr, nullptr, 1.f, gB);                // gA = dH1
-        // norm1: gA -> gB = dR1 (also dH_in through the residual), gBm through drop1
-        tt_layernorm_bwd(st, gA, L.R1, L.ST, w[8], gB, gBm, mk(2 + 4 * l), sc, slabs, N, g[8], g[9]);
-        const float* dA = masks ? gBm : gB;
-        tt_linear_dw(st, dA, L.O, slabs, N, kTtD, kTtD, g[2], g[3]);
-        tt_linear_dx(st, dA, w[2], gC, N, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);           // gC = dO
-        hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes((int)T, true), st,
-                           L.QKV, gC, mk(1 + 4 * l), sc, gQ, (int)T);
-        tt_linear_dw(st, gQ, Hin, slabs, N, kTtD, 3 * kTtD, g[0], g[1]);
-        tt_linear_dx(st, gQ, w[0], gA, N, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, gB);            // gA = dH_in
-    }
+    const float* Hlast = tt_layer(Ls, N, m->nlayers - 1).H2;
+    tt_linear_dw(st, dy, Hlast, G.slabs, N, kTtD, kOutCh, grads[oh - 1], grads[oh]);
+    tt_linear_dx(st, dy, params[oh], G.gA, N, kTtD, kOutCh, nullptr, nullptr, 1.f, nullptr);
+    for (int l = m->nlayers - 1; l >= 0; --l)
+        tt_enc_layer_backward(st, params + 3 + 12 * l, grads + 2 + 12 * l, tt_layer(Ls, N, l),
+                              l ? tt_layer(Ls, N, l - 1).H2 : H0, G, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
     // pose2hidden_projection (:171) and the positional encoding's dropout (:101-103)
-    tt_linear_dw(st, gA, X0, slabs, N, kInCh, kTtD, grads[0], grads[1]);
-    if (dx) tt_linear_dx(st, gA, params[1], dx, N, kInCh, kTtD, nullptr, mk(0), sc, nullptr);
+    tt_linear_dw(st, G.gA, X0, G.slabs, N, kInCh, kTtD, grads[0], grads[1]);
+    if (dx) tt_linear_dx(st, G.gA, params[1], dx, N, kInCh, kTtD, nullptr, mk(0), sc, nullptr);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+} // extern "C"
+
+// ---- TextPoseTransformer training (kernel_tpt_train.h) --------------------------------------------------------
+// torch.nn.Transformer in .train() mode between token_embedding and the two pose projections
+// (HandPoseModels.py:201-222 under autograd).  Ns = B*S token rows, Nt = B*T frame rows.
+namespace {
+
+// Saved activations (floats).  Token rows: E0 (the embeddings), every encoder layer as TransformerEnc saves it,
+// MEM (encoder.norm's output) with {mean, rstd, -, -}, and [K | V] of MEM per decoder layer.  Frame rows: X0 (a
+// copy of x, which the backward does not receive), XT0 (pose2hidden_projection), every decoder layer, YN
+// (decoder.norm's output) with its statistics.
+constexpr int64_t kTptSavedToken = 2 * kTtD + 4, kTptSavedTokenDec = 2 * kTtD;
+constexpr int64_t kTptSavedFrame = kInCh + 2 * kTtD + 4;
+constexpr int64_t kTptSavedFrameDec = 3 * kTtD + 10 * kTtD + 8; // QKV, O, R1, H1, QC, OC, R2, H2, F1, R3, H3, statistics
+// Backward scratch: TtGrad over max(Ns, Nt) rows, then per token [dK | dV] and two dMEM rows (the sum over the
+// decoder layers alternates between them), then the slabs.
+constexpr int64_t kTptScratchToken = 2 * kTtD + 2 * kTtD;
+
+struct TptDecLayer {
+    float *QKV, *O, *R1, *H1, *QC, *OC, *R2, *H2, *F1, *R3, *H3, *ST12, *ST3, *KV;
+};
+struct TptSaved {
+    float *E0, *enc, *MEM, *STm, *KV, *X0, *XT0, *dec, *YN, *STy;
+    int64_t Ns, Nt;
+    TtLayer enc_layer(int l) const { return tt_layer(enc, Ns, l); }
+    const float* enc_out(int n_enc) const { return enc_layer(n_enc - 1).H2; }
+    TptDecLayer dec_layer(int l) const {
+        float* p = dec + (int64_t)l * Nt * kTptSavedFrameDec;
+        const int64_t D = Nt * kTtD;
+        return TptDecLayer{p, p + 3 * D, p + 4 * D, p + 5 * D, p + 6 * D, p + 7 * D, p + 8 * D, p + 9 * D, p + 10 * D,
+                           p + 11 * D, p + 12 * D, p + 13 * D, p + 13 * D + 4 * Nt, KV + (int64_t)l * Ns * kTptSavedTokenDec};
+    }
+};
+TptSaved tpt_saved(const b2h_tpt* m, void* saved, int64_t Ns, int64_t Nt) {
+    TptSaved s;
+    s.Ns = Ns; s.Nt = Nt;
+    s.E0 = static_cast<float*>(saved);
+    s.enc = s.E0 + Ns * kTtD;
+    s.MEM = s.enc + Ns * kTtSavedLayer * m->n_enc;
+    s.STm = s.MEM + Ns * kTtD;
+    s.KV = s.STm + Ns * 4;
+    s.X0 = s.KV + Ns * kTptSavedTokenDec * m->n_dec;
+    s.XT0 = s.X0 + Nt * kInCh;
+    s.dec = s.XT0 + Nt * kTtD;
+    s.YN = s.dec + Nt * kTptSavedFrameDec * m->n_dec;
+    s.STy = s.YN + Nt * kTtD;
+    return s;
+}
+
+size_t tpt_saved_bytes(const b2h_tpt* m, int64_t Ns, int64_t Nt) {
+    return ((size_t)Ns * (kTptSavedToken + m->n_enc * kTtSavedLayer + m->n_dec * kTptSavedTokenDec) +
+            (size_t)Nt * (kTptSavedFrame + m->n_dec * kTptSavedFrameDec)) * 4;
+}
+size_t tpt_scratch_bytes(int64_t Ns, int64_t Nt) {
+    const int64_t Nmax = std::max(Ns, Nt);
+    return ((size_t)Nmax * kTtScratchFrame + (size_t)Ns * kTptScratchToken + (size_t)tt_nslabs(Nmax) * kTtSlab) * 4;
+}
+
+int tpt_nparams(const b2h_tpt* m) { return 9 + 12 * m->n_enc + 18 * m->n_dec; }
+int tpt_nmasks(const b2h_tpt* m) { return 4 * m->n_enc + 6 * m->n_dec; }
+
+// Elements of keep-mask i: per encoder layer attn, drop1, ff, drop2; per decoder layer self_attn, drop1,
+// cross_attn, drop2, ff, drop3.
+size_t tpt_mask_bytes(const b2h_tpt* m, int i, int64_t B, int64_t S, int64_t T) {
+    if (i < 4 * m->n_enc) return i % 4 == 0 ? (size_t)B * kTtHeads * S * S : (size_t)B * S * kTtD;
+    const int k = (i - 4 * m->n_enc) % 6;
+    return k == 0 ? (size_t)B * kTtHeads * T * T : (k == 2 ? (size_t)B * kTtHeads * T * S : (size_t)B * T * kTtD);
+}
+
+// Checks shared by b2h_tpt_train_forward / b2h_tpt_backward, as tt_check makes them.
+int tptt_check(const b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks, float p,
+               int64_t B, int64_t S, int64_t T) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (!params) return fail(B2H_ERR_INVALID, "params is NULL");
+    if (!(p >= 0.f && p <= 1.f)) return fail(B2H_ERR_INVALID, "dropout p must be in [0, 1]");
+    if ((p > 0.f) != (masks != nullptr)) return fail(B2H_ERR_INVALID, "masks must be given exactly when p > 0");
+    if (B < 0 || S < 1 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0, S >= 1 and T >= 1");
+    if (S > kTptMaxLen || T > kTptMaxLen) return fail(B2H_ERR_SHAPE, "TextPoseTransformer: S and T are limited to 128");
+    // grid limits: attention launches B x heads workgroups, LayerNorm N / 4 (the largest row grid)
+    if (B * kTtHeads > 0x7fffffff || B * std::max(S, T) / 4 >= 0x7fffffff)
+        return fail(B2H_ERR_SHAPE, "batch too large for one launch");
+    for (int i = 0; i < tpt_nparams(m); ++i) {
+        if (!params[i]) return fail(B2H_ERR_INVALID, "params[" + std::to_string(i) + "] is NULL");
+        if (misaligned(params[i], 4)) return fail(B2H_ERR_INVALID, "params must be 4-byte aligned fp32 tensors");
+    }
+    if (masks)
+        for (int i = 0; i < tpt_nmasks(m); ++i)
+            if (!masks[i]) return fail(B2H_ERR_INVALID, "masks[" + std::to_string(i) + "] is NULL");
+    if (B > 0 && !tokens) return fail(B2H_ERR_INVALID, "tokens is NULL");
+    if (misaligned(tokens, 8)) return fail(B2H_ERR_INVALID, "tokens must be 8-byte aligned");
+    return B2H_OK;
+}
+
+// The read-only operands of a training call for check_overlap: its plain inputs, the parameters and the masks.
+std::vector<Span> tptt_read_only(const b2h_tpt* m, const float* const* params, const uint8_t* const* masks, int64_t B,
+                                 int64_t S, int64_t T, std::vector<Span> ins) {
+    for (Span& in : ins) in.what = "an input";
+    const std::vector<size_t> sizes = tpt_param_floats(m);
+    for (size_t i = 0; i < sizes.size(); ++i) ins.push_back({params[i], sizes[i] * 4, "a parameter"});
+    if (masks)
+        for (int i = 0; i < tpt_nmasks(m); ++i) ins.push_back({masks[i], tpt_mask_bytes(m, i, B, S, T), "a mask"});
+    return ins;
+}
+
+void tt_layernorm(hipStream_t st, const float* X, const float* gamma, const float* beta, float* Y, float* stats, int64_t N) {
+    hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, X, gamma, beta, Y, stats, 4, N);
+}
+
+// The cross-attention operands of decoder layer L: queries QC (Nt, 128), [K | V] rows (Ns, 256).
+XsdpaSrc tpt_xsrc(const TptDecLayer& L) { return XsdpaSrc{L.QC, kTtD, 0, L.KV, 2 * kTtD, 0, kTtD}; }
+
+} // namespace
+
+extern "C" {
+
+size_t b2h_tpt_train_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int which) {
+    if (!m || B < 1 || S < 1 || T < 1 || (which != 0 && which != 1)) return 0;
+    return which == 0 ? tpt_saved_bytes(m, B * S, B * T) : tpt_scratch_bytes(B * S, B * T);
+}
+
+int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t* tokens, const float* x,
+                          const uint8_t* const* masks, float p, float* y, void* saved, size_t saved_bytes, int64_t B,
+                          int64_t S, int64_t T, void* stream) {
+    if (int rc = tptt_check(m, params, tokens, masks, p, B, S, T)) return rc;
+    if (B == 0) return B2H_OK;
+    if (!x || !y || !saved) return fail(B2H_ERR_INVALID, "NULL pointer");
+    if (int rc = check_device(m->device)) return rc;
+    if (misaligned(x, 16) || misaligned(y, 16) || misaligned(saved, 16))
+        return fail(B2H_ERR_INVALID, "x, y and the saved buffer must be 16-byte aligned");
+    const int64_t Ns = B * S, Nt = B * T;
+    const size_t need = tpt_saved_bytes(m, Ns, Nt);
+    if (saved_bytes < need)
+        return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes (" + std::to_string(need) + " B)");
+    if (int rc = check_overlap({{y, (size_t)Nt * kOutCh * 4}, {saved, need}},
+                               tptt_read_only(m, params, masks, B, S, T,
+                                              {{tokens, (size_t)Ns * 8}, {x, (size_t)Nt * kInCh * 4}})))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const float sc = tt_scale(p);
+    const auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
+    const TptSaved sv = tpt_saved(m, saved, Ns, Nt);
+
+    // encoder: token_embedding (:206) -> layers -> encoder.norm
+    const float* const* wt = params + 4 + 12 * m->n_enc + 18 * m->n_dec; // token_embedding, hidden2pose, pose2hidden
+    hipLaunchKernelGGL(b2h_tpt_embed, dim3((unsigned)((Ns * 32 + 255) / 256)), dim3(256), 0, st, tokens, wt[0], sv.E0, Ns,
+                       m->n_tokens);
+    const float* H = sv.E0;
+    for (int l = 0; l < m->n_enc; ++l) {
+        const TtLayer L = sv.enc_layer(l);
+        tt_enc_layer_forward(st, params + 12 * l, L, H, B, (int)S, masks ? masks + 4 * l : nullptr, sc);
+        H = L.H2;
+    }
+    const float* const* wn = params + 12 * m->n_enc;
+    tt_layernorm(st, H, wn[0], wn[1], sv.MEM, sv.STm, Ns);
+
+    // decoder: pose2hidden_projection (:209) -> layers -> decoder.norm -> hidden2pose_projection (:213)
+    HIP_TRY(hipMemcpyAsync(sv.X0, x, (size_t)Nt * kInCh * 4, hipMemcpyDeviceToDevice, st));
+    tt_linear(st, sv.X0, wt[3], wt[4], sv.XT0, Nt, kInCh, kTtD, 0, nullptr, 1.f, nullptr);
+    H = sv.XT0;
+    const unsigned heads = (unsigned)(B * kTtHeads);
+    for (int l = 0; l < m->n_dec; ++l) { // torch.nn.TransformerDecoderLayer, post-norm, ReLU
+        const float* const* w = params + 12 * m->n_enc + 2 + 18 * l;
+        const int mi = 4 * m->n_enc + 6 * l;
+        const TptDecLayer L = sv.dec_layer(l);
+        tt_linear(st, H, w[0], w[1], L.QKV, Nt, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
+        hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, false), st, L.QKV, mk(mi), sc, L.O,
+                           (int)T);
+        tt_linear(st, L.O, w[2], w[3], L.R1, Nt, kTtD, kTtD, 0, mk(mi + 1), sc, H);
+        tt_layernorm(st, L.R1, w[12], w[13], L.H1, L.ST12, Nt);
+        // multihead_attn: the query of H1 (in_proj rows 0..127), [K | V] of the memory (rows 128..383)
+        tt_linear(st, L.H1, w[4], w[5], L.QC, Nt, kTtD, kTtD, 0, nullptr, 1.f, nullptr);
+        tt_linear(st, sv.MEM, w[4] + kDD, w[5] + kTtD, L.KV, Ns, kTtD, 2 * kTtD, 0, nullptr, 1.f, nullptr);
+        hipLaunchKernelGGL(b2h_tptt_xsdpa, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, false), st,
+                           tpt_xsrc(L), mk(mi + 2), sc, L.OC, (int)T, (int)S);
+        tt_linear(st, L.OC, w[6], w[7], L.R2, Nt, kTtD, kTtD, 0, mk(mi + 3), sc, L.H1);
+        tt_layernorm(st, L.R2, w[14], w[15], L.H2, L.ST12 + 2, Nt);
+        tt_linear(st, L.H2, w[8], w[9], L.F1, Nt, kTtD, kTtD, 1, mk(mi + 4), sc, nullptr);
+        tt_linear(st, L.F1, w[10], w[11], L.R3, Nt, kTtD, kTtD, 0, mk(mi + 5), sc, L.H2);
+        tt_layernorm(st, L.R3, w[16], w[17], L.H3, L.ST3, Nt);
+        H = L.H3;
+    }
+    const float* const* wd = params + 12 * m->n_enc + 2 + 18 * m->n_dec;
+    tt_layernorm(st, H, wd[0], wd[1], sv.YN, sv.STy, Nt);
+    tt_linear(st, sv.YN, wt[1], wt[2], y, Nt, kTtD, kOutCh, 0, nullptr, 1.f, nullptr);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks, float p,
+                     const float* dy, const void* saved, size_t saved_bytes, float* dx, float* const* grads, void* scratch,
+                     size_t scratch_bytes, int64_t B, int64_t S, int64_t T, void* stream) {
+    if (int rc = tptt_check(m, params, tokens, masks, p, B, S, T)) return rc;
+    if (B == 0) return fail(B2H_ERR_SHAPE, "b2h_tpt_backward needs B >= 1 (the gradients of an empty batch are not defined here)");
+    if (!dy || !saved || !scratch) return fail(B2H_ERR_INVALID, "dy / saved / scratch is NULL");
+    if (!grads) return fail(B2H_ERR_INVALID, "grads is NULL");
+    if (int rc = check_device(m->device)) return rc;
+    if (misaligned(dy, 16) || misaligned(saved, 16) || misaligned(scratch, 16) || (dx && misaligned(dx, 16)))
+        return fail(B2H_ERR_INVALID, "dy, dx, the saved buffer and the scratch must be 16-byte aligned");
+    const int64_t Ns = B * S, Nt = B * T;
+    const size_t need_saved = tpt_saved_bytes(m, Ns, Nt), need = tpt_scratch_bytes(Ns, Nt);
+    if (saved_bytes < need_saved) return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes");
+    if (scratch_bytes < need)
+        return fail(B2H_ERR_INVALID, "scratch smaller than b2h_tpt_train_bytes (" + std::to_string(need) + " B)");
+    const std::vector<size_t> sizes = tpt_param_floats(m);
+    std::vector<Span> outs;
+    for (size_t i = 0; i < sizes.size(); ++i) {
+        if (!grads[i]) return fail(B2H_ERR_INVALID, "grads[" + std::to_string(i) + "] is NULL");
+        if (misaligned(grads[i], 4)) return fail(B2H_ERR_INVALID, "grads must be 4-byte aligned");
+        outs.push_back({grads[i], sizes[i] * 4});
+    }
+    if (dx) outs.push_back({dx, (size_t)Nt * kInCh * 4});
+    outs.push_back({scratch, need});
+    if (int rc = check_overlap(outs, tptt_read_only(m, params, masks, B, S, T,
+                                                    {{tokens, (size_t)Ns * 8}, {dy, (size_t)Nt * kOutCh * 4}, {saved, need_saved}})))
+        return rc;
+
+    hipStream_t st = (hipStream_t)stream;
+    const float sc = tt_scale(p);
+    const auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
+    const TptSaved sv = tpt_saved(m, const_cast<void*>(saved), Ns, Nt); // read only
+    const int64_t Nmax = std::max(Ns, Nt);
+    float* scr = static_cast<float*>(scratch);
+    float* dKV = scr + Nmax * kTtScratchFrame;
+    float* dM[2] = {dKV + Ns * 2 * kTtD, dKV + Ns * 3 * kTtD};
+    TtGrad G = tt_grad(scr, Nt); // the frame rows first; the slabs lie behind both row sets
+    G.slabs = dM[1] + Ns * kTtD;
+    const unsigned heads = (unsigned)(B * kTtHeads);
+    const int od = 12 * m->n_enc + 2, ot = od + 18 * m->n_dec + 2; // the first decoder layer; token_embedding
+
+    // hidden2pose_projection (:213) and decoder.norm
+    tt_linear_dw(st, dy, sv.YN, G.slabs, Nt, kTtD, kOutCh, grads[ot + 1], grads[ot + 2]);
+    tt_linear_dx(st, dy, params[ot + 1], G.gB, Nt, kTtD, kOutCh, nullptr, nullptr, 1.f, nullptr);
+    tt_layernorm_bwd(st, G.gB, sv.dec_layer(m->n_dec - 1).H3, sv.STy, params[ot - 2], G.gA, G.gBm, nullptr, 1.f, G.slabs, Nt,
+                     grads[ot - 2], grads[ot - 1]);
+    float* dMEM = nullptr; // the sum over the decoder layers done so far
+    for (int l = m->n_dec - 1; l >= 0; --l) {
+        const float* const* w = params + od + 18 * l;
+        float* const* g = grads + od + 18 * l;
+        const int mi = 4 * m->n_enc + 6 * l;
+        const TptDecLayer L = sv.dec_layer(l);
+        const float* Hin = l ? sv.dec_layer(l - 1).H3 : sv.XT0;
+        // norm3: gA = dH3 -> gB = dR3 (also dH2 through the residual), gBm = dR3 through drop3
+        tt_layernorm_bwd(st, G.gA, L.R3, L.ST3, w[16], G.gB, G.gBm, mk(mi + 5), sc, G.slabs, Nt, g[16], g[17]);
+        const float* dF = masks ? G.gBm : G.gB;
+        tt_linear_dw(st, dF, L.F1, G.slabs, Nt, kTtD, kTtD, g[10], g[11]);
+        tt_linear_dx(st, dF, w[10], G.gC, Nt, kTtD, kTtD, L.F1, nullptr, masks ? sc : 1.f, nullptr); // through drop_ff and ReLU
+        tt_linear_dw(st, G.gC, L.H2, G.slabs, Nt, kTtD, kTtD, g[8], g[9]);
+        tt_linear_dx(st, G.gC, w[8], G.gA, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, G.gB);             // gA = dH2
+        // norm2: gA -> gB = dR2 (also dH1 through the residual), gBm through drop2
+        tt_layernorm_bwd(st, G.gA, L.R2, L.ST12 + 2, w[14], G.gB, G.gBm, mk(mi + 3), sc, G.slabs, Nt, g[14], g[15]);
+        const float* dC = masks ? G.gBm : G.gB;
+        tt_linear_dw(st, dC, L.OC, G.slabs, Nt, kTtD, kTtD, g[6], g[7]);
+        tt_linear_dx(st, dC, w[6], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dOC
+        hipLaunchKernelGGL(b2h_tptt_xsdpa_bwd, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, true), st,
+                           tpt_xsrc(L), G.gC, mk(mi + 2), sc, G.gA, dKV, (int)T, (int)S);            // gA = dQC
+        // multihead_attn.in_proj: rows 0..127 from (dQC, H1) over the frames, rows 128..383 from ([dK | dV], MEM)
+        // over the tokens, each with the slab count of its own row set
+        tt_linear_dw(st, G.gA, L.H1, G.slabs, Nt, kTtD, kTtD, g[4], g[5]);
+        tt_linear_dw(st, dKV, sv.MEM, G.slabs, Ns, kTtD, 2 * kTtD, g[4] + kDD, g[5] + kTtD);
+        tt_linear_dx(st, G.gA, w[4], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, G.gB);             // gC = dH1
+        float* dMnext = dMEM == dM[0] ? dM[1] : dM[0];
+        tt_linear_dx(st, dKV, w[4] + kDD, dMnext, Ns, kTtD, 2 * kTtD, nullptr, nullptr, 1.f, dMEM);  // dMEM += [dK | dV] W_kv
+        dMEM = dMnext;
+        // norm1: gC -> gB = dR1 (also dH_in through the residual), gBm through drop1
+        tt_layernorm_bwd(st, G.gC, L.R1, L.ST12, w[12], G.gB, G.gBm, mk(mi + 1), sc, G.slabs, Nt, g[12], g[13]);
+        const float* dA = masks ? G.gBm : G.gB;
+        tt_linear_dw(st, dA, L.O, G.slabs, Nt, kTtD, kTtD, g[2], g[3]);
+        tt_linear_dx(st, dA, w[2], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dO
+        hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, true), st, L.QKV, G.gC, mk(mi),
+                           sc, G.gQ, (int)T);
+        tt_linear_dw(st, G.gQ, Hin, G.slabs, Nt, kTtD, 3 * kTtD, g[0], g[1]);
+        tt_linear_dx(st, G.gQ, w[0], G.gA, Nt, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);         // gA = dH_in
+    }
+    // pose2hidden_projection (:209)
+    tt_linear_dw(st, G.gA, sv.X0, G.slabs, Nt, kInCh, kTtD, grads[ot + 3], grads[ot + 4]);
+    if (dx) tt_linear_dx(st, G.gA, params[ot + 3], dx, Nt, kInCh, kTtD, nullptr, nullptr, 1.f, nullptr);
+
+    // encoder.norm, the encoder layers, token_embedding (:206)
+    float* slabs = G.slabs;
+    G = tt_grad(scr, Ns);
+    G.slabs = slabs;
+    tt_layernorm_bwd(st, dMEM, sv.enc_out(m->n_enc), sv.STm, params[od - 2], G.gA, G.gBm, nullptr, 1.f, G.slabs, Ns,
+                     grads[od - 2], grads[od - 1]);
+    for (int l = m->n_enc - 1; l >= 0; --l)
+        tt_enc_layer_backward(st, params + 12 * l, grads + 12 * l, sv.enc_layer(l), l ? sv.enc_layer(l - 1).H2 : sv.E0, G, B,
+                              (int)S, masks ? masks + 4 * l : nullptr, sc);
+    hipLaunchKernelGGL(b2h_tptt_embed_bwd, dim3((unsigned)m->n_tokens), dim3(128), 0, st, tokens, G.gA, grads[ot], Ns);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }

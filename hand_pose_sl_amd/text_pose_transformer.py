@@ -10,7 +10,14 @@ caller, as in the reference (traintest.py:105-107).  The torch containers only h
 through the C ABI (`b2h_tpt_forward`).  Like the reference, the model passes no mask (padded token id 0 is attended
 like any other id) and never applies its two positional encodings, which exist only as `pe` buffers.
 
-Inference only, exact fp32, S <= 128 and T <= 128.  No path ever falls back to PyTorch ops.
+Training: in training mode with autograd enabled and a parameter or `input_pose` requiring a gradient,
+`model(input_tokens, input_pose)` runs `_TptTrainFn` -- an exact-fp32 HIP forward and backward
+(b2h_tpt_train_forward / b2h_tpt_backward, kernel_tpt_train.h) that read the parameters' own storage -- so the
+reference's loop body (steps/traintest.py:105-121) runs unchanged with any torch optimizer.  The dropout keep-masks
+are drawn by torch on the model's device (`_draw_dropout_masks`; they follow torch.manual_seed) and handed to the
+kernels.  Every other call (eval mode or no_grad) runs the inference kernels.
+
+Exact fp32, S <= 128 and T <= 128.  No path ever falls back to PyTorch ops.
 """
 import ctypes
 import warnings
@@ -19,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import NativeModule
+from ._native import NativeModule, _aligned, _ptrs
 from .transformer_enc import PositionalEncoding
 
 
@@ -64,10 +71,37 @@ class TextPoseTransformer(NativeModule, nn.Module):
         """(library, device): this model's callers have always unpacked the pair."""
         return super()._ensure_handle(), self._device()
 
-    def forward(self, input_tokens, input_pose):
-        if self.training and self._dropout_p > 0.0:
-            raise RuntimeError("hand_pose_sl_amd.TextPoseTransformer is inference-only: in training mode the reference "
-                               f"applies dropout (p = {self._dropout_p}) and this path has none; call model.eval()")
+    def _wants_grad(self, input_tokens, input_pose):
+        """The training path's condition: training mode, autograd on, a parameter or the pose needs a gradient."""
+        return (self.training and torch.is_grad_enabled() and
+                (input_pose.requires_grad or any(p.requires_grad for p in self._tensors())))
+
+    def _mask_order(self, B, S, T):
+        """(key, shape) of every keep-mask in the order of b2h_tpt_train_forward (include/b2h.h)."""
+        nhead, nhid, n_enc, n_dec = self._geom[2], self._geom[3], self._geom[5], self._geom[6]
+        order = []
+        for l in range(n_enc):
+            order.append((("enc", l, "attn"), (B, nhead, S, S)))
+            order += [(("enc", l, name), (B, S, nhid)) for name in ("drop1", "ff", "drop2")]
+        for l in range(n_dec):
+            order += [(("dec", l, "self_attn"), (B, nhead, T, T)), (("dec", l, "drop1"), (B, T, nhid)),
+                      (("dec", l, "cross_attn"), (B, nhead, T, S)), (("dec", l, "drop2"), (B, T, nhid)),
+                      (("dec", l, "ff"), (B, T, nhid)), (("dec", l, "drop3"), (B, T, nhid))]
+        return order
+
+    def _draw_dropout_masks(self, B, S, T):
+        """The keep-masks of one training forward: uint8, 1 = keep with probability 1 - p, drawn on the model's
+        device with torch's generator (so they follow torch.manual_seed) in this fixed order, which is that of
+        torch's layers: per encoder layer ("enc", l, name) with name = `attn` (B, 4, S, S), `drop1`, `ff`, `drop2`
+        (B, S, 128 each); then per decoder layer ("dec", l, name) with name = `self_attn` (B, 4, T, T), `drop1`
+        (B, T, 128), `cross_attn` (B, 4, T, S), `drop2`, `ff`, `drop3` (B, T, 128 each).  An empty dict at p = 0."""
+        p = self._dropout_p
+        if p == 0.0:
+            return {}
+        dev = self._device()
+        return {key: (torch.rand(shape, device=dev) >= p).to(torch.uint8) for key, shape in self._mask_order(B, S, T)}
+
+    def _check_inputs(self, input_tokens, input_pose):
         if input_pose.dim() != 4 or input_pose.shape[2] * input_pose.shape[3] != self.ninp:
             raise RuntimeError(f"expected input_pose of shape (B, T, {self.ninp // 2}, 2), got {tuple(input_pose.shape)}")
         if input_tokens.dim() != 2:
@@ -82,6 +116,34 @@ class TextPoseTransformer(NativeModule, nn.Module):
             lo, hi = int(input_tokens.min()), int(input_tokens.max())
             if lo < 0 or hi >= self.n_tokens:
                 raise IndexError("index out of range in self")  # nn.Embedding's message
+
+    def _forward_train(self, input_tokens, input_pose, masks):
+        """The differentiable forward (`_TptTrainFn`) with the given keep-masks (`_draw_dropout_masks`)."""
+        self._check_inputs(input_tokens, input_pose)
+        dev = self._device()
+        tok = input_tokens.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+        x = input_pose.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        p = self._dropout_p
+        if (p > 0.0) != bool(masks):
+            raise ValueError("masks must be given exactly when the dropout probability is > 0")
+        order = self._mask_order(tok.shape[0], tok.shape[1], x.shape[1]) if masks else []
+        for key, shape in order:
+            m = masks[key]
+            if m.shape != shape or m.dtype != torch.uint8 or m.device != x.device or not m.is_contiguous():
+                raise RuntimeError(f"mask {key}: expected a contiguous uint8 tensor of shape {shape} on {x.device}")
+        return _TptTrainFn.apply(self, p, [masks[k] for k, _ in order], tok, x, *self._tensors())
+
+    def forward(self, input_tokens, input_pose):
+        train = self._wants_grad(input_tokens, input_pose) and self._device().type == "cuda"
+        if not train and self.training and self._dropout_p > 0.0:
+            raise RuntimeError("hand_pose_sl_amd.TextPoseTransformer: this call runs the inference kernels (autograd is "
+                               "off, nothing requires a gradient, or the parameters are not on a GPU), which are "
+                               f"inference-only: in training mode the reference applies dropout (p = {self._dropout_p}) "
+                               "and this path has none; call model.eval()")
+        self._check_inputs(input_tokens, input_pose)
+        if train:
+            return self._forward_train(input_tokens, input_pose, self._draw_dropout_masks(
+                input_tokens.shape[0], input_tokens.shape[1], input_pose.shape[1]))
         lib, dev = self._ensure_handle()
         tok = input_tokens.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
         x = input_pose.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
@@ -95,3 +157,61 @@ class TextPoseTransformer(NativeModule, nn.Module):
                                            ctypes.c_void_p(y.data_ptr()), B, S, T, ctypes.c_void_p(ws.data_ptr()),
                                            ws.numel(), ctypes.c_void_p(st)))
         return y
+
+
+class _TptTrainFn(torch.autograd.Function):
+    """y = TextPoseTransformer(tokens, x) in training mode with its gradient: b2h_tpt_train_forward /
+    b2h_tpt_backward (exact fp32, kernel_tpt_train.h), after transformer_enc._TencTrainFn.  The parameters go in
+    as themselves (their own data_ptr, saved for backward, so autograd's version check catches an in-place edit
+    between forward and backward).  The context keeps the saved-activation buffer, the token ids and the masks
+    alive; the backward needs neither x nor y (the reference's loop overwrites the prediction's tail in place
+    before the loss).  The token ids get no gradient; token_embedding.weight's is dense."""
+
+    @staticmethod
+    def forward(ctx, model, p, masks, tok, x, *params):
+        for t in params:
+            if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("training needs contiguous float32 parameters on the input's device")
+        lib, dev = model._ensure_created()
+        x = _aligned(x)
+        tok = _aligned(tok)
+        B, S, T = tok.shape[0], tok.shape[1], x.shape[1]
+        y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=x.device)
+        nbytes = lib.b2h_tpt_train_bytes(model._handle, B, S, T, 0)
+        saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
+        with _lib.on_device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.b2h_tpt_train_forward(model._handle, _ptrs(params), ctypes.c_void_p(tok.data_ptr()),
+                                                 ctypes.c_void_p(x.data_ptr()), _ptrs(masks) if masks else None, p,
+                                                 ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(saved.data_ptr()), nbytes,
+                                                 B, S, T, ctypes.c_void_p(st)))
+        ctx.model, ctx.p, ctx.masks, ctx.shape = model, p, masks, (B, S, T)
+        ctx.save_for_backward(saved, tok, *params)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        saved, tok, *params = ctx.saved_tensors
+        model, masks = ctx.model, ctx.masks
+        need_dx = ctx.needs_input_grad[4]
+        B, S, T = ctx.shape
+        dev = saved.device
+        if B == 0:
+            grads = [torch.zeros_like(t) for t in params]
+            dx = torch.zeros((B, T, 12, 2), dtype=torch.float32, device=dev) if need_dx else None
+        else:
+            lib, dev = model._ensure_created()
+            dy = _aligned(dy.to(torch.float32).contiguous())   # autograd may hand over an expanded / CopySlices gradient
+            grads = [torch.empty_like(t) for t in params]
+            dx = torch.empty((B, T, 12, 2), dtype=torch.float32, device=dev) if need_dx else None
+            nbytes = lib.b2h_tpt_train_bytes(model._handle, B, S, T, 1)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            with _lib.on_device(dev):
+                st = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(lib.b2h_tpt_backward(model._handle, _ptrs(params), ctypes.c_void_p(tok.data_ptr()),
+                                                _ptrs(masks) if masks else None, ctx.p, ctypes.c_void_p(dy.data_ptr()),
+                                                ctypes.c_void_p(saved.data_ptr()), saved.numel(),
+                                                ctypes.c_void_p(dx.data_ptr()) if dx is not None else None, _ptrs(grads),
+                                                ctypes.c_void_p(ws.data_ptr()), nbytes, B, S, T, ctypes.c_void_p(st)))
+        return (None, None, None, None, dx) + tuple(g if ctx.needs_input_grad[5 + i] else None for i, g in enumerate(grads))

@@ -300,8 +300,9 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
  * scaled), pose2hidden_projection, torch.nn.Transformer(nhid, nhead, n_enc_layers, n_dec_layers, nhid) with the
  * token embeddings as source and the projected pose as target, hidden2pose_projection.  Post-norm layers, ReLU,
  * eps 1e-5, both stacks end with their LayerNorm; the reference passes no mask of any kind (:211), so padded
- * token id 0 is attended like any other, and never applies its two positional encodings.  Inference only
- * (dropout = identity), exact fp32 on the matrix cores.  Tokenisation stays with the caller: the model's boundary
+ * token id 0 is attended like any other, and never applies its two positional encodings.  The entry points of
+ * this block are the inference path (dropout = identity), exact fp32 on the matrix cores; training is
+ * b2h_tpt_train_forward / b2h_tpt_backward below.  Tokenisation stays with the caller: the model's boundary
  * is integer ids (:201, traintest.py:105-107). */
 typedef struct b2h_tpt b2h_tpt;
 /* Replaces TextPoseTransformer.__init__ (HandPoseModels.py:181-230) as run.py:148-151 calls it.  `ninp` is
@@ -341,6 +342,60 @@ size_t b2h_tpt_workspace_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T
  * and a sequence's output does not depend on the rest of the batch. */
 int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y, int64_t B, int64_t S,
                     int64_t T, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Training (TextPoseTransformer) -------------------------------------------------
+ * The reference trains its default model with `prediction = model(batch["text_tokens"], batch["input_kp"])`,
+ * mask_output, the criterion, loss.backward() and optimizer.step() (traintest.py:105-121).  These entry points
+ * are TextPoseTransformer.forward in .train() mode (HandPoseModels.py:201-222 under autograd: token_embedding,
+ * pose2hidden_projection, torch's post-norm nn.Transformer with ReLU and its two final LayerNorms,
+ * hidden2pose_projection) and its backward, built like the TransformerEnc pair above: exact fp32 on the
+ * vector ALU, one kernel per operation, the parameters read straight from the caller's tensors
+ * (b2h_tpt_load_weights is neither needed nor called).
+ *   params: host array of the 9 + 12*n_enc_layers + 18*n_dec_layers device fp32 tensors in the order of
+ *           b2h_tpt_load_weights, 4-byte aligned.
+ *   tokens: device int64 (B, S), 8-byte aligned.  An id outside [0, n_tokens) never indexes anything: its
+ *           sequence's y becomes NaN in the forward, and the backward skips it in the embedding gradient.
+ *   p     : the dropout probability (the reference passes one value everywhere), 0 <= p <= 1.
+ *   masks : NULL when p == 0; else a host array of 4*n_enc_layers + 6*n_dec_layers device uint8 keep-masks
+ *           (1 = keep; kept values are scaled by 1 / (1 - p), everything is dropped at p == 1) in the order of
+ *           torch's layers:
+ *             per encoder layer: attn (B, 4, S, S), drop1, ff, drop2 (B, S, 128 each);
+ *             per decoder layer: self_attn (B, 4, T, T), drop1 (B, T, 128), cross_attn (B, 4, T, S),
+ *               drop2, ff, drop3 (B, T, 128 each).
+ *           There is no embedding or positional mask: the reference never applies its positional encoders.
+ * 1 <= S, T <= 128.  Stream-ordered and asynchronous: none synchronises, allocates or reads device memory on the
+ * host, so they can be captured into a HIP graph.  x, y, dy, dx, the saved buffer and the scratch must be
+ * 16-byte aligned and no output may overlap another operand (B2H_ERR_INVALID). */
+
+/* Bytes a (B, S, T) batch needs, pure functions of (B, S, T) and the layer counts.
+ *   which = 0, the saved-activation buffer b2h_tpt_train_forward fills for b2h_tpt_backward:
+ *     B*S * (1040 + 4624*n_enc_layers + 1024*n_dec_layers) + B*T * (1136 + 6688*n_dec_layers)
+ *   which = 1, the scratch of b2h_tpt_backward, with N = max(B*S, B*T):
+ *     N * 3584 + B*S * 2048 + clamp(ceil(N / 128), 1, 64) * 198144
+ * 0 for a NULL model, B < 1, S < 1, T < 1 or another `which`. */
+size_t b2h_tpt_train_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int which);
+/* y = TextPoseTransformer(tokens, x) in .train() mode with the given dropout masks (HandPoseModels.py:201-222):
+ * x (B, T, 12, 2) -> y (B, T, 21, 2), device fp32; fills `saved` (device, >= b2h_tpt_train_bytes(m, B, S, T, 0)).
+ * B == 0 is a no-op. */
+int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t* tokens, const float* x,
+                          const uint8_t* const* masks, float p, float* y, void* saved, size_t saved_bytes,
+                          int64_t B, int64_t S, int64_t T, void* stream);
+/* loss.backward() through TextPoseTransformer.forward (HandPoseModels.py:201-222 under autograd,
+ * traintest.py:105-121), B >= 1.  Needs neither x nor y.
+ *   tokens, masks, p: the same as in the forward;  dy: device fp32 (B, T, 21, 2), dL/dy
+ *   saved   : what b2h_tpt_train_forward wrote for this batch (read only)
+ *   dx      : device fp32 (B, T, 12, 2) dL/dinput_pose, or NULL
+ *   grads   : host array of device fp32 tensors shaped like params, OVERWRITTEN (not accumulated); the gradient
+ *             of token_embedding.weight is dense, rows of ids the batch does not contain are +0
+ *   scratch : device, >= b2h_tpt_train_bytes(m, B, S, T, 1); its prior contents do not matter.
+ * Deterministic (no atomics): the partial sums of the parameter gradients depend on (B, S, T) only and are
+ * added in a fixed order, the embedding gradient adds its rows in ascending token position, and the memory's
+ * gradient adds the decoder layers in descending order; dx of a sequence does not depend on the other
+ * sequences of the batch. */
+int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks,
+                     float p, const float* dy, const void* saved, size_t saved_bytes, float* dx,
+                     float* const* grads, void* scratch, size_t scratch_bytes, int64_t B, int64_t S, int64_t T,
+                     void* stream);
 
 /* Introspection / measurement -------------------------------------------- */
 
