@@ -65,6 +65,7 @@ SYMBOLS = {
                                          ctypes.c_int64, _vp]),
     "b2h_tpt_create": (ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(_vp)]),
     "b2h_tpt_destroy": (ctypes.c_int, [_vp]),
+    "b2h_tpt_set_kernel": (ctypes.c_int, [_vp, ctypes.c_int]),
     "b2h_tpt_load_weights": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int]),
     "b2h_tpt_workspace_bytes": (ctypes.c_size_t, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     "b2h_tpt_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,

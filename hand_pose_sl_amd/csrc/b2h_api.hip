@@ -604,6 +604,7 @@ struct TencBlob {
 // One torch.nn.TransformerEncoderLayer (post-norm, ReLU): attn_out carries norm1, ff2 carries norm2.
 struct EncLayer {
     TencBlob q, k, v, attn_out, ff1, ff2;
+    TencBlob qkv_head[kTencHeads]; // rows of Q_h, K_h, V_h of in_proj_weight: the projection inside b2h_attn_qkv_h3
 };
 
 // Floats of its twelve tensors in state_dict order: self_attn in_proj weight, bias; out_proj; linear1; linear2;
@@ -621,11 +622,8 @@ struct b2h_tenc {
     std::vector<size_t> sizes;
     DevBuf pe;
     TencBlob in_proj, out_proj;
-    struct Layer : EncLayer {
-        TencBlob qkv_head[kTencHeads]; // rows of Q_h, K_h, V_h of in_proj_weight: the projection inside b2h_attn_qkv_h3
-    };
     int num_cus = 256;
-    std::vector<Layer> layers;
+    std::vector<EncLayer> layers;
 };
 
 namespace {
@@ -633,7 +631,7 @@ namespace {
 // rows [r0, r0 + nout) of W (*, k) row-major fp32 -> [mt][g][lane][4] with
 // W[r0 + 16mt + (lane&15)][16g + 4(lane>>4) + j], followed by bias, gamma, beta (128 each)
 int pack_blob(TencBlob& B, const float* w, const float* b, int r0, int nout, int k, const float* gamma,
-              const float* beta, bool with_f16 = true) {
+              const float* beta) {
     B.kgroups = (k + 15) / 16;
     B.mtiles = (nout + 15) / 16;
     B.nout = nout;
@@ -651,7 +649,7 @@ int pack_blob(TencBlob& B, const float* w, const float* b, int r0, int nout, int
     if (gamma) std::memcpy(blob.data() + nw + kTencD, gamma, kTencD * 4);
     if (beta) std::memcpy(blob.data() + nw + 2 * kTencD, beta, kTencD * 4);
     int rc = B.buf.upload(blob.data(), blob.size() * 4);
-    if (rc || !with_f16) return rc; // (TextPoseTransformer is fp32 only)
+    if (rc) return rc;
     // f16 hi/lo fragments for v_mfma_f32_16x16x32_f16: [part][mt][g][lane][8] with k-slot (g, q, j)
     // = input feature 32g + 16(j>>2) + 4q + (j&3) (kernel_tenc.h), then the same fp32 parameters
     B.kgroups32 = (k + 31) / 32;
@@ -674,6 +672,22 @@ int pack_blob(TencBlob& B, const float* w, const float* b, int r0, int nout, int
     std::memcpy(blob16.data(), frag.data(), 2 * nh * 2);
     std::memcpy(blob16.data() + 2 * nh * 2, blob.data() + nw, kStageParams * 4);
     return B.buf16.upload(blob16.data(), blob16.size());
+}
+
+// The per-head blobs [Q_h | K_h | V_h] of one attention block: rows 32 hd .. of each third of its in_proj weight
+// (384, 128) and bias (384), for the projection inside b2h_attn_qkv_h3 / b2h_attn_cross_h3
+int pack_qkv_heads(TencBlob (&heads)[kTencHeads], const float* w, const float* b) {
+    const int D = kTencD;
+    for (int hd = 0; hd < kTencHeads; ++hd) {
+        std::vector<float> wh((size_t)3 * kTencHd * D), bhd((size_t)3 * kTencHd);
+        for (int part = 0; part < 3; ++part)
+            for (int r = 0; r < kTencHd; ++r) {
+                std::memcpy(&wh[((size_t)part * kTencHd + r) * D], &w[((size_t)part * D + hd * kTencHd + r) * D], D * 4);
+                bhd[part * kTencHd + r] = b[part * D + hd * kTencHd + r];
+            }
+        if (int rc = pack_blob(heads[hd], wh.data(), bhd.data(), 0, 3 * kTencHd, D, nullptr, nullptr)) return rc;
+    }
+    return B2H_OK;
 }
 
 // One launch of the chain kernel under construction: the rows that enter, then the stages in order.  h3 selects the
@@ -718,6 +732,12 @@ using AttnQkvKernel = void (*)(AttnQkvArgs);
 constexpr AttnQkvKernel kAttnQkvH3[kAttnMaxTiles] = {b2h_attn_qkv_h3<1>, b2h_attn_qkv_h3<2>, b2h_attn_qkv_h3<3>,
                                                      b2h_attn_qkv_h3<4>, b2h_attn_qkv_h3<5>, b2h_attn_qkv_h3<6>,
                                                      b2h_attn_qkv_h3<7>, b2h_attn_qkv_h3<8>};
+// f16x3 cross-attention (TextPoseTransformer) by KEY tiles, [nk - 1] with nk = ceil(S / 16); the block size carries
+// the query tiles
+using AttnCrossH3Kernel = void (*)(AttnCrossArgs);
+constexpr AttnCrossH3Kernel kAttnCrossH3[kAttnMaxTiles] = {b2h_attn_cross_h3<1>, b2h_attn_cross_h3<2>, b2h_attn_cross_h3<3>,
+                                                           b2h_attn_cross_h3<4>, b2h_attn_cross_h3<5>, b2h_attn_cross_h3<6>,
+                                                           b2h_attn_cross_h3<7>, b2h_attn_cross_h3<8>};
 using AttnKernel = void (*)(const float*, float*, int);
 constexpr AttnKernel kAttn[kAttnMaxTiles] = {b2h_attn_mfma_f32<1>, b2h_attn_mfma_f32<2>, b2h_attn_mfma_f32<3>,
                                              b2h_attn_mfma_f32<4>, b2h_attn_mfma_f32<5>, b2h_attn_mfma_f32<6>,
@@ -732,12 +752,27 @@ int set_tenc_kernel_attributes() {
         if ((rc = raise_lds_cap(b2h_tenc_chain<false>, kChainLdsBytes)) || (rc = raise_lds_cap(b2h_tenc_chain<true>, kChainLdsBytes)))
             return rc;
         for (int nt = 1; nt <= kAttnMaxTiles; ++nt)
-            if ((rc = raise_lds_cap(kAttnQkvH3[nt - 1], attn_qkv_lds_bytes(nt)))) return rc;
+            if ((rc = raise_lds_cap(kAttnQkvH3[nt - 1], attn_qkv_lds_bytes(nt))) ||
+                (rc = raise_lds_cap(kAttnCrossH3[nt - 1], attn_qkv_lds_bytes(nt))))
+                return rc;
         if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd)) ||
             (rc = raise_lds_cap(b2h_tptt_xsdpa)) || (rc = raise_lds_cap(b2h_tptt_xsdpa_bwd)))
             return rc;
         return B2H_OK;
     });
+}
+
+// The persistent grid of the f16x3 attention kernels: one workgroup per CU, bound to a head
+// (blockIdx = 8 (4 slot + head) + xcd: 32 per sequence slot)
+unsigned attn_h3_grid(int num_cus) { return (unsigned)std::max(32, num_cus / 32 * 32); }
+
+// f16x3 self-attention of B sequences of T <= 128 rows with its projections inside: x (B*T, 128) -> OC (B*T, 128)
+void self_attn_h3(const TencBlob (&heads)[kTencHeads], const float* x, float* OC, int64_t B, int T, int num_cus, hipStream_t st) {
+    const int nt = (T + 15) / 16;
+    AttnQkvArgs qa{};
+    qa.x = x; qa.out = OC; qa.T = T; qa.B = B;
+    for (int hd = 0; hd < kTencHeads; ++hd) qa.blob[hd] = (const float*)heads[hd].buf16.p;
+    hipLaunchKernelGGL(kAttnQkvH3[nt - 1], dim3(attn_h3_grid(num_cus)), dim3(64 * nt), (size_t)attn_qkv_lds_bytes(nt), st, qa);
 }
 
 // fp32 self-attention of B sequences of T <= 128 rows: Q | K | V rows (B*T, 384) -> OC (B*T, 128)
@@ -810,12 +845,7 @@ int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, con
     chain_in(m, x, n, (int)T, fa, ws, st);
     for (int l = 0; l < m->nlayers; ++l) { // torch.nn.TransformerEncoderLayer, post-norm, ReLU
         if (h3) {
-            // persistent: one workgroup per CU, bound to a head (blockIdx = 8 (4 slot + head) + xcd: 32 per sequence slot)
-            const unsigned grid = (unsigned)std::max(32, m->num_cus / 32 * 32);
-            AttnQkvArgs qa{};
-            qa.x = ws.XA; qa.out = ws.OC; qa.T = (int)T; qa.B = B;
-            for (int hd = 0; hd < kTencHeads; ++hd) qa.blob[hd] = (const float*)m->layers[l].qkv_head[hd].buf16.p;
-            hipLaunchKernelGGL(kAttnQkvH3[nt - 1], dim3(grid), dim3(64 * nt), (size_t)attn_qkv_lds_bytes(nt), st, qa);
+            self_attn_h3(m->layers[l].qkv_head, ws.XA, ws.OC, B, (int)T, m->num_cus, st);
         } else {
             self_attn_f32(ws.QKV, ws.OC, B, (int)T, st);
         }
@@ -881,15 +911,7 @@ int b2h_tenc_load_weights(b2h_tenc* m, const float* const* tensors, int count, i
         if ((rc = pack_blob(L.q, h[o].data(), h[o + 1].data(), 0, D, D, nullptr, nullptr))) return rc;
         if ((rc = pack_blob(L.k, h[o].data(), h[o + 1].data(), D, D, D, nullptr, nullptr))) return rc;
         if ((rc = pack_blob(L.v, h[o].data(), h[o + 1].data(), 2 * D, D, D, nullptr, nullptr))) return rc;
-        for (int hd = 0; hd < kTencHeads; ++hd) { // [Q_h | K_h | V_h]: rows 32 hd .. of each third of in_proj_weight / bias
-            std::vector<float> wh((size_t)3 * kTencHd * D), bhd((size_t)3 * kTencHd);
-            for (int part = 0; part < 3; ++part)
-                for (int r = 0; r < kTencHd; ++r) {
-                    std::memcpy(&wh[((size_t)part * kTencHd + r) * D], &h[o][((size_t)part * D + hd * kTencHd + r) * D], D * 4);
-                    bhd[part * kTencHd + r] = h[o + 1][part * D + hd * kTencHd + r];
-                }
-            if ((rc = pack_blob(L.qkv_head[hd], wh.data(), bhd.data(), 0, 3 * kTencHd, D, nullptr, nullptr))) return rc;
-        }
+        if ((rc = pack_qkv_heads(L.qkv_head, h[o].data(), h[o + 1].data()))) return rc;
         if ((rc = pack_blob(L.attn_out, h[o + 2].data(), h[o + 3].data(), 0, D, D, h[o + 8].data(), h[o + 9].data()))) return rc;
         if ((rc = pack_blob(L.ff1, h[o + 4].data(), h[o + 5].data(), 0, D, D, nullptr, nullptr))) return rc;
         if ((rc = pack_blob(L.ff2, h[o + 6].data(), h[o + 7].data(), 0, D, D, h[o + 10].data(), h[o + 11].data()))) return rc;
@@ -923,15 +945,18 @@ int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, 
 
 // ---- TextPoseTransformer (kernel_tpt.h) -----------------------------------------------------------------------
 // torch.nn.Transformer(128, 4, n_enc, n_dec, 128) between a token embedding and the two pose projections
-// (HandPoseModels.py:181-230), inference, exact fp32.  Per-frame work is b2h_tenc_chain<false> by descriptors.
+// (HandPoseModels.py:181-230), inference, exact fp32 or f16x3.  Per-frame work is b2h_tenc_chain<H3> by descriptors.
 struct b2h_tpt {
     int n_tokens = 0, n_enc = 0, n_dec = 0, device = 0, num_cus = 256;
     bool has_weights = false;
+    int kernel = B2H_TENC_F32;
+    float w_absmax = 0.f; // largest |parameter|, the embedding table included (NaN counts as inf): B2H_TENC_F16X3 needs < 65504
     DevBuf table;               // token_embedding.weight (n_tokens, 128)
     DevBuf enc_norm, dec_norm;  // encoder.norm / decoder.norm: gamma (128), beta (128)
     TencBlob in_proj, out_proj; // pose2hidden_projection, hidden2pose_projection
     struct DecLayer : EncLayer {          // q, k, v, attn_out: self_attn, its out_proj carries norm1; ff2 carries norm3
         TencBlob cq, ck, cv, cross_out;   // multihead_attn on the encoder memory; out_proj carries norm2
+        TencBlob cross_head[kTencHeads];  // its [Q_h | K_h | V_h] rows: the projections inside b2h_attn_cross_h3
     };
     std::vector<EncLayer> enc;
     std::vector<DecLayer> dec;
@@ -941,7 +966,8 @@ namespace {
 
 constexpr int kTptMaxLen = 16 * kAttnMaxTiles; // tokens and frames per sequence: one workgroup holds all keys
 
-// Workspace (floats; Ns = B*S token rows, Nt = B*T frame rows).  Every region is written before it is read:
+// Workspace (floats; Ns = B*S token rows, Nt = B*T frame rows).  Every region is written before it is read; the
+// f16x3 path uses MEM, OCs, XT, X1 and OCt only (its attention kernels project Q, K, V themselves):
 //   MEM  Ns x 128  encoder residual stream, at the end the memory (after encoder.norm)
 //   OCs  Ns x 128  encoder attention output          QKVs Ns x 384  encoder Q | K | V
 //   MKV  n_dec x (Ns x 256)  K | V of the memory for each decoder layer's multihead_attn
@@ -971,9 +997,9 @@ constexpr AttnCrossKernel kAttnCross[kAttnMaxTiles] = {b2h_attn_cross_f32<1>, b2
                                                        b2h_attn_cross_f32<4>, b2h_attn_cross_f32<5>, b2h_attn_cross_f32<6>,
                                                        b2h_attn_cross_f32<7>, b2h_attn_cross_f32<8>};
 
-// A chain of b2h_tenc_chain<false> without the item transforms: (n, ldx) rows, optional (n, 128) residual rows
-Chain tpt_rows(const float* x, int ldx, const float* res, int64_t n) {
-    Chain c;
+// A chain without the item transforms: (n, ldx) rows, optional (n, 128) residual rows
+Chain tpt_rows(const float* x, int ldx, const float* res, int64_t n, bool h3 = false) {
+    Chain c{h3};
     c.rows(x, ldx, res, n);
     c.a.Tseq = 1; c.a.factor = 1.0f;
     return c;
@@ -1032,6 +1058,13 @@ int b2h_tpt_destroy(b2h_tpt* m) {
     return B2H_OK;
 }
 
+int b2h_tpt_set_kernel(b2h_tpt* m, int kernel) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (kernel != B2H_TENC_F32 && kernel != B2H_TENC_F16X3) return fail(B2H_ERR_INVALID, "unknown TextPoseTransformer kernel");
+    m->kernel = kernel;
+    return B2H_OK;
+}
+
 int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int on_device) {
     if (!m || !tensors) return fail(B2H_ERR_INVALID, "NULL argument");
     if (count != 9 + 12 * m->n_enc + 18 * m->n_dec)
@@ -1042,12 +1075,15 @@ int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int
     std::vector<std::vector<float>> h;
     int rc;
     if ((rc = fetch_tensors(tensors, sizes, on_device, h)) || (rc = check_device(m->device))) return rc;
+    m->w_absmax = 0.f;
+    for (int i = 0; i < count; ++i) m->w_absmax = absmax_of(h[i], m->w_absmax); // the table too: its rows are activations
     const int Di = kTencD;
     // one Linear of 128 inputs: rows [r0, r0 + 128) of tensor i with bias i + 1, and the LayerNorm that follows it
     const auto lin = [&](TencBlob& blob, int i, int r0, int norm) {
         return pack_blob(blob, h[i].data(), h[i + 1].data(), r0, Di, Di, norm >= 0 ? h[norm].data() : nullptr,
-                         norm >= 0 ? h[norm + 1].data() : nullptr, false);
+                         norm >= 0 ? h[norm + 1].data() : nullptr);
     };
+    const auto heads = [&](TencBlob (&hb)[kTencHeads], int i) { return pack_qkv_heads(hb, h[i].data(), h[i + 1].data()); };
     const auto norm = [&](DevBuf& buf, int i) {
         std::vector<float> gb(h[i]);
         gb.insert(gb.end(), h[i + 1].begin(), h[i + 1].end());
@@ -1057,7 +1093,8 @@ int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int
         auto& L = m->enc[l];
         const int o = 12 * l;
         if ((rc = lin(L.q, o, 0, -1)) || (rc = lin(L.k, o, Di, -1)) || (rc = lin(L.v, o, 2 * Di, -1)) ||
-            (rc = lin(L.attn_out, o + 2, 0, o + 8)) || (rc = lin(L.ff1, o + 4, 0, -1)) || (rc = lin(L.ff2, o + 6, 0, o + 10)))
+            (rc = lin(L.attn_out, o + 2, 0, o + 8)) || (rc = lin(L.ff1, o + 4, 0, -1)) || (rc = lin(L.ff2, o + 6, 0, o + 10)) ||
+            (rc = heads(L.qkv_head, o)))
             return rc;
     }
     int o = 12 * m->n_enc;
@@ -1068,14 +1105,15 @@ int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int
         if ((rc = lin(L.q, o, 0, -1)) || (rc = lin(L.k, o, Di, -1)) || (rc = lin(L.v, o, 2 * Di, -1)) ||
             (rc = lin(L.attn_out, o + 2, 0, o + 12)) || (rc = lin(L.cq, o + 4, 0, -1)) || (rc = lin(L.ck, o + 4, Di, -1)) ||
             (rc = lin(L.cv, o + 4, 2 * Di, -1)) || (rc = lin(L.cross_out, o + 6, 0, o + 14)) ||
-            (rc = lin(L.ff1, o + 8, 0, -1)) || (rc = lin(L.ff2, o + 10, 0, o + 16)))
+            (rc = lin(L.ff1, o + 8, 0, -1)) || (rc = lin(L.ff2, o + 10, 0, o + 16)) || (rc = heads(L.qkv_head, o)) ||
+            (rc = heads(L.cross_head, o + 4)))
             return rc;
     }
     if ((rc = norm(m->dec_norm, o))) return rc;
     o += 2;
     if ((rc = m->table.upload(h[o].data(), h[o].size() * 4))) return rc;
-    if ((rc = pack_blob(m->out_proj, h[o + 1].data(), h[o + 2].data(), 0, kOutCh, Di, nullptr, nullptr, false))) return rc;
-    if ((rc = pack_blob(m->in_proj, h[o + 3].data(), h[o + 4].data(), 0, Di, kInCh, nullptr, nullptr, false))) return rc;
+    if ((rc = pack_blob(m->out_proj, h[o + 1].data(), h[o + 2].data(), 0, kOutCh, Di, nullptr, nullptr))) return rc;
+    if ((rc = pack_blob(m->in_proj, h[o + 3].data(), h[o + 4].data(), 0, Di, kInCh, nullptr, nullptr))) return rc;
     m->has_weights = true;
     return B2H_OK;
 }
@@ -1104,12 +1142,59 @@ int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y,
     if (B * kTencHeads > 0x7fffffff || std::max(Ns, Nt) / 8 >= 0x7fffffff)
         return fail(B2H_ERR_SHAPE, "batch too large for one launch");
     if (int rc = check_device(m->device)) return rc;
+    if (m->kernel == B2H_TENC_F16X3 && !(m->w_absmax < kF16Max))
+        return fail(B2H_ERR_UNSUPPORTED, "B2H_TENC_F16X3: a parameter is outside the f16 range (|w| >= 65504 or not "
+                                         "finite); use B2H_TENC_F32");
     hipStream_t st = (hipStream_t)stream;
     const TptWs ws = tpt_ws(workspace, Ns, Nt, m->n_dec);
+    const int nk = (int)((S + 15) / 16), nq = (int)((T + 15) / 16);
 
     // encoder (torch.nn.TransformerEncoder, post-norm, ReLU): token_embedding -> layers -> encoder.norm
     hipLaunchKernelGGL(b2h_tpt_embed, dim3((unsigned)((Ns * 32 + 255) / 256)), dim3(256), 0, st, tokens,
                        (const float*)m->table.p, ws.MEM, Ns, m->n_tokens);
+    if (m->kernel == B2H_TENC_F16X3) {
+        // 4 + 2 n_enc + 4 n_dec launches: the attention kernels project Q, K, V themselves, so the chains carry no
+        // Q, K, V stages and QKVs, MKV, QC and QKVt stay untouched
+        for (int l = 0; l < m->n_enc; ++l) {
+            const EncLayer& L = m->enc[l];
+            self_attn_h3(L.qkv_head, ws.MEM, ws.OCs, B, (int)S, m->num_cus, st);
+            Chain c = tpt_rows(ws.OCs, kTencD, ws.MEM, Ns, true);
+            c.add_layer_tail(L.attn_out, L.ff1, L.ff2, ws.MEM, nullptr, nullptr);
+            c.launch(m->num_cus, st);
+        }
+        tpt_layernorm(m->enc_norm, ws.MEM, Ns, st);
+        {
+            Chain c = tpt_rows(x, kInCh, nullptr, Nt, true);
+            c.add(m->in_proj, ST_SET, ws.XT);
+            c.launch(m->num_cus, st);
+        }
+        for (int l = 0; l < m->n_dec; ++l) {
+            const auto& L = m->dec[l];
+            self_attn_h3(L.qkv_head, ws.XT, ws.OCt, B, (int)T, m->num_cus, st);
+            {   // self out_proj + x -> norm1 -> X1: one stage, whose result is copied out
+                Chain c = tpt_rows(ws.OCt, kTencD, ws.XT, Nt, true);
+                c.add(L.attn_out, ST_RESLN_GLOBAL, ws.X1);
+                c.launch(m->num_cus, st);
+            }
+            AttnCrossArgs xa{};
+            xa.x = ws.X1; xa.mem = ws.MEM; xa.out = ws.OCt; xa.T = (int)T; xa.S = (int)S; xa.B = B;
+            for (int hd = 0; hd < kTencHeads; ++hd) xa.blob[hd] = (const float*)L.cross_head[hd].buf16.p;
+            hipLaunchKernelGGL(kAttnCrossH3[nk - 1], dim3(attn_h3_grid(m->num_cus)), dim3(64 * nq),
+                               (size_t)attn_qkv_lds_bytes(nk), st, xa);
+            // cross out_proj + X1 -> norm2 -> linear1 ReLU -> linear2 + res -> norm3 -> XT
+            Chain c = tpt_rows(ws.OCt, kTencD, ws.X1, Nt, true);
+            c.add_layer_tail(L.cross_out, L.ff1, L.ff2, ws.XT, nullptr, nullptr);
+            c.launch(m->num_cus, st);
+        }
+        tpt_layernorm(m->dec_norm, ws.XT, Nt, st);
+        {
+            Chain c = tpt_rows(ws.XT, kTencD, nullptr, Nt, true);
+            c.add(m->out_proj, ST_STORE, y, kOutCh);
+            c.launch(m->num_cus, st);
+        }
+        HIP_TRY(hipGetLastError());
+        return B2H_OK;
+    }
     const auto qkv = [](Chain& c, const EncLayer& L, float* QKV) { c.add_qkv(L.q, L.k, L.v, QKV); };
     {
         Chain c = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
@@ -1142,7 +1227,6 @@ int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y,
         qkv(c, m->dec[0], ws.QKVt);
         c.launch(m->num_cus, st);
     }
-    const int nk = (int)((S + 15) / 16), nq = (int)((T + 15) / 16);
     for (int l = 0; l < m->n_dec; ++l) {
         const auto& L = m->dec[l];
         self_attn_f32(ws.QKVt, ws.OCt, B, (int)T, st);

@@ -255,11 +255,12 @@ __device__ __forceinline__ void chain_split(const f32x4 (&v)[8], f16x8 (&bh)[4],
         }
 }
 
+// MT M-tiles whose hi fragments start at `whi` and whose lo fragments start at `wlo`, [mt][g][lane] each: a blob's
+// lo half lies MT_blob*KG*64 fragments behind its hi half, so a run of M-tiles inside a larger blob
+// (b2h_attn_cross_h3: tiles 0-1 and 2-5 of a head's six) is addressed by moving both pointers.
 template <int KG, int MT>
-__device__ __forceinline__ void chain_gemm_h3(const f32x4* __restrict__ wl, int lane, const f16x8 (&bh)[4],
-                                              const f16x8 (&bl)[4], f32x4 (&acc)[8]) {
-    const f16x8* whi = reinterpret_cast<const f16x8*>(wl);
-    const f16x8* wlo = whi + MT * KG * 64;
+__device__ __forceinline__ void chain_gemm_h3_at(const f16x8* whi, const f16x8* wlo, int lane, const f16x8 (&bh)[4],
+                                                 const f16x8 (&bl)[4], f32x4 (&acc)[8]) {
 #pragma unroll
     for (int g = 0; g < KG; ++g) {
         f16x8 ah[MT], al[MT];
@@ -275,6 +276,12 @@ __device__ __forceinline__ void chain_gemm_h3(const f32x4* __restrict__ wl, int 
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bh[g], acc[mt], 0, 0, 0);
     }
+}
+template <int KG, int MT> // a whole blob: [hi][lo]
+__device__ __forceinline__ void chain_gemm_h3(const f32x4* __restrict__ wl, int lane, const f16x8 (&bh)[4],
+                                              const f16x8 (&bl)[4], f32x4 (&acc)[8]) {
+    const f16x8* whi = reinterpret_cast<const f16x8*>(wl);
+    chain_gemm_h3_at<KG, MT>(whi, whi + MT * KG * 64, lane, bh, bl, acc);
 }
 
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression

@@ -17,7 +17,9 @@ reference's loop body (steps/traintest.py:105-121) runs unchanged with any torch
 are drawn by torch on the model's device (`_draw_dropout_masks`; they follow torch.manual_seed) and handed to the
 kernels.  Every other call (eval mode or no_grad) runs the inference kernels.
 
-Exact fp32, S <= 128 and T <= 128.  No path ever falls back to PyTorch ops.
+Inference is exact fp32 by default; `model.set_precision("f16x3")` selects the f16 hi + lo split path (three
+v_mfma_f32_16x16x32_f16 per product, Q, K, V projected inside the attention kernels), valid while every weight and
+activation is below 65504 in magnitude.  S <= 128 and T <= 128.  No path ever falls back to PyTorch ops.
 """
 import ctypes
 import warnings
@@ -27,11 +29,16 @@ import torch.nn as nn
 
 from . import _lib
 from ._native import NativeModule, _aligned, _ptrs
-from .transformer_enc import PositionalEncoding
+from .transformer_enc import TENC_KERNELS, PositionalEncoding
 
 
 class TextPoseTransformer(NativeModule, nn.Module):
-    """`precision` (not in the reference; keyword only): only "fp32" = fp32 operands on the matrix cores."""
+    """`precision` (not in the reference; keyword only): the constructor accepts only "fp32" = fp32 operands on the
+    matrix cores, the default.  `set_precision("f16x3")` switches the inference forward to the f16 hi + lo split
+    (fp32-grade results, the same 2e-5 parity bar; needs |weights| and |activations| < 65504, else the forward
+    raises) and `set_precision("fp32")` switches back; no reload of the weights.  The constructor itself keeps
+    refusing "f16x3" because tests/test_tpt_cpu.py::test_python_side_errors pins that refusal; a later change that
+    may touch that test lifts it.  Training is exact fp32 whatever the precision."""
 
     def __init__(self, n_tokens, n_joints, joints_dim, nhead, nhid, nout, n_enc_layers, n_dec_layers, dropout=0.5, *,
                  precision="fp32"):
@@ -53,6 +60,13 @@ class TextPoseTransformer(NativeModule, nn.Module):
         self.ninp = int(n_joints * joints_dim)
         self._dropout_p = float(dropout)
         self._geom = (self.n_tokens, self.ninp, int(nhead), int(nhid), int(nout), int(n_enc_layers), int(n_dec_layers))
+
+    def set_precision(self, name):
+        """Select the inference arithmetic, "fp32" or "f16x3", for later forwards; returns self."""
+        if name not in TENC_KERNELS:
+            raise ValueError(f"precision must be one of {sorted(TENC_KERNELS)}, got {name!r}")
+        self.precision = name
+        return self
 
     _NAME, _CREATE, _LOAD, _DESTROY = "TextPoseTransformer", "b2h_tpt_create", "b2h_tpt_load_weights", "b2h_tpt_destroy"
 
@@ -153,6 +167,7 @@ class TextPoseTransformer(NativeModule, nn.Module):
         ws = self._grown_workspace(need, dev)
         with _lib.on_device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.b2h_tpt_set_kernel(self._handle, TENC_KERNELS[self.precision]))
             _lib.check(lib.b2h_tpt_forward(self._handle, ctypes.c_void_p(tok.data_ptr()), ctypes.c_void_p(x.data_ptr()),
                                            ctypes.c_void_p(y.data_ptr()), B, S, T, ctypes.c_void_p(ws.data_ptr()),
                                            ws.numel(), ctypes.c_void_p(st)))

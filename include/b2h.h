@@ -301,9 +301,14 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
  * token embeddings as source and the projected pose as target, hidden2pose_projection.  Post-norm layers, ReLU,
  * eps 1e-5, both stacks end with their LayerNorm; the reference passes no mask of any kind (:211), so padded
  * token id 0 is attended like any other, and never applies its two positional encodings.  The entry points of
- * this block are the inference path (dropout = identity), exact fp32 on the matrix cores; training is
- * b2h_tpt_train_forward / b2h_tpt_backward below.  Tokenisation stays with the caller: the model's boundary
- * is integer ids (:201, traintest.py:105-107). */
+ * this block are the inference path (dropout = identity); training is b2h_tpt_train_forward / b2h_tpt_backward
+ * below.  Tokenisation stays with the caller: the model's boundary is integer ids (:201, traintest.py:105-107).
+ * Two arithmetics, the b2h_tenc_kernel values above: B2H_TENC_F32, exact fp32 on the matrix cores, is the default
+ * and stays it; B2H_TENC_F16X3 (b2h_tpt_set_kernel) splits every operand of every Linear and of both attention
+ * products into f16 hi + lo and uses three v_mfma_f32_16x16x32_f16 per product with fp32 accumulation, projects
+ * Q, K and V inside the attention kernels (self- and cross-attention) and keeps the same 2e-5 parity bar.  It is
+ * valid while every weight, embedding row and activation is below 65504 in magnitude (f16 range):
+ * b2h_tpt_forward returns B2H_ERR_UNSUPPORTED for a model with a parameter outside it. */
 typedef struct b2h_tpt b2h_tpt;
 /* Replaces TextPoseTransformer.__init__ (HandPoseModels.py:181-230) as run.py:148-151 calls it.  `ninp` is
  * n_joints * joints_dim.  Accepts ninp = 24, nhead = 4, nhid = 128, nout = 42, 1 <= n_enc_layers, n_dec_layers
@@ -311,6 +316,9 @@ typedef struct b2h_tpt b2h_tpt;
 int b2h_tpt_create(int n_tokens, int ninp, int nhead, int nhid, int nout, int n_enc_layers, int n_dec_layers,
                    b2h_tpt** out);
 int b2h_tpt_destroy(b2h_tpt* m);
+/* Selects the kernel (a b2h_tenc_kernel value) for later b2h_tpt_forward calls; no reload of the weights needed.
+ * B2H_ERR_INVALID for a NULL model or an unknown value.  Training is exact fp32 whatever is selected. */
+int b2h_tpt_set_kernel(b2h_tpt* m, int kernel);
 /* Replaces load_state_dict for this model (HandPoseModels.py:181-230; traintest.py:62).  `tensors`:
  * 9 + 12*n_enc_layers + 18*n_dec_layers fp32 contiguous arrays in state_dict order WITHOUT the two `pe` buffers
  * (token_pos_encoder.pe, pose_pos_encoder.pe: constructed at :187-190, never applied):

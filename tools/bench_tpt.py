@@ -8,13 +8,19 @@ line with, per shape,
   cpu16_ms      for context: the same modules on the CPU with 16 threads
 The timed runs are in this process, one after the other, with no other GPU work; the profiled child runs after them.
 
-    python tools/bench_tpt.py [--iters N] > profiles/tpt/bench_tpt.json
+`--precision fp32` (default) times the exact-fp32 path, `f16x3` the f16 hi + lo split path (`set_precision`), `both`
+the two one after the other on the same weights and inputs: the fp32 figures stay where they are and the f16x3 ones
+go under "f16x3" per shape, with its speed-up over fp32 and max|y_f16x3 - y_fp32|.  `--reps R` repeats every
+timing R times: `hip_ms` is then the median and `hip_ms_reps` lists all of them.
+
+    python tools/bench_tpt.py [--iters N] [--precision fp32|f16x3|both] [--reps R] > profiles/tpt/bench_tpt.json
 """
 import csv
 import glob
 import json
 import os
 import shutil
+import statistics
 import subprocess
 import sys
 import tempfile
@@ -63,20 +69,20 @@ def event_ms(fn, warmup, iters):
     return a.elapsed_time(b) / iters
 
 
-def child(B, S, T, iters):
+def child(B, S, T, iters, precision="fp32"):
     dev = torch.device("cuda:0")
-    model = make(dev)
+    model = make(dev).set_precision(precision)
     tok, pose = inputs(B, S, T, dev)
     for _ in range(iters):
         model(tok, pose)
     torch.cuda.synchronize()
 
 
-def kernel_split(B, S, T, iters):
+def kernel_split(B, S, T, iters, precision="fp32"):
     tmp = tempfile.mkdtemp(prefix="bench_tpt_")
     try:
         r = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "tpt", "--",
-                            sys.executable, os.path.abspath(__file__), "--child", str(B), str(S), str(T), str(iters)],
+                            sys.executable, os.path.abspath(__file__), "--child", str(B), str(S), str(T), str(iters), precision],
                            capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             return {"error": r.stderr[-500:]}
@@ -97,21 +103,44 @@ def kernel_split(B, S, T, iters):
 def main():
     if "--child" in sys.argv:
         i = sys.argv.index("--child")
-        return child(*[int(v) for v in sys.argv[i + 1:i + 5]])
-    iters = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 20
+        return child(*[int(v) for v in sys.argv[i + 1:i + 5]], *sys.argv[i + 5:i + 6])
+
+    def option(name, default):
+        return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+
+    iters, reps, precision = int(option("--iters", 20)), int(option("--reps", 1)), option("--precision", "fp32")
+    if precision not in ("fp32", "f16x3", "both"):
+        raise SystemExit("--precision is one of fp32, f16x3, both")
+    first, second = ("fp32", "f16x3") if precision == "both" else (precision, None)
     dev = torch.device("cuda:0")
     model = make(dev)
     out = {"tool": "tools/bench_tpt.py", "model": "TextPoseTransformer(1000, 12, 2, 4, 128, 42, 4, 4)",
-           "device": torch.cuda.get_device_name(0), "iters": iters, "shapes": []}
+           "device": torch.cuda.get_device_name(0), "iters": iters, "precision": first, "shapes": []}
+
+    def timed(rec):
+        ms = [round(event_ms(lambda: model(tok, pose), 5, iters), 4) for _ in range(reps)]
+        rec["hip_ms"] = statistics.median(ms)
+        if reps > 1:
+            rec["hip_ms_reps"] = ms
+
     for B, S, T in SHAPES:
         tok, pose = inputs(B, S, T, dev)
         rec = {"B": B, "S": S, "T": T}
         with torch.no_grad():
-            rec["hip_ms"] = round(event_ms(lambda: model(tok, pose), 5, iters), 4)
+            model.set_precision(first)
+            timed(rec)
             rec["eager_ms"] = round(event_ms(lambda: eager(model, tok, pose), 3, max(3, iters // 4)), 4)
             rec["max_abs_hip_vs_eager"] = float((model(tok, pose) - eager(model, tok, pose)).abs().max())
             rec["hip_frames_per_s"] = round(B * T / rec["hip_ms"] * 1e3)
             rec["speedup_vs_eager"] = round(rec["eager_ms"] / rec["hip_ms"], 2)
+            if second:
+                y = model(tok, pose)
+                model.set_precision(second)
+                sub = rec[second] = {}
+                timed(sub)
+                sub["max_abs_vs_" + first] = float((model(tok, pose) - y).abs().max())
+                sub["hip_frames_per_s"] = round(B * T / sub["hip_ms"] * 1e3)
+                sub["speedup_vs_" + first] = round(rec["hip_ms"] / sub["hip_ms"], 3)
         out["shapes"].append(rec)
     # context: the same modules on the CPU, 16 threads (a fresh copy: the model above stays on the GPU)
     torch.set_num_threads(16)
@@ -126,7 +155,9 @@ def main():
     del model
     torch.cuda.synchronize()
     for rec in out["shapes"]:
-        rec["kernels"] = kernel_split(rec["B"], rec["S"], rec["T"], 6)
+        rec["kernels"] = kernel_split(rec["B"], rec["S"], rec["T"], 6, first)
+        if second:
+            rec[second]["kernels"] = kernel_split(rec["B"], rec["S"], rec["T"], 6, second)
     print(json.dumps(out))
 
 
