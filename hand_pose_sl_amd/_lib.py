@@ -70,6 +70,8 @@ SYMBOLS = {
     "b2h_tpt_workspace_bytes": (ctypes.c_size_t, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     "b2h_tpt_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,
                                        ctypes.c_size_t, _vp]),
+    "b2h_tpt_forward_fused": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_int, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]),
     "b2h_tpt_train_bytes": (ctypes.c_size_t, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "b2h_tpt_train_forward": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp), ctypes.c_float, _vp,
                                              _vp, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp]),

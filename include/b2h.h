@@ -333,8 +333,10 @@ int b2h_tpt_set_kernel(b2h_tpt* m, int kernel);
  *   pose2hidden_projection.weight (128,24), .bias (128).
  * `on_device` as for b2h_load_weights; synchronous; may be called again to replace the weights. */
 int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int on_device);
-/* Bytes of device scratch b2h_tpt_forward needs: a function of (B, S, T) and the layer counts only --
- * 2560 + 1024*n_dec_layers per token and 3584 per frame.  0 for a NULL model or a negative size. */
+/* Bytes of device scratch b2h_tpt_forward and b2h_tpt_forward_fused need: a function of (B, S, T) and the layer
+ * counts only -- B*S*(2560 + 1024*n_dec_layers) + B*T*3584, i.e. 2560 + 1024*n_dec_layers per token and 3584 per
+ * frame, for every T (the kernels for T > 128 use the regions the fp32 path already has: Q | K | V rows, the cross
+ * query and the memory's K | V; they need nothing more).  0 for a NULL model or a negative size. */
 size_t b2h_tpt_workspace_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T);
 /* Replaces TextPoseTransformer.forward(input_tokens, input_pose) (HandPoseModels.py:181-230, :201-222; called at
  * traintest.py:105-107 and through run.py:148-151):
@@ -350,6 +352,24 @@ size_t b2h_tpt_workspace_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T
  * and a sequence's output does not depend on the rest of the batch. */
 int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y, int64_t B, int64_t S,
                     int64_t T, void* workspace, size_t workspace_bytes, void* stream);
+/* The same forward with the reference's item transforms inside the model's own kernels and with long targets:
+ * what `infer_utterance.py` runs around its default model at its default `--max-frames 200`.
+ *   body    : device fp32 (B, T, 12, 2), raw pixel keypoints (or already transformed ones with flags = 0)
+ *   flags, factor, n_frames: as for b2h_tenc_forward_fused.  B2H_PRE_CHEST_DIFF and B2H_PRE_NORMALIZE are applied to
+ *             the pose rows as they enter pose2hidden_projection (the model adds no positional encoding),
+ *             B2H_POST_DENORMALIZE and B2H_POST_MASK_TAIL (needs n_frames, device int64 (B)) in the store of
+ *             hidden2pose_projection's output.
+ * 1 <= S <= 128 and 1 <= T <= B2H_TPT_MAX_FRAMES (B2H_ERR_SHAPE).  Everything else -- tokens, alignment, NULL
+ * rules, B == 0, the workspace, token ids outside the table, determinism -- is as for b2h_tpt_forward.  With
+ * flags == 0 and T <= 128 it launches exactly what b2h_tpt_forward launches: the same bits.  For T > 128 the
+ * decoder's self-attention walks the keys in blocks with an online softmax (b2h_attn_long_f32 / b2h_attn_long_h3);
+ * in B2H_TENC_F16X3 the Q, K, V projections then run in the per-frame chain instead of inside the attention kernel.
+ * b2h_tpt_forward itself keeps T <= 128 because a pinned test requires its refusal of T = 129; a later change
+ * allowed to touch that test should route it here. */
+#define B2H_TPT_MAX_FRAMES 1024
+int b2h_tpt_forward_fused(b2h_tpt* m, const int64_t* tokens, const float* body, float* y, int64_t B, int64_t S,
+                          int64_t T, int flags, float factor, const int64_t* n_frames, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* Training (TextPoseTransformer) -------------------------------------------------
  * The reference trains its default model with `prediction = model(batch["text_tokens"], batch["input_kp"])`,

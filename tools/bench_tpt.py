@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""TextPoseTransformer forward (4 + 4 layers, 1000 tokens) at (B, S, T) = (4096, 40, 100) and (64, 40, 100): one JSON
-line with, per shape,
+"""TextPoseTransformer forward (4 + 4 layers, 1000 tokens) at (B, S, T) = (4096, 40, 100) and (64, 40, 100) through
+`model(tokens, pose)`, and at (4096, 40, 200) and (64, 40, 200) -- the reference CLIs' default 200 frames -- through
+`model.forward_fused` with no flags (the long-attention kernels): one JSON line with, per shape,
   hip_ms        milliseconds per forward by HIP events around `iters` back-to-back calls, after warm-up
   kernels       the per-kernel split of a `rocprofv3 --kernel-trace --stats` run of its own (a child process that
                 only runs the HIP forward), as a fraction of the GPU time and microseconds per forward
@@ -13,7 +14,7 @@ the two one after the other on the same weights and inputs: the fp32 figures sta
 go under "f16x3" per shape, with its speed-up over fp32 and max|y_f16x3 - y_fp32|.  `--reps R` repeats every
 timing R times: `hip_ms` is then the median and `hip_ms_reps` lists all of them.
 
-    python tools/bench_tpt.py [--iters N] [--precision fp32|f16x3|both] [--reps R] > profiles/tpt/bench_tpt.json
+    python tools/bench_tpt.py [--iters N] [--precision fp32|f16x3|both] [--reps R] > profiles/tpt_long/bench_tpt_long.json
 """
 import csv
 import glob
@@ -33,7 +34,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import hand_pose_sl_amd as hps  # noqa: E402
 
-SHAPES = [(4096, 40, 100), (64, 40, 100)]
+SHAPES = [(4096, 40, 100), (64, 40, 100), (4096, 40, 200), (64, 40, 200)]
+OFF = dict(dif_encoding=False, normalize=False, denormalize=False, mask_tail=False)
+
+
+def hip(model, tok, pose):
+    """The HIP forward: `model(tokens, pose)` up to its 128 frames, beyond them `forward_fused` with no flags."""
+    return model(tok, pose) if pose.shape[1] <= 128 else model.forward_fused(tok, pose, **OFF)
 
 
 def make(dev):
@@ -73,8 +80,9 @@ def child(B, S, T, iters, precision="fp32"):
     dev = torch.device("cuda:0")
     model = make(dev).set_precision(precision)
     tok, pose = inputs(B, S, T, dev)
-    for _ in range(iters):
-        model(tok, pose)
+    with torch.no_grad():
+        for _ in range(iters):
+            hip(model, tok, pose)
     torch.cuda.synchronize()
 
 
@@ -118,7 +126,7 @@ def main():
            "device": torch.cuda.get_device_name(0), "iters": iters, "precision": first, "shapes": []}
 
     def timed(rec):
-        ms = [round(event_ms(lambda: model(tok, pose), 5, iters), 4) for _ in range(reps)]
+        ms = [round(event_ms(lambda: hip(model, tok, pose), 5, iters), 4) for _ in range(reps)]
         rec["hip_ms"] = statistics.median(ms)
         if reps > 1:
             rec["hip_ms_reps"] = ms
@@ -130,15 +138,15 @@ def main():
             model.set_precision(first)
             timed(rec)
             rec["eager_ms"] = round(event_ms(lambda: eager(model, tok, pose), 3, max(3, iters // 4)), 4)
-            rec["max_abs_hip_vs_eager"] = float((model(tok, pose) - eager(model, tok, pose)).abs().max())
+            rec["max_abs_hip_vs_eager"] = float((hip(model, tok, pose) - eager(model, tok, pose)).abs().max())
             rec["hip_frames_per_s"] = round(B * T / rec["hip_ms"] * 1e3)
             rec["speedup_vs_eager"] = round(rec["eager_ms"] / rec["hip_ms"], 2)
             if second:
-                y = model(tok, pose)
+                y = hip(model, tok, pose)
                 model.set_precision(second)
                 sub = rec[second] = {}
                 timed(sub)
-                sub["max_abs_vs_" + first] = float((model(tok, pose) - y).abs().max())
+                sub["max_abs_vs_" + first] = float((hip(model, tok, pose) - y).abs().max())
                 sub["hip_frames_per_s"] = round(B * T / sub["hip_ms"] * 1e3)
                 sub["speedup_vs_" + first] = round(rec["hip_ms"] / sub["hip_ms"], 3)
         out["shapes"].append(rec)
