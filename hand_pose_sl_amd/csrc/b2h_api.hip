@@ -315,6 +315,23 @@ std::vector<char> pack_frags(const HostWeights& hw, int l, const FragGeo& g, Ele
     return out;
 }
 
+// Layer-1 fragments of the persistent 16-bit kernel for a model without pos_emb (kernel_mfma16.h, PK): the 5 x 24
+// operands of a frame are contiguous in its unpadded image, so the k dimension is the flat index 24 tap + channel
+// in kL1Steps steps of 32, [mt][step][lane][8]; positions 120..127 lie over the next row's channels: zero weights.
+std::vector<char> pack_frags_l1_flat(const HostWeights& hw, const FragGeo& g, Elem el) {
+    std::vector<char> out((size_t)g.mt * kL1Steps * 64 * 8 * 2);
+    uint16_t* h = reinterpret_cast<uint16_t*>(out.data());
+    for (int mt = 0; mt < g.mt; ++mt)
+        for (int ks = 0; ks < kL1Steps; ++ks)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 8; ++j) {
+                    const int f = 32 * ks + 8 * (lane >> 4) + j;
+                    const float v = f < kTaps * kInCh ? hw.at(0, g.chan(mt, lane & 15), f % kInCh, f / kInCh, true) : 0.f;
+                    h[(((size_t)mt * kL1Steps + ks) * 64 + lane) * 8 + j] = el == EL_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
+                }
+    return out;
+}
+
 // bias of layer l in the fragments' out-slot order: [mt][q][4] fp32
 std::vector<float> pack_bias(const HostWeights& hw, int l, const FragGeo& g) {
     std::vector<float> b((size_t)g.mt * 16);
@@ -376,7 +393,8 @@ int pack_all(b2h_model* m, const HostWeights& hw) {
         std::vector<char> img(kPacked16, 0);
         for (int l = 0; l < 4; ++l) {
             const FragGeo g = frag_geo(false, l, false);
-            const std::vector<char> w = pack_frags(hw, l, g, (Elem)el);
+            const bool flat = l == 0 && !m->pos_emb; // 24 inputs: layer 1 reads the unpadded image
+            const std::vector<char> w = flat ? pack_frags_l1_flat(hw, g, (Elem)el) : pack_frags(hw, l, g, (Elem)el);
             const std::vector<float> b = pack_bias(hw, l, g);
             std::memcpy(img.data() + kWLayerOff16[l], w.data(), w.size());
             std::memcpy(img.data() + kBiasOff16[l], b.data(), b.size() * 4);

@@ -8,18 +8,35 @@
 //   once per workgroup : all four layers' weight fragments + biases -> LDS (46.6 KB)
 //   per chunk, per wave:
 //     commit   : the chunk's (T,24) fp32 rows, already waiting in registers, are
-//                cast and written to this wave's LDS image [time][32 ch] (64-B rows)
+//                cast and written to this wave's LDS image: [time][24 ch] (48-B rows, the linear cast
+//                of the input) or, for a pos_emb model (25 inputs), [time][32 ch] (64-B rows)
 //     prefetch : the NEXT chunk's rows are requested from HBM into registers (20 x 16 B
 //                per lane), fly under layers 1-2, and are cast to 16 bit in registers
 //                before the register-hungry head
 //     layers   : per 16-frame tile 5 ds_read_b128 (one per tap) feed 10 (15 for the
-//                head) v_mfma_f32_16x16x32; D = W[chan][(tap,ch)] x Act[(tap,ch)][time]
+//                head) v_mfma_f32_16x16x32 -- layer 1 over the 48-B rows: 4 reads (k-steps over the
+//                120 contiguous operands of a frame) and 8 --; D = W[chan][(tap,ch)] x Act[(tap,ch)][time]
 //                starts from the bias fragment; ReLU (integer max), zero-padding
 //                mask (last tile only) and the 16-bit cast stay in registers; one
 //                ds_write_b128 per lane puts the tile back, 2 rows lower (in-place
 //                image, see kernel_mfma.h); the head's fp32 tile (16 x 168 B) turns once through
 //                already-consumed rows of the image and leaves as three lane-linear stores.
 //   No workgroup barrier after the weight copy; waves never exchange data.
+//
+// The 48-byte image starts at byte kImg48 = 2048 of the wave's area; layer 1 writes its output, layer 2's input
+// (64-B rows), in place from byte 0 on.  With fragments read two tiles ahead, tile m's write must lie below what
+// tile m + 3 reads:
+//   s == 0 (whole sequences <= 208 frames, first chunk of a split one: <= 13 tiles, m <= 12):
+//       tile m writes bytes [1024 m + 384, 1024 m + 1408), tile m + 3 reads from kImg48 + 768 m + 2592:
+//       kImg48 >= 256 m - 1184 = 1888;
+//   s > 0 (192-, 96-, 48-frame chunks with halo: 204 / 108 / 60 frames = 13 / 7 / 4 tiles):
+//       tile m writes [1024 m, 1024 m + 1024), tile m + 3 reads from kImg48 + 768 m + 2304:
+//       kImg48 >= 256 m - 1280 = 1792 / 256 / none.
+// The commit rewrites 10240 bytes from the first loaded frame's row on, every chunk: bytes kImg48 + [384, 10624) at
+// s == 0 (with rows 0..7 zeroed: all of kImg48 + [0, 10624), end 12672 <= 14336) and kImg48 + [0, 10240) at s > 0.
+// The furthest fragment byte read is 256 bytes from row t - 2 of a layer's last frame: s == 0, 13 tiles: frame 207
+// = row 213, byte kImg48 + 48 * 213 + 256 = kImg48 + 10480 (16 bytes into row 218, under the zero weights of
+// k-step 3); s > 0, 13 tiles from frame s - 6: row 207, byte kImg48 + 10192.  Both lie inside what was rewritten.
 //
 // HBM traffic per frame = 96 B read + 168 B written (the algorithmic minimum);
 // weights are read once per workgroup.
@@ -43,6 +60,9 @@ constexpr int kLdsAlloc16 = kLds16 + 16;
 constexpr int kChunkWhole16 = 208;                 // a sequence up to this long is one chunk
 constexpr int kChunkSplit16 = 192;                 // longer sequences: chunks of 192 (+-8 halo)
 constexpr int kInRegs = 20;                        // ceil(208 * 6 / 64) float4 per lane (<= 208 input frames)
+constexpr int kImg48 = 2048;                       // byte offset of the unpadded layer-1 input image [time][24] (48-B rows)
+constexpr int kL1Steps = 4;                        // its k-steps: 5 taps x 24 channels = 120 operands of 128
+static_assert(kImg48 + 8 * 48 + kInRegs * 64 * 8 <= kWaveLds16, "the committed rows fit the wave's area");
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -92,9 +112,15 @@ struct InRegs16 { uint2 p[kInRegs]; };  // the same, cast to 4 x 16-bit
 template <int AUX>
 __device__ __forceinline__ void issue_loads16(InRegs& R, const float* base, int bytes, int lane) {
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(base, bytes);
+    // Offset of load j: 4096 (j / 4) in the scalar field, 1024 (j % 4) in the 12-bit immediate.  The scalar field
+    // takes no literal, so every distinct non-inline value in it is a scalar register live across the whole chunk
+    // loop: four this way, seventeen with j * 1024 there.  The fused instantiations stand at 256 VGPRs (all there
+    // are at two waves per SIMD) and 101 SGPRs (tools/kernel_resources.py): whatever is added to this kernel has
+    // to fit in that.
 #pragma unroll
     for (int j = 0; j < kInRegs; ++j) {
-        const i32x4 r = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, j * 1024, AUX));
+        const i32x4 r = __builtin_bit_cast(
+            i32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16 + (j & 3) * 1024, (j >> 2) * 4096, AUX));
         R.v[j] = __builtin_bit_cast(float4, r);
     }
 }
@@ -210,24 +236,52 @@ __device__ __forceinline__ void commit16(const InRegs16& Q, char* lds, const Geo
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int PREC, int L, bool FUSED, bool STREAM>
+// The same for a model without pos_emb: the image is the linear cast of the input, [time][24] from byte kImg48,
+// so a lane's 20 registers go out lane-linear.  All 20 are written whatever the chunk's length: lanes past its
+// last float4 hold the zeros of the buffer load's range check, so every row from the first loaded frame to
+// 213 rows on is rewritten -- the zero padding behind the sequence end, and every byte the last tile's k-step 3
+// fetches under its zero weights (0 x stale NaN would be NaN).
+__device__ __forceinline__ void commit16_packed(const InRegs16& Q, char* lds, const Geom16& g, int lane) {
+    // t in [-8,0): zero padding, of the later layers' image (64-byte rows 0..7) and of this one.  One lane
+    // predicate for both: 512 bytes each, which in this image run 128 bytes into the first frame's rows --
+    // the rows below are written after it, and LDS operations of one wave execute in order.
+    if (g.s == 0 && lane < 32) {
+        const uint4 z4 = {0u, 0u, 0u, 0u};
+        *reinterpret_cast<uint4*>(lds + lane * 16) = z4;
+        *reinterpret_cast<uint4*>(lds + kImg48 + lane * 16) = z4;
+    }
+    asm volatile("" ::: "memory"); // (the compiler keeps that order too)
+    const int P0 = g.in_lo + 8 - g.s;
+    char* base = lds + kImg48 + P0 * 48 + lane * 8;
+#pragma unroll
+    for (int j = 0; j < kInRegs; ++j) *reinterpret_cast<uint2*>(base + j * 512) = Q.p[j];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// PK (layer 1 only): the input is the unpadded image of commit16_packed, read in kL1Steps k-steps.
+template <int PREC, int L, bool FUSED, bool STREAM, bool PK = false>
 __device__ __forceinline__ void layer16p(char* lds, const char* wlds, const Geom16& g, int T,
                                          int lane, float* __restrict__ yseq, float mul, int nvalid) {
     using P = Prec<PREC>;
     using vec8 = typename P::vec8;
+    static_assert(!PK || L == 0, "only layer 1 reads the unpadded image");
     constexpr int MT = (L == 3) ? 3 : 2;
+    constexpr int KS = PK ? kL1Steps : kTaps;        // k-steps per tile
+    constexpr int kTileB = PK ? 16 * 48 : 1024;      // bytes from a tile's fragments to the next tile's
     constexpr int h = 6 - 2 * L;
     const int tcol = lane & 15, q = lane >> 4;
     const int lo = max(g.s - h, 0), hi = min(g.e + h, T);
     const int ntiles = (hi - lo + 15) >> 4;
 
-    vec8 A[MT][kTaps];
+    vec8 A[MT][KS];
     f32x4 bias[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int s = 0; s < kTaps; ++s)
-            A[mt][s] = *reinterpret_cast<const vec8*>(wlds + kWLayerOff16[L] + (mt * kTaps + s) * kWFrag16 + lane * 16);
+        for (int s = 0; s < KS; ++s)
+            A[mt][s] = *reinterpret_cast<const vec8*>(wlds + kWLayerOff16[L] + (mt * KS + s) * kWFrag16 + lane * 16);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
         bias[mt] = *reinterpret_cast<const f32x4*>(wlds + kBiasOff16[L] + (mt * 4 + q) * 16);
@@ -242,9 +296,15 @@ __device__ __forceinline__ void layer16p(char* lds, const char* wlds, const Geom
     typedef __attribute__((address_space(3))) char lds_char;
     typedef __attribute__((address_space(3))) const vec8 lds_vec8;
     typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
-    lds_char* rd[kTaps];
+    // PK: frame t's 120 operands (tap, channel) are the contiguous bytes from row t - 2 of the 48-byte image
+    // on; k-step s hands lane (tcol, q) the 16 bytes at + 64 s + 16 q (16-byte aligned, never across a tap;
+    // 16 lanes at a 48-byte stride start at banks 12 tcol mod 64: disjoint groups of four, no swizzle).  The
+    // last 16 bytes of k-step 3 are row t + 3's first eight channels, under zero weights.
+    lds_char* rd[KS];
 #pragma unroll
-    for (int s = 0; s < kTaps; ++s) rd[s] = (lds_char*)(lds + lds_off<64>(lo + tcol + s - kPad + pin, q));
+    for (int s = 0; s < KS; ++s)
+        rd[s] = PK ? (lds_char*)(lds + kImg48 + (lo + tcol - kPad + pin) * 48 + 64 * s + 16 * q)
+                   : (lds_char*)(lds + lds_off<64>(lo + tcol + s - kPad + pin, q));
     lds_char* wr = (lds_char*)(lds + lds_off<64>(lo + tcol + pout, q));
     int tq = lo + tcol;  // this lane's frame in the tile the loop stands at
     int sbase = 0;       // head: byte offset of that tile's rows in the output buffer (wave-uniform)
@@ -273,11 +333,11 @@ __device__ __forceinline__ void layer16p(char* lds, const char* wlds, const Geom
         strd = (lds_char*)lds + lane * 16;
     }
     // M: the 10 (15) MFMAs of one tile on fragments already in registers.
-    auto mma = [&](f32x4 (&acc)[MT], const vec8 (&Bf)[kTaps]) {
+    auto mma = [&](f32x4 (&acc)[MT], const vec8 (&Bf)[KS]) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[mt] = bias[mt];
 #pragma unroll
-        for (int s = 0; s < kTaps; ++s)
+        for (int s = 0; s < KS; ++s)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 acc[mt] = P::mfma(A[mt][s], Bf[s], acc[mt]);
@@ -331,45 +391,57 @@ __device__ __forceinline__ void layer16p(char* lds, const char* wlds, const Geom
             __builtin_amdgcn_raw_buffer_store_b128(o[2], yrs, yoff2, so + 2048, STREAM ? kStStream : 0);
         }
     };
-    // F: the five fragments of the tile k tiles ahead.  Unconditional: past the last tile it reads
-    // rows that nobody uses (LDS reads beyond the allocation return 0), which keeps the loop free
-    // of branches between the MFMAs and the epilogue they overlap with.
-    auto fetch = [&](vec8 (&Bf)[kTaps], int k) {
+    // F: the fragments of the tile k tiles ahead.
+    auto fetch = [&](vec8 (&Bf)[KS], int k) {
 #pragma unroll
-        for (int s = 0; s < kTaps; ++s) Bf[s] = *(lds_vec8*)(rd[s] + k * 1024);
+        for (int s = 0; s < KS; ++s) Bf[s] = *(lds_vec8*)(rd[s] + k * kTileB);
     };
-    auto advance2 = [&]() { // two tiles on
+    auto advance = [&](int n) { // n tiles on
 #pragma unroll
-        for (int s = 0; s < kTaps; ++s) {
-            rd[s] += 2048;
+        for (int s = 0; s < KS; ++s) {
+            rd[s] += n * kTileB;
             asm volatile("" : "+v"(rd[s]));
         }
-        wr += 2048;
+        wr += n * 1024;
         asm volatile("" : "+v"(wr));
-        tq += 32;
-        sbase += 2 * (16 * kOutCh * 4);
+        tq += n * 16;
+        sbase += n * (16 * kOutCh * 4);
     };
     // Software pipeline over tiles, two deep: fragments are read two tiles ahead (ping-pong
-    // B0/B1) and a tile's epilogue runs one tile late (ping-pong accA/accB), next to the
+    // Bf[0]/Bf[1]) and a tile's epilogue runs one tile late (ping-pong acc[0]/acc[1]), next to the
     // following tile's MFMAs, so the matrix pipe does not wait for VALU/LDS work.
     // Legal in the in-place image: tile m writes rows [tau-2, tau+14) of the next image,
     // every fragment read issued before that write belongs to tiles <= m+2, and tiles > m
-    // read rows >= tau+14.
-    vec8 B0[kTaps], B1[kTaps];
-    f32x4 accA[MT], accB[MT];
-    fetch(B0, 0);
-    fetch(B1, 1);
-    mma(accA, B0); // tile 0
-    fetch(B0, 2);
+    // read rows >= tau+14 (PK: see the file header).
+    // The loop body is U tiles without a branch; it runs while every fragment read it issues belongs to a
+    // tile of this layer, and the peeled tail below reads no fragment past the last tile.
+    constexpr int U = 2;           // tiles per loop iteration (even: the ping-pong closes)
+    constexpr int RMAX = U + 1;    // most tiles the tail can be left with
+    vec8 Bf[2][KS];
+    f32x4 acc[2][MT];
+    fetch(Bf[0], 0);
+    if (ntiles > 1) fetch(Bf[1], 1);
+    mma(acc[0], Bf[0]); // tile 0
+    if (ntiles > 2) fetch(Bf[0], 2);
     int m = 1; // the offsets stand at tile m - 1
 #pragma unroll 1
-    for (; m + 1 < ntiles; m += 2) {
-        mma(accB, B1); epi(accA, 0, false); fetch(B1, 3);
-        mma(accA, B0); epi(accB, 1, false); fetch(B0, 4);
-        advance2();
+    for (; m + RMAX < ntiles; m += U) {
+#pragma unroll
+        for (int k = 0; k < U; ++k) { // tile m + k; epilogue of the tile before it; fragments two tiles on
+            mma(acc[(k + 1) & 1], Bf[(k + 1) & 1]); epi(acc[k & 1], k, false); fetch(Bf[(k + 1) & 1], k + 3);
+        }
+        advance(U);
     }
-    if (m < ntiles) { mma(accB, B1); epi(accA, 0, false); epi(accB, 1, true); }
-    else epi(accA, 0, true);
+    // Tail: tiles m .. ntiles - 1 (at most RMAX), then the last tile's epilogue, the only one with the mask.
+#pragma unroll
+    for (int k = 0; k <= RMAX; ++k) {
+        if (m + k < ntiles) {
+            mma(acc[(k + 1) & 1], Bf[(k + 1) & 1]); epi(acc[k & 1], k, false);
+            if (m + k + 2 < ntiles) fetch(Bf[(k + 1) & 1], k + 3);
+        } else if (m + k == ntiles) {
+            epi(acc[k & 1], k, true);
+        }
+    }
     if constexpr (L < 3) {
         if (hi == T) { // sequence end: next layer reads frames T, T+1 as zeros
             const int t = T + (lane >> 2);
@@ -462,7 +534,13 @@ __global__ __launch_bounds__(64 * kWaves16, 2) void b2h_fwd_mfma16(
         // claim the chunk after the next one: static launches from the workgroup's share ...
         unsigned kn = 0;
         if (!dyn && lane == 0) kn = __hip_atomic_fetch_add(queue, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        commit16<PREC>(Q, lds, g, T, lane, pos_emb);
+        const bool packed = !pos_emb; // (wave-uniform) 24 channels: the unpadded layer-1 image
+        if (packed) commit16_packed(Q, lds, g, lane);
+        else { // (its lane tables and predicates are worked out here, per chunk, not kept in registers across the loop)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            commit16<PREC>(Q, lds, g, T, ln, pos_emb);
+        }
         kn = __builtin_amdgcn_readfirstlane(kn);
         // ... dynamic ones, when `next` ends its run, a new run from the device-wide counter.  The atomic is issued BEFORE the prefetch loads, so
         // the wait that the loads need anyway (pin_loads16, after layer 2) covers it: vmcnt counts in order.
@@ -485,7 +563,8 @@ __global__ __launch_bounds__(64 * kWaves16, 2) void b2h_fwd_mfma16(
         if constexpr (FUSED)
             if (fu.mask) nvalid = (int)min((int64_t)T, max((int64_t)0, fa.n_frames[g.seq]));
         B2H_STAMP16(wave, lane, it, 2);
-        layer16p<PREC, 0, FUSED, STREAM>(lds, smem16, g, T, lane, yseq, fu.mul, nvalid);
+        if (packed) layer16p<PREC, 0, FUSED, STREAM, true>(lds, smem16, g, T, lane, yseq, fu.mul, nvalid);
+        else layer16p<PREC, 0, FUSED, STREAM>(lds, smem16, g, T, lane, yseq, fu.mul, nvalid);
         B2H_STAMP16(wave, lane, it, 3);
         layer16p<PREC, 1, FUSED, STREAM>(lds, smem16, g, T, lane, yseq, fu.mul, nvalid);
         B2H_STAMP16(wave, lane, it, 4);
