@@ -16,8 +16,8 @@
 //     layers   : per 16-frame tile 5 ds_read_b128 (one per tap) feed 10 (15 for the
 //                head) v_mfma_f32_16x16x32 -- layer 1 over the 48-B rows: 4 reads (k-steps over the
 //                120 contiguous operands of a frame) and 8 --; D = W[chan][(tap,ch)] x Act[(tap,ch)][time]
-//                starts from the bias fragment; ReLU (integer max), zero-padding
-//                mask (last tile only) and the 16-bit cast stay in registers; one
+//                starts from the bias fragment; the 16-bit cast, ReLU (on the packed pairs) and the
+//                zero-padding mask (last tile only) stay in registers; one
 //                ds_write_b128 per lane puts the tile back, 2 rows lower (in-place
 //                image, see kernel_mfma.h); the head's fp32 tile (16 x 168 B) turns once through
 //                already-consumed rows of the image and leaves as three lane-linear stores.
@@ -76,8 +76,18 @@ template <int PREC> __device__ __forceinline__ uint32_t pack2(float a, float b) 
     return __builtin_bit_cast(uint32_t, p);
 }
 
-__device__ __forceinline__ float relu_bits(float v) { // max(v,0) as one v_max_i32
+__device__ __forceinline__ float relu_bits(float v) { // max(v,0) as one v_max_i32 (the other matrix-core kernels)
     return __builtin_bit_cast(float, max(__builtin_bit_cast(int, v), 0));
+}
+
+// ReLU after the cast, on the packed pair: one v_pk_max_i16 against 0 per dword where the fp32 form takes two
+// v_max_i32.  The same bits as max(v, 0) followed by the round-to-nearest cast, in bf16 and in f16: a set sign bit
+// survives the cast and makes the 16-bit integer negative (-> +0, also for -0.0 and for what rounds to -0), and
+// whatever has a clear one -- +0, positive values, +Inf, positive NaN -- is a non-negative integer either way.
+template <int PREC> __device__ __forceinline__ uint32_t relu_pack2(float a, float b) {
+    typedef short s16x2 __attribute__((ext_vector_type(2)));
+    const s16x2 p = __builtin_bit_cast(s16x2, pack2<PREC>(a, b));
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(p, s16x2{0, 0}));
 }
 
 struct Geom16 {
@@ -300,12 +310,20 @@ __device__ __forceinline__ void layer16p(char* lds, const char* wlds, const Geom
     // on; k-step s hands lane (tcol, q) the 16 bytes at + 64 s + 16 q (16-byte aligned, never across a tap;
     // 16 lanes at a 48-byte stride start at banks 12 tcol mod 64: disjoint groups of four, no swizzle).  The
     // last 16 bytes of k-step 3 are row t + 3's first eight channels, under zero weights.
-    lds_char* rd[KS];
+    // Address registers: PK needs one for its reads (the k-steps are immediates on it) and one for the write; the
+    // padded image one per tap (each row has its own swizzle term), and the write goes through tap 0's: a tile is
+    // written two rows below where it was read, P(t, L + 1) = P(t - kPad, L), the row of tap 0.
+    constexpr bool PIN = L < 3;                    // the ReLU layers' pinned schedule (below)
+    constexpr int NP = (PK && PIN) ? 1 : KS;
+    lds_char* rd[NP];
 #pragma unroll
-    for (int s = 0; s < KS; ++s)
+    for (int s = 0; s < NP; ++s)
         rd[s] = PK ? (lds_char*)(lds + kImg48 + (lo + tcol - kPad + pin) * 48 + 64 * s + 16 * q)
                    : (lds_char*)(lds + lds_off<64>(lo + tcol + s - kPad + pin, q));
     lds_char* wr = (lds_char*)(lds + lds_off<64>(lo + tcol + pout, q));
+    static_assert(kPad == 2, "the write pointer below is tap 0's read pointer");
+    auto rdp = [&](int s) { return NP == 1 ? rd[0] + 64 * s : rd[s]; };
+    auto wrp = [&]() { return (PIN && !PK) ? rd[0] : wr; };
     int tq = lo + tcol;  // this lane's frame in the tile the loop stands at
     int sbase = 0;       // head: byte offset of that tile's rows in the output buffer (wave-uniform)
 
@@ -348,19 +366,15 @@ __device__ __forceinline__ void layer16p(char* lds, const char* wlds, const Geom
     // tile's epilogue, so its body carries no padding mask and no branch.
     auto epi = [&](const f32x4 (&acc)[MT], int k, bool mask) {
         if constexpr (L < 3) {
-            float v[8];
+            u32x4 o;
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[mt * 4 + r] = relu_bits(acc[mt][r]);
+            for (int j = 0; j < 4; ++j) o[j] = relu_pack2<PREC>(acc[j >> 1][2 * (j & 1)], acc[j >> 1][2 * (j & 1) + 1]);
             if (mask) { // frames >= T are the zero padding of the next layer
                 const bool inside = tq + 16 * k < T;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = inside ? v[j] : 0.f;
+                for (int j = 0; j < 4; ++j) o[j] = inside ? o[j] : 0u;
             }
-            const u32x4 o = {pack2<PREC>(v[0], v[1]), pack2<PREC>(v[2], v[3]), pack2<PREC>(v[4], v[5]),
-                             pack2<PREC>(v[6], v[7])};
-            *(lds_u32x4*)(wr + k * 1024) = o;
+            *(lds_u32x4*)(wrp() + k * 1024) = o;
         } else {
             // lane (tcol,q) owns channels 16mt + 4q .. +3 of its frame: 16 B at byte 168 (t - lo) + 64 mt
             // + 16 q of the tile's rows (8-byte aligned: 8-byte LDS writes)
@@ -394,11 +408,11 @@ __device__ __forceinline__ void layer16p(char* lds, const char* wlds, const Geom
     // F: the fragments of the tile k tiles ahead.
     auto fetch = [&](vec8 (&Bf)[KS], int k) {
 #pragma unroll
-        for (int s = 0; s < KS; ++s) Bf[s] = *(lds_vec8*)(rd[s] + k * kTileB);
+        for (int s = 0; s < KS; ++s) Bf[s] = *(lds_vec8*)(rdp(s) + k * kTileB);
     };
-    auto advance = [&](int n) { // n tiles on
+    auto advance = [&](int n) { // n tiles on (the head; the ReLU layers advance inside their loop body)
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
+        for (int s = 0; s < NP; ++s) {
             rd[s] += n * kTileB;
             asm volatile("" : "+v"(rd[s]));
         }
@@ -415,6 +429,14 @@ __device__ __forceinline__ void layer16p(char* lds, const char* wlds, const Geom
     // read rows >= tau+14 (PK: see the file header).
     // The loop body is U tiles without a branch; it runs while every fragment read it issues belongs to a
     // tile of this layer, and the peeled tail below reads no fragment past the last tile.
+    //
+    // ReLU layers (PIN): the issue order of a tile's block is pinned, one plain vector instruction behind each MFMA
+    // (tools/mfma_mix_bench.hip: one VALU per MFMA is free, two cost a third more; left alone hipcc merges the two
+    // tiles' MFMA chains and runs the second epilogue, the fragment reads and the pointer adds after the last MFMA).
+    // The epilogue is 8 VALU (4 casts, 4 packed ReLUs), then the tile's ds_write_b128, then the fragment reads --
+    // they overwrite the registers this tile's MFMAs read, and follow the write as they always did.  The address
+    // registers advance inside the body as well, each in the tile adv_tile() names, between that tile's write and
+    // its reads, so the adds sit in MFMA shadows too; what follows an add in the body takes U tiles off its offset.
     constexpr int U = 2;           // tiles per loop iteration (even: the ping-pong closes)
     constexpr int RMAX = U + 1;    // most tiles the tail can be left with
     vec8 Bf[2][KS];
@@ -423,21 +445,60 @@ __device__ __forceinline__ void layer16p(char* lds, const char* wlds, const Geom
     if (ntiles > 1) fetch(Bf[1], 1);
     mma(acc[0], Bf[0]); // tile 0
     if (ntiles > 2) fetch(Bf[0], 2);
+    auto adv_tile = [](int p) { return (PK || p == 1 || p == 2) ? 0 : 1; }; // body tile in which rd[p] advances
+    auto pinned = [&](bool more) { // more: the block holds one VALU more than it has MFMAs
+        if constexpr (PIN) {
+            constexpr int NM = MT * KS;   // 10, or 8 (PK): the epilogue's eight VALU are through behind MFMA 7
+#pragma unroll
+            for (int i = 0; i < NM; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); // MFMA
+                __builtin_amdgcn_sched_group_barrier(0x002, 1, 0); // VALU
+                if (more && i == 0) __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+                if (i == 7) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); // DS write
+                if (i == NM - 2 && i >= 7) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); // DS read
+                if (i == NM - 1) {
+                    if (NM - 2 >= 7) __builtin_amdgcn_sched_group_barrier(0x100, KS - 2, 0);
+                    else __builtin_amdgcn_sched_group_barrier(0x100, KS, 0);
+                }
+            }
+        }
+    };
     int m = 1; // the offsets stand at tile m - 1
 #pragma unroll 1
     for (; m + RMAX < ntiles; m += U) {
 #pragma unroll
         for (int k = 0; k < U; ++k) { // tile m + k; epilogue of the tile before it; fragments two tiles on
-            mma(acc[(k + 1) & 1], Bf[(k + 1) & 1]); epi(acc[k & 1], k, false); fetch(Bf[(k + 1) & 1], k + 3);
+            if constexpr (PIN) {
+                mma(acc[(k + 1) & 1], Bf[(k + 1) & 1]); epi(acc[k & 1], k, false);
+#pragma unroll
+                for (int s = 0; s < NP; ++s)
+                    if (adv_tile(s) == k) {
+                        rd[s] += U * kTileB;
+                        asm("" : "+v"(rd[s]));
+                    }
+                if (PK && k == U - 1) {
+                    wr += U * 1024;
+                    asm("" : "+v"(wr));
+                }
+#pragma unroll
+                for (int s = 0; s < KS; ++s)
+                    Bf[(k + 1) & 1][s] =
+                        *(lds_vec8*)(rdp(s) + (k + 3 - (adv_tile(NP == 1 ? 0 : s) <= k ? U : 0)) * kTileB);
+                pinned(PK || k == 1);
+            } else {
+                mma(acc[(k + 1) & 1], Bf[(k + 1) & 1]); epi(acc[k & 1], k, false); fetch(Bf[(k + 1) & 1], k + 3);
+            }
         }
-        advance(U);
+        if constexpr (!PIN) advance(U);
     }
+    if constexpr (PIN) tq += 16 * (m - 1); // (only the tail's mask reads it)
     // Tail: tiles m .. ntiles - 1 (at most RMAX), then the last tile's epilogue, the only one with the mask.
 #pragma unroll
     for (int k = 0; k <= RMAX; ++k) {
         if (m + k < ntiles) {
             mma(acc[(k + 1) & 1], Bf[(k + 1) & 1]); epi(acc[k & 1], k, false);
             if (m + k + 2 < ntiles) fetch(Bf[(k + 1) & 1], k + 3);
+            pinned(false);
         } else if (m + k == ntiles) {
             epi(acc[k & 1], k, true);
         }
