@@ -25,6 +25,10 @@ KERNELS = {"auto": KERNEL_AUTO, "fp32": KERNEL_AUTO, "f32": KERNEL_AUTO,
 # b2h_forward_fused flags
 PRE_CHEST_DIFF, PRE_NORMALIZE, POST_DENORMALIZE, POST_MASK_TAIL = 1, 2, 4, 8
 
+# enum b2h_predict (b2h_tpt_build_item), by the CLIs' `--predict` names, and the model input width of each
+PREDICT = {"right_hand": 0, "right_index": 1, "right_3fingers": 2}
+PREDICT_NINP = {58: "right_index", 42: "right_3fingers"}
+
 # enum b2h_status
 OK, ERR_INVALID, ERR_SHAPE, ERR_NO_WEIGHTS, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 
@@ -43,6 +47,11 @@ SYMBOLS = {
                                             ctypes.c_float, _vp]),
     "b2h_masked_l1": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp]),
     "b2h_weighted_l1": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp]),
+    "b2h_masked_l1_joints": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
+    "b2h_weighted_l1_joints": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
+    "b2h_masked_l1_joints_backward": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
+    "b2h_weighted_l1_joints_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp,
+                                                       _vp]),
     "b2h_train_forward": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp]),
     "b2h_backward_workspace_bytes": (ctypes.c_size_t, [_vp, ctypes.c_int64, ctypes.c_int64]),
     "b2h_backward": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.c_int64,
@@ -72,6 +81,9 @@ SYMBOLS = {
                                        ctypes.c_size_t, _vp]),
     "b2h_tpt_forward_fused": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]),
+    "b2h_tpt_info": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_int)] * 6),
+    "b2h_tpt_build_item": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_float, _vp]),
     "b2h_tpt_train_bytes": (ctypes.c_size_t, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "b2h_tpt_train_forward": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp), ctypes.c_float, _vp,
                                              _vp, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp]),

@@ -649,10 +649,12 @@ namespace {
 
 // rows [r0, r0 + nout) of W (*, k) row-major fp32 -> [mt][g][lane][4] with
 // W[r0 + 16mt + (lane&15)][16g + 4(lane>>4) + j], followed by bias, gamma, beta (128 each)
+// kpad >= k / mpad >= nout (0 = none): the fragment grid is laid out for that many inputs / outputs, the surplus zero,
+// so that a Linear of another width runs one of the GEMM shapes the chain kernel has (tpt_front_kpad, kTptHeadMpad)
 int pack_blob(TencBlob& B, const float* w, const float* b, int r0, int nout, int k, const float* gamma,
-              const float* beta) {
-    B.kgroups = (k + 15) / 16;
-    B.mtiles = (nout + 15) / 16;
+              const float* beta, int kpad = 0, int mpad = 0) {
+    B.kgroups = (std::max(k, kpad) + 15) / 16;
+    B.mtiles = (std::max(nout, mpad) + 15) / 16;
     B.nout = nout;
     const size_t nw = (size_t)B.mtiles * B.kgroups * 64 * 4;
     std::vector<float> blob(nw + kStageParams, 0.f);
@@ -671,7 +673,7 @@ int pack_blob(TencBlob& B, const float* w, const float* b, int r0, int nout, int
     if (rc) return rc;
     // f16 hi/lo fragments for v_mfma_f32_16x16x32_f16: [part][mt][g][lane][8] with k-slot (g, q, j)
     // = input feature 32g + 16(j>>2) + 4q + (j&3) (kernel_tenc.h), then the same fp32 parameters
-    B.kgroups32 = (k + 31) / 32;
+    B.kgroups32 = (std::max(k, kpad) + 31) / 32;
     const size_t nh = (size_t)B.mtiles * B.kgroups32 * 64 * 8; // halves per part
     std::vector<_Float16> frag(2 * nh, (_Float16)0.f);
     for (int mt = 0; mt < B.mtiles; ++mt)
@@ -990,6 +992,7 @@ int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, 
 // (HandPoseModels.py:181-230), inference, exact fp32 or f16x3.  Per-frame work is b2h_tenc_chain<H3> by descriptors.
 struct b2h_tpt {
     int n_tokens = 0, n_enc = 0, n_dec = 0, device = 0, num_cus = 256;
+    int ninp = kInCh, nout = kOutCh; // n_joints*joints_dim in {16, 24, 42, 58}, head width in {8, 24, 42}
     bool has_weights = false;
     int kernel = B2H_TENC_F32;
     float w_absmax = 0.f; // largest |parameter|, the embedding table included (NaN counts as inf): B2H_TENC_F16X3 needs < 65504
@@ -1006,6 +1009,17 @@ struct b2h_tpt {
 
 namespace {
 
+// The geometry lives in the front (pose2hidden_projection) and the head (hidden2pose_projection) only, and both run
+// GEMM shapes the chain kernel already has, on zero-padded fragment grids (pack_blob's kpad / mpad):
+//   front  ninp 16, 24: two k-groups of 16 (fp32) / one of 32 (f16x3), the default model's shape; rows read in place
+//          ninp 42, 58: the 128-input shape of every inner Linear, rows read from a zero-padded 64-float copy
+//                       (b2h_item_pad_rows), of which the chain loads k-groups 0..3 and leaves 4..7 zero
+//   head   nout 8, 24, 42: three M-tiles; the store's range check keeps it to nout columns.
+constexpr int kTptHeadMpad = 48;
+int tpt_front_kpad(int ninp) { return ninp <= 32 ? 32 : kTencD; }
+bool tpt_padded_rows(const b2h_tpt* m) { return m->ninp > 32; }
+int tpt_front_ld(const b2h_tpt* m) { return tpt_padded_rows(m) ? kTptPadLd : m->ninp; }
+
 constexpr int kTptMaxLen = 16 * kAttnMaxTiles; // tokens and frames per sequence: one workgroup holds all keys
 
 // Workspace (floats; Ns = B*S token rows, Nt = B*T frame rows).  Every region is written before it is read; the
@@ -1016,9 +1030,10 @@ constexpr int kTptMaxLen = 16 * kAttnMaxTiles; // tokens and frames per sequence
 //   XT   Nt x 128  decoder residual stream           X1   Nt x 128  norm1 output (residual of the cross block)
 //   OCt  Nt x 128  attention output (self, cross)    QC   Nt x 128  cross-attention query
 //   QKVt Nt x 384  decoder self-attention Q | K | V
+//   XP   Nt x 64   the pose rows zero-padded, for ninp in {42, 58} only
 constexpr int64_t kTptTokenFloats = 5 * kTencD, kTptTokenLayerFloats = 2 * kTencD, kTptFrameFloats = 7 * kTencD;
 struct TptWs {
-    float *MEM, *OCs, *QKVs, *MKV, *XT, *X1, *OCt, *QC, *QKVt;
+    float *MEM, *OCs, *QKVs, *MKV, *XT, *X1, *OCt, *QC, *QKVt, *XP;
 };
 TptWs tpt_ws(void* workspace, int64_t Ns, int64_t Nt, int n_dec) {
     TptWs w;
@@ -1031,6 +1046,7 @@ TptWs tpt_ws(void* workspace, int64_t Ns, int64_t Nt, int n_dec) {
     w.OCt = w.X1 + Nt * kTencD;
     w.QC = w.OCt + Nt * kTencD;
     w.QKVt = w.QC + Nt * kTencD;
+    w.XP = w.QKVt + Nt * 3 * kTencD;
     return w;
 }
 
@@ -1061,7 +1077,7 @@ std::vector<size_t> tpt_param_floats(const b2h_tpt* m) {
         sizes.insert(sizes.end(), 6, D);
     }
     sizes.insert(sizes.end(), 2, D);
-    sizes.insert(sizes.end(), {(size_t)m->n_tokens * D, (size_t)kOutCh * D, (size_t)kOutCh, D * kInCh, D});
+    sizes.insert(sizes.end(), {(size_t)m->n_tokens * D, (size_t)m->nout * D, (size_t)m->nout, D * m->ninp, D});
     return sizes;
 }
 
@@ -1078,15 +1094,18 @@ int b2h_tpt_create(int n_tokens, int ninp, int nhead, int nhid, int nout, int n_
                    b2h_tpt** out) {
     if (!out) return fail(B2H_ERR_INVALID, "out is NULL");
     *out = nullptr;
-    if (ninp != kInCh || nhead != kTencHeads || nhid != kTencD || nout != kOutCh)
-        return fail(B2H_ERR_UNSUPPORTED, "TextPoseTransformer: only n_joints*joints_dim=24, nhead=4, nhid=128, nout=42 "
-                                         "(run.py:148-151) is implemented");
+    const bool geom = (ninp == 16 || ninp == 24 || ninp == 42 || ninp == 58) && (nout == 8 || nout == 24 || nout == 42);
+    if (!geom || nhead != kTencHeads || nhid != kTencD)
+        return fail(B2H_ERR_UNSUPPORTED, "TextPoseTransformer: only n_joints*joints_dim in {16, 24, 42, 58}, nout in "
+                                         "{8, 24, 42} (run.py:85-104), nhead=4, nhid=128 (run.py:148-151) is implemented");
     if (n_enc_layers < 1 || n_enc_layers > 16 || n_dec_layers < 1 || n_dec_layers > 16 || n_tokens < 1)
         return fail(B2H_ERR_UNSUPPORTED, "TextPoseTransformer: 1 <= n_enc_layers, n_dec_layers <= 16 and n_tokens >= 1");
     std::unique_ptr<b2h_tpt> m(new b2h_tpt()); // released to the caller only on success
     if (int rc = probe_device(m->device, m->num_cus)) return rc;
     if (int rc = set_tenc_kernel_attributes()) return rc;
     m->n_tokens = n_tokens;
+    m->ninp = ninp;
+    m->nout = nout;
     m->n_enc = n_enc_layers;
     m->n_dec = n_dec_layers;
     m->enc.resize(n_enc_layers);
@@ -1154,15 +1173,17 @@ int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int
     if ((rc = norm(m->dec_norm, o))) return rc;
     o += 2;
     if ((rc = m->table.upload(h[o].data(), h[o].size() * 4))) return rc;
-    if ((rc = pack_blob(m->out_proj, h[o + 1].data(), h[o + 2].data(), 0, kOutCh, Di, nullptr, nullptr))) return rc;
-    if ((rc = pack_blob(m->in_proj, h[o + 3].data(), h[o + 4].data(), 0, Di, kInCh, nullptr, nullptr))) return rc;
+    if ((rc = pack_blob(m->out_proj, h[o + 1].data(), h[o + 2].data(), 0, m->nout, Di, nullptr, nullptr, 0, kTptHeadMpad))) return rc;
+    if ((rc = pack_blob(m->in_proj, h[o + 3].data(), h[o + 4].data(), 0, Di, m->ninp, nullptr, nullptr, tpt_front_kpad(m->ninp))))
+        return rc;
     m->has_weights = true;
     return B2H_OK;
 }
 
 size_t b2h_tpt_workspace_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T) {
     if (!m || B < 0 || S < 0 || T < 0) return 0;
-    return ((size_t)B * S * (kTptTokenFloats + kTptTokenLayerFloats * m->n_dec) + (size_t)B * T * kTptFrameFloats) * sizeof(float);
+    const int64_t frame = kTptFrameFloats + (tpt_padded_rows(m) ? kTptPadLd : 0);
+    return ((size_t)B * S * (kTptTokenFloats + kTptTokenLayerFloats * m->n_dec) + (size_t)B * T * frame) * sizeof(float);
 }
 
 
@@ -1187,16 +1208,27 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
         return fail(B2H_ERR_INVALID, "x and workspace must be 16-byte aligned, tokens and y 8-byte aligned");
     if (workspace_bytes < b2h_tpt_workspace_bytes(m, B, S, T)) return fail(B2H_ERR_INVALID, "workspace too small");
     const int64_t Ns = B * S, Nt = B * T;
-    // grid limits: attention launches B x heads workgroups, the row kernels 8 rows per workgroup
-    if (B * kTencHeads > 0x7fffffff || std::max(Ns, Nt) / 8 >= 0x7fffffff)
+    // grid limits: attention launches B x heads workgroups, the row kernels 8 rows per workgroup, the copy of
+    // 42- / 58-float pose rows (b2h_item_pad_rows) 4 rows per workgroup
+    if (B * kTencHeads > 0x7fffffff || std::max(Ns, Nt) / 8 >= 0x7fffffff || (tpt_padded_rows(m) && Nt / 4 >= 0x7fffffff))
         return fail(B2H_ERR_SHAPE, "batch too large for one launch");
     if (int rc = check_device(m->device)) return rc;
     if (m->kernel == B2H_TENC_F16X3 && !(m->w_absmax < kF16Max))
         return fail(B2H_ERR_UNSUPPORTED, "B2H_TENC_F16X3: a parameter is outside the f16 range (|w| >= 65504 or not "
                                          "finite); use B2H_TENC_F32");
+    if (tpt_padded_rows(m) && (fa.flags & (kPreChest | kPreNorm)))
+        return fail(B2H_ERR_INVALID, "B2H_PRE_CHEST_DIFF / B2H_PRE_NORMALIZE apply to body-only rows (ninp 16 or 24); the "
+                                     "composite rows of ninp 42 / 58 are transformed by b2h_tpt_build_item");
     hipStream_t st = (hipStream_t)stream;
     const TptWs ws = tpt_ws(workspace, Ns, Nt, m->n_dec);
     const int nk = (int)((S + 15) / 16), nq = (int)((T + 15) / 16);
+    // the rows pose2hidden_projection reads: x itself, or its zero-padded copy
+    const float* xf = x;
+    if (tpt_padded_rows(m)) {
+        hipLaunchKernelGGL(b2h_item_pad_rows, dim3((unsigned)((Nt * kTptPadLd + 255) / 256)), dim3(256), 0, st, x, ws.XP, Nt, m->ninp);
+        xf = ws.XP;
+    }
+    const int ldf = tpt_front_ld(m);
     const bool h3 = m->kernel == B2H_TENC_F16X3, long_t = T > kTptMaxLen;
     // the item transforms: on the pose rows as they enter pose2hidden_projection, in hidden2pose_projection's store
     const auto pre = [&](Chain& c) { c.a.flags = fa.flags & (kPreChest | kPreNorm); c.a.factor = fa.factor; };
@@ -1221,7 +1253,7 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
     }
     if (h3 && !long_t) {
         {
-            Chain c = tpt_rows(x, kInCh, nullptr, Nt, true);
+            Chain c = tpt_rows(xf, ldf, nullptr, Nt, true);
             pre(c);
             c.add(m->in_proj, ST_SET, ws.XT);
             c.launch(m->num_cus, st);
@@ -1248,7 +1280,7 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
         {
             Chain c = tpt_rows(ws.XT, kTencD, nullptr, Nt, true);
             post(c);
-            c.add(m->out_proj, ST_STORE, y, kOutCh);
+            c.add(m->out_proj, ST_STORE, y, m->nout);
             c.launch(m->num_cus, st);
         }
         HIP_TRY(hipGetLastError());
@@ -1284,7 +1316,7 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
 
     // decoder (torch.nn.TransformerDecoder): pose2hidden_projection -> layers -> decoder.norm -> hidden2pose_projection
     {
-        Chain c = tpt_rows(x, kInCh, nullptr, Nt, h3);
+        Chain c = tpt_rows(xf, ldf, nullptr, Nt, h3);
         pre(c);
         c.add(m->in_proj, ST_SET, ws.XT);
         qkv(c, m->dec[0], ws.QKVt);
@@ -1316,7 +1348,7 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
     {
         Chain c = tpt_rows(ws.XT, kTencD, nullptr, Nt, h3);
         post(c);
-        c.add(m->out_proj, ST_STORE, y, kOutCh);
+        c.add(m->out_proj, ST_STORE, y, m->nout);
         c.launch(m->num_cus, st);
     }
     HIP_TRY(hipGetLastError());
@@ -1336,6 +1368,45 @@ int b2h_tpt_forward_fused(b2h_tpt* m, const int64_t* tokens, const float* body, 
     if ((flags & kPostMask) && !n_frames) return fail(B2H_ERR_INVALID, "B2H_POST_MASK_TAIL needs n_frames");
     const FusedArgs fa{flags, factor, n_frames};
     return tpt_launch(m, tokens, body, y, B, S, T, fa, B2H_TPT_MAX_FRAMES, workspace, workspace_bytes, stream);
+}
+
+int b2h_tpt_info(const b2h_tpt* m, int* n_tokens, int* ninp, int* nout, int* n_enc_layers, int* n_dec_layers,
+                 int* has_weights) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (n_tokens) *n_tokens = m->n_tokens;
+    if (ninp) *ninp = m->ninp;
+    if (nout) *nout = m->nout;
+    if (n_enc_layers) *n_enc_layers = m->n_enc;
+    if (n_dec_layers) *n_dec_layers = m->n_dec;
+    if (has_weights) *has_weights = m->has_weights ? 1 : 0;
+    return B2H_OK;
+}
+
+int b2h_tpt_build_item(const float* body, const float* right_hand, float* item, int64_t B, int64_t T, int predict,
+                       int flags, float factor, void* stream) {
+    if (B < 0 || T < 0) return fail(B2H_ERR_SHAPE, "negative shape");
+    if (predict != B2H_PREDICT_RIGHT_INDEX && predict != B2H_PREDICT_RIGHT_3FINGERS)
+        return fail(B2H_ERR_INVALID, "predict must be B2H_PREDICT_RIGHT_INDEX or B2H_PREDICT_RIGHT_3FINGERS");
+    if (flags & ~(kPreChest | kPreNorm)) return fail(B2H_ERR_INVALID, "unknown flag bits (only B2H_PRE_* apply)");
+    if ((flags & kPreNorm) && !(factor > 0.f)) return fail(B2H_ERR_INVALID, "factor must be > 0");
+    if (B * T == 0) return B2H_OK;
+    if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
+    int rc;
+    if ((rc = check_device_ptr(body, "body")) || (rc = check_device_ptr(right_hand, "right_hand")) ||
+        (rc = check_device_ptr(item, "item")))
+        return rc;
+    if (misaligned(body, 8) || misaligned(right_hand, 8) || misaligned(item, 8))
+        return fail(B2H_ERR_INVALID, "body, right_hand and item must be 8-byte aligned");
+    const int nj = predict == B2H_PREDICT_RIGHT_INDEX ? 29 : 21;
+    const size_t in = (size_t)B * T * nj * 8;
+    if (overlaps(item, in, body, (size_t)B * T * kInCh * 4) || overlaps(item, in, right_hand, (size_t)B * T * kOutCh * 4))
+        return fail(B2H_ERR_INVALID, "item overlaps an input");
+    const int64_t n = B * T * nj;
+    if ((n + 255) / 256 > 0x7fffffff) return fail(B2H_ERR_SHAPE, "shape too large");
+    hipLaunchKernelGGL(b2h_item_build_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, body,
+                       right_hand, item, B * T, predict, flags, factor);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
 }
 
 } // extern "C"
@@ -1584,11 +1655,13 @@ namespace {
 // copy of x, which the backward does not receive), XT0 (pose2hidden_projection), every decoder layer, YN
 // (decoder.norm's output) with its statistics.
 constexpr int64_t kTptSavedToken = 2 * kTtD + 4, kTptSavedTokenDec = 2 * kTtD;
-constexpr int64_t kTptSavedFrame = kInCh + 2 * kTtD + 4;
+constexpr int64_t kTptSavedFrame = 2 * kTtD + 4; // + X0: the model's ninp rounded up to a float4 (tpt_x0_ld)
 constexpr int64_t kTptSavedFrameDec = 3 * kTtD + 10 * kTtD + 8; // QKV, O, R1, H1, QC, OC, R2, H2, F1, R3, H3, statistics
 // Backward scratch: TtGrad over max(Ns, Nt) rows, then per token [dK | dV] and two dMEM rows (the sum over the
 // decoder layers alternates between them), then the slabs.
 constexpr int64_t kTptScratchToken = 2 * kTtD + 2 * kTtD;
+
+int64_t tpt_x0_ld(const b2h_tpt* m) { return (m->ninp + 3) / 4 * 4; } // keeps XT0 .. 16-byte aligned
 
 struct TptDecLayer {
     float *QKV, *O, *R1, *H1, *QC, *OC, *R2, *H2, *F1, *R3, *H3, *ST12, *ST3, *KV;
@@ -1614,7 +1687,7 @@ TptSaved tpt_saved(const b2h_tpt* m, void* saved, int64_t Ns, int64_t Nt) {
     s.STm = s.MEM + Ns * kTtD;
     s.KV = s.STm + Ns * 4;
     s.X0 = s.KV + Ns * kTptSavedTokenDec * m->n_dec;
-    s.XT0 = s.X0 + Nt * kInCh;
+    s.XT0 = s.X0 + Nt * tpt_x0_ld(m); // X0 itself is (Nt, ninp), dense
     s.dec = s.XT0 + Nt * kTtD;
     s.YN = s.dec + Nt * kTptSavedFrameDec * m->n_dec;
     s.STy = s.YN + Nt * kTtD;
@@ -1623,7 +1696,7 @@ TptSaved tpt_saved(const b2h_tpt* m, void* saved, int64_t Ns, int64_t Nt) {
 
 size_t tpt_saved_bytes(const b2h_tpt* m, int64_t Ns, int64_t Nt) {
     return ((size_t)Ns * (kTptSavedToken + m->n_enc * kTtSavedLayer + m->n_dec * kTptSavedTokenDec) +
-            (size_t)Nt * (kTptSavedFrame + m->n_dec * kTptSavedFrameDec)) * 4;
+            (size_t)Nt * (tpt_x0_ld(m) + kTptSavedFrame + m->n_dec * kTptSavedFrameDec)) * 4;
 }
 size_t tpt_scratch_bytes(int64_t Ns, int64_t Nt) {
     const int64_t Nmax = std::max(Ns, Nt);
@@ -1705,9 +1778,9 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     const size_t need = tpt_saved_bytes(m, Ns, Nt);
     if (saved_bytes < need)
         return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes (" + std::to_string(need) + " B)");
-    if (int rc = check_overlap({{y, (size_t)Nt * kOutCh * 4}, {saved, need}},
+    if (int rc = check_overlap({{y, (size_t)Nt * m->nout * 4}, {saved, need}},
                                tptt_read_only(m, params, masks, B, S, T,
-                                              {{tokens, (size_t)Ns * 8}, {x, (size_t)Nt * kInCh * 4}})))
+                                              {{tokens, (size_t)Ns * 8}, {x, (size_t)Nt * m->ninp * 4}})))
         return rc;
     hipStream_t st = (hipStream_t)stream;
     const float sc = tt_scale(p);
@@ -1728,8 +1801,8 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     tt_layernorm(st, H, wn[0], wn[1], sv.MEM, sv.STm, Ns);
 
     // decoder: pose2hidden_projection (:209) -> layers -> decoder.norm -> hidden2pose_projection (:213)
-    HIP_TRY(hipMemcpyAsync(sv.X0, x, (size_t)Nt * kInCh * 4, hipMemcpyDeviceToDevice, st));
-    tt_linear(st, sv.X0, wt[3], wt[4], sv.XT0, Nt, kInCh, kTtD, 0, nullptr, 1.f, nullptr);
+    HIP_TRY(hipMemcpyAsync(sv.X0, x, (size_t)Nt * m->ninp * 4, hipMemcpyDeviceToDevice, st));
+    tt_linear(st, sv.X0, wt[3], wt[4], sv.XT0, Nt, m->ninp, kTtD, 0, nullptr, 1.f, nullptr);
     H = sv.XT0;
     const unsigned heads = (unsigned)(B * kTtHeads);
     for (int l = 0; l < m->n_dec; ++l) { // torch.nn.TransformerDecoderLayer, post-norm, ReLU
@@ -1755,7 +1828,7 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     }
     const float* const* wd = params + 12 * m->n_enc + 2 + 18 * m->n_dec;
     tt_layernorm(st, H, wd[0], wd[1], sv.YN, sv.STy, Nt);
-    tt_linear(st, sv.YN, wt[1], wt[2], y, Nt, kTtD, kOutCh, 0, nullptr, 1.f, nullptr);
+    tt_linear(st, sv.YN, wt[1], wt[2], y, Nt, kTtD, m->nout, 0, nullptr, 1.f, nullptr);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
@@ -1782,10 +1855,10 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         if (misaligned(grads[i], 4)) return fail(B2H_ERR_INVALID, "grads must be 4-byte aligned");
         outs.push_back({grads[i], sizes[i] * 4});
     }
-    if (dx) outs.push_back({dx, (size_t)Nt * kInCh * 4});
+    if (dx) outs.push_back({dx, (size_t)Nt * m->ninp * 4});
     outs.push_back({scratch, need});
     if (int rc = check_overlap(outs, tptt_read_only(m, params, masks, B, S, T,
-                                                    {{tokens, (size_t)Ns * 8}, {dy, (size_t)Nt * kOutCh * 4}, {saved, need_saved}})))
+                                                    {{tokens, (size_t)Ns * 8}, {dy, (size_t)Nt * m->nout * 4}, {saved, need_saved}})))
         return rc;
 
     hipStream_t st = (hipStream_t)stream;
@@ -1802,8 +1875,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     const int od = 12 * m->n_enc + 2, ot = od + 18 * m->n_dec + 2; // the first decoder layer; token_embedding
 
     // hidden2pose_projection (:213) and decoder.norm
-    tt_linear_dw(st, dy, sv.YN, G.slabs, Nt, kTtD, kOutCh, grads[ot + 1], grads[ot + 2]);
-    tt_linear_dx(st, dy, params[ot + 1], G.gB, Nt, kTtD, kOutCh, nullptr, nullptr, 1.f, nullptr);
+    tt_linear_dw(st, dy, sv.YN, G.slabs, Nt, kTtD, m->nout, grads[ot + 1], grads[ot + 2]);
+    tt_linear_dx(st, dy, params[ot + 1], G.gB, Nt, kTtD, m->nout, nullptr, nullptr, 1.f, nullptr);
     tt_layernorm_bwd(st, G.gB, sv.dec_layer(m->n_dec - 1).H3, sv.STy, params[ot - 2], G.gA, G.gBm, nullptr, 1.f, G.slabs, Nt,
                      grads[ot - 2], grads[ot - 1]);
     float* dMEM = nullptr; // the sum over the decoder layers done so far
@@ -1846,8 +1919,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         tt_linear_dx(st, G.gQ, w[0], G.gA, Nt, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);         // gA = dH_in
     }
     // pose2hidden_projection (:209)
-    tt_linear_dw(st, G.gA, sv.X0, G.slabs, Nt, kInCh, kTtD, grads[ot + 3], grads[ot + 4]);
-    if (dx) tt_linear_dx(st, G.gA, params[ot + 3], dx, Nt, kInCh, kTtD, nullptr, nullptr, 1.f, nullptr);
+    tt_linear_dw(st, G.gA, sv.X0, G.slabs, Nt, m->ninp, kTtD, grads[ot + 3], grads[ot + 4]);
+    if (dx) tt_linear_dx(st, G.gA, params[ot + 3], dx, Nt, m->ninp, kTtD, nullptr, nullptr, 1.f, nullptr);
 
     // encoder.norm, the encoder layers, token_embedding (:206)
     float* slabs = G.slabs;
@@ -1931,7 +2004,8 @@ int train_check(const b2h_model* m, const float* const* params, int64_t B, int64
 // Shape and device-pointer checks of the L1 metrics (grad = false: outputs a, b = per_seq, loss) and of their
 // gradients (grad = true: a, b = dloss, dpred).
 int l1_check(bool grad, const float* pred, const float* target, const float* scores, const int64_t* n_frames,
-             int64_t B, int64_t T, const float* a, const char* a_name, const float* b, const char* b_name) {
+             int64_t B, int64_t T, int J, const float* a, const char* a_name, const float* b, const char* b_name) {
+    if (J < 1 || J > 1024) return fail(B2H_ERR_SHAPE, "the L1 metrics take 1 <= n_joints <= 1024 joints per frame");
     if (B < 1 || T < 1)
         return grad ? fail(B2H_ERR_SHAPE, "the L1 loss gradients need B >= 1 and T >= 1")
                     : fail(B2H_ERR_SHAPE, "the L1 metrics need B >= 1 and T >= 1");
@@ -1945,30 +2019,30 @@ int l1_check(bool grad, const float* pred, const float* target, const float* sco
 }
 
 int l1_metric(const float* pred, const float* target, const float* scores, const int64_t* n_frames, int64_t B,
-              int64_t T, float* per_seq, float* loss, void* stream) {
-    if (int rc = l1_check(false, pred, target, scores, n_frames, B, T, per_seq, "per_seq", loss, "loss")) return rc;
+              int64_t T, int J, float* per_seq, float* loss, void* stream) {
+    if (int rc = l1_check(false, pred, target, scores, n_frames, B, T, J, per_seq, "per_seq", loss, "loss")) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(scores ? b2h_masked_l1_seq_kernel<true> : b2h_masked_l1_seq_kernel<false>, dim3((unsigned)B),
-                       dim3(256), 0, st, pred, target, scores, n_frames, per_seq, (int)T);
+                       dim3(256), 0, st, pred, target, scores, n_frames, per_seq, (int)T, 2 * J);
     hipLaunchKernelGGL(b2h_mean_kernel, dim3(1), dim3(256), 0, st, per_seq, loss, B, scores ? 0 : 1);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
 
 int l1_backward(const float* pred, const float* target, const float* scores, const int64_t* n_frames, int64_t B,
-                int64_t T, const float* dloss, float* dpred, void* stream) {
-    if (int rc = l1_check(true, pred, target, scores, n_frames, B, T, dloss, "dloss", dpred, "dpred")) return rc;
+                int64_t T, int J, const float* dloss, float* dpred, void* stream) {
+    if (int rc = l1_check(true, pred, target, scores, n_frames, B, T, J, dloss, "dloss", dpred, "dpred")) return rc;
     if (misaligned(pred, 16) || misaligned(target, 16) || misaligned(dpred, 16))
         return fail(B2H_ERR_INVALID, "pred, target and dpred must be 16-byte aligned");
-    const size_t pn = (size_t)B * T * kOutCh * 4;
+    const size_t pn = (size_t)B * T * 2 * J * 4;
     if (overlaps(dpred, pn, pred, pn) || overlaps(dpred, pn, target, pn) || overlaps(dpred, pn, dloss, 4) ||
         (scores && overlaps(dpred, pn, scores, pn / 2)) || (n_frames && overlaps(dpred, pn, n_frames, (size_t)B * 8)))
         return fail(B2H_ERR_INVALID, "dpred overlaps an input");
-    const int64_t n = B * T * (kOutCh / 2);
+    const int64_t n = B * T * J;
     const int64_t blocks = std::min<int64_t>((n + 255) / 256, 256 * 16);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(scores ? b2h_l1_backward_kernel<true> : b2h_l1_backward_kernel<false>, dim3((unsigned)blocks),
-                       dim3(256), 0, st, pred, target, scores, n_frames, dloss, dpred, B, (int)T);
+                       dim3(256), 0, st, pred, target, scores, n_frames, dloss, dpred, B, (int)T, 2 * J);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
@@ -2073,15 +2147,36 @@ int b2h_target_transform(const float* body, const float* hand, float* hand_out, 
     return B2H_OK;
 }
 
+int b2h_masked_l1_joints(const float* pred, const float* target, const int64_t* n_frames, int64_t B, int64_t T,
+                         int n_joints, float* per_seq, float* loss, void* stream) {
+    return l1_metric(pred, target, nullptr, n_frames, B, T, n_joints, per_seq, loss, stream);
+}
+
+int b2h_weighted_l1_joints(const float* pred, const float* target, const float* scores, const int64_t* n_frames, int64_t B,
+                           int64_t T, int n_joints, float* per_seq, float* loss, void* stream) {
+    if (!scores) return fail(B2H_ERR_INVALID, "scores is NULL");
+    return l1_metric(pred, target, scores, n_frames, B, T, n_joints, per_seq, loss, stream);
+}
+
+int b2h_masked_l1_joints_backward(const float* pred, const float* target, const int64_t* n_frames, int64_t B, int64_t T,
+                                  int n_joints, const float* dloss, float* dpred, void* stream) {
+    return l1_backward(pred, target, nullptr, n_frames, B, T, n_joints, dloss, dpred, stream);
+}
+
+int b2h_weighted_l1_joints_backward(const float* pred, const float* target, const float* scores, const int64_t* n_frames,
+                                    int64_t B, int64_t T, int n_joints, const float* dloss, float* dpred, void* stream) {
+    if (!scores) return fail(B2H_ERR_INVALID, "scores is NULL");
+    return l1_backward(pred, target, scores, n_frames, B, T, n_joints, dloss, dpred, stream);
+}
+
 int b2h_masked_l1(const float* pred, const float* target, const int64_t* n_frames, int64_t B, int64_t T,
                   float* per_seq, float* loss, void* stream) {
-    return l1_metric(pred, target, nullptr, n_frames, B, T, per_seq, loss, stream);
+    return b2h_masked_l1_joints(pred, target, n_frames, B, T, kOutCh / 2, per_seq, loss, stream);
 }
 
 int b2h_weighted_l1(const float* pred, const float* target, const float* scores, const int64_t* n_frames, int64_t B,
                     int64_t T, float* per_seq, float* loss, void* stream) {
-    if (!scores) return fail(B2H_ERR_INVALID, "scores is NULL");
-    return l1_metric(pred, target, scores, n_frames, B, T, per_seq, loss, stream);
+    return b2h_weighted_l1_joints(pred, target, scores, n_frames, B, T, kOutCh / 2, per_seq, loss, stream);
 }
 
 int b2h_train_forward(b2h_model* m, const float* const* params, const float* x, float* y, int64_t B, int64_t T,
@@ -2155,13 +2250,13 @@ int b2h_backward(b2h_model* m, const float* const* params, const float* x, const
 
 int b2h_masked_l1_backward(const float* pred, const float* target, const int64_t* n_frames, int64_t B, int64_t T,
                            const float* dloss, float* dpred, void* stream) {
-    return l1_backward(pred, target, nullptr, n_frames, B, T, dloss, dpred, stream);
+    return b2h_masked_l1_joints_backward(pred, target, n_frames, B, T, kOutCh / 2, dloss, dpred, stream);
 }
 
 int b2h_weighted_l1_backward(const float* pred, const float* target, const float* scores, const int64_t* n_frames,
                              int64_t B, int64_t T, const float* dloss, float* dpred, void* stream) {
     if (!scores) return fail(B2H_ERR_INVALID, "scores is NULL");
-    return l1_backward(pred, target, scores, n_frames, B, T, dloss, dpred, stream);
+    return b2h_weighted_l1_joints_backward(pred, target, scores, n_frames, B, T, kOutCh / 2, dloss, dpred, stream);
 }
 
 int b2h_model_info(const b2h_model* m, int* conv_channels, int* pos_emb, int* has_weights) {

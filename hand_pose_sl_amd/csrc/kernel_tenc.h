@@ -208,7 +208,7 @@ struct ChainArgs {
     //                 encoding is added (the reference transforms the item, then the model adds pe:
     //                 steps/utils.py:180-210, HandPoseModels.py:167);
     //   last launch : kPostDenorm y *= factor (traintest.py:270-271) and kPostMask
-    //                 y[seq, n_frames[seq]:] = 0 (utils.py:309-312) in the 42-wide output store.
+    //                 y[seq, n_frames[seq]:] = 0 (utils.py:309-312) in the output head's store (nout <= 42).
     int flags;
     float factor;
     const int64_t* n_frames; // (B) for kPostMask
@@ -600,7 +600,7 @@ __global__ __launch_bounds__(64 * kLinWaves, 2) void b2h_tenc_chain(ChainArgs a)
             resid[g] = chain_ld(rrs, (uint32_t)(fr * kTencD + k0) * 4u);
         }
     }
-    // output-side transforms of the 42-wide head (last launch only)
+    // output-side transforms of the output head, 42 or fewer columns wide (last launch only)
     const int post = __builtin_amdgcn_readfirstlane(a.flags) & (kPostDenorm | kPostMask);
     const float omul = (post & kPostDenorm) ? a.factor : 1.0f;
     bool odead = false;
@@ -698,17 +698,19 @@ __global__ __launch_bounds__(64 * kLinWaves, 2) void b2h_tenc_chain(ChainArgs a)
         B2H_STAMP(); // 5 + 6s: epilogue (+ split) done
         // ST_STORE writes the accumulators, other types an optional copy of the stage's result;
         // no output = an empty descriptor (skipping the block instead measured no faster).  Rows are nout floats wide: whole float4 where they fit
-        // and the two-float tail of the 42-wide head (nout is 128 or 42).
+        // and the two-float tail of the 42-wide head (nout is 128, or the head's 42, 24 or 8: the narrower heads are
+        // packed as three M-tiles too, and the range check on nout drops their surplus columns).
         {
             const bool on = st.out != nullptr && !(B2H_ABLATE & 4096);
             const __amdgpu_buffer_rsrc_t ors = make_rsrc(on ? st.out + n0 * st.ldo : nullptr, on ? rows * st.ldo * 4 : 0);
             const bool raw = st.type == ST_STORE;
-            if (post && raw && st.nout == kOutCh) { // wave-uniform: the output head of a fused forward only
+            if (post && raw && st.nout <= kOutCh) { // wave-uniform: the output head (8, 24 or 42 wide; every other
+                // ST_STORE stage is 128 wide) of a fused forward only
                 // (a real branch: the empty asm keeps hipcc from if-converting it into ~80 selects and
                 // multiplies that every stage of every launch would then execute)
                 asm volatile("" ::: "memory");
 #pragma unroll
-                for (int m = 0; m < 3; ++m) { // the 42 outputs live in M-tiles 0..2
+                for (int m = 0; m < 3; ++m) { // the head's <= 42 outputs live in M-tiles 0..2
                     acc[m] = acc[m] * omul;                 // x factor, or x 1.0f (exact)
                     if (odead) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
                 }

@@ -78,8 +78,10 @@ __global__ __launch_bounds__(256) void b2h_tt_posenc(const float* __restrict__ x
     }
 }
 
-// Y[n][m] = b[m] + sum_k X[n][k] W[m][k], K in {24, 128} (multiple of 4), any M; then, in torch's order:
+// Y[n][m] = b[m] + sum_k X[n][k] W[m][k], any K <= 128, any M; then, in torch's order:
 // ReLU, keep-mask (mask (N, M)), + res (N, M).  One workgroup (128 threads) per 16 rows, a thread per column.
+// The rows lie in LDS at the pitch Kp = K rounded up to 4 with zeros behind column K, and the weights past a row's end
+// enter as zeros, so the float4 steps stay aligned and add exact zeros; per output the sum runs over k ascending.
 __global__ __launch_bounds__(128) void b2h_tt_linear(const float* __restrict__ X, const float* __restrict__ W,
                                                      const float* __restrict__ bias, float* __restrict__ Y,
                                                      int64_t N, int K, int M, int relu,
@@ -88,9 +90,11 @@ __global__ __launch_bounds__(128) void b2h_tt_linear(const float* __restrict__ X
     __shared__ __attribute__((aligned(16))) float Xs[kTtRows * kTtD];
     const int64_t n0 = (int64_t)blockIdx.x * kTtRows;
     const int nrows = (int)(N - n0 < kTtRows ? N - n0 : kTtRows); // a 32-bit scalar bound for the store loops
-    for (int i = threadIdx.x; i < kTtRows * K; i += 128) {
-        const int64_t n = n0 + i / K;
-        Xs[i] = n < N ? X[n * K + i % K] : 0.f;
+    const int Kp = (K + 3) & ~3;
+    for (int i = threadIdx.x; i < kTtRows * Kp; i += 128) {
+        const int64_t n = n0 + i / Kp;
+        const int k = i % Kp;
+        Xs[i] = (n < N && k < K) ? X[n * K + k] : 0.f;
     }
     __syncthreads();
     for (int m = threadIdx.x; m < M; m += 128) {
@@ -100,10 +104,10 @@ __global__ __launch_bounds__(128) void b2h_tt_linear(const float* __restrict__ X
         for (int r = 0; r < kTtRows; ++r) acc[r] = b;
         const float* w = W + (size_t)m * K;
         for (int k = 0; k < K; k += 4) {
-            const float w0 = w[k], w1 = w[k + 1], w2 = w[k + 2], w3 = w[k + 3];
+            const float w0 = w[k], w1 = k + 1 < K ? w[k + 1] : 0.f, w2 = k + 2 < K ? w[k + 2] : 0.f, w3 = k + 3 < K ? w[k + 3] : 0.f;
 #pragma unroll
             for (int r = 0; r < kTtRows; ++r) {
-                const float4 xv = *reinterpret_cast<const float4*>(Xs + r * K + k);
+                const float4 xv = *reinterpret_cast<const float4*>(Xs + r * Kp + k);
                 acc[r] = fmaf(xv.w, w3, fmaf(xv.z, w2, fmaf(xv.y, w1, fmaf(xv.x, w0, acc[r]))));
             }
         }
@@ -159,7 +163,8 @@ __global__ __launch_bounds__(128) void b2h_tt_linear_dx(const float* __restrict_
     }
 }
 
-// Slab partials of dW[m][k] = sum_n dY[n][m] X[n][k] and db[m] = sum_n dY[n][m], K <= 128 (multiple of 4).
+// Slab partials of dW[m][k] = sum_n dY[n][m] X[n][k] and db[m] = sum_n dY[n][m], any K <= 128 (X in LDS at the pitch
+// Kp = K rounded up to 4, zeros behind column K; a thread stores only its columns < K).
 // grid (S, ceil(M / 32)): workgroup (s, j) owns output rows 32 j .. and the row tiles s, s + S, ... of 64 rows,
 // summed in ascending row order in registers (a thread: 4 output rows x 4 columns), and writes them into
 // slab s = [dW (M, K) | db (M)].
@@ -171,6 +176,7 @@ __global__ __launch_bounds__(256) void b2h_tt_linear_dw(const float* __restrict_
     const int m0 = blockIdx.y * kTtDwM;
     const int tm = threadIdx.x >> 5, tk = threadIdx.x & 31; // output rows m0 + 4 tm .., columns 4 tk ..
     const bool live = 4 * tk < K;
+    const int Kp = (K + 3) & ~3;
     float acc[4][4], accb[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -187,15 +193,16 @@ __global__ __launch_bounds__(256) void b2h_tt_linear_dw(const float* __restrict_
             const int m = m0 + i % kTtDwM;
             Ys[i] = (n < N && m < M) ? dY[n * M + m] : 0.f;
         }
-        for (int i = threadIdx.x; i < kTtDwRows * K; i += 256) {
-            const int64_t n = n0 + i / K;
-            Xs[i] = n < N ? X[n * K + i % K] : 0.f;
+        for (int i = threadIdx.x; i < kTtDwRows * Kp; i += 256) {
+            const int64_t n = n0 + i / Kp;
+            const int k = i % Kp;
+            Xs[i] = (n < N && k < K) ? X[n * K + k] : 0.f;
         }
         __syncthreads();
         if (live)
             for (int r = 0; r < kTtDwRows; ++r) { // rows past N hold zeros
                 const float4 y = *reinterpret_cast<const float4*>(Ys + r * kTtDwM + 4 * tm);
-                const float4 x = *reinterpret_cast<const float4*>(Xs + r * K + 4 * tk);
+                const float4 x = *reinterpret_cast<const float4*>(Xs + r * Kp + 4 * tk);
                 const float yy[4] = {y.x, y.y, y.z, y.w}, xx[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -212,7 +219,8 @@ __global__ __launch_bounds__(256) void b2h_tt_linear_dw(const float* __restrict_
         const int m = m0 + 4 * tm + u;
         if (m >= M) continue;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) out[(size_t)m * K + 4 * tk + v] = acc[u][v];
+        for (int v = 0; v < 4; ++v)
+            if (4 * tk + v < K) out[(size_t)m * K + 4 * tk + v] = acc[u][v];
         if (tk == 0) out[(size_t)M * K + m] = accb[u];
     }
 }

@@ -9,6 +9,8 @@
 //   b2h_attn_cross_h3    the same attention for B2H_TENC_F16X3, with its Q, K and V projections inside: it reads the
 //                        frames' norm1 rows and the memory rows, so neither Q nor the memory's K | V cross HBM.
 //   b2h_tpt_layernorm    encoder.norm / decoder.norm, the LayerNorm that ends each stack of torch.nn.Transformer.
+//   b2h_item_pad_rows     42- and 58-float pose rows -> zero-padded 64-float rows for the chain's front.
+//   b2h_item_build_kernel  the composite input rows of `--predict right_index` / `right_3fingers`.
 //
 // Everything else of the model is per-frame and runs as descriptors of b2h_tenc_chain<H3>; the self-attention of
 // both stacks is b2h_attn_mfma_f32 or b2h_attn_qkv_h3 (b2h_api.hip: tpt_launch has the launch lists).  Targets of
@@ -32,6 +34,48 @@ __global__ __launch_bounds__(256) void b2h_tpt_embed(const int64_t* __restrict__
     float4 v = make_float4(NAN, NAN, NAN, NAN);
     if (id >= 0 && id < n_tokens) v = reinterpret_cast<const float4*>(table + id * kTencD)[c];
     reinterpret_cast<float4*>(out + row * kTencD)[c] = v;
+}
+
+// Pose rows of 42 or 58 floats (the composite inputs of `--predict right_index` / `right_3fingers`) end inside a
+// lane's float4 of the chain kernel's row load, and their 168- / 232-byte pitch is no multiple of 16.  The chain
+// therefore reads them from a copy at a pitch of kTptPadLd floats whose surplus columns are zeros: out[n][c] =
+// c < ninp ? x[n][c] : 0.  One thread per output float; 256 B per frame in front of ~1 Mflop per frame.
+constexpr int kTptPadLd = 64;
+__global__ __launch_bounds__(256) void b2h_item_pad_rows(const float* __restrict__ x, float* __restrict__ out, int64_t n,
+                                                        int ninp) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = i / kTptPadLd;
+    const int c = (int)(i % kTptPadLd);
+    if (row >= n) return;
+    out[i] = c < ninp ? x[row * ninp + c] : 0.f;
+}
+
+// The model input of `--predict right_index` (predict = 1) and `right_3fingers` (predict = 2) from raw body (N, 12, 2)
+// and right-hand (N, 21, 2) keypoints, in run.py:85-104's order: WristDifference on the hand with the RAW body wrist
+// (joint 4), ChestDifference on the body (joint 1) [flags & kPreChest], / factor on both [flags & kPreNorm], then
+//   predict 1 (BuildIndexItem,   29 joints): body 0..11, hand 0..4, hand 9..20
+//   predict 2 (Build3fingerItem, 21 joints): hand 13..20, hand 0, body 0..11        (steps/utils.py:194-259)
+// One thread per (frame, output joint): a subtraction and a true division, each correctly rounded.
+__global__ __launch_bounds__(256) void b2h_item_build_kernel(const float* __restrict__ body,
+                                                                 const float* __restrict__ hand, float* __restrict__ item,
+                                                                 int64_t frames, int predict, int flags, float factor) {
+    const int nj = predict == 1 ? 29 : 21;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= frames * nj) return;
+    const int64_t f = i / nj;
+    const int j = (int)(i % nj);
+    int src; // < 12: body joint src; otherwise hand joint src - 12
+    if (predict == 1) src = j < 12 ? j : (j < 17 ? j : j + 4);           // hand 0..4 -> 12..16, hand 9..20 -> 21..32
+    else src = j < 8 ? 12 + 13 + j : (j == 8 ? 12 : j - 9);
+    const bool is_body = src < 12;
+    const float2* b2 = reinterpret_cast<const float2*>(body + f * kInCh);
+    float2 v = is_body ? b2[src] : reinterpret_cast<const float2*>(hand + f * kOutCh)[src - 12];
+    if (flags & kPreChest) {
+        const float2 w = b2[is_body ? 1 : 4];
+        v.x -= w.x; v.y -= w.y;
+    }
+    if (flags & kPreNorm) { v.x = v.x / factor; v.y = v.y / factor; }
+    *reinterpret_cast<float2*>(item + i * 2) = v;
 }
 
 // y = (x - mean) / sqrt(var + 1e-5) * gamma + beta over 128 features, var biased (torch.nn.LayerNorm).

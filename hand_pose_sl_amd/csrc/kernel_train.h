@@ -318,12 +318,13 @@ __global__ __launch_bounds__(256) void b2h_l1_backward_kernel(const float* __res
                                                               const float* __restrict__ scores,
                                                               const int64_t* __restrict__ n_frames,
                                                               const float* __restrict__ dloss,
-                                                              float* __restrict__ dpred, int64_t B, int T) {
+                                                              float* __restrict__ dpred, int64_t B, int T,
+                                                              int nch) { // nch = 2 x joints per frame
     const float g = WEIGHTED ? dloss[0] : dloss[0] / (float)B;
-    const int64_t total = B * (int64_t)T * (kOutCh / 2); // one (frame, joint) per step
+    const int64_t total = B * (int64_t)T * (nch / 2); // one (frame, joint) per step
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total;
          e += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t bt = e / (kOutCh / 2);
+        const int64_t bt = e / (nch / 2);
         const int64_t b = bt / T;
         const int t = (int)(bt % T);
         int64_t nf = n_frames ? n_frames[b] : T;
@@ -332,7 +333,7 @@ __global__ __launch_bounds__(256) void b2h_l1_backward_kernel(const float* __res
         if (t < nf) {
             const float2 p = reinterpret_cast<const float2*>(pred)[e];
             const float2 q = reinterpret_cast<const float2*>(target)[e];
-            const float cnt = (float)(nf * kOutCh);
+            const float cnt = (float)(nf * nch);
             auto sgn = [](float v) { return (float)((v > 0.f) - (v < 0.f)); };
             if constexpr (WEIGHTED) {
                 const float s = scores[e];

@@ -176,7 +176,8 @@ __global__ __launch_bounds__(256) void b2h_target_transform_kernel(const float* 
 }
 
 // maskedPoseL1 (steps/utils.py:413-428): per sequence the mean of |pred - target| over its
-// first n_frames[i] frames x 21 joints x 2, then the mean over the batch.
+// first n_frames[i] frames x J joints x 2 (nch = 2 J floats per frame; 21 joints for the whole hand, 4 and 12 for
+// `--predict right_index` / `right_3fingers`), then the mean over the batch.
 // WEIGHTED = poderatedPoseL1 (steps/utils.py:431-452): |pred * s - target * s| with one score per
 // (frame, joint), both products rounded to fp32 before the subtraction as torch does; the batch
 // reduction is then a SUM (b2h_mean_kernel's `divide` = 0).
@@ -186,15 +187,15 @@ __global__ __launch_bounds__(256) void b2h_masked_l1_seq_kernel(const float* __r
                                                                 const float* __restrict__ target,
                                                                 const float* __restrict__ scores,
                                                                 const int64_t* __restrict__ n_frames,
-                                                                float* __restrict__ per_seq, int T) {
+                                                                float* __restrict__ per_seq, int T, int nch) {
     __shared__ float part[4];
     const int64_t b = blockIdx.x;
     int64_t n = n_frames ? n_frames[b] : T;
     n = n < 0 ? 0 : (n > T ? T : n);
-    const int64_t cnt = n * kOutCh;                       // floats of this sequence that count
-    const float2* p = reinterpret_cast<const float2*>(pred + b * (int64_t)T * kOutCh);
-    const float2* t = reinterpret_cast<const float2*>(target + b * (int64_t)T * kOutCh);
-    const float* sc = WEIGHTED ? scores + b * (int64_t)T * (kOutCh / 2) : nullptr;
+    const int64_t cnt = n * nch;                          // floats of this sequence that count
+    const float2* p = reinterpret_cast<const float2*>(pred + b * (int64_t)T * nch);
+    const float2* t = reinterpret_cast<const float2*>(target + b * (int64_t)T * nch);
+    const float* sc = WEIGHTED ? scores + b * (int64_t)T * (nch / 2) : nullptr;
     float acc = 0.f;
     for (int64_t i = threadIdx.x; i < cnt / 2; i += 256) { // one (frame, joint) per step
         const float2 a = p[i], c = t[i];

@@ -3,7 +3,7 @@ the hot path): `validate(model, val_loader, criterion, device, args)`, body2hand
 
 Per batch the reference computes  prediction = model(batch["body_kp"])  (traintest.py:183,194) or, for its
 TextPoseTransformer,  model(batch["text_tokens"], batch["input_kp"])  (:193-195; batches of more than 128 frames
-run through TextPoseTransformer.forward_fused with every transform off),
+run through TextPoseTransformer.forward_long, the same forward on the long-attention path),
 mask_output(prediction, n_frames)  (:203, steps/utils.py:309-312),  loss = criterion(prediction,
 batch["target_kp"], n_frames[, batch["target_conf"]])  (:207-210)  and averages `loss.item()` over the
 batches with AverageMeter (steps/utils.py:11-25).  Here the forward is the HIP model, the criterion one
@@ -48,7 +48,8 @@ def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=
     "body_kp" --, "target_kp" (B,T,21,2), "n_frames", and "target_conf" (B,T,21)
     for confL1), tensors on the host or the device as the reference's loader yields them.
     Returns the mean over batches of the batch losses (a float), like the reference; with
-    return_pixels also L12Pixels(21, 1280) of it (traintest.py:27-28,139)."""
+    return_pixels also L12Pixels(J, 1280) of it with J the prediction's joint count -- 21, or 4 / 12 for a model of
+    `--predict right_index` / `right_3fingers` (traintest.py:21-28,139)."""
     loss = _loss_name(criterion, args, loss)
     if loss not in LOSSES:
         # MSE / huber make the reference's validate() fail with an unbound `loss` (traintest.py:207-211)
@@ -67,13 +68,13 @@ def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=
             if text:   # traintest.py:193-195
                 pose = batch["input_kp"] if "input_kp" in batch else batch["body_kp"]
                 if pose.shape[1] > 128:   # model(tokens, pose) keeps its 128-frame limit: the long path, no transforms
-                    prediction = model.forward_fused(batch["text_tokens"], pose, dif_encoding=False, normalize=False,
-                                                     denormalize=False, mask_tail=False)
+                    prediction = model.forward_long(batch["text_tokens"], pose)
                 else:
                     prediction = model(batch["text_tokens"], pose)
             else:
                 prediction = model(batch["body_kp"])
             target = batch["target_kp"].to(dev)
+            joints = prediction.shape[2]
             if loss == "L1":
                 losses.append(masked_pose_l1(prediction, target, batch["n_frames"]))
             else:
@@ -81,4 +82,4 @@ def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=
     if not losses:
         raise ZeroDivisionError("empty loader")  # AverageMeter.get_average() divides by its count
     value = float(torch.stack(losses).double().mean())
-    return (value, l1_to_pixels(value)) if return_pixels else value
+    return (value, l1_to_pixels(value, joints)) if return_pixels else value

@@ -7,6 +7,7 @@ The working equivalent of the reference's `infer_utterance.py` (:52-111) + `step
         --model-checkpoint best_model.pth --output-folder out/ [--model Conv|TransformerEnc|TextPoseTransformer]
         [--conv-channels 30] [--conv-pos-emb] [--max-frames 200] [--no-normalize] [--dif-encoding]
         [--precision fp32] [--tokens ids.json | --text "..." --tokenizer tokenizer.json]
+        [--predict right_hand|right_index|right_3fingers]
 
 With `--model Conv` (default) transforms, model and de-normalisation run as ONE fused kernel
 (`ConvModel.forward_fused`); with `--model TransformerEnc` (infer_utterance.py:99-101) the item
@@ -19,6 +20,10 @@ object mapping each utterance folder's base name to its list -- or from `--text 
 tokenizer.json` through the `tokenizers` package.  Ids are staged as the reference's dataset stages them
 (text_pose_dataset.py:467-470): the first 40, right-padded with id 0 (`pad_tokens`).  At the default
 `--max-frames 200` it runs the long-attention kernels (`TextPoseTransformer.forward_fused`).
+With `--predict right_index` / `right_3fingers` (TextPoseTransformer only; infer_utterance.py:62-85) the model's input is
+the 12 body joints and the right hand without the predicted fingers (29 or 21 joints, built by one HIP kernel,
+`TextPoseTransformer.build_item`), its output the 4 or 12 finger joints, and only those joints of each frame's
+`hand_right_keypoints_2d` are rewritten.
 No torch elementwise kernel runs on any of the three paths.
 Several utterances (sub-folders) are batched into one launch.
 """
@@ -37,6 +42,9 @@ from .text_pose_transformer import TextPoseTransformer
 from .transformer_enc import TransformerEnc
 
 N_TOKENS_PER_UTTERANCE = 40   # text_pose_dataset.py:467-470
+# --predict -> (n_joints, nout) of the TextPoseTransformer the reference's inference scripts build for it
+# (infer_utterance.py:62-85): 12 body joints, alone or with the 17 / 9 hand joints that are not predicted
+PREDICT_GEOMETRY = {"right_hand": (12, 21 * 2), "right_index": (12 + 17, 4 * 2), "right_3fingers": (9 + 12, 12 * 2)}
 
 
 def pad_tokens(ids, n=N_TOKENS_PER_UTTERANCE):
@@ -46,23 +54,26 @@ def pad_tokens(ids, n=N_TOKENS_PER_UTTERANCE):
 
 
 def predict_utterances(model, utterances, max_frames=200, dif_encoding=False, normalize=True, tokens=None):
-    """`utterances`: list of frame lists (paths or dicts).  Returns (pred_px (U, max_frames, 21, 2)
-    numpy in pixel units, list of n_frames).  Same staging as the reference's dataset (first
+    """`utterances`: list of frame lists (paths or dicts).  Returns (pred_px (U, max_frames, J, 2)
+    numpy in pixel units, list of n_frames), J = 21, or the 4 / 12 finger joints of a composite TextPoseTransformer,
+    which also reads the utterances' right hands.  Same staging as the reference's dataset (first
     `max_frames` frames, short utterances padded by repeating frame 0).  `tokens`: for a
     TextPoseTransformer, one list of token ids per utterance (staged with `pad_tokens`)."""
     items = [openpose.load_utterance(u, max_frames) for u in utterances]
     body = torch.from_numpy(np.stack([it["body_kp"] for it in items]))
     dev = next(model.parameters()).device
-    lead = ()
+    lead, extra = (), {}
     if isinstance(model, TextPoseTransformer):
         if tokens is None or len(tokens) != len(items):
             raise ValueError("a TextPoseTransformer needs `tokens`: one list of token ids per utterance")
         lead = (torch.tensor([pad_tokens(t) for t in tokens], dtype=torch.int64),)
+        if model.ninp in (42, 58):   # `--predict right_3fingers` / `right_index`
+            extra = {"right_hand": torch.from_numpy(np.stack([it["right_hand_kp"] for it in items])).to(dev)}
     elif tokens is not None:
         raise ValueError("`tokens` is for a TextPoseTransformer")
     with torch.no_grad():   # steps/utils.py:180-210 and traintest.py:270-271 fused into the model's kernels
         pred = model.forward_fused(*lead, body.to(dev), dif_encoding=dif_encoding, normalize=normalize,
-                                   denormalize=normalize, mask_tail=False)
+                                   denormalize=normalize, mask_tail=False, **extra)
     return pred.cpu().numpy(), [it["n_frames"] for it in items]
 
 
@@ -120,7 +131,13 @@ def main(argv=None):
                                      "object mapping each utterance folder's base name to a list")
     ap.add_argument("--text", help="TextPoseTransformer: the utterance's text, tokenised with --tokenizer")
     ap.add_argument("--tokenizer", help="TextPoseTransformer: a `tokenizers` tokenizer.json for --text")
+    ap.add_argument("--predict", default="right_hand", choices=sorted(PREDICT_GEOMETRY),
+                    help="what the model predicts (infer_utterance.py:62-85): the whole right hand, or -- TextPoseTransformer "
+                         "only -- its index finger / three fingers from the body and the rest of the hand")
     args = ap.parse_args(argv)
+    if args.predict != "right_hand" and args.model != "TextPoseTransformer":
+        # the reference's ConvModel / TransformerEnc hard-code 12 input and 21 output joints (HandPoseModels.py:28,32)
+        raise SystemExit(f"--predict {args.predict} needs --model TextPoseTransformer")
     if args.model == "TextPoseTransformer":
         if not args.tokens and not (args.text is not None and args.tokenizer):
             _utterance_tokens(args, [])   # raises SystemExit with the message
@@ -150,7 +167,8 @@ def main(argv=None):
         model = TransformerEnc(ninp=12 * 2, nhead=4, nhid=128, nout=21 * 2, nlayers=4, precision=args.precision)
     else:  # infer_utterance.py:102-105; the geometry the reference hard-codes is read from the checkpoint
         n_tokens, n_enc, n_dec = _tpt_geometry(state)
-        model = TextPoseTransformer(n_tokens=n_tokens, n_joints=12, joints_dim=2, nhead=4, nhid=128, nout=21 * 2,
+        n_joints, nout = PREDICT_GEOMETRY[args.predict]
+        model = TextPoseTransformer(n_tokens=n_tokens, n_joints=n_joints, joints_dim=2, nhead=4, nhid=128, nout=nout,
                                     n_enc_layers=n_enc, n_dec_layers=n_dec).set_precision(args.precision)
         tokens = _utterance_tokens(args, [os.path.basename(os.path.normpath(f)) for f, _ in utts])
     model.load_state_dict(state)
@@ -160,10 +178,11 @@ def main(argv=None):
     os.mkdir(args.output_folder)
     for (folder, frames), p, n in zip(utts, pred, n_frames):
         if merged:
-            openpose.write_merged_predictions(frames[:n], p, os.path.join(args.output_folder, os.path.basename(folder)))
+            openpose.write_merged_predictions(frames[:n], p, os.path.join(args.output_folder, os.path.basename(folder)),
+                                              predict=args.predict)
             continue
         out = args.output_folder if len(utts) == 1 else os.path.join(args.output_folder, os.path.basename(folder))
-        openpose.write_predictions(frames[:n], p, out)
+        openpose.write_predictions(frames[:n], p, out, predict=args.predict)
     print(f"wrote {sum(n_frames)} frames of {len(utts)} utterance(s) to {args.output_folder}")
 
 

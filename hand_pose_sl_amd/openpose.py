@@ -123,14 +123,15 @@ def load_utterance(frames, max_frames):
     return out
 
 
-def write_merged_predictions(entries, prediction, out_path):
+def write_merged_predictions(entries, prediction, out_path, predict="right_hand"):
     """The merged-file counterpart of write_predictions: `entries` as read by load_merged_utterance
-    (or any frame entries), `prediction` (>= len(entries), 21, 2) in pixels -> one merged file of
-    {"id", "data"} records with every frame's right hand replaced."""
+    (or any frame entries), `prediction` (>= len(entries), J, 2) in pixels with J = 21, 4 (`right_index`) or 12
+    (`right_3fingers`) -> one merged file of {"id", "data"} records with every frame's right hand, or only its
+    predicted finger joints, replaced."""
     out = []
     for i, e in enumerate(entries):
         data = json.loads(json.dumps(frame_data(e)))        # the caller's frames stay untouched
-        replace_right_hand(data, prediction[i])
+        replace_right_hand(data, prediction[i], predict)
         fid = e.get("id") if isinstance(e, dict) else None
         if fid is None:
             p = frame_path(e)

@@ -5,8 +5,11 @@ infer_utterance.py:27-28,102-103), on libb2h's gfx950 kernels.
 Same constructor `TextPoseTransformer(n_tokens, n_joints, joints_dim, nhead, nhid, nout, n_enc_layers,
 n_dec_layers, dropout=0.5)` and the same `state_dict`: the torch.nn containers are built in the reference's order,
 so a seeded default init is identical and its checkpoints load as they are.  `model(input_tokens, input_pose)`
-with int64 token ids (B, S) and float32 pose (B, T, 12, 2) -> float32 (B, T, 21, 2); tokenisation stays with the
-caller, as in the reference (traintest.py:105-107).  The torch containers only hold parameters: the forward runs
+with int64 token ids (B, S) and float32 pose (B, T, n_joints, 2) -> float32 (B, T, nout / 2, 2); tokenisation stays
+with the caller, as in the reference (traintest.py:105-107).  The geometries are the four the reference's CLIs build:
+(n_joints, nout) = (12, 42) (infer_utterance.py:79-80), (8, 42) (run.py:100-101, the trainer's default), (29, 8)
+(`--predict right_index`, run.py:92-93) and (21, 24) (`right_3fingers`, :96-97), and any other pairing of those
+values (n_joints * joints_dim in {16, 24, 42, 58}, nout in {8, 24, 42}).  The torch containers only hold parameters: the forward runs
 through the C ABI (`b2h_tpt_forward`).  Like the reference, the model passes no mask (padded token id 0 is attended
 like any other id) and never applies its two positional encodings, which exist only as `pe` buffers.
 
@@ -59,6 +62,7 @@ class TextPoseTransformer(NativeModule, nn.Module):
         self.pose2hidden_projection = nn.Linear(n_joints * joints_dim, nhid)
         self.n_tokens = int(n_tokens)
         self.ninp = int(n_joints * joints_dim)
+        self.nout = int(nout)
         self._dropout_p = float(dropout)
         self._geom = (self.n_tokens, self.ninp, int(nhead), int(nhid), int(nout), int(n_enc_layers), int(n_dec_layers))
 
@@ -174,7 +178,7 @@ class TextPoseTransformer(NativeModule, nn.Module):
             nf = torch.as_tensor(fused[2]).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
             if nf.shape != (B,):
                 raise RuntimeError(f"expected n_frames of shape ({B},), got {tuple(nf.shape)}")
-        y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=dev)
+        y = torch.empty((B, T, self.nout // 2, 2), dtype=torch.float32, device=dev)
         need = lib.b2h_tpt_workspace_bytes(self._handle, B, S, T)
         ws = self._grown_workspace(need, dev)
         args = (ctypes.c_void_p(ws.data_ptr()), ws.numel())
@@ -191,8 +195,44 @@ class TextPoseTransformer(NativeModule, nn.Module):
                                                      ctypes.c_void_p(st)))
         return y
 
+    def forward_long(self, input_tokens, input_pose):
+        """`model(input_tokens, input_pose)` in inference for 1 <= T <= 1024 frames, in any geometry: the long path on
+        rows that are already the model's input (for a composite model the (B, T, 21 | 29, 2) rows of `build_item` or of
+        the reference's dataset), no transform on either side.  Equal to `model(tokens, pose)` bit for bit at T <= 128."""
+        if self._wants_grad(input_tokens, input_pose) or (self.training and self._dropout_p > 0.0):
+            raise RuntimeError("TextPoseTransformer.forward_long is inference-only (no gradient, no dropout): call "
+                               "model.eval() or wrap the call in torch.no_grad(); train through model(tokens, pose)")
+        self._check_inputs(input_tokens, input_pose)
+        return self._run(input_tokens, input_pose, (0, 1.0, None))
+
+    def build_item(self, body, right_hand, dif_encoding=True, normalize=True, factor=1280.0):
+        """The (B, T, n_joints, 2) input rows of a composite model (`--predict right_index`: 29 joints, `right_3fingers`:
+        21) from raw body (B, T, 12, 2) and right-hand (B, T, 21, 2) keypoints: WristDifference, ChestDifference,
+        / factor and the Build*Item concatenation of steps/utils.py:194-259 in run.py:85-104's order, one HIP kernel
+        (b2h_tpt_build_item).  The predict mode follows from the model's input width."""
+        predict = _lib.PREDICT_NINP.get(self.ninp)
+        if predict is None:
+            raise ValueError(f"build_item is for the composite inputs (n_joints 21 or 29); this model takes {self.ninp // 2} "
+                             "body joints")
+        if body.dim() != 4 or tuple(body.shape[2:]) != (12, 2):
+            raise RuntimeError(f"expected body of shape (B, T, 12, 2), got {tuple(body.shape)}")
+        if right_hand.dim() != 4 or tuple(right_hand.shape) != tuple(body.shape[:2]) + (21, 2):
+            raise RuntimeError(f"expected right_hand of shape {tuple(body.shape[:2]) + (21, 2)}, got {tuple(right_hand.shape)}")
+        lib, dev = self._ensure_handle()
+        b = body.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        h = right_hand.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        B, T = b.shape[0], b.shape[1]
+        item = torch.empty((B, T, self.ninp // 2, 2), dtype=torch.float32, device=dev)
+        flags = (_lib.PRE_CHEST_DIFF if dif_encoding else 0) | (_lib.PRE_NORMALIZE if normalize else 0)
+        with _lib.on_device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.b2h_tpt_build_item(ctypes.c_void_p(b.data_ptr()), ctypes.c_void_p(h.data_ptr()),
+                                              ctypes.c_void_p(item.data_ptr()), B, T, _lib.PREDICT[predict], flags,
+                                              float(factor), ctypes.c_void_p(st)))
+        return item
+
     def forward_fused(self, input_tokens, body, n_frames=None, dif_encoding=True, normalize=True, denormalize=True,
-                      mask_tail=False, factor=1280.0):
+                      mask_tail=False, factor=1280.0, right_hand=None):
         """Token ids and raw-pixel body keypoints in, pixel-space hand keypoints out, with the item transforms inside
         the model's own kernels (b2h_tpt_forward_fused): ChestDifference + /factor (steps/utils.py:180-210) on the pose
         rows as they enter pose2hidden_projection -> the model -> x factor (traintest.py:270-271) and the optional
@@ -204,7 +244,16 @@ class TextPoseTransformer(NativeModule, nn.Module):
         with an online softmax.  With every transform off and T <= 128 the result equals `model(tokens, pose)` bit for
         bit.  `model(tokens, pose)` itself keeps refusing T > 128 because
         tests/test_tpt_gpu.py::test_errors_and_weight_replacement pins that refusal; a later change that may touch
-        that test should route `forward` to this path."""
+        that test should route `forward` to this path.
+
+        `right_hand` (B, T, 21, 2), raw pixels: required exactly when the model takes a composite input (n_joints 21 or
+        29, `--predict right_3fingers` / `right_index`).  `body` is then the 12 body joints, the input rows are made by
+        `build_item` (where `dif_encoding` and `normalize` then apply) and the model runs with its own pre-transforms
+        off; the output side is as for the body-only models."""
+        composite = self.ninp in _lib.PREDICT_NINP
+        if composite != (right_hand is not None):
+            raise ValueError(f"right_hand must be given exactly when the model takes a composite input (n_joints 21 or 29); "
+                             f"this model takes {self.ninp // 2} joints")
         if self._wants_grad(input_tokens, body):
             raise RuntimeError("TextPoseTransformer.forward_fused is inference-only (no gradient): call model.eval() or "
                                "wrap the call in torch.no_grad(); train through model(tokens, pose)")
@@ -214,6 +263,9 @@ class TextPoseTransformer(NativeModule, nn.Module):
                                "model.eval()")
         if mask_tail and n_frames is None:
             raise ValueError("mask_tail=True needs n_frames")
+        if composite:
+            body = self.build_item(body, right_hand, dif_encoding, normalize, factor)
+            dif_encoding = normalize = False
         self._check_inputs(input_tokens, body)
         flags = ((_lib.PRE_CHEST_DIFF if dif_encoding else 0) | (_lib.PRE_NORMALIZE if normalize else 0) |
                  (_lib.POST_DENORMALIZE if denormalize else 0) | (_lib.POST_MASK_TAIL if mask_tail else 0))
@@ -237,7 +289,7 @@ class _TptTrainFn(torch.autograd.Function):
         x = _aligned(x)
         tok = _aligned(tok)
         B, S, T = tok.shape[0], tok.shape[1], x.shape[1]
-        y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=x.device)
+        y = torch.empty((B, T, model.nout // 2, 2), dtype=torch.float32, device=x.device)
         nbytes = lib.b2h_tpt_train_bytes(model._handle, B, S, T, 0)
         saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
         with _lib.on_device(dev):
@@ -258,14 +310,15 @@ class _TptTrainFn(torch.autograd.Function):
         need_dx = ctx.needs_input_grad[4]
         B, S, T = ctx.shape
         dev = saved.device
+        xshape = (B, T, model.ninp // 2, 2)
         if B == 0:
             grads = [torch.zeros_like(t) for t in params]
-            dx = torch.zeros((B, T, 12, 2), dtype=torch.float32, device=dev) if need_dx else None
+            dx = torch.zeros(xshape, dtype=torch.float32, device=dev) if need_dx else None
         else:
             lib, dev = model._ensure_created()
             dy = _aligned(dy.to(torch.float32).contiguous())   # autograd may hand over an expanded / CopySlices gradient
             grads = [torch.empty_like(t) for t in params]
-            dx = torch.empty((B, T, 12, 2), dtype=torch.float32, device=dev) if need_dx else None
+            dx = torch.empty(xshape, dtype=torch.float32, device=dev) if need_dx else None
             nbytes = lib.b2h_tpt_train_bytes(model._handle, B, S, T, 1)
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             with _lib.on_device(dev):

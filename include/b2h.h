@@ -151,6 +151,13 @@ int b2h_masked_l1(const float* pred, const float* target, const int64_t* n_frame
  * OpenPose confidence of each target joint; everything else as b2h_masked_l1. */
 int b2h_weighted_l1(const float* pred, const float* target, const float* scores, const int64_t* n_frames,
                     int64_t B, int64_t T, float* per_seq, float* loss, void* stream);
+/* The same two losses over (B, T, n_joints, 2) predictions, 1 <= n_joints <= 1024 (scores (B, T, n_joints)): the
+ * targets of `--predict right_index` (4 joints) and `right_3fingers` (12) beside the whole hand's 21
+ * (L12Pixels(4 | 12 | 21, 1280), traintest.py:21-28).  b2h_masked_l1 / b2h_weighted_l1 are these with 21. */
+int b2h_masked_l1_joints(const float* pred, const float* target, const int64_t* n_frames, int64_t B, int64_t T,
+                         int n_joints, float* per_seq, float* loss, void* stream);
+int b2h_weighted_l1_joints(const float* pred, const float* target, const float* scores, const int64_t* n_frames,
+                           int64_t B, int64_t T, int n_joints, float* per_seq, float* loss, void* stream);
 
 /* Training (ConvModel) ------------------------------------------------------
  * The reference trains ConvModel with the loop body of steps/traintest.py:111-121:
@@ -196,6 +203,13 @@ int b2h_masked_l1_backward(const float* pred, const float* target, const int64_t
 int b2h_weighted_l1_backward(const float* pred, const float* target, const float* scores,
                              const int64_t* n_frames, int64_t B, int64_t T, const float* dloss,
                              float* dpred, void* stream);
+/* The two gradients over (B, T, n_joints, 2), as b2h_masked_l1_joints; the two above are these with 21 (42 in their
+ * formulas is 2 * n_joints). */
+int b2h_masked_l1_joints_backward(const float* pred, const float* target, const int64_t* n_frames, int64_t B,
+                                  int64_t T, int n_joints, const float* dloss, float* dpred, void* stream);
+int b2h_weighted_l1_joints_backward(const float* pred, const float* target, const float* scores,
+                                    const int64_t* n_frames, int64_t B, int64_t T, int n_joints,
+                                    const float* dloss, float* dpred, void* stream);
 
 /* TransformerEnc -------------------------------------------
  * The reference's second text-free body->hand model, `TransformerEnc(ninp, nhead, nhid, nout,
@@ -311,8 +325,14 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
  * b2h_tpt_forward returns B2H_ERR_UNSUPPORTED for a model with a parameter outside it. */
 typedef struct b2h_tpt b2h_tpt;
 /* Replaces TextPoseTransformer.__init__ (HandPoseModels.py:181-230) as run.py:148-151 calls it.  `ninp` is
- * n_joints * joints_dim.  Accepts ninp = 24, nhead = 4, nhid = 128, nout = 42, 1 <= n_enc_layers, n_dec_layers
- * <= 16 and n_tokens >= 1; B2H_ERR_UNSUPPORTED for anything else.  Bound to the current HIP device. */
+ * n_joints * joints_dim.  Accepts the geometries the reference's CLIs build, in any combination:
+ *   ninp in {16, 24, 42, 58}: 8 body joints (run.py:100-101, infer_utterance_h5.py:83-84), 12 body joints
+ *                             (infer_utterance.py:79-80), 21 = 9 hand + 12 body (`--predict right_3fingers`,
+ *                             run.py:96-97), 29 = 12 body + 17 hand (`--predict right_index`, run.py:92-93)
+ *   nout in {8, 24, 42}     : 4 (right_index), 12 (right_3fingers) or 21 (right_hand) joints x 2
+ * with nhead = 4, nhid = 128, 1 <= n_enc_layers, n_dec_layers <= 16 and n_tokens >= 1; B2H_ERR_UNSUPPORTED for
+ * anything else.  Wherever this header writes (B, T, 12, 2) and (B, T, 21, 2) for this model's input and output,
+ * read (B, T, ninp / 2, 2) and (B, T, nout / 2, 2).  Bound to the current HIP device. */
 int b2h_tpt_create(int n_tokens, int ninp, int nhead, int nhid, int nout, int n_enc_layers, int n_dec_layers,
                    b2h_tpt** out);
 int b2h_tpt_destroy(b2h_tpt* m);
@@ -329,14 +349,15 @@ int b2h_tpt_set_kernel(b2h_tpt* m, int kernel);
  *   per decoder layer i, transformer.decoder.layers.i.: self_attn.* (4 tensors as above), multihead_attn.* (the same
  *     4 shapes), linear1.*, linear2.*, norm1.*, norm2.*, norm3.*;
  *   transformer.decoder.norm.weight, .bias;
- *   token_embedding.weight (n_tokens,128); hidden2pose_projection.weight (42,128), .bias (42);
- *   pose2hidden_projection.weight (128,24), .bias (128).
+ *   token_embedding.weight (n_tokens,128); hidden2pose_projection.weight (nout,128), .bias (nout);
+ *   pose2hidden_projection.weight (128,ninp), .bias (128).
  * `on_device` as for b2h_load_weights; synchronous; may be called again to replace the weights. */
 int b2h_tpt_load_weights(b2h_tpt* m, const float* const* tensors, int count, int on_device);
 /* Bytes of device scratch b2h_tpt_forward and b2h_tpt_forward_fused need: a function of (B, S, T) and the layer
  * counts only -- B*S*(2560 + 1024*n_dec_layers) + B*T*3584, i.e. 2560 + 1024*n_dec_layers per token and 3584 per
  * frame, for every T (the kernels for T > 128 use the regions the fp32 path already has: Q | K | V rows, the cross
- * query and the memory's K | V; they need nothing more).  0 for a NULL model or a negative size. */
+ * query and the memory's K | V; they need nothing more).  A model with ninp 42 or 58 adds 256 per frame: the chain
+ * kernel reads its pose rows from a copy at a 64-float pitch.  0 for a NULL model or a negative size. */
 size_t b2h_tpt_workspace_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T);
 /* Replaces TextPoseTransformer.forward(input_tokens, input_pose) (HandPoseModels.py:181-230, :201-222; called at
  * traintest.py:105-107 and through run.py:148-151):
@@ -370,6 +391,24 @@ int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y,
 int b2h_tpt_forward_fused(b2h_tpt* m, const int64_t* tokens, const float* body, float* y, int64_t B, int64_t S,
                           int64_t T, int flags, float factor, const int64_t* n_frames, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* The B2H_PRE_* flags transform body-only rows (ninp 16 or 24: ChestDifference has the chest at joint 1 of either).
+ * A model with ninp 42 or 58 answers them with B2H_ERR_INVALID: its rows are made by b2h_tpt_build_item, which
+ * applies them, and enter b2h_tpt_forward_fused with the B2H_POST_* flags only. */
+
+/* The geometry of a model and whether weights are loaded; any output pointer may be NULL. */
+int b2h_tpt_info(const b2h_tpt* m, int* n_tokens, int* ninp, int* nout, int* n_enc_layers, int* n_dec_layers,
+                 int* has_weights);
+
+/* The model input of `--predict right_index` / `right_3fingers` from raw body and right-hand keypoints, in the
+ * order of run.py:85-104: WristDifference on the hand with the RAW body wrist (joint 4) and ChestDifference on the
+ * body (B2H_PRE_CHEST_DIFF, steps/utils.py:194-210), / factor on both (B2H_PRE_NORMALIZE), then
+ *   B2H_PREDICT_RIGHT_INDEX    (BuildIndexItem, :217-236)  : body 0..11, hand 0..4, hand 9..20      -> (B, T, 29, 2)
+ *   B2H_PREDICT_RIGHT_3FINGERS (Build3fingerItem, :238-259): hand 13..20, hand 0, body 0..11        -> (B, T, 21, 2)
+ *   body (B, T, 12, 2), right_hand (B, T, 21, 2), item: device fp32, 8-byte aligned, item overlapping neither input.
+ * flags: B2H_PRE_* only.  Every element is one subtraction and one true division: equal to torch's, bit for bit. */
+enum b2h_predict { B2H_PREDICT_RIGHT_HAND = 0, B2H_PREDICT_RIGHT_INDEX = 1, B2H_PREDICT_RIGHT_3FINGERS = 2 };
+int b2h_tpt_build_item(const float* body, const float* right_hand, float* item, int64_t B, int64_t T, int predict,
+                       int flags, float factor, void* stream);
 
 /* Training (TextPoseTransformer) -------------------------------------------------
  * The reference trains its default model with `prediction = model(batch["text_tokens"], batch["input_kp"])`,
@@ -397,7 +436,8 @@ int b2h_tpt_forward_fused(b2h_tpt* m, const int64_t* tokens, const float* body, 
 
 /* Bytes a (B, S, T) batch needs, pure functions of (B, S, T) and the layer counts.
  *   which = 0, the saved-activation buffer b2h_tpt_train_forward fills for b2h_tpt_backward:
- *     B*S * (1040 + 4624*n_enc_layers + 1024*n_dec_layers) + B*T * (1136 + 6688*n_dec_layers)
+ *     B*S * (1040 + 4624*n_enc_layers + 1024*n_dec_layers) + B*T * (1040 + 4*ceil4(ninp) + 6688*n_dec_layers)
+ *     (ceil4: rounded up to a multiple of 4; 1136 per frame for the default ninp = 24)
  *   which = 1, the scratch of b2h_tpt_backward, with N = max(B*S, B*T):
  *     N * 3584 + B*S * 2048 + clamp(ceil(N / 128), 1, 64) * 198144
  * 0 for a NULL model, B < 1, S < 1, T < 1 or another `which`. */

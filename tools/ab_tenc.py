@@ -21,8 +21,9 @@ dev = torch.device("cuda:0")
 def typed(path):
     lib = ctypes.CDLL(os.path.abspath(path))
     for name, (res, args) in _lib.SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
+        if hasattr(lib, name):  # an older build lacks the entry points added since
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
     return lib
 
 
