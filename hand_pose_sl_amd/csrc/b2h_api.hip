@@ -24,6 +24,7 @@
 #include "kernel_tenc_train.h"
 #include "kernel_tpt.h"
 #include "kernel_attn_long.h"
+#include "kernel_train_attn_long.h"
 #include "kernel_tpt_train.h"
 #include "kernel_train.h"
 #include "kernel_valu.h"
@@ -789,6 +790,9 @@ int set_tenc_kernel_attributes() {
                 return rc;
         if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd)) ||
             (rc = raise_lds_cap(b2h_tptt_xsdpa)) || (rc = raise_lds_cap(b2h_tptt_xsdpa_bwd)))
+            return rc;
+        if ((rc = raise_lds_cap(b2h_lt_sdpa, (int)kLtFwdLds)) || (rc = raise_lds_cap(b2h_lt_sdpa_bwd_kv, (int)kLtBwdKvLds)) ||
+            (rc = raise_lds_cap(b2h_lt_sdpa_bwd_q, (int)kLtBwdQLds)))
             return rc;
         return B2H_OK;
     });
@@ -1660,6 +1664,11 @@ constexpr int64_t kTptSavedFrameDec = 3 * kTtD + 10 * kTtD + 8; // QKV, O, R1, H
 // Backward scratch: TtGrad over max(Ns, Nt) rows, then per token [dK | dV] and two dMEM rows (the sum over the
 // decoder layers alternates between them), then the slabs.
 constexpr int64_t kTptScratchToken = 2 * kTtD + 2 * kTtD;
+// Beyond 128 frames (kernel_train_attn_long.h) the two attentions of every decoder layer also save their rows'
+// log-sum-exp, (B, 4, T) each, behind everything else, and the backward keeps the row terms {D, sigma},
+// (B, 4, T, 2), behind the slabs.  Nothing is added at T <= 128.
+constexpr int64_t kTptSavedFrameLong = 2 * kTtHeads, kTptScratchFrameLong = 2 * kTtHeads;
+bool tpt_long(int64_t T) { return T > kTptMaxLen; }
 
 int64_t tpt_x0_ld(const b2h_tpt* m) { return (m->ninp + 3) / 4 * 4; } // keeps XT0 .. 16-byte aligned
 
@@ -1667,7 +1676,7 @@ struct TptDecLayer {
     float *QKV, *O, *R1, *H1, *QC, *OC, *R2, *H2, *F1, *R3, *H3, *ST12, *ST3, *KV;
 };
 struct TptSaved {
-    float *E0, *enc, *MEM, *STm, *KV, *X0, *XT0, *dec, *YN, *STy;
+    float *E0, *enc, *MEM, *STm, *KV, *X0, *XT0, *dec, *YN, *STy, *LSE;
     int64_t Ns, Nt;
     TtLayer enc_layer(int l) const { return tt_layer(enc, Ns, l); }
     const float* enc_out(int n_enc) const { return enc_layer(n_enc - 1).H2; }
@@ -1691,16 +1700,18 @@ TptSaved tpt_saved(const b2h_tpt* m, void* saved, int64_t Ns, int64_t Nt) {
     s.dec = s.XT0 + Nt * kTtD;
     s.YN = s.dec + Nt * kTptSavedFrameDec * m->n_dec;
     s.STy = s.YN + Nt * kTtD;
+    s.LSE = s.STy + Nt * 4; // long T only: per decoder layer the self-attention's rows, then the cross-attention's
     return s;
 }
 
-size_t tpt_saved_bytes(const b2h_tpt* m, int64_t Ns, int64_t Nt) {
+size_t tpt_saved_bytes(const b2h_tpt* m, int64_t Ns, int64_t Nt, bool lng) {
     return ((size_t)Ns * (kTptSavedToken + m->n_enc * kTtSavedLayer + m->n_dec * kTptSavedTokenDec) +
-            (size_t)Nt * (tpt_x0_ld(m) + kTptSavedFrame + m->n_dec * kTptSavedFrameDec)) * 4;
+            (size_t)Nt * (tpt_x0_ld(m) + kTptSavedFrame + m->n_dec * (kTptSavedFrameDec + (lng ? kTptSavedFrameLong : 0)))) * 4;
 }
-size_t tpt_scratch_bytes(int64_t Ns, int64_t Nt) {
+size_t tpt_scratch_bytes(int64_t Ns, int64_t Nt, bool lng) {
     const int64_t Nmax = std::max(Ns, Nt);
-    return ((size_t)Nmax * kTtScratchFrame + (size_t)Ns * kTptScratchToken + (size_t)tt_nslabs(Nmax) * kTtSlab) * 4;
+    return ((size_t)Nmax * kTtScratchFrame + (size_t)Ns * kTptScratchToken + (size_t)tt_nslabs(Nmax) * kTtSlab +
+            (lng ? (size_t)Nt * kTptScratchFrameLong : 0)) * 4;
 }
 
 int tpt_nparams(const b2h_tpt* m) { return 9 + 12 * m->n_enc + 18 * m->n_dec; }
@@ -1722,7 +1733,8 @@ int tptt_check(const b2h_tpt* m, const float* const* params, const int64_t* toke
     if (!(p >= 0.f && p <= 1.f)) return fail(B2H_ERR_INVALID, "dropout p must be in [0, 1]");
     if ((p > 0.f) != (masks != nullptr)) return fail(B2H_ERR_INVALID, "masks must be given exactly when p > 0");
     if (B < 0 || S < 1 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0, S >= 1 and T >= 1");
-    if (S > kTptMaxLen || T > kTptMaxLen) return fail(B2H_ERR_SHAPE, "TextPoseTransformer: S and T are limited to 128");
+    if (S > kTptMaxLen || T > B2H_TPT_MAX_FRAMES)
+        return fail(B2H_ERR_SHAPE, "TextPoseTransformer training: S is limited to 128 and T to B2H_TPT_MAX_FRAMES = 1024");
     // grid limits: attention launches B x heads workgroups, LayerNorm N / 4 (the largest row grid)
     if (B * kTtHeads > 0x7fffffff || B * std::max(S, T) / 4 >= 0x7fffffff)
         return fail(B2H_ERR_SHAPE, "batch too large for one launch");
@@ -1755,6 +1767,26 @@ void tt_layernorm(hipStream_t st, const float* X, const float* gamma, const floa
 
 // The cross-attention operands of decoder layer L: queries QC (Nt, 128), [K | V] rows (Ns, 256).
 XsdpaSrc tpt_xsrc(const TptDecLayer& L) { return XsdpaSrc{L.QC, kTtD, 0, L.KV, 2 * kTtD, 0, kTtD}; }
+// The self-attention operands as the long kernels take them: [Q | K | V] rows (Nt, 384).
+XsdpaSrc tpt_ssrc(const TptDecLayer& L) { return XsdpaSrc{L.QKV, 3 * kTtD, 0, L.QKV, 3 * kTtD, kTtD, 2 * kTtD}; }
+
+// Attention of B sequences of Tq > 128 query rows over Tk key rows in training (kernel_train_attn_long.h):
+// O (B*Tq, 128) and the rows' log-sum-exp (B, 4, Tq).
+void lt_sdpa(hipStream_t st, const XsdpaSrc& src, const uint8_t* mask, float sc, float* O, float* lse, int64_t B, int Tq,
+             int Tk) {
+    hipLaunchKernelGGL(b2h_lt_sdpa, dim3((unsigned)(B * kTtHeads), lt_blocks(Tq, kLtQb)), dim3(256), kLtFwdLds, st, src,
+                       mask, sc, O, lse, Tq, Tk);
+}
+
+// Its backward: the query owner (dQ, and the row terms D for the key owner), then the key owner ([dK | dV]).
+void lt_sdpa_bwd(hipStream_t st, const XsdpaSrc& src, const float* dO, const float* lse, float* D, const uint8_t* mask,
+                 float sc, const LtGradDst& dst, int64_t B, int Tq, int Tk) {
+    const unsigned heads = (unsigned)(B * kTtHeads);
+    hipLaunchKernelGGL(b2h_lt_sdpa_bwd_q, dim3(heads, lt_blocks(Tq, kLtQb)), dim3(256), kLtBwdQLds, st, src, dO, lse, D, mask,
+                       sc, dst, Tq, Tk);
+    hipLaunchKernelGGL(b2h_lt_sdpa_bwd_kv, dim3(heads, lt_blocks(Tk, kLtKb)), dim3(256), kLtBwdKvLds, st, src, dO, lse, D,
+                       mask, sc, dst, Tq, Tk);
+}
 
 } // namespace
 
@@ -1762,7 +1794,7 @@ extern "C" {
 
 size_t b2h_tpt_train_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int which) {
     if (!m || B < 1 || S < 1 || T < 1 || (which != 0 && which != 1)) return 0;
-    return which == 0 ? tpt_saved_bytes(m, B * S, B * T) : tpt_scratch_bytes(B * S, B * T);
+    return which == 0 ? tpt_saved_bytes(m, B * S, B * T, tpt_long(T)) : tpt_scratch_bytes(B * S, B * T, tpt_long(T));
 }
 
 int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t* tokens, const float* x,
@@ -1775,7 +1807,8 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     if (misaligned(x, 16) || misaligned(y, 16) || misaligned(saved, 16))
         return fail(B2H_ERR_INVALID, "x, y and the saved buffer must be 16-byte aligned");
     const int64_t Ns = B * S, Nt = B * T;
-    const size_t need = tpt_saved_bytes(m, Ns, Nt);
+    const bool lng = tpt_long(T);
+    const size_t need = tpt_saved_bytes(m, Ns, Nt, lng);
     if (saved_bytes < need)
         return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes (" + std::to_string(need) + " B)");
     if (int rc = check_overlap({{y, (size_t)Nt * m->nout * 4}, {saved, need}},
@@ -1810,15 +1843,22 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
         const int mi = 4 * m->n_enc + 6 * l;
         const TptDecLayer L = sv.dec_layer(l);
         tt_linear(st, H, w[0], w[1], L.QKV, Nt, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
-        hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, false), st, L.QKV, mk(mi), sc, L.O,
-                           (int)T);
+        float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
+        if (lng)
+            lt_sdpa(st, tpt_ssrc(L), mk(mi), sc, L.O, lse, B, (int)T, (int)T);
+        else
+            hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, false), st, L.QKV, mk(mi), sc,
+                               L.O, (int)T);
         tt_linear(st, L.O, w[2], w[3], L.R1, Nt, kTtD, kTtD, 0, mk(mi + 1), sc, H);
         tt_layernorm(st, L.R1, w[12], w[13], L.H1, L.ST12, Nt);
         // multihead_attn: the query of H1 (in_proj rows 0..127), [K | V] of the memory (rows 128..383)
         tt_linear(st, L.H1, w[4], w[5], L.QC, Nt, kTtD, kTtD, 0, nullptr, 1.f, nullptr);
         tt_linear(st, sv.MEM, w[4] + kDD, w[5] + kTtD, L.KV, Ns, kTtD, 2 * kTtD, 0, nullptr, 1.f, nullptr);
-        hipLaunchKernelGGL(b2h_tptt_xsdpa, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, false), st,
-                           tpt_xsrc(L), mk(mi + 2), sc, L.OC, (int)T, (int)S);
+        if (lng)
+            lt_sdpa(st, tpt_xsrc(L), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S);
+        else
+            hipLaunchKernelGGL(b2h_tptt_xsdpa, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, false), st,
+                               tpt_xsrc(L), mk(mi + 2), sc, L.OC, (int)T, (int)S);
         tt_linear(st, L.OC, w[6], w[7], L.R2, Nt, kTtD, kTtD, 0, mk(mi + 3), sc, L.H1);
         tt_layernorm(st, L.R2, w[14], w[15], L.H2, L.ST12 + 2, Nt);
         tt_linear(st, L.H2, w[8], w[9], L.F1, Nt, kTtD, kTtD, 1, mk(mi + 4), sc, nullptr);
@@ -1844,7 +1884,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     if (misaligned(dy, 16) || misaligned(saved, 16) || misaligned(scratch, 16) || (dx && misaligned(dx, 16)))
         return fail(B2H_ERR_INVALID, "dy, dx, the saved buffer and the scratch must be 16-byte aligned");
     const int64_t Ns = B * S, Nt = B * T;
-    const size_t need_saved = tpt_saved_bytes(m, Ns, Nt), need = tpt_scratch_bytes(Ns, Nt);
+    const bool lng = tpt_long(T);
+    const size_t need_saved = tpt_saved_bytes(m, Ns, Nt, lng), need = tpt_scratch_bytes(Ns, Nt, lng);
     if (saved_bytes < need_saved) return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes");
     if (scratch_bytes < need)
         return fail(B2H_ERR_INVALID, "scratch smaller than b2h_tpt_train_bytes (" + std::to_string(need) + " B)");
@@ -1871,6 +1912,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     float* dM[2] = {dKV + Ns * 2 * kTtD, dKV + Ns * 3 * kTtD};
     TtGrad G = tt_grad(scr, Nt); // the frame rows first; the slabs lie behind both row sets
     G.slabs = dM[1] + Ns * kTtD;
+    float* Drow = G.slabs + (int64_t)tt_nslabs(Nmax) * kTtSlab; // long T only
     const unsigned heads = (unsigned)(B * kTtHeads);
     const int od = 12 * m->n_enc + 2, ot = od + 18 * m->n_dec + 2; // the first decoder layer; token_embedding
 
@@ -1898,8 +1940,13 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         const float* dC = masks ? G.gBm : G.gB;
         tt_linear_dw(st, dC, L.OC, G.slabs, Nt, kTtD, kTtD, g[6], g[7]);
         tt_linear_dx(st, dC, w[6], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dOC
-        hipLaunchKernelGGL(b2h_tptt_xsdpa_bwd, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, true), st,
-                           tpt_xsrc(L), G.gC, mk(mi + 2), sc, G.gA, dKV, (int)T, (int)S);            // gA = dQC
+        const float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
+        if (lng)
+            lt_sdpa_bwd(st, tpt_xsrc(L), G.gC, lse + Nt * kTtHeads, Drow, mk(mi + 2), sc,
+                        LtGradDst{G.gA, kTtD, 0, dKV, 2 * kTtD, 0, kTtD}, B, (int)T, (int)S);
+        else
+            hipLaunchKernelGGL(b2h_tptt_xsdpa_bwd, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, true), st,
+                               tpt_xsrc(L), G.gC, mk(mi + 2), sc, G.gA, dKV, (int)T, (int)S);        // gA = dQC
         // multihead_attn.in_proj: rows 0..127 from (dQC, H1) over the frames, rows 128..383 from ([dK | dV], MEM)
         // over the tokens, each with the slab count of its own row set
         tt_linear_dw(st, G.gA, L.H1, G.slabs, Nt, kTtD, kTtD, g[4], g[5]);
@@ -1913,8 +1960,12 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         const float* dA = masks ? G.gBm : G.gB;
         tt_linear_dw(st, dA, L.O, G.slabs, Nt, kTtD, kTtD, g[2], g[3]);
         tt_linear_dx(st, dA, w[2], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dO
-        hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, true), st, L.QKV, G.gC, mk(mi),
-                           sc, G.gQ, (int)T);
+        if (lng)
+            lt_sdpa_bwd(st, tpt_ssrc(L), G.gC, lse, Drow, mk(mi), sc,
+                        LtGradDst{G.gQ, 3 * kTtD, 0, G.gQ, 3 * kTtD, kTtD, 2 * kTtD}, B, (int)T, (int)T);
+        else
+            hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, true), st, L.QKV, G.gC,
+                               mk(mi), sc, G.gQ, (int)T);
         tt_linear_dw(st, G.gQ, Hin, G.slabs, Nt, kTtD, 3 * kTtD, g[0], g[1]);
         tt_linear_dx(st, G.gQ, w[0], G.gA, Nt, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);         // gA = dH_in
     }

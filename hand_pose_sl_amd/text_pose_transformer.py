@@ -16,14 +16,16 @@ like any other id) and never applies its two positional encodings, which exist o
 Training: in training mode with autograd enabled and a parameter or `input_pose` requiring a gradient,
 `model(input_tokens, input_pose)` runs `_TptTrainFn` -- an exact-fp32 HIP forward and backward
 (b2h_tpt_train_forward / b2h_tpt_backward, kernel_tpt_train.h) that read the parameters' own storage -- so the
-reference's loop body (steps/traintest.py:105-121) runs unchanged with any torch optimizer.  The dropout keep-masks
+reference's loop body (steps/traintest.py:105-121) runs unchanged with any torch optimizer, at S <= 128 tokens and
+T <= 1024 frames (the trainer pads to `--max-frames 200`, run.py:28; beyond 128 frames the decoder's two attentions
+run blocked, kernel_train_attn_long.h).  The dropout keep-masks
 are drawn by torch on the model's device (`_draw_dropout_masks`; they follow torch.manual_seed) and handed to the
 kernels.  Every other call (eval mode or no_grad) runs the inference kernels.
 
 Inference is exact fp32 by default; `model.set_precision("f16x3")` selects the f16 hi + lo split path (three
 v_mfma_f32_16x16x32_f16 per product, Q, K, V projected inside the attention kernels), valid while every weight and
-activation is below 65504 in magnitude.  S <= 128; `model(tokens, pose)` takes T <= 128, `forward_fused` T <= 1024
-(the reference's CLIs default to 200 frames) together with the item transforms.  No path ever falls back to PyTorch ops.
+activation is below 65504 in magnitude.  S <= 128; in inference `model(tokens, pose)` takes T <= 128, `forward_fused`
+and `forward_long` T <= 1024 (the reference's CLIs default to 200 frames), the former with the item transforms.  No path ever falls back to PyTorch ops.
 """
 import ctypes
 import warnings
@@ -42,7 +44,8 @@ class TextPoseTransformer(NativeModule, nn.Module):
     (fp32-grade results, the same 2e-5 parity bar; needs |weights| and |activations| < 65504, else the forward
     raises) and `set_precision("fp32")` switches back; no reload of the weights.  The constructor itself keeps
     refusing "f16x3" because tests/test_tpt_cpu.py::test_python_side_errors pins that refusal; a later change that
-    may touch that test lifts it.  Training is exact fp32 whatever the precision."""
+    may touch that test lifts it.  Training is exact fp32 whatever the precision, and takes T <= 1024 frames; the
+    inference route of `model(tokens, pose)` stops at 128 (`forward_long` / `forward_fused` go to 1024)."""
 
     def __init__(self, n_tokens, n_joints, joints_dim, nhead, nhid, nout, n_enc_layers, n_dec_layers, dropout=0.5, *,
                  precision="fp32"):
@@ -274,7 +277,8 @@ class TextPoseTransformer(NativeModule, nn.Module):
 
 class _TptTrainFn(torch.autograd.Function):
     """y = TextPoseTransformer(tokens, x) in training mode with its gradient: b2h_tpt_train_forward /
-    b2h_tpt_backward (exact fp32, kernel_tpt_train.h), after transformer_enc._TencTrainFn.  The parameters go in
+    b2h_tpt_backward (exact fp32, kernel_tpt_train.h; kernel_train_attn_long.h for the decoder's attentions at
+    128 < T <= 1024), after transformer_enc._TencTrainFn.  The parameters go in
     as themselves (their own data_ptr, saved for backward, so autograd's version check catches an in-place edit
     between forward and backward).  The context keeps the saved-activation buffer, the token ids and the masks
     alive; the backward needs neither x nor y (the reference's loop overwrites the prediction's tail in place

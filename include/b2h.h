@@ -430,7 +430,12 @@ int b2h_tpt_build_item(const float* body, const float* right_hand, float* item, 
  *             per decoder layer: self_attn (B, 4, T, T), drop1 (B, T, 128), cross_attn (B, 4, T, S),
  *               drop2, ff, drop3 (B, T, 128 each).
  *           There is no embedding or positional mask: the reference never applies its positional encoders.
- * 1 <= S, T <= 128.  Stream-ordered and asynchronous: none synchronises, allocates or reads device memory on the
+ * 1 <= S <= 128 and 1 <= T <= B2H_TPT_MAX_FRAMES (B2H_ERR_SHAPE; the reference's trainer pads every item to
+ * --max-frames 200, run.py:28).  For T <= 128 each decoder attention is one workgroup per (sequence, head) with the
+ * whole score matrix in LDS; for T > 128 the decoder's two attentions and their backwards walk the keys and the
+ * queries in blocks (kernel_train_attn_long.h: an online softmax that saves each row's log-sum-exp, a key-owner and
+ * a query-owner backward kernel that recompute the probabilities from it), and everything else is the same launch
+ * list.  Stream-ordered and asynchronous: none synchronises, allocates or reads device memory on the
  * host, so they can be captured into a HIP graph.  x, y, dy, dx, the saved buffer and the scratch must be
  * 16-byte aligned and no output may overlap another operand (B2H_ERR_INVALID). */
 
@@ -440,6 +445,8 @@ int b2h_tpt_build_item(const float* body, const float* right_hand, float* item, 
  *     (ceil4: rounded up to a multiple of 4; 1136 per frame for the default ninp = 24)
  *   which = 1, the scratch of b2h_tpt_backward, with N = max(B*S, B*T):
  *     N * 3584 + B*S * 2048 + clamp(ceil(N / 128), 1, 64) * 198144
+ *   for T > 128 in addition: which = 0, B*T * 32*n_dec_layers (the log-sum-exp of every (frame, head) of both
+ *     decoder attentions); which = 1, B*T * 32 (the backward's two row terms per (frame, head)).
  * 0 for a NULL model, B < 1, S < 1, T < 1 or another `which`. */
 size_t b2h_tpt_train_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int which);
 /* y = TextPoseTransformer(tokens, x) in .train() mode with the given dropout masks (HandPoseModels.py:201-222):

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""GPU box: one training step of TextPoseTransformer (kernel_tpt_train.h, kernel_tenc_train.h), one JSON line.
+"""GPU box: one training step of TextPoseTransformer (kernel_tpt_train.h, kernel_tenc_train.h, and
+kernel_train_attn_long.h beyond 128 frames), one JSON line.
 Context only: the training kernels are plain per-operation fp32 kernels and carry no speed bar.
-  * one full step of the reference loop body (steps/traintest.py:105-121) at B x S x T = 128 x 40 x 100, 4 + 4
-    layers, n_tokens = 1000, dropout 0.1: forward (masks drawn by torch), mask_output, maskedPoseL1, backward,
-    torch.optim.Adam (lr 2e-4), steady state, HIP events;
+  * one full step of the reference loop body (steps/traintest.py:105-121), 4 + 4 layers, n_tokens = 1000,
+    dropout 0.1: forward (masks drawn by torch), mask_output, maskedPoseL1, backward, torch.optim.Adam (lr 2e-4),
+    steady state, HIP events, the median (and the minimum) of `reps` repetitions of ten steps;
   * the same step with torch-ROCm's own nn.Transformer (the reference's model restated with torch modules) on
     the same GPU.
-    python tools/bench_train_tpt.py [B=128] [S=40] [T=100]"""
+The two shapes of the record (DESIGN.md sections 13 and 16):
+    python tools/bench_train_tpt.py                  B x S x T = 128 x 40 x 100, 12 joints (the datasets' 100 frames)
+    python tools/bench_train_tpt.py 128 40 200 8     the trainer's default batch: --max-frames 200, geometry (8, 42)
+    python tools/bench_train_tpt.py [B=128] [S=40] [T=100] [n_joints=12] [reps=5]"""
 import json
 import os
 import sys
@@ -22,6 +26,8 @@ import hand_pose_sl_amd as hps  # noqa: E402
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 100
+J = int(sys.argv[4]) if len(sys.argv) > 4 else 12
+REPS = int(sys.argv[5]) if len(sys.argv) > 5 else 5
 N_TOKENS, L, P, LR = 1000, 4, 0.1, 2e-4
 dev = torch.device("cuda:0")
 
@@ -30,17 +36,17 @@ def events_ms(fn, iters, warm=5):
     for _ in range(warm):
         fn()
     torch.cuda.synchronize()
-    best = None
-    for _ in range(3):
+    ms = []
+    for _ in range(REPS):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(iters):
             fn()
         e1.record()
         e1.synchronize()
-        ms = e0.elapsed_time(e1) / iters
-        best = ms if best is None else min(best, ms)
-    return best
+        ms.append(e0.elapsed_time(e1) / iters)
+    ms.sort()
+    return ms[len(ms) // 2], ms[0]
 
 
 class TorchTpt(nn.Module):
@@ -53,22 +59,22 @@ class TorchTpt(nn.Module):
             self.tr = nn.Transformer(128, 4, L, L, 128, dropout=P)
         self.emb = nn.Embedding(N_TOKENS, 128)
         self.h2p = nn.Linear(128, 42)
-        self.p2h = nn.Linear(24, 128)
+        self.p2h = nn.Linear(2 * J, 128)
 
     def forward(self, tok, pose):
         b, t = pose.shape[0], pose.shape[1]
-        tgt = self.p2h(pose.view(b, t, 24).permute(1, 0, 2))
+        tgt = self.p2h(pose.view(b, t, 2 * J).permute(1, 0, 2))
         return self.h2p(self.tr(self.emb(tok).permute(1, 0, 2), tgt)).permute(1, 0, 2).reshape(b, t, 21, 2)
 
 
 torch.manual_seed(0)
 with warnings.catch_warnings():
     warnings.simplefilter("ignore", UserWarning)
-    m = hps.TextPoseTransformer(N_TOKENS, 12, 2, 4, 128, 42, L, L, dropout=P).to(dev).train()
+    m = hps.TextPoseTransformer(N_TOKENS, J, 2, 4, 128, 42, L, L, dropout=P).to(dev).train()
 g = torch.Generator(device=dev).manual_seed(1)
 lengths = [T - (i * 37) % (T // 2 + 1) for i in range(B)]
 toks = torch.randint(0, N_TOKENS, (B, S), device=dev, generator=g)
-xs = torch.rand((B, T, 12, 2), device=dev, generator=g) - 0.5
+xs = torch.rand((B, T, J, 2), device=dev, generator=g) - 0.5
 ts = (torch.rand((B, T, 21, 2), device=dev, generator=g) - 0.5) * 0.2
 crit = hps.maskedPoseL1()
 
@@ -87,8 +93,9 @@ def make_step(forward, params):
     return step
 
 
-out = {"B": B, "S": S, "T": T, "n_enc": L, "n_dec": L, "n_tokens": N_TOKENS, "dropout": P}
-out["reference_step_ms"] = events_ms(make_step(m, list(m.parameters())), 10)
+out = {"B": B, "S": S, "T": T, "n_joints": J, "n_enc": L, "n_dec": L, "n_tokens": N_TOKENS, "dropout": P, "reps": REPS}
+out["reference_step_ms"], out["reference_step_ms_min"] = events_ms(make_step(m, list(m.parameters())), 10)
 tm = TorchTpt().to(dev).train()
-out["torch_rocm_nn_transformer_step_ms_context_only"] = events_ms(make_step(tm, list(tm.parameters())), 10)
+out["torch_rocm_nn_transformer_step_ms_context_only"], out["torch_rocm_nn_transformer_step_ms_min"] = events_ms(
+    make_step(tm, list(tm.parameters())), 10)
 print(json.dumps(out))
