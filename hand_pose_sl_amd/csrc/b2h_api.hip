@@ -25,6 +25,7 @@
 #include "kernel_tpt.h"
 #include "kernel_attn_long.h"
 #include "kernel_train_attn_long.h"
+#include "kernel_train_attn_mfma.h"
 #include "kernel_tpt_train.h"
 #include "kernel_train.h"
 #include "kernel_valu.h"
@@ -794,6 +795,9 @@ int set_tenc_kernel_attributes() {
         if ((rc = raise_lds_cap(b2h_lt_sdpa, (int)kLtFwdLds)) || (rc = raise_lds_cap(b2h_lt_sdpa_bwd_kv, (int)kLtBwdKvLds)) ||
             (rc = raise_lds_cap(b2h_lt_sdpa_bwd_q, (int)kLtBwdQLds)))
             return rc;
+        if ((rc = raise_lds_cap(b2h_mt_sdpa, (int)kMtFwdLds)) || (rc = raise_lds_cap(b2h_mt_sdpa_bwd_kv, (int)kMtBwdKvLds)) ||
+            (rc = raise_lds_cap(b2h_mt_sdpa_bwd_q, (int)kMtBwdQLds)))
+            return rc;
         return B2H_OK;
     });
 }
@@ -999,6 +1003,7 @@ struct b2h_tpt {
     int ninp = kInCh, nout = kOutCh; // n_joints*joints_dim in {16, 24, 42, 58}, head width in {8, 24, 42}
     bool has_weights = false;
     int kernel = B2H_TENC_F32;
+    int train_kernel = B2H_TRAIN_VALU; // b2h_tpt_set_train_kernel
     float w_absmax = 0.f; // largest |parameter|, the embedding table included (NaN counts as inf): B2H_TENC_F16X3 needs < 65504
     DevBuf table;               // token_embedding.weight (n_tokens, 128)
     DevBuf enc_norm, dec_norm;  // encoder.norm / decoder.norm: gamma (128), beta (128)
@@ -1127,6 +1132,13 @@ int b2h_tpt_set_kernel(b2h_tpt* m, int kernel) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
     if (kernel != B2H_TENC_F32 && kernel != B2H_TENC_F16X3) return fail(B2H_ERR_INVALID, "unknown TextPoseTransformer kernel");
     m->kernel = kernel;
+    return B2H_OK;
+}
+
+int b2h_tpt_set_train_kernel(b2h_tpt* m, int kernel) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (kernel != B2H_TRAIN_VALU && kernel != B2H_TRAIN_MFMA) return fail(B2H_ERR_INVALID, "unknown TextPoseTransformer train kernel");
+    m->train_kernel = kernel;
     return B2H_OK;
 }
 
@@ -1770,27 +1782,52 @@ XsdpaSrc tpt_xsrc(const TptDecLayer& L) { return XsdpaSrc{L.QC, kTtD, 0, L.KV, 2
 // The self-attention operands as the long kernels take them: [Q | K | V] rows (Nt, 384).
 XsdpaSrc tpt_ssrc(const TptDecLayer& L) { return XsdpaSrc{L.QKV, 3 * kTtD, 0, L.QKV, 3 * kTtD, kTtD, 2 * kTtD}; }
 
-// Attention of B sequences of Tq > 128 query rows over Tk key rows in training (kernel_train_attn_long.h):
-// O (B*Tq, 128) and the rows' log-sum-exp (B, 4, Tq).
-void lt_sdpa(hipStream_t st, const XsdpaSrc& src, const uint8_t* mask, float sc, float* O, float* lse, int64_t B, int Tq,
-             int Tk) {
-    hipLaunchKernelGGL(b2h_lt_sdpa, dim3((unsigned)(B * kTtHeads), lt_blocks(Tq, kLtQb)), dim3(256), kLtFwdLds, st, src,
-                       mask, sc, O, lse, Tq, Tk);
+// Which kernels run the decoder's two attentions in training: the whole-matrix kernels up to 128 frames, beyond them
+// the blocked ones, on the vector ALU (kernel_train_attn_long.h) or on the matrix cores (kernel_train_attn_mfma.h) as
+// b2h_tpt_set_train_kernel chose.  The one place that decides: the dispatch and b2h_tpt_train_attn_name both ask it.
+enum class TrainAttn { kWhole, kBlockedValu, kBlockedMfma };
+TrainAttn tpt_train_attn(const b2h_tpt* m, int64_t T) {
+    if (!tpt_long(T)) return TrainAttn::kWhole;
+    return m->train_kernel == B2H_TRAIN_MFMA ? TrainAttn::kBlockedMfma : TrainAttn::kBlockedValu;
+}
+
+// Attention of B sequences of Tq > 128 query rows over Tk key rows in training (kernel_train_attn_long.h, or
+// kernel_train_attn_mfma.h with mfma): O (B*Tq, 128) and the rows' log-sum-exp (B, 4, Tq).
+void lt_sdpa(hipStream_t st, bool mfma, const XsdpaSrc& src, const uint8_t* mask, float sc, float* O, float* lse, int64_t B,
+             int Tq, int Tk) {
+    const dim3 grid((unsigned)(B * kTtHeads), lt_blocks(Tq, kLtQb));
+    if (mfma)
+        hipLaunchKernelGGL(b2h_mt_sdpa, grid, dim3(256), kMtFwdLds, st, src, mask, sc, O, lse, Tq, Tk);
+    else
+        hipLaunchKernelGGL(b2h_lt_sdpa, grid, dim3(256), kLtFwdLds, st, src, mask, sc, O, lse, Tq, Tk);
 }
 
 // Its backward: the query owner (dQ, and the row terms D for the key owner), then the key owner ([dK | dV]).
-void lt_sdpa_bwd(hipStream_t st, const XsdpaSrc& src, const float* dO, const float* lse, float* D, const uint8_t* mask,
-                 float sc, const LtGradDst& dst, int64_t B, int Tq, int Tk) {
+void lt_sdpa_bwd(hipStream_t st, bool mfma, const XsdpaSrc& src, const float* dO, const float* lse, float* D,
+                 const uint8_t* mask, float sc, const LtGradDst& dst, int64_t B, int Tq, int Tk) {
     const unsigned heads = (unsigned)(B * kTtHeads);
-    hipLaunchKernelGGL(b2h_lt_sdpa_bwd_q, dim3(heads, lt_blocks(Tq, kLtQb)), dim3(256), kLtBwdQLds, st, src, dO, lse, D, mask,
-                       sc, dst, Tq, Tk);
-    hipLaunchKernelGGL(b2h_lt_sdpa_bwd_kv, dim3(heads, lt_blocks(Tk, kLtKb)), dim3(256), kLtBwdKvLds, st, src, dO, lse, D,
-                       mask, sc, dst, Tq, Tk);
+    const dim3 gq(heads, lt_blocks(Tq, kLtQb)), gkv(heads, lt_blocks(Tk, kLtKb));
+    if (mfma) {
+        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_q, gq, dim3(256), kMtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_kv, gkv, dim3(256), kMtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+    } else {
+        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_q, gq, dim3(256), kLtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_kv, gkv, dim3(256), kLtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+    }
 }
 
 } // namespace
 
 extern "C" {
+
+const char* b2h_tpt_train_attn_name(const b2h_tpt* m, int64_t T) {
+    if (!m || T < 1) return nullptr;
+    switch (tpt_train_attn(m, T)) {
+    case TrainAttn::kWhole: return "b2h_tt_sdpa";
+    case TrainAttn::kBlockedValu: return "b2h_lt_sdpa";
+    default: return "b2h_mt_sdpa";
+    }
+}
 
 size_t b2h_tpt_train_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int which) {
     if (!m || B < 1 || S < 1 || T < 1 || (which != 0 && which != 1)) return 0;
@@ -1807,7 +1844,7 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     if (misaligned(x, 16) || misaligned(y, 16) || misaligned(saved, 16))
         return fail(B2H_ERR_INVALID, "x, y and the saved buffer must be 16-byte aligned");
     const int64_t Ns = B * S, Nt = B * T;
-    const bool lng = tpt_long(T);
+    const bool lng = tpt_long(T), mfma = tpt_train_attn(m, T) == TrainAttn::kBlockedMfma;
     const size_t need = tpt_saved_bytes(m, Ns, Nt, lng);
     if (saved_bytes < need)
         return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes (" + std::to_string(need) + " B)");
@@ -1845,7 +1882,7 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
         tt_linear(st, H, w[0], w[1], L.QKV, Nt, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
         float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
         if (lng)
-            lt_sdpa(st, tpt_ssrc(L), mk(mi), sc, L.O, lse, B, (int)T, (int)T);
+            lt_sdpa(st, mfma, tpt_ssrc(L), mk(mi), sc, L.O, lse, B, (int)T, (int)T);
         else
             hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, false), st, L.QKV, mk(mi), sc,
                                L.O, (int)T);
@@ -1855,7 +1892,7 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
         tt_linear(st, L.H1, w[4], w[5], L.QC, Nt, kTtD, kTtD, 0, nullptr, 1.f, nullptr);
         tt_linear(st, sv.MEM, w[4] + kDD, w[5] + kTtD, L.KV, Ns, kTtD, 2 * kTtD, 0, nullptr, 1.f, nullptr);
         if (lng)
-            lt_sdpa(st, tpt_xsrc(L), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S);
+            lt_sdpa(st, mfma, tpt_xsrc(L), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S);
         else
             hipLaunchKernelGGL(b2h_tptt_xsdpa, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, false), st,
                                tpt_xsrc(L), mk(mi + 2), sc, L.OC, (int)T, (int)S);
@@ -1884,7 +1921,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     if (misaligned(dy, 16) || misaligned(saved, 16) || misaligned(scratch, 16) || (dx && misaligned(dx, 16)))
         return fail(B2H_ERR_INVALID, "dy, dx, the saved buffer and the scratch must be 16-byte aligned");
     const int64_t Ns = B * S, Nt = B * T;
-    const bool lng = tpt_long(T);
+    const bool lng = tpt_long(T), mfma = tpt_train_attn(m, T) == TrainAttn::kBlockedMfma;
     const size_t need_saved = tpt_saved_bytes(m, Ns, Nt, lng), need = tpt_scratch_bytes(Ns, Nt, lng);
     if (saved_bytes < need_saved) return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes");
     if (scratch_bytes < need)
@@ -1942,7 +1979,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         tt_linear_dx(st, dC, w[6], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dOC
         const float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
         if (lng)
-            lt_sdpa_bwd(st, tpt_xsrc(L), G.gC, lse + Nt * kTtHeads, Drow, mk(mi + 2), sc,
+            lt_sdpa_bwd(st, mfma, tpt_xsrc(L), G.gC, lse + Nt * kTtHeads, Drow, mk(mi + 2), sc,
                         LtGradDst{G.gA, kTtD, 0, dKV, 2 * kTtD, 0, kTtD}, B, (int)T, (int)S);
         else
             hipLaunchKernelGGL(b2h_tptt_xsdpa_bwd, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, true), st,
@@ -1961,7 +1998,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         tt_linear_dw(st, dA, L.O, G.slabs, Nt, kTtD, kTtD, g[2], g[3]);
         tt_linear_dx(st, dA, w[2], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dO
         if (lng)
-            lt_sdpa_bwd(st, tpt_ssrc(L), G.gC, lse, Drow, mk(mi), sc,
+            lt_sdpa_bwd(st, mfma, tpt_ssrc(L), G.gC, lse, Drow, mk(mi), sc,
                         LtGradDst{G.gQ, 3 * kTtD, 0, G.gQ, 3 * kTtD, kTtD, 2 * kTtD}, B, (int)T, (int)T);
         else
             hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, true), st, L.QKV, G.gC,

@@ -18,7 +18,8 @@ Training: in training mode with autograd enabled and a parameter or `input_pose`
 (b2h_tpt_train_forward / b2h_tpt_backward, kernel_tpt_train.h) that read the parameters' own storage -- so the
 reference's loop body (steps/traintest.py:105-121) runs unchanged with any torch optimizer, at S <= 128 tokens and
 T <= 1024 frames (the trainer pads to `--max-frames 200`, run.py:28; beyond 128 frames the decoder's two attentions
-run blocked, kernel_train_attn_long.h).  The dropout keep-masks
+run blocked, kernel_train_attn_long.h, or after `model.set_train_kernels("mfma")` on the matrix cores in exact fp32,
+kernel_train_attn_mfma.h).  The dropout keep-masks
 are drawn by torch on the model's device (`_draw_dropout_masks`; they follow torch.manual_seed) and handed to the
 kernels.  Every other call (eval mode or no_grad) runs the inference kernels.
 
@@ -44,7 +45,9 @@ class TextPoseTransformer(NativeModule, nn.Module):
     (fp32-grade results, the same 2e-5 parity bar; needs |weights| and |activations| < 65504, else the forward
     raises) and `set_precision("fp32")` switches back; no reload of the weights.  The constructor itself keeps
     refusing "f16x3" because tests/test_tpt_cpu.py::test_python_side_errors pins that refusal; a later change that
-    may touch that test lifts it.  Training is exact fp32 whatever the precision, and takes T <= 1024 frames; the
+    may touch that test lifts it.  Training is exact fp32 whatever the precision, and takes T <= 1024 frames;
+    `set_train_kernels("mfma")` (attribute `train_kernels`, default "valu") moves the decoder's attentions beyond 128
+    frames to fp32 MFMA kernels.  The
     inference route of `model(tokens, pose)` stops at 128 (`forward_long` / `forward_fused` go to 1024)."""
 
     def __init__(self, n_tokens, n_joints, joints_dim, nhead, nhid, nout, n_enc_layers, n_dec_layers, dropout=0.5, *,
@@ -53,6 +56,7 @@ class TextPoseTransformer(NativeModule, nn.Module):
         if precision != "fp32":
             raise ValueError(f"precision must be 'fp32', got {precision!r}")
         self.precision = precision
+        self.train_kernels = "valu"
         self.model_type = "Transformer"
         self.src_mask = None
         self.token_pos_encoder = PositionalEncoding(nhid, dropout, max_len=40)
@@ -76,6 +80,17 @@ class TextPoseTransformer(NativeModule, nn.Module):
         if name not in TENC_KERNELS:
             raise ValueError(f"precision must be one of {sorted(TENC_KERNELS)}, got {name!r}")
         self.precision = name
+        return self
+
+    def set_train_kernels(self, name):
+        """Select the kernels of later training forwards, "valu" (the default) or "mfma"; returns self.  "mfma" runs
+        the decoder's two attentions beyond 128 frames, forward and backward, on v_mfma_f32_16x16x4_f32
+        (kernel_train_attn_mfma.h): exact fp32 like the default and as deterministic, in another summation order.  Up
+        to 128 frames and in the encoder it changes nothing.  A backward runs the route its forward ran, whatever the
+        model says by then.  Measurements: DESIGN.md section 17."""
+        if name not in _lib.TRAIN_KERNELS:
+            raise ValueError(f"train kernels must be one of {sorted(_lib.TRAIN_KERNELS)}, got {name!r}")
+        self.train_kernels = name
         return self
 
     _NAME, _CREATE, _LOAD, _DESTROY = "TextPoseTransformer", "b2h_tpt_create", "b2h_tpt_load_weights", "b2h_tpt_destroy"
@@ -278,7 +293,9 @@ class TextPoseTransformer(NativeModule, nn.Module):
 class _TptTrainFn(torch.autograd.Function):
     """y = TextPoseTransformer(tokens, x) in training mode with its gradient: b2h_tpt_train_forward /
     b2h_tpt_backward (exact fp32, kernel_tpt_train.h; kernel_train_attn_long.h for the decoder's attentions at
-    128 < T <= 1024), after transformer_enc._TencTrainFn.  The parameters go in
+    128 < T <= 1024, or kernel_train_attn_mfma.h when the model's `train_kernels` is "mfma": the forward sets the
+    handle's train kernel from the model and records it, the backward sets it from that record), after
+    transformer_enc._TencTrainFn.  The parameters go in
     as themselves (their own data_ptr, saved for backward, so autograd's version check catches an in-place edit
     between forward and backward).  The context keeps the saved-activation buffer, the token ids and the masks
     alive; the backward needs neither x nor y (the reference's loop overwrites the prediction's tail in place
@@ -296,13 +313,15 @@ class _TptTrainFn(torch.autograd.Function):
         y = torch.empty((B, T, model.nout // 2, 2), dtype=torch.float32, device=x.device)
         nbytes = lib.b2h_tpt_train_bytes(model._handle, B, S, T, 0)
         saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
+        kernels = model.train_kernels
         with _lib.on_device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.b2h_tpt_set_train_kernel(model._handle, _lib.TRAIN_KERNELS[kernels]))
             _lib.check(lib.b2h_tpt_train_forward(model._handle, _ptrs(params), ctypes.c_void_p(tok.data_ptr()),
                                                  ctypes.c_void_p(x.data_ptr()), _ptrs(masks) if masks else None, p,
                                                  ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(saved.data_ptr()), nbytes,
                                                  B, S, T, ctypes.c_void_p(st)))
-        ctx.model, ctx.p, ctx.masks, ctx.shape = model, p, masks, (B, S, T)
+        ctx.model, ctx.p, ctx.masks, ctx.shape, ctx.kernels = model, p, masks, (B, S, T), kernels
         ctx.save_for_backward(saved, tok, *params)
         return y
 
@@ -327,6 +346,7 @@ class _TptTrainFn(torch.autograd.Function):
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             with _lib.on_device(dev):
                 st = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(lib.b2h_tpt_set_train_kernel(model._handle, _lib.TRAIN_KERNELS[ctx.kernels]))
                 _lib.check(lib.b2h_tpt_backward(model._handle, _ptrs(params), ctypes.c_void_p(tok.data_ptr()),
                                                 _ptrs(masks) if masks else None, ctx.p, ctypes.c_void_p(dy.data_ptr()),
                                                 ctypes.c_void_p(saved.data_ptr()), saved.numel(),

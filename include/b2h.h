@@ -471,6 +471,22 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
                      float p, const float* dy, const void* saved, size_t saved_bytes, float* dx,
                      float* const* grads, void* scratch, size_t scratch_bytes, int64_t B, int64_t S, int64_t T,
                      void* stream);
+/* Which kernels the training calls use where there is a choice (not `attention`: further kernels will hang off the
+ * same switch).  Today the choice covers the decoder's two attentions at T > 128:
+ *   B2H_TRAIN_VALU  the default of every new model: kernel_train_attn_long.h, fp32 FMAs on the vector ALU
+ *   B2H_TRAIN_MFMA  kernel_train_attn_mfma.h: the same grids, operands, saved layouts and mathematics with all six
+ *                   products on v_mfma_f32_16x16x4_f32 (exact fp32, a k-ordered fmaf chain); deterministic like
+ *                   the default, but in its own summation order, so not bitwise equal to it
+ * At T <= 128, for the encoder at every T and for b2h_tpt_train_bytes the switch has no effect.  The routes share
+ * every layout, so either backward accepts either forward's saved buffer (hand_pose_sl_amd's autograd Function runs
+ * a backward under the setting of its own forward, for reproducible bits).  Both routes' LDS caps are
+ * raised at b2h_tpt_create, so switching between captures is safe.  B2H_ERR_INVALID: NULL model, other value. */
+typedef enum b2h_train_kernel { B2H_TRAIN_VALU = 0, B2H_TRAIN_MFMA = 1 } b2h_train_kernel;
+int b2h_tpt_set_train_kernel(b2h_tpt* m, int kernel);
+/* Unmangled name of the decoder's self-attention forward kernel that b2h_tpt_train_forward would launch at T frames
+ * under the current setting: "b2h_tt_sdpa" (T <= 128), "b2h_lt_sdpa" or "b2h_mt_sdpa"; static storage, for tests and
+ * for matching rocprofv3 kernel-trace rows.  NULL for a NULL model or T < 1. */
+const char* b2h_tpt_train_attn_name(const b2h_tpt* m, int64_t T);
 
 /* Introspection / measurement -------------------------------------------- */
 
