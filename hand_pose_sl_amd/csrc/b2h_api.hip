@@ -26,6 +26,7 @@
 #include "kernel_attn_long.h"
 #include "kernel_train_attn_long.h"
 #include "kernel_train_attn_mfma.h"
+#include "kernel_train_linear_mfma.h"
 #include "kernel_tpt_train.h"
 #include "kernel_train.h"
 #include "kernel_valu.h"
@@ -798,6 +799,9 @@ int set_tenc_kernel_attributes() {
         if ((rc = raise_lds_cap(b2h_mt_sdpa, (int)kMtFwdLds)) || (rc = raise_lds_cap(b2h_mt_sdpa_bwd_kv, (int)kMtBwdKvLds)) ||
             (rc = raise_lds_cap(b2h_mt_sdpa_bwd_q, (int)kMtBwdQLds)))
             return rc;
+        if ((rc = raise_lds_cap(b2h_ml_linear, (int)kMlFwdLds)) || (rc = raise_lds_cap(b2h_ml_linear_dx, (int)kMlDxLds)) ||
+            (rc = raise_lds_cap(b2h_ml_linear_dw, (int)kMlDwLds)))
+            return rc;
         return B2H_OK;
     });
 }
@@ -1004,6 +1008,7 @@ struct b2h_tpt {
     bool has_weights = false;
     int kernel = B2H_TENC_F32;
     int train_kernel = B2H_TRAIN_VALU; // b2h_tpt_set_train_kernel
+    int train_linear = B2H_TRAIN_VALU; // b2h_tpt_set_train_linear
     float w_absmax = 0.f; // largest |parameter|, the embedding table included (NaN counts as inf): B2H_TENC_F16X3 needs < 65504
     DevBuf table;               // token_embedding.weight (n_tokens, 128)
     DevBuf enc_norm, dec_norm;  // encoder.norm / decoder.norm: gamma (128), beta (128)
@@ -1139,6 +1144,13 @@ int b2h_tpt_set_train_kernel(b2h_tpt* m, int kernel) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
     if (kernel != B2H_TRAIN_VALU && kernel != B2H_TRAIN_MFMA) return fail(B2H_ERR_INVALID, "unknown TextPoseTransformer train kernel");
     m->train_kernel = kernel;
+    return B2H_OK;
+}
+
+int b2h_tpt_set_train_linear(b2h_tpt* m, int kernel) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (kernel != B2H_TRAIN_VALU && kernel != B2H_TRAIN_MFMA) return fail(B2H_ERR_INVALID, "unknown TextPoseTransformer train Linear kernel");
+    m->train_linear = kernel;
     return B2H_OK;
 }
 
@@ -1485,24 +1497,47 @@ std::vector<Span> tt_read_only(const b2h_tenc* m, const float* const* params, co
 
 unsigned tt_row_blocks(int64_t N, int rows) { return (unsigned)((N + rows - 1) / rows); }
 
-void tt_linear(hipStream_t st, const float* X, const float* W, const float* b, float* Y, int64_t N, int K, int M,
+// Where a training call runs and which Linear trio it launches: kernel_tenc_train.h's on the vector ALU, or
+// kernel_train_linear_mfma.h's on the matrix cores (TextPoseTransformer after b2h_tpt_set_train_linear only).
+struct TtLin {
+    hipStream_t st;
+    bool mfma;
+};
+
+void tt_linear(const TtLin& ln, const float* X, const float* W, const float* b, float* Y, int64_t N, int K, int M,
                int relu, const uint8_t* mask, float scale, const float* res) {
+    hipStream_t st = ln.st;
+    if (ln.mfma) {
+        hipLaunchKernelGGL(b2h_ml_linear, dim3(tt_row_blocks(N, kMlRows)), dim3(256), kMlFwdLds, st, X, W, b, Y, N, K, M, relu,
+                           mask, scale, res);
+        return;
+    }
     hipLaunchKernelGGL(b2h_tt_linear, dim3(tt_row_blocks(N, kTtRows)), dim3(128), 0, st, X, W, b, Y, N, K, M, relu, mask,
                        scale, res);
 }
 
-void tt_linear_dx(hipStream_t st, const float* dY, const float* W, float* dX, int64_t N, int K, int M, const float* gate,
+void tt_linear_dx(const TtLin& ln, const float* dY, const float* W, float* dX, int64_t N, int K, int M, const float* gate,
                   const uint8_t* mask, float scale, const float* add) {
+    hipStream_t st = ln.st;
+    if (ln.mfma) {
+        hipLaunchKernelGGL(b2h_ml_linear_dx, dim3(tt_row_blocks(N, kMlRows)), dim3(256), kMlDxLds, st, dY, W, dX, N, K, M, gate,
+                           mask, scale, add);
+        return;
+    }
     hipLaunchKernelGGL(b2h_tt_linear_dx, dim3(tt_row_blocks(N, kTtRows)), dim3(128), 0, st, dY, W, dX, N, K, M, gate,
                        mask, scale, add);
 }
 
 // dW, db of one Linear: slab partials, then the fixed-order sum into the gradient tensors.
-void tt_linear_dw(hipStream_t st, const float* dY, const float* X, float* slabs, int64_t N, int K, int M, float* gW,
+void tt_linear_dw(const TtLin& ln, const float* dY, const float* X, float* slabs, int64_t N, int K, int M, float* gW,
                   float* gb) {
+    hipStream_t st = ln.st;
     const int S = tt_nslabs(N);
-    hipLaunchKernelGGL(b2h_tt_linear_dw, dim3(S, (M + kTtDwM - 1) / kTtDwM), dim3(256), 0, st, dY, X, slabs, kTtSlab, N,
-                       K, M);
+    const dim3 grid(S, (M + kTtDwM - 1) / kTtDwM);
+    if (ln.mfma)
+        hipLaunchKernelGGL(b2h_ml_linear_dw, grid, dim3(256), kMlDwLds, st, dY, X, slabs, kTtSlab, N, K, M);
+    else
+        hipLaunchKernelGGL(b2h_tt_linear_dw, grid, dim3(256), 0, st, dY, X, slabs, kTtSlab, N, K, M);
     hipLaunchKernelGGL(b2h_tt_reduce, dim3((M * K + M + 255) / 256), dim3(256), 0, st, slabs, kTtSlab, S, gW, M * K, gb, M);
 }
 
@@ -1518,17 +1553,18 @@ float tt_scale(float p) { return p < 1.f ? 1.f / (1.f - p) : 0.f; }
 
 // One torch.nn.TransformerEncoderLayer (post-norm, ReLU) over N = B * T rows in training mode: H -> L.H2.
 // w: its twelve tensors in state_dict order; mk: its four keep-masks attn, drop1, ff, drop2, or nullptr.
-void tt_enc_layer_forward(hipStream_t st, const float* const* w, const TtLayer& L, const float* H, int64_t B, int T,
+void tt_enc_layer_forward(const TtLin& ln, const float* const* w, const TtLayer& L, const float* H, int64_t B, int T,
                           const uint8_t* const* mk, float sc) {
+    hipStream_t st = ln.st;
     const int64_t N = B * T;
     const auto mask = [&](int i) { return mk ? mk[i] : nullptr; };
-    tt_linear(st, H, w[0], w[1], L.QKV, N, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
+    tt_linear(ln, H, w[0], w[1], L.QKV, N, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
     hipLaunchKernelGGL(b2h_tt_sdpa, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes(T, false), st, L.QKV,
                        mask(0), sc, L.O, T);
-    tt_linear(st, L.O, w[2], w[3], L.R1, N, kTtD, kTtD, 0, mask(1), sc, H);
+    tt_linear(ln, L.O, w[2], w[3], L.R1, N, kTtD, kTtD, 0, mask(1), sc, H);
     hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R1, w[8], w[9], L.H1, L.ST, 4, N);
-    tt_linear(st, L.H1, w[4], w[5], L.F1, N, kTtD, kTtD, 1, mask(2), sc, nullptr);
-    tt_linear(st, L.F1, w[6], w[7], L.R2, N, kTtD, kTtD, 0, mask(3), sc, L.H1);
+    tt_linear(ln, L.H1, w[4], w[5], L.F1, N, kTtD, kTtD, 1, mask(2), sc, nullptr);
+    tt_linear(ln, L.F1, w[6], w[7], L.R2, N, kTtD, kTtD, 0, mask(3), sc, L.H1);
     hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R2, w[10], w[11], L.H2, L.ST + 2, 4, N);
 }
 
@@ -1542,26 +1578,27 @@ TtGrad tt_grad(float* scratch, int64_t N) {
 }
 
 // Backward of tt_enc_layer_forward: G.gA = dH2 on entry, = dH_in on return; g: the layer's twelve gradients.
-void tt_enc_layer_backward(hipStream_t st, const float* const* w, float* const* g, const TtLayer& L, const float* Hin,
+void tt_enc_layer_backward(const TtLin& ln, const float* const* w, float* const* g, const TtLayer& L, const float* Hin,
                            const TtGrad& G, int64_t B, int T, const uint8_t* const* mk, float sc) {
+    hipStream_t st = ln.st;
     const int64_t N = B * T;
     const auto mask = [&](int i) { return mk ? mk[i] : nullptr; };
     // norm2: gA = dH2 -> gB = dR2 (also dH1 through the residual), gBm = dR2 through drop2
     tt_layernorm_bwd(st, G.gA, L.R2, L.ST + 2, w[10], G.gB, G.gBm, mask(3), sc, G.slabs, N, g[10], g[11]);
     const float* dF = mk ? G.gBm : G.gB;
-    tt_linear_dw(st, dF, L.F1, G.slabs, N, kTtD, kTtD, g[6], g[7]);
-    tt_linear_dx(st, dF, w[6], G.gC, N, kTtD, kTtD, L.F1, nullptr, mk ? sc : 1.f, nullptr); // through drop_ff and ReLU
-    tt_linear_dw(st, G.gC, L.H1, G.slabs, N, kTtD, kTtD, g[4], g[5]);
-    tt_linear_dx(st, G.gC, w[4], G.gA, N, kTtD, kTtD, nullptr, nullptr, 1.f, G.gB);              // gA = dH1
+    tt_linear_dw(ln, dF, L.F1, G.slabs, N, kTtD, kTtD, g[6], g[7]);
+    tt_linear_dx(ln, dF, w[6], G.gC, N, kTtD, kTtD, L.F1, nullptr, mk ? sc : 1.f, nullptr); // through drop_ff and ReLU
+    tt_linear_dw(ln, G.gC, L.H1, G.slabs, N, kTtD, kTtD, g[4], g[5]);
+    tt_linear_dx(ln, G.gC, w[4], G.gA, N, kTtD, kTtD, nullptr, nullptr, 1.f, G.gB);              // gA = dH1
     // norm1: gA -> gB = dR1 (also dH_in through the residual), gBm through drop1
     tt_layernorm_bwd(st, G.gA, L.R1, L.ST, w[8], G.gB, G.gBm, mask(1), sc, G.slabs, N, g[8], g[9]);
     const float* dA = mk ? G.gBm : G.gB;
-    tt_linear_dw(st, dA, L.O, G.slabs, N, kTtD, kTtD, g[2], g[3]);
-    tt_linear_dx(st, dA, w[2], G.gC, N, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);             // gC = dO
+    tt_linear_dw(ln, dA, L.O, G.slabs, N, kTtD, kTtD, g[2], g[3]);
+    tt_linear_dx(ln, dA, w[2], G.gC, N, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);             // gC = dO
     hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes(T, true), st, L.QKV,
                        G.gC, mask(0), sc, G.gQ, T);
-    tt_linear_dw(st, G.gQ, Hin, G.slabs, N, kTtD, 3 * kTtD, g[0], g[1]);
-    tt_linear_dx(st, G.gQ, w[0], G.gA, N, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);          // gA = dH_in
+    tt_linear_dw(ln, G.gQ, Hin, G.slabs, N, kTtD, 3 * kTtD, g[0], g[1]);
+    tt_linear_dx(ln, G.gQ, w[0], G.gA, N, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);          // gA = dH_in
 }
 
 } // namespace
@@ -1589,6 +1626,7 @@ int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float*
                                tt_read_only(m, params, masks, N, T, {{x, (size_t)N * kInCh * 4}})))
         return rc;
     hipStream_t st = (hipStream_t)stream;
+    const TtLin ln{st, false}; // TransformerEnc keeps the Linear kernels of kernel_tenc_train.h
     const float sc = tt_scale(p);
     auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
     float* S = static_cast<float*>(saved);
@@ -1597,14 +1635,14 @@ int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float*
     float* Ls = S + N * kTtSavedFrame;
     hipLaunchKernelGGL(b2h_tt_posenc, dim3((unsigned)std::min<int64_t>((N * kInCh + 255) / 256, 4096)), dim3(256), 0, st, x,
                        params[0], mk(0), sc, X0, N, (int)T);
-    tt_linear(st, X0, params[1], params[2], H, N, kInCh, kTtD, 0, nullptr, 1.f, nullptr);
+    tt_linear(ln, X0, params[1], params[2], H, N, kInCh, kTtD, 0, nullptr, 1.f, nullptr);
     for (int l = 0; l < m->nlayers; ++l) {
         const TtLayer L = tt_layer(Ls, N, l);
-        tt_enc_layer_forward(st, params + 3 + 12 * l, L, H, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
+        tt_enc_layer_forward(ln, params + 3 + 12 * l, L, H, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
         H = L.H2;
     }
     const float* const* wh = params + 3 + 12 * m->nlayers;
-    tt_linear(st, H, wh[0], wh[1], y, N, kTtD, kOutCh, 0, nullptr, 1.f, nullptr);
+    tt_linear(ln, H, wh[0], wh[1], y, N, kTtD, kOutCh, 0, nullptr, 1.f, nullptr);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
@@ -1637,6 +1675,7 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
         return rc;
 
     hipStream_t st = (hipStream_t)stream;
+    const TtLin ln{st, false}; // TransformerEnc keeps the Linear kernels of kernel_tenc_train.h
     const float sc = tt_scale(p);
     auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
     float* S = const_cast<float*>(static_cast<const float*>(saved)); // read only
@@ -1647,14 +1686,14 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
     // hidden2pose_projection (HandPoseModels.py:173)
     const int oh = 3 + 12 * m->nlayers;
     const float* Hlast = tt_layer(Ls, N, m->nlayers - 1).H2;
-    tt_linear_dw(st, dy, Hlast, G.slabs, N, kTtD, kOutCh, grads[oh - 1], grads[oh]);
-    tt_linear_dx(st, dy, params[oh], G.gA, N, kTtD, kOutCh, nullptr, nullptr, 1.f, nullptr);
+    tt_linear_dw(ln, dy, Hlast, G.slabs, N, kTtD, kOutCh, grads[oh - 1], grads[oh]);
+    tt_linear_dx(ln, dy, params[oh], G.gA, N, kTtD, kOutCh, nullptr, nullptr, 1.f, nullptr);
     for (int l = m->nlayers - 1; l >= 0; --l)
-        tt_enc_layer_backward(st, params + 3 + 12 * l, grads + 2 + 12 * l, tt_layer(Ls, N, l),
+        tt_enc_layer_backward(ln, params + 3 + 12 * l, grads + 2 + 12 * l, tt_layer(Ls, N, l),
                               l ? tt_layer(Ls, N, l - 1).H2 : H0, G, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
     // pose2hidden_projection (:171) and the positional encoding's dropout (:101-103)
-    tt_linear_dw(st, G.gA, X0, G.slabs, N, kInCh, kTtD, grads[0], grads[1]);
-    if (dx) tt_linear_dx(st, G.gA, params[1], dx, N, kInCh, kTtD, nullptr, mk(0), sc, nullptr);
+    tt_linear_dw(ln, G.gA, X0, G.slabs, N, kInCh, kTtD, grads[0], grads[1]);
+    if (dx) tt_linear_dx(ln, G.gA, params[1], dx, N, kInCh, kTtD, nullptr, mk(0), sc, nullptr);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
@@ -1791,6 +1830,13 @@ TrainAttn tpt_train_attn(const b2h_tpt* m, int64_t T) {
     return m->train_kernel == B2H_TRAIN_MFMA ? TrainAttn::kBlockedMfma : TrainAttn::kBlockedValu;
 }
 
+// Which Linear trio the training calls launch, as b2h_tpt_set_train_linear chose, at every (B, S, T): the one place
+// that decides; the dispatch and b2h_tpt_train_linear_name both ask it.
+enum class TrainLinear { kValu, kMfma };
+TrainLinear tpt_train_linear(const b2h_tpt* m) {
+    return m->train_linear == B2H_TRAIN_MFMA ? TrainLinear::kMfma : TrainLinear::kValu;
+}
+
 // Attention of B sequences of Tq > 128 query rows over Tk key rows in training (kernel_train_attn_long.h, or
 // kernel_train_attn_mfma.h with mfma): O (B*Tq, 128) and the rows' log-sum-exp (B, 4, Tq).
 void lt_sdpa(hipStream_t st, bool mfma, const XsdpaSrc& src, const uint8_t* mask, float sc, float* O, float* lse, int64_t B,
@@ -1829,6 +1875,11 @@ const char* b2h_tpt_train_attn_name(const b2h_tpt* m, int64_t T) {
     }
 }
 
+const char* b2h_tpt_train_linear_name(const b2h_tpt* m) {
+    if (!m) return nullptr;
+    return tpt_train_linear(m) == TrainLinear::kMfma ? "b2h_ml_linear" : "b2h_tt_linear";
+}
+
 size_t b2h_tpt_train_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int which) {
     if (!m || B < 1 || S < 1 || T < 1 || (which != 0 && which != 1)) return 0;
     return which == 0 ? tpt_saved_bytes(m, B * S, B * T, tpt_long(T)) : tpt_scratch_bytes(B * S, B * T, tpt_long(T));
@@ -1853,6 +1904,7 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
                                               {{tokens, (size_t)Ns * 8}, {x, (size_t)Nt * m->ninp * 4}})))
         return rc;
     hipStream_t st = (hipStream_t)stream;
+    const TtLin ln{st, tpt_train_linear(m) == TrainLinear::kMfma};
     const float sc = tt_scale(p);
     const auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
     const TptSaved sv = tpt_saved(m, saved, Ns, Nt);
@@ -1864,7 +1916,7 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     const float* H = sv.E0;
     for (int l = 0; l < m->n_enc; ++l) {
         const TtLayer L = sv.enc_layer(l);
-        tt_enc_layer_forward(st, params + 12 * l, L, H, B, (int)S, masks ? masks + 4 * l : nullptr, sc);
+        tt_enc_layer_forward(ln, params + 12 * l, L, H, B, (int)S, masks ? masks + 4 * l : nullptr, sc);
         H = L.H2;
     }
     const float* const* wn = params + 12 * m->n_enc;
@@ -1872,40 +1924,40 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
 
     // decoder: pose2hidden_projection (:209) -> layers -> decoder.norm -> hidden2pose_projection (:213)
     HIP_TRY(hipMemcpyAsync(sv.X0, x, (size_t)Nt * m->ninp * 4, hipMemcpyDeviceToDevice, st));
-    tt_linear(st, sv.X0, wt[3], wt[4], sv.XT0, Nt, m->ninp, kTtD, 0, nullptr, 1.f, nullptr);
+    tt_linear(ln, sv.X0, wt[3], wt[4], sv.XT0, Nt, m->ninp, kTtD, 0, nullptr, 1.f, nullptr);
     H = sv.XT0;
     const unsigned heads = (unsigned)(B * kTtHeads);
     for (int l = 0; l < m->n_dec; ++l) { // torch.nn.TransformerDecoderLayer, post-norm, ReLU
         const float* const* w = params + 12 * m->n_enc + 2 + 18 * l;
         const int mi = 4 * m->n_enc + 6 * l;
         const TptDecLayer L = sv.dec_layer(l);
-        tt_linear(st, H, w[0], w[1], L.QKV, Nt, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
+        tt_linear(ln, H, w[0], w[1], L.QKV, Nt, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
         float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
         if (lng)
             lt_sdpa(st, mfma, tpt_ssrc(L), mk(mi), sc, L.O, lse, B, (int)T, (int)T);
         else
             hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, false), st, L.QKV, mk(mi), sc,
                                L.O, (int)T);
-        tt_linear(st, L.O, w[2], w[3], L.R1, Nt, kTtD, kTtD, 0, mk(mi + 1), sc, H);
+        tt_linear(ln, L.O, w[2], w[3], L.R1, Nt, kTtD, kTtD, 0, mk(mi + 1), sc, H);
         tt_layernorm(st, L.R1, w[12], w[13], L.H1, L.ST12, Nt);
         // multihead_attn: the query of H1 (in_proj rows 0..127), [K | V] of the memory (rows 128..383)
-        tt_linear(st, L.H1, w[4], w[5], L.QC, Nt, kTtD, kTtD, 0, nullptr, 1.f, nullptr);
-        tt_linear(st, sv.MEM, w[4] + kDD, w[5] + kTtD, L.KV, Ns, kTtD, 2 * kTtD, 0, nullptr, 1.f, nullptr);
+        tt_linear(ln, L.H1, w[4], w[5], L.QC, Nt, kTtD, kTtD, 0, nullptr, 1.f, nullptr);
+        tt_linear(ln, sv.MEM, w[4] + kDD, w[5] + kTtD, L.KV, Ns, kTtD, 2 * kTtD, 0, nullptr, 1.f, nullptr);
         if (lng)
             lt_sdpa(st, mfma, tpt_xsrc(L), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S);
         else
             hipLaunchKernelGGL(b2h_tptt_xsdpa, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, false), st,
                                tpt_xsrc(L), mk(mi + 2), sc, L.OC, (int)T, (int)S);
-        tt_linear(st, L.OC, w[6], w[7], L.R2, Nt, kTtD, kTtD, 0, mk(mi + 3), sc, L.H1);
+        tt_linear(ln, L.OC, w[6], w[7], L.R2, Nt, kTtD, kTtD, 0, mk(mi + 3), sc, L.H1);
         tt_layernorm(st, L.R2, w[14], w[15], L.H2, L.ST12 + 2, Nt);
-        tt_linear(st, L.H2, w[8], w[9], L.F1, Nt, kTtD, kTtD, 1, mk(mi + 4), sc, nullptr);
-        tt_linear(st, L.F1, w[10], w[11], L.R3, Nt, kTtD, kTtD, 0, mk(mi + 5), sc, L.H2);
+        tt_linear(ln, L.H2, w[8], w[9], L.F1, Nt, kTtD, kTtD, 1, mk(mi + 4), sc, nullptr);
+        tt_linear(ln, L.F1, w[10], w[11], L.R3, Nt, kTtD, kTtD, 0, mk(mi + 5), sc, L.H2);
         tt_layernorm(st, L.R3, w[16], w[17], L.H3, L.ST3, Nt);
         H = L.H3;
     }
     const float* const* wd = params + 12 * m->n_enc + 2 + 18 * m->n_dec;
     tt_layernorm(st, H, wd[0], wd[1], sv.YN, sv.STy, Nt);
-    tt_linear(st, sv.YN, wt[1], wt[2], y, Nt, kTtD, m->nout, 0, nullptr, 1.f, nullptr);
+    tt_linear(ln, sv.YN, wt[1], wt[2], y, Nt, kTtD, m->nout, 0, nullptr, 1.f, nullptr);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
@@ -1940,6 +1992,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         return rc;
 
     hipStream_t st = (hipStream_t)stream;
+    const TtLin ln{st, tpt_train_linear(m) == TrainLinear::kMfma};
     const float sc = tt_scale(p);
     const auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
     const TptSaved sv = tpt_saved(m, const_cast<void*>(saved), Ns, Nt); // read only
@@ -1954,8 +2007,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     const int od = 12 * m->n_enc + 2, ot = od + 18 * m->n_dec + 2; // the first decoder layer; token_embedding
 
     // hidden2pose_projection (:213) and decoder.norm
-    tt_linear_dw(st, dy, sv.YN, G.slabs, Nt, kTtD, m->nout, grads[ot + 1], grads[ot + 2]);
-    tt_linear_dx(st, dy, params[ot + 1], G.gB, Nt, kTtD, m->nout, nullptr, nullptr, 1.f, nullptr);
+    tt_linear_dw(ln, dy, sv.YN, G.slabs, Nt, kTtD, m->nout, grads[ot + 1], grads[ot + 2]);
+    tt_linear_dx(ln, dy, params[ot + 1], G.gB, Nt, kTtD, m->nout, nullptr, nullptr, 1.f, nullptr);
     tt_layernorm_bwd(st, G.gB, sv.dec_layer(m->n_dec - 1).H3, sv.STy, params[ot - 2], G.gA, G.gBm, nullptr, 1.f, G.slabs, Nt,
                      grads[ot - 2], grads[ot - 1]);
     float* dMEM = nullptr; // the sum over the decoder layers done so far
@@ -1968,15 +2021,15 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         // norm3: gA = dH3 -> gB = dR3 (also dH2 through the residual), gBm = dR3 through drop3
         tt_layernorm_bwd(st, G.gA, L.R3, L.ST3, w[16], G.gB, G.gBm, mk(mi + 5), sc, G.slabs, Nt, g[16], g[17]);
         const float* dF = masks ? G.gBm : G.gB;
-        tt_linear_dw(st, dF, L.F1, G.slabs, Nt, kTtD, kTtD, g[10], g[11]);
-        tt_linear_dx(st, dF, w[10], G.gC, Nt, kTtD, kTtD, L.F1, nullptr, masks ? sc : 1.f, nullptr); // through drop_ff and ReLU
-        tt_linear_dw(st, G.gC, L.H2, G.slabs, Nt, kTtD, kTtD, g[8], g[9]);
-        tt_linear_dx(st, G.gC, w[8], G.gA, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, G.gB);             // gA = dH2
+        tt_linear_dw(ln, dF, L.F1, G.slabs, Nt, kTtD, kTtD, g[10], g[11]);
+        tt_linear_dx(ln, dF, w[10], G.gC, Nt, kTtD, kTtD, L.F1, nullptr, masks ? sc : 1.f, nullptr); // through drop_ff and ReLU
+        tt_linear_dw(ln, G.gC, L.H2, G.slabs, Nt, kTtD, kTtD, g[8], g[9]);
+        tt_linear_dx(ln, G.gC, w[8], G.gA, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, G.gB);             // gA = dH2
         // norm2: gA -> gB = dR2 (also dH1 through the residual), gBm through drop2
         tt_layernorm_bwd(st, G.gA, L.R2, L.ST12 + 2, w[14], G.gB, G.gBm, mk(mi + 3), sc, G.slabs, Nt, g[14], g[15]);
         const float* dC = masks ? G.gBm : G.gB;
-        tt_linear_dw(st, dC, L.OC, G.slabs, Nt, kTtD, kTtD, g[6], g[7]);
-        tt_linear_dx(st, dC, w[6], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dOC
+        tt_linear_dw(ln, dC, L.OC, G.slabs, Nt, kTtD, kTtD, g[6], g[7]);
+        tt_linear_dx(ln, dC, w[6], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dOC
         const float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
         if (lng)
             lt_sdpa_bwd(st, mfma, tpt_xsrc(L), G.gC, lse + Nt * kTtHeads, Drow, mk(mi + 2), sc,
@@ -1986,29 +2039,29 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
                                tpt_xsrc(L), G.gC, mk(mi + 2), sc, G.gA, dKV, (int)T, (int)S);        // gA = dQC
         // multihead_attn.in_proj: rows 0..127 from (dQC, H1) over the frames, rows 128..383 from ([dK | dV], MEM)
         // over the tokens, each with the slab count of its own row set
-        tt_linear_dw(st, G.gA, L.H1, G.slabs, Nt, kTtD, kTtD, g[4], g[5]);
-        tt_linear_dw(st, dKV, sv.MEM, G.slabs, Ns, kTtD, 2 * kTtD, g[4] + kDD, g[5] + kTtD);
-        tt_linear_dx(st, G.gA, w[4], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, G.gB);             // gC = dH1
+        tt_linear_dw(ln, G.gA, L.H1, G.slabs, Nt, kTtD, kTtD, g[4], g[5]);
+        tt_linear_dw(ln, dKV, sv.MEM, G.slabs, Ns, kTtD, 2 * kTtD, g[4] + kDD, g[5] + kTtD);
+        tt_linear_dx(ln, G.gA, w[4], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, G.gB);             // gC = dH1
         float* dMnext = dMEM == dM[0] ? dM[1] : dM[0];
-        tt_linear_dx(st, dKV, w[4] + kDD, dMnext, Ns, kTtD, 2 * kTtD, nullptr, nullptr, 1.f, dMEM);  // dMEM += [dK | dV] W_kv
+        tt_linear_dx(ln, dKV, w[4] + kDD, dMnext, Ns, kTtD, 2 * kTtD, nullptr, nullptr, 1.f, dMEM);  // dMEM += [dK | dV] W_kv
         dMEM = dMnext;
         // norm1: gC -> gB = dR1 (also dH_in through the residual), gBm through drop1
         tt_layernorm_bwd(st, G.gC, L.R1, L.ST12, w[12], G.gB, G.gBm, mk(mi + 1), sc, G.slabs, Nt, g[12], g[13]);
         const float* dA = masks ? G.gBm : G.gB;
-        tt_linear_dw(st, dA, L.O, G.slabs, Nt, kTtD, kTtD, g[2], g[3]);
-        tt_linear_dx(st, dA, w[2], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dO
+        tt_linear_dw(ln, dA, L.O, G.slabs, Nt, kTtD, kTtD, g[2], g[3]);
+        tt_linear_dx(ln, dA, w[2], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dO
         if (lng)
             lt_sdpa_bwd(st, mfma, tpt_ssrc(L), G.gC, lse, Drow, mk(mi), sc,
                         LtGradDst{G.gQ, 3 * kTtD, 0, G.gQ, 3 * kTtD, kTtD, 2 * kTtD}, B, (int)T, (int)T);
         else
             hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, true), st, L.QKV, G.gC,
                                mk(mi), sc, G.gQ, (int)T);
-        tt_linear_dw(st, G.gQ, Hin, G.slabs, Nt, kTtD, 3 * kTtD, g[0], g[1]);
-        tt_linear_dx(st, G.gQ, w[0], G.gA, Nt, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);         // gA = dH_in
+        tt_linear_dw(ln, G.gQ, Hin, G.slabs, Nt, kTtD, 3 * kTtD, g[0], g[1]);
+        tt_linear_dx(ln, G.gQ, w[0], G.gA, Nt, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);         // gA = dH_in
     }
     // pose2hidden_projection (:209)
-    tt_linear_dw(st, G.gA, sv.X0, G.slabs, Nt, m->ninp, kTtD, grads[ot + 3], grads[ot + 4]);
-    if (dx) tt_linear_dx(st, G.gA, params[ot + 3], dx, Nt, m->ninp, kTtD, nullptr, nullptr, 1.f, nullptr);
+    tt_linear_dw(ln, G.gA, sv.X0, G.slabs, Nt, m->ninp, kTtD, grads[ot + 3], grads[ot + 4]);
+    if (dx) tt_linear_dx(ln, G.gA, params[ot + 3], dx, Nt, m->ninp, kTtD, nullptr, nullptr, 1.f, nullptr);
 
     // encoder.norm, the encoder layers, token_embedding (:206)
     float* slabs = G.slabs;
@@ -2017,7 +2070,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     tt_layernorm_bwd(st, dMEM, sv.enc_out(m->n_enc), sv.STm, params[od - 2], G.gA, G.gBm, nullptr, 1.f, G.slabs, Ns,
                      grads[od - 2], grads[od - 1]);
     for (int l = m->n_enc - 1; l >= 0; --l)
-        tt_enc_layer_backward(st, params + 12 * l, grads + 12 * l, sv.enc_layer(l), l ? sv.enc_layer(l - 1).H2 : sv.E0, G, B,
+        tt_enc_layer_backward(ln, params + 12 * l, grads + 12 * l, sv.enc_layer(l), l ? sv.enc_layer(l - 1).H2 : sv.E0, G, B,
                               (int)S, masks ? masks + 4 * l : nullptr, sc);
     hipLaunchKernelGGL(b2h_tptt_embed_bwd, dim3((unsigned)m->n_tokens), dim3(128), 0, st, tokens, G.gA, grads[ot], Ns);
     HIP_TRY(hipGetLastError());

@@ -47,7 +47,8 @@ class TextPoseTransformer(NativeModule, nn.Module):
     refusing "f16x3" because tests/test_tpt_cpu.py::test_python_side_errors pins that refusal; a later change that
     may touch that test lifts it.  Training is exact fp32 whatever the precision, and takes T <= 1024 frames;
     `set_train_kernels("mfma")` (attribute `train_kernels`, default "valu") moves the decoder's attentions beyond 128
-    frames to fp32 MFMA kernels.  The
+    frames to fp32 MFMA kernels, and `set_train_linear("mfma")` (attribute `train_linear`, default "valu") moves every
+    Linear layer of a training step, forward and backward at every length, to fp32 MFMA kernels.  The
     inference route of `model(tokens, pose)` stops at 128 (`forward_long` / `forward_fused` go to 1024)."""
 
     def __init__(self, n_tokens, n_joints, joints_dim, nhead, nhid, nout, n_enc_layers, n_dec_layers, dropout=0.5, *,
@@ -57,6 +58,7 @@ class TextPoseTransformer(NativeModule, nn.Module):
             raise ValueError(f"precision must be 'fp32', got {precision!r}")
         self.precision = precision
         self.train_kernels = "valu"
+        self.train_linear = "valu"
         self.model_type = "Transformer"
         self.src_mask = None
         self.token_pos_encoder = PositionalEncoding(nhid, dropout, max_len=40)
@@ -91,6 +93,18 @@ class TextPoseTransformer(NativeModule, nn.Module):
         if name not in _lib.TRAIN_KERNELS:
             raise ValueError(f"train kernels must be one of {sorted(_lib.TRAIN_KERNELS)}, got {name!r}")
         self.train_kernels = name
+        return self
+
+    def set_train_linear(self, name):
+        """Select the Linear kernels of later training forwards, "valu" (the default) or "mfma"; returns self.  "mfma"
+        runs every Linear layer of the step -- Y = X W^T + b, dX = dY W and the slab partials of dW, db, in the encoder
+        and the decoder at every length -- on v_mfma_f32_16x16x4_f32 (kernel_train_linear_mfma.h): exact fp32, the
+        default's summation order per element, as deterministic.  Independent of `set_train_kernels`; LayerNorm, the
+        embedding, the attentions and inference are untouched.  A backward runs the Linears its forward ran, whatever
+        the model says by then.  Measurements: DESIGN.md section 19."""
+        if name not in _lib.TRAIN_KERNELS:
+            raise ValueError(f"train linear must be one of {sorted(_lib.TRAIN_KERNELS)}, got {name!r}")
+        self.train_linear = name
         return self
 
     _NAME, _CREATE, _LOAD, _DESTROY = "TextPoseTransformer", "b2h_tpt_create", "b2h_tpt_load_weights", "b2h_tpt_destroy"
@@ -294,7 +308,8 @@ class _TptTrainFn(torch.autograd.Function):
     """y = TextPoseTransformer(tokens, x) in training mode with its gradient: b2h_tpt_train_forward /
     b2h_tpt_backward (exact fp32, kernel_tpt_train.h; kernel_train_attn_long.h for the decoder's attentions at
     128 < T <= 1024, or kernel_train_attn_mfma.h when the model's `train_kernels` is "mfma": the forward sets the
-    handle's train kernel from the model and records it, the backward sets it from that record), after
+    handle's train kernel from the model and records it, the backward sets it from that record; the Linear kernels
+    of `train_linear`, kernel_tenc_train.h or kernel_train_linear_mfma.h, travel the same way), after
     transformer_enc._TencTrainFn.  The parameters go in
     as themselves (their own data_ptr, saved for backward, so autograd's version check catches an in-place edit
     between forward and backward).  The context keeps the saved-activation buffer, the token ids and the masks
@@ -313,15 +328,17 @@ class _TptTrainFn(torch.autograd.Function):
         y = torch.empty((B, T, model.nout // 2, 2), dtype=torch.float32, device=x.device)
         nbytes = lib.b2h_tpt_train_bytes(model._handle, B, S, T, 0)
         saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
-        kernels = model.train_kernels
+        kernels, linear = model.train_kernels, model.train_linear
         with _lib.on_device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.b2h_tpt_set_train_kernel(model._handle, _lib.TRAIN_KERNELS[kernels]))
+            _lib.check(lib.b2h_tpt_set_train_linear(model._handle, _lib.TRAIN_KERNELS[linear]))
             _lib.check(lib.b2h_tpt_train_forward(model._handle, _ptrs(params), ctypes.c_void_p(tok.data_ptr()),
                                                  ctypes.c_void_p(x.data_ptr()), _ptrs(masks) if masks else None, p,
                                                  ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(saved.data_ptr()), nbytes,
                                                  B, S, T, ctypes.c_void_p(st)))
         ctx.model, ctx.p, ctx.masks, ctx.shape, ctx.kernels = model, p, masks, (B, S, T), kernels
+        ctx.linear = linear
         ctx.save_for_backward(saved, tok, *params)
         return y
 
@@ -347,6 +364,7 @@ class _TptTrainFn(torch.autograd.Function):
             with _lib.on_device(dev):
                 st = torch.cuda.current_stream(dev).cuda_stream
                 _lib.check(lib.b2h_tpt_set_train_kernel(model._handle, _lib.TRAIN_KERNELS[ctx.kernels]))
+                _lib.check(lib.b2h_tpt_set_train_linear(model._handle, _lib.TRAIN_KERNELS[ctx.linear]))
                 _lib.check(lib.b2h_tpt_backward(model._handle, _ptrs(params), ctypes.c_void_p(tok.data_ptr()),
                                                 _ptrs(masks) if masks else None, ctx.p, ctypes.c_void_p(dy.data_ptr()),
                                                 ctypes.c_void_p(saved.data_ptr()), saved.numel(),

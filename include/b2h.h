@@ -471,8 +471,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
                      float p, const float* dy, const void* saved, size_t saved_bytes, float* dx,
                      float* const* grads, void* scratch, size_t scratch_bytes, int64_t B, int64_t S, int64_t T,
                      void* stream);
-/* Which kernels the training calls use where there is a choice (not `attention`: further kernels will hang off the
- * same switch).  Today the choice covers the decoder's two attentions at T > 128:
+/* Which kernels the training calls use where there is a choice.  This switch covers the decoder's two attentions at
+ * T > 128 (the Linear layers have a switch of their own, b2h_tpt_set_train_linear below):
  *   B2H_TRAIN_VALU  the default of every new model: kernel_train_attn_long.h, fp32 FMAs on the vector ALU
  *   B2H_TRAIN_MFMA  kernel_train_attn_mfma.h: the same grids, operands, saved layouts and mathematics with all six
  *                   products on v_mfma_f32_16x16x4_f32 (exact fp32, a k-ordered fmaf chain); deterministic like
@@ -487,6 +487,20 @@ int b2h_tpt_set_train_kernel(b2h_tpt* m, int kernel);
  * under the current setting: "b2h_tt_sdpa" (T <= 128), "b2h_lt_sdpa" or "b2h_mt_sdpa"; static storage, for tests and
  * for matching rocprofv3 kernel-trace rows.  NULL for a NULL model or T < 1. */
 const char* b2h_tpt_train_attn_name(const b2h_tpt* m, int64_t T);
+/* A second, independent switch (the same enum): which kernels run the Linear layers of the training calls, forward
+ * and backward, in the encoder and the decoder at every (B, S, T):
+ *   B2H_TRAIN_VALU  the default of every new model: b2h_tt_linear / _dx / _dw of kernel_tenc_train.h
+ *   B2H_TRAIN_MFMA  kernel_train_linear_mfma.h: b2h_ml_linear / _dx / _dw, the same arguments, epilogues, slab
+ *                   contract and per-element summation order on v_mfma_f32_16x16x4_f32 (exact fp32); as
+ *                   deterministic as the default
+ * It leaves alone LayerNorm, the embedding, the attentions (b2h_tpt_set_train_kernel), b2h_tpt_train_bytes and every
+ * layout, inference, and TransformerEnc, which keeps the vector-ALU trio.  Either backward accepts either forward's
+ * saved buffer.  Both trios' LDS caps are raised at b2h_tpt_create, so switching between captures is safe.
+ * B2H_ERR_INVALID: NULL model, other value (nothing changes). */
+int b2h_tpt_set_train_linear(b2h_tpt* m, int kernel);
+/* Unmangled name of the Linear forward kernel that b2h_tpt_train_forward would launch under the current setting:
+ * "b2h_tt_linear" or "b2h_ml_linear"; static storage.  NULL for a NULL model. */
+const char* b2h_tpt_train_linear_name(const b2h_tpt* m);
 
 /* Introspection / measurement -------------------------------------------- */
 

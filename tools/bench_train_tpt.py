@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """GPU box: one training step of TextPoseTransformer (kernel_tpt_train.h, kernel_tenc_train.h, and
-kernel_train_attn_long.h beyond 128 frames, or kernel_train_attn_mfma.h there with kernels=mfma), one JSON line.
+kernel_train_attn_long.h beyond 128 frames, or kernel_train_attn_mfma.h there with kernels=mfma; the Linear layers on
+kernel_train_linear_mfma.h with linear=mfma), one JSON line.
 Context only: the training kernels are plain per-operation fp32 kernels and carry no speed bar.
   * one full step of the reference loop body (steps/traintest.py:105-121), 4 + 4 layers, n_tokens = 1000,
     dropout 0.1: forward (masks drawn by torch), mask_output, maskedPoseL1, backward, torch.optim.Adam (lr 2e-4),
@@ -11,7 +12,8 @@ The two shapes of the record (DESIGN.md sections 13 and 16):
     python tools/bench_train_tpt.py                  B x S x T = 128 x 40 x 100, 12 joints (the datasets' 100 frames)
     python tools/bench_train_tpt.py 128 40 200 8     the trainer's default batch: --max-frames 200, geometry (8, 42)
     python tools/bench_train_tpt.py 128 40 200 8 5 mfma   the same with model.set_train_kernels("mfma")
-    python tools/bench_train_tpt.py [B=128] [S=40] [T=100] [n_joints=12] [reps=5] [kernels=valu|mfma]"""
+    python tools/bench_train_tpt.py 128 40 200 8 5 mfma mfma   and with model.set_train_linear("mfma") (section 19)
+    python tools/bench_train_tpt.py [B=128] [S=40] [T=100] [n_joints=12] [reps=5] [kernels=valu|mfma] [linear=valu|mfma]"""
 import json
 import os
 import sys
@@ -30,6 +32,7 @@ T = int(sys.argv[3]) if len(sys.argv) > 3 else 100
 J = int(sys.argv[4]) if len(sys.argv) > 4 else 12
 REPS = int(sys.argv[5]) if len(sys.argv) > 5 else 5
 KERNELS = sys.argv[6] if len(sys.argv) > 6 else "valu"
+LINEAR = sys.argv[7] if len(sys.argv) > 7 else None    # absent: the model's default, and no key in the record
 N_TOKENS, L, P, LR = 1000, 4, 0.1, 2e-4
 dev = torch.device("cuda:0")
 
@@ -78,6 +81,8 @@ with warnings.catch_warnings():
     warnings.simplefilter("ignore", UserWarning)
     m = hps.TextPoseTransformer(N_TOKENS, J, 2, 4, 128, 42, L, L, dropout=P).to(dev).train()
 m.set_train_kernels(KERNELS)
+if LINEAR is not None:
+    m.set_train_linear(LINEAR)
 g = torch.Generator(device=dev).manual_seed(1)
 lengths = [T - (i * 37) % (T // 2 + 1) for i in range(B)]
 toks = torch.randint(0, N_TOKENS, (B, S), device=dev, generator=g)
@@ -102,6 +107,8 @@ def make_step(forward, params):
 
 out = {"B": B, "S": S, "T": T, "n_joints": J, "n_enc": L, "n_dec": L, "n_tokens": N_TOKENS, "dropout": P, "reps": REPS,
        "kernels": KERNELS}
+if LINEAR is not None:
+    out["linear"] = LINEAR
 out["reference_step_ms"], out["reference_step_ms_min"] = events_ms(make_step(m, list(m.parameters())), 10)
 out["reference_step_ms_max"] = SPREAD[0]
 tm = TorchTpt().to(dev).train()
