@@ -98,6 +98,10 @@ SYMBOLS = {
     "b2h_tpt_backward": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp), ctypes.c_float, _vp, _vp,
                                         ctypes.c_size_t, _vp, ctypes.POINTER(_vp), _vp, ctypes.c_size_t, ctypes.c_int64,
                                         ctypes.c_int64, ctypes.c_int64, _vp]),
+    "b2h_dropout_masks": (ctypes.c_int, [ctypes.POINTER(_vp), _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                         ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
+    "b2h_tpt_mask_numel": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _i64p, ctypes.c_int]),
+    "b2h_tenc_mask_numel": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int64, _i64p, ctypes.c_int]),
     "b2h_model_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                       ctypes.POINTER(ctypes.c_int)]),
     "b2h_kernel_supported": (ctypes.c_int, [_vp, ctypes.c_int]),

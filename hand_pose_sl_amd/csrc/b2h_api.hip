@@ -24,6 +24,7 @@
 #include "kernel_tenc_train.h"
 #include "kernel_tpt.h"
 #include "kernel_attn_long.h"
+#include "kernel_dropout_masks.h"
 #include "kernel_train_attn_long.h"
 #include "kernel_train_attn_mfma.h"
 #include "kernel_train_linear_mfma.h"
@@ -1459,18 +1460,23 @@ TtLayer tt_layer(float* layers, int64_t N, int l) { // layers: where layer 0 sta
 size_t tt_saved_bytes(int nlayers, int64_t N) { return (size_t)N * (kTtSavedFrame + nlayers * kTtSavedLayer) * 4; }
 size_t tt_scratch_bytes(int64_t N) { return ((size_t)N * kTtScratchFrame + (size_t)tt_nslabs(N) * kTtSlab) * 4; }
 
+// Why the training calls refuse a (B, T) batch, or nullptr (b2h_tenc_mask_numel answers the same shapes).
+const char* tt_shape_refusal(const b2h_tenc* m, int64_t B, int64_t T) {
+    if (B < 0 || T < 1) return "expected B >= 0 and T >= 1";
+    if (T > m->max_len || T > 128)
+        return "TransformerEnc: T exceeds the positional encoding's max_len (src + pe[:T], HandPoseModels.py:101,167)";
+    // grid limits: attention launches B x heads workgroups, LayerNorm N / 4 (the largest row grid), the Linears N / 16
+    if (B * kTtHeads > 0x7fffffff || B * T / 4 >= 0x7fffffff) return "batch too large for one launch";
+    return nullptr;
+}
+
 // Checks shared by b2h_tenc_train_forward / b2h_tenc_backward, as tenc_launch makes them.
 int tt_check(const b2h_tenc* m, const float* const* params, const uint8_t* const* masks, float p, int64_t B, int64_t T) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
     if (!params) return fail(B2H_ERR_INVALID, "params is NULL");
     if (!(p >= 0.f && p <= 1.f)) return fail(B2H_ERR_INVALID, "dropout p must be in [0, 1]");
     if ((p > 0.f) != (masks != nullptr)) return fail(B2H_ERR_INVALID, "masks must be given exactly when p > 0");
-    if (B < 0 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0 and T >= 1");
-    if (T > m->max_len || T > 128)
-        return fail(B2H_ERR_SHAPE, "TransformerEnc: T exceeds the positional encoding's max_len (src + pe[:T], "
-                                   "HandPoseModels.py:101,167)");
-    // grid limits: attention launches B x heads workgroups, LayerNorm N / 4 (the largest row grid), the Linears N / 16
-    if (B * kTtHeads > 0x7fffffff || B * T / 4 >= 0x7fffffff) return fail(B2H_ERR_SHAPE, "batch too large for one launch");
+    if (const char* why = tt_shape_refusal(m, B, T)) return fail(B2H_ERR_SHAPE, why);
     for (size_t i = 0; i < m->sizes.size(); ++i) {
         if (!params[i]) return fail(B2H_ERR_INVALID, "params[" + std::to_string(i) + "] is NULL");
         if (misaligned(params[i], 4)) return fail(B2H_ERR_INVALID, "params must be 4-byte aligned fp32 tensors");
@@ -1776,6 +1782,16 @@ size_t tpt_mask_bytes(const b2h_tpt* m, int i, int64_t B, int64_t S, int64_t T) 
     return k == 0 ? (size_t)B * kTtHeads * T * T : (k == 2 ? (size_t)B * kTtHeads * T * S : (size_t)B * T * kTtD);
 }
 
+// Why the training calls refuse a (B, S, T) batch, or nullptr (b2h_tpt_mask_numel answers the same shapes).
+const char* tptt_shape_refusal(int64_t B, int64_t S, int64_t T) {
+    if (B < 0 || S < 1 || T < 1) return "expected B >= 0, S >= 1 and T >= 1";
+    if (S > kTptMaxLen || T > B2H_TPT_MAX_FRAMES)
+        return "TextPoseTransformer training: S is limited to 128 and T to B2H_TPT_MAX_FRAMES = 1024";
+    // grid limits: attention launches B x heads workgroups, LayerNorm N / 4 (the largest row grid)
+    if (B * kTtHeads > 0x7fffffff || B * std::max(S, T) / 4 >= 0x7fffffff) return "batch too large for one launch";
+    return nullptr;
+}
+
 // Checks shared by b2h_tpt_train_forward / b2h_tpt_backward, as tt_check makes them.
 int tptt_check(const b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks, float p,
                int64_t B, int64_t S, int64_t T) {
@@ -1783,12 +1799,7 @@ int tptt_check(const b2h_tpt* m, const float* const* params, const int64_t* toke
     if (!params) return fail(B2H_ERR_INVALID, "params is NULL");
     if (!(p >= 0.f && p <= 1.f)) return fail(B2H_ERR_INVALID, "dropout p must be in [0, 1]");
     if ((p > 0.f) != (masks != nullptr)) return fail(B2H_ERR_INVALID, "masks must be given exactly when p > 0");
-    if (B < 0 || S < 1 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0, S >= 1 and T >= 1");
-    if (S > kTptMaxLen || T > B2H_TPT_MAX_FRAMES)
-        return fail(B2H_ERR_SHAPE, "TextPoseTransformer training: S is limited to 128 and T to B2H_TPT_MAX_FRAMES = 1024");
-    // grid limits: attention launches B x heads workgroups, LayerNorm N / 4 (the largest row grid)
-    if (B * kTtHeads > 0x7fffffff || B * std::max(S, T) / 4 >= 0x7fffffff)
-        return fail(B2H_ERR_SHAPE, "batch too large for one launch");
+    if (const char* why = tptt_shape_refusal(B, S, T)) return fail(B2H_ERR_SHAPE, why);
     for (int i = 0; i < tpt_nparams(m); ++i) {
         if (!params[i]) return fail(B2H_ERR_INVALID, "params[" + std::to_string(i) + "] is NULL");
         if (misaligned(params[i], 4)) return fail(B2H_ERR_INVALID, "params must be 4-byte aligned fp32 tensors");
@@ -2075,6 +2086,61 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     hipLaunchKernelGGL(b2h_tptt_embed_bwd, dim3((unsigned)m->n_tokens), dim3(128), 0, st, tokens, G.gA, grads[ot], Ns);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
+}
+
+} // extern "C"
+
+// ---- dropout keep-masks (kernel_dropout_masks.h) ------------------------------------------------------------
+extern "C" {
+
+int b2h_dropout_masks(uint8_t* const* masks, const int64_t* numel, int n_masks, int first_index, float p, uint64_t seed,
+                      uint64_t step, const uint64_t* step_dev, void* stream) {
+    if (n_masks < 0) return fail(B2H_ERR_INVALID, "n_masks must be >= 0");
+    if (first_index < 0) return fail(B2H_ERR_INVALID, "first_index must be >= 0");
+    if (!(p >= 0.f && p <= 1.f)) return fail(B2H_ERR_INVALID, "dropout p must be in [0, 1]");
+    if (n_masks > 0 && (!masks || !numel)) return fail(B2H_ERR_INVALID, "masks / numel is NULL");
+    for (int i = 0; i < n_masks; ++i) {
+        if (numel[i] < 0) return fail(B2H_ERR_INVALID, "numel[" + std::to_string(i) + "] is negative");
+        if (!masks[i]) return fail(B2H_ERR_INVALID, "masks[" + std::to_string(i) + "] is NULL");
+        if (misaligned(masks[i], 16)) return fail(B2H_ERR_INVALID, "masks[" + std::to_string(i) + "] must be 16-byte aligned");
+    }
+    DmArgs a;
+    a.key0 = (uint32_t)seed;
+    a.key1 = (uint32_t)(seed >> 32);
+    a.thr = (uint64_t)std::ceil((double)p * 4294967296.0);
+    a.step = step;
+    a.step_dev = step_dev;
+    for (int base = 0; base < n_masks; base += kDmMaxMasks) { // at most kDmMaxMasks masks per launch
+        a.n = std::min(n_masks - base, kDmMaxMasks);
+        a.number0 = (uint32_t)first_index + (uint32_t)base;
+        a.first[0] = 0;
+        for (int i = 0; i < kDmMaxMasks; ++i) {
+            a.ptr[i] = i < a.n ? masks[base + i] : nullptr;
+            a.numel[i] = i < a.n ? numel[base + i] : 0;
+            a.first[i + 1] = a.first[i] + (a.numel[i] + 15) / 16;
+        }
+        const int64_t chunks = a.first[a.n];
+        if (chunks == 0) continue;
+        const unsigned blocks = (unsigned)std::min<int64_t>((chunks + kDmThreads - 1) / kDmThreads, kDmMaxBlocks);
+        hipLaunchKernelGGL(b2h_dropout_masks_k, dim3(blocks), dim3(kDmThreads), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return B2H_OK;
+}
+
+int64_t b2h_tenc_mask_numel(const b2h_tenc* m, int64_t B, int64_t T, int64_t* numel, int capacity) {
+    if (!m || tt_shape_refusal(m, B, T)) return 0;
+    const int count = 1 + 4 * m->nlayers;
+    for (int i = 0; numel && i < std::min(count, capacity); ++i)
+        numel[i] = i == 0 ? B * T * kInCh : ((i - 1) % 4 == 0 ? B * kTtHeads * T * T : B * T * kTtD);
+    return count;
+}
+
+int64_t b2h_tpt_mask_numel(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int64_t* numel, int capacity) {
+    if (!m || tptt_shape_refusal(B, S, T)) return 0;
+    const int count = tpt_nmasks(m);
+    for (int i = 0; numel && i < std::min(count, capacity); ++i) numel[i] = (int64_t)tpt_mask_bytes(m, i, B, S, T);
+    return count;
 }
 
 } // extern "C"

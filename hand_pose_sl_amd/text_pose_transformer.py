@@ -21,7 +21,8 @@ T <= 1024 frames (the trainer pads to `--max-frames 200`, run.py:28; beyond 128 
 run blocked, kernel_train_attn_long.h, or after `model.set_train_kernels("mfma")` on the matrix cores in exact fp32,
 kernel_train_attn_mfma.h).  The dropout keep-masks
 are drawn by torch on the model's device (`_draw_dropout_masks`; they follow torch.manual_seed) and handed to the
-kernels.  Every other call (eval mode or no_grad) runs the inference kernels.
+kernels; after `model.set_dropout_source("native", seed)` libb2h draws them itself, all of a step in one launch
+(b2h_dropout_masks, kernel_dropout_masks.h).  Every other call (eval mode or no_grad) runs the inference kernels.
 
 Inference is exact fp32 by default; `model.set_precision("f16x3")` selects the f16 hi + lo split path (three
 v_mfma_f32_16x16x32_f16 per product, Q, K, V projected inside the attention kernels), valid while every weight and
@@ -35,11 +36,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import NativeModule, _aligned, _ptrs
+from ._native import NativeDropout, NativeModule, _aligned, _ptrs
 from .transformer_enc import TENC_KERNELS, PositionalEncoding
 
 
-class TextPoseTransformer(NativeModule, nn.Module):
+class TextPoseTransformer(NativeDropout, NativeModule, nn.Module):
     """`precision` (not in the reference; keyword only): the constructor accepts only "fp32" = fp32 operands on the
     matrix cores, the default.  `set_precision("f16x3")` switches the inference forward to the f16 hi + lo split
     (fp32-grade results, the same 2e-5 parity bar; needs |weights| and |activations| < 65504, else the forward
@@ -144,13 +145,17 @@ class TextPoseTransformer(NativeModule, nn.Module):
 
     def _draw_dropout_masks(self, B, S, T):
         """The keep-masks of one training forward: uint8, 1 = keep with probability 1 - p, drawn on the model's
-        device with torch's generator (so they follow torch.manual_seed) in this fixed order, which is that of
+        device with torch's generator (so they follow torch.manual_seed), or under `dropout_source` "native" by
+        b2h_dropout_masks as views of one allocation (mask number = position; `set_dropout_source`), in either
+        case in this fixed order, which is that of
         torch's layers: per encoder layer ("enc", l, name) with name = `attn` (B, 4, S, S), `drop1`, `ff`, `drop2`
         (B, S, 128 each); then per decoder layer ("dec", l, name) with name = `self_attn` (B, 4, T, T), `drop1`
         (B, T, 128), `cross_attn` (B, 4, T, S), `drop2`, `ff`, `drop3` (B, T, 128 each).  An empty dict at p = 0."""
         p = self._dropout_p
         if p == 0.0:
             return {}
+        if self.dropout_source == "native":
+            return self._native_dropout_masks(self._mask_order(B, S, T), p)
         dev = self._device()
         return {key: (torch.rand(shape, device=dev) >= p).to(torch.uint8) for key, shape in self._mask_order(B, S, T)}
 

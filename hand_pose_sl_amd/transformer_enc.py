@@ -13,7 +13,8 @@ Training: in training mode with autograd enabled and a parameter or the input re
 b2h_tenc_backward, kernel_tenc_train.h) that read the parameters' own storage -- so the reference's loop
 body (steps/traintest.py:87-121) runs unchanged with any torch optimizer.  The dropout keep-masks are
 drawn by torch on the model's device (`_draw_dropout_masks`; they follow torch.manual_seed) and handed
-to the kernels.  Every other call (eval mode or no_grad) runs the inference kernels selected by
+to the kernels; after `model.set_dropout_source("native", seed)` libb2h draws them itself, all of a step in one
+launch (b2h_dropout_masks, kernel_dropout_masks.h).  Every other call (eval mode or no_grad) runs the inference kernels selected by
 `precision`.  No path ever falls back to PyTorch ops.
 """
 import ctypes
@@ -24,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import NativeModule, _aligned, _ptrs
+from ._native import NativeDropout, NativeModule, _aligned, _ptrs
 
 
 class PositionalEncoding(nn.Module):
@@ -47,7 +48,7 @@ class PositionalEncoding(nn.Module):
 TENC_KERNELS = {"fp32": 0, "f16x3": 1}   # b2h_tenc_kernel (include/b2h.h)
 
 
-class TransformerEnc(NativeModule, nn.Module):
+class TransformerEnc(NativeDropout, NativeModule, nn.Module):
     """`precision` (not in the reference; keyword only): "fp32" = fp32 operands on the matrix cores
     (default); "f16x3" = every Linear operand split into f16 hi + lo, three f16 MFMAs per product
     with fp32 accumulation: fp32-grade error at 3/16 of the matrix cycles, for activations and
@@ -115,14 +116,26 @@ class TransformerEnc(NativeModule, nn.Module):
             raise RuntimeError(f"expected input of shape (B, T, {self.ninp // 2}, 2), got {tuple(src.shape)}")
         return src.to(device=self._device(), dtype=torch.float32, non_blocking=True).contiguous()
 
+    def _mask_order(self, B, T):
+        """(key, shape) of every keep-mask in the order of b2h_tenc_train_forward (include/b2h.h)."""
+        order = [("pos", (B, T, self.ninp))]
+        for l in range(self._geom[4]):
+            order.append(((l, "attn"), (B, self._geom[1], T, T)))
+            order += [((l, name), (B, T, self._geom[2])) for name in ("drop1", "ff", "drop2")]
+        return order
+
     def _draw_dropout_masks(self, B, T):
         """The keep-masks of one training forward: uint8, 1 = keep with probability 1 - p, drawn on the model's
-        device with torch's generator (so they follow torch.manual_seed) in this fixed order: `pos` (B, T, 24);
+        device with torch's generator (so they follow torch.manual_seed), or under `dropout_source` "native" by
+        b2h_dropout_masks as views of one allocation (mask number = position; `set_dropout_source`), in either
+        case in this fixed order: `pos` (B, T, 24);
         then layer by layer `attn` (B, 4, T, T), `drop1`, `ff`, `drop2` (B, T, 128 each), keyed (layer, name).
         An empty dict at p = 0."""
         p = float(self._modules["pos_encoder"]._modules["dropout"].p)
         if p == 0.0:
             return {}
+        if self.dropout_source == "native":
+            return self._native_dropout_masks(self._mask_order(B, T), p)
         dev = self._device()
 
         def draw(*shape):
@@ -142,13 +155,8 @@ class TransformerEnc(NativeModule, nn.Module):
         p = float(self._modules["pos_encoder"]._modules["dropout"].p)
         if (p > 0.0) != bool(masks):
             raise ValueError("masks must be given exactly when the dropout probability is > 0")
-        order = []
+        order = self._mask_order(x.shape[0], x.shape[1]) if masks else []
         if masks:
-            B, T = x.shape[0], x.shape[1]
-            order = [("pos", (B, T, self.ninp))]
-            for l in range(self._geom[4]):
-                order.append(((l, "attn"), (B, self._geom[1], T, T)))
-                order += [((l, name), (B, T, self._geom[2])) for name in ("drop1", "ff", "drop2")]
             for key, shape in order:
                 m = masks[key]
                 if m.shape != shape or m.dtype != torch.uint8 or m.device != x.device or not m.is_contiguous():

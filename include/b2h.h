@@ -271,7 +271,8 @@ int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, 
  *   p     : the dropout probability (the reference passes one value everywhere), 0 <= p <= 1.
  *   masks : NULL when p == 0 (nothing is dropped or scaled); else a host array of 1 + 4*nlayers device
  *           uint8 keep-masks (1 = keep; kept values are scaled by 1 / (1 - p), everything is dropped at
- *           p == 1), drawn by the caller:
+ *           p == 1).  b2h_dropout_masks below draws them and b2h_tenc_mask_numel gives their element counts; a
+ *           caller may as well fill them from a generator of its own.  In this order:
  *             pos (B, T, 24); then per layer: attn (B, 4, T, T) on the softmax probabilities,
  *             drop1 (B, T, 128) on out_proj's output, ff (B, T, 128) after linear1's ReLU,
  *             drop2 (B, T, 128) on linear2's output.
@@ -424,8 +425,9 @@ int b2h_tpt_build_item(const float* body, const float* right_hand, float* item, 
  *           sequence's y becomes NaN in the forward, and the backward skips it in the embedding gradient.
  *   p     : the dropout probability (the reference passes one value everywhere), 0 <= p <= 1.
  *   masks : NULL when p == 0; else a host array of 4*n_enc_layers + 6*n_dec_layers device uint8 keep-masks
- *           (1 = keep; kept values are scaled by 1 / (1 - p), everything is dropped at p == 1) in the order of
- *           torch's layers:
+ *           (1 = keep; kept values are scaled by 1 / (1 - p), everything is dropped at p == 1).  b2h_dropout_masks
+ *           below draws them and b2h_tpt_mask_numel gives their element counts; a caller may as well fill them
+ *           from a generator of its own.  In the order of torch's layers:
  *             per encoder layer: attn (B, 4, S, S), drop1, ff, drop2 (B, S, 128 each);
  *             per decoder layer: self_attn (B, 4, T, T), drop1 (B, T, 128), cross_attn (B, 4, T, S),
  *               drop2, ff, drop3 (B, T, 128 each).
@@ -501,6 +503,35 @@ int b2h_tpt_set_train_linear(b2h_tpt* m, int kernel);
 /* Unmangled name of the Linear forward kernel that b2h_tpt_train_forward would launch under the current setting:
  * "b2h_tt_linear" or "b2h_ml_linear"; static storage.  NULL for a NULL model. */
 const char* b2h_tpt_train_linear_name(const b2h_tpt* m);
+
+/* Dropout keep-masks ---------------------------------------------------------
+ * The masks of b2h_tenc_train_forward / b2h_tpt_train_forward (uint8, 1 = keep with probability 1 - p) from one
+ * HIP kernel (kernel_dropout_masks.h), so that a host needs no random generator of its own to train with dropout.
+ * Counter based, Philox4x32-10 (multipliers D2511F53, CD9E8D57; key increments 9E3779B9, BB67AE85; ten rounds, the key
+ * bumped between rounds).  Element e of mask number k, e the flat index in the mask's contiguous layout:
+ *   block b = e / 4;  counter (b mod 2^32, b >> 32, k, s), s = (step + *step_dev) mod 2^32 (without the *step_dev
+ *   term when step_dev is NULL);  key (seed mod 2^32, seed >> 32);  word = output word e mod 4 of that block;
+ *   keep = word >= thr, thr = ceil((double)p * 2^32) compared in 64 bits: p == 0 keeps everything, p == 1 nothing.
+ * A byte depends on (seed, s, k, e, p) only: not on the launch grid, on how many masks the call has or on the size of
+ * any other mask; p is exact to 2^-32.
+ *   masks, numel: HOST arrays of n_masks device pointers (16-byte aligned, written) and element counts; mask i of the
+ *                 call has number first_index + i, so the masks of a step may be drawn in several calls.  For the
+ *                 training forwards number them from 0 in the order their comments above list.
+ *   step        : the training step; a captured HIP graph that shall draw new masks on every replay passes the
+ *                 device word step_dev (read by the kernel, never written) and advances it itself between replays.
+ * One launch per 64 masks, their pointers and sizes in the kernel arguments.  Stream-ordered and asynchronous: it
+ * does not synchronise, allocate or read device memory on the host, so it can be captured.  Nothing is written
+ * past numel[i] bytes.  B2H_ERR_INVALID, before anything is launched: NULL masks or numel with n_masks > 0,
+ * n_masks < 0, first_index < 0, a NULL or not 16-byte-aligned mask pointer, numel[i] < 0, p outside [0, 1] or NaN.
+ * n_masks == 0 or all sizes 0 is a no-op (B2H_OK). */
+int b2h_dropout_masks(uint8_t* const* masks, const int64_t* numel, int n_masks, int first_index, float p,
+                      uint64_t seed, uint64_t step, const uint64_t* step_dev, void* stream);
+/* How many keep-masks the model's training forward takes for this batch (4*n_enc_layers + 6*n_dec_layers;
+ * 1 + 4*nlayers) and, in numel[0 .. min(count, capacity)), their element counts in the order documented at the
+ * training forwards (numel may be NULL with capacity 0).  0 for a NULL model or a shape the forward refuses.  Pure
+ * host functions: nothing is read from the device. */
+int64_t b2h_tpt_mask_numel(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int64_t* numel, int capacity);
+int64_t b2h_tenc_mask_numel(const b2h_tenc* m, int64_t B, int64_t T, int64_t* numel, int capacity);
 
 /* Introspection / measurement -------------------------------------------- */
 

@@ -7,7 +7,8 @@ training kernels are plain per-operation fp32 kernels and carry no speed bar.
   * the same step with torch-ROCm's own nn.TransformerEncoder (the reference's model restated with torch
     modules) on the same GPU;
   * the same step of the tests' torch port (tests/tenc_train_ref.py) on the host CPU.
-    python tools/bench_train_tenc.py [B=128] [T=100]"""
+    python tools/bench_train_tenc.py [B=128] [T=100] [dropout_source=torch|native]
+The third argument selects model.set_dropout_source and is recorded only when given."""
 import json
 import os
 import sys
@@ -25,6 +26,7 @@ from tenc_train_ref import leaf_state, param_keys, port_forward  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 100
+DROPOUT_SOURCE = sys.argv[3] if len(sys.argv) > 3 else None    # absent: the model's default, and no key in the record
 L, P, LR = 4, 0.1, 2e-4
 dev = torch.device("cuda:0")
 
@@ -66,6 +68,8 @@ class TorchEnc(nn.Module):
 
 torch.manual_seed(0)
 m = hps.TransformerEnc(24, 4, 128, 42, L, dropout=P).to(dev).train()
+if DROPOUT_SOURCE is not None:
+    m.set_dropout_source(DROPOUT_SOURCE, seed=0)
 g = torch.Generator(device=dev).manual_seed(1)
 lengths = [T - (i * 37) % (T // 2 + 1) for i in range(B)]
 xs = torch.rand((B, T, 12, 2), device=dev, generator=g) - 0.5
@@ -88,6 +92,8 @@ def make_step(forward, params):
 
 
 out = {"B": B, "T": T, "nlayers": L, "dropout": P}
+if DROPOUT_SOURCE is not None:
+    out["dropout_source"] = DROPOUT_SOURCE
 out["reference_step_ms"] = events_ms(make_step(m, list(m.parameters())), 20)
 tm = TorchEnc().to(dev).train()
 pe = m.pos_encoder.pe

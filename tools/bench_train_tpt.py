@@ -13,7 +13,9 @@ The two shapes of the record (DESIGN.md sections 13 and 16):
     python tools/bench_train_tpt.py 128 40 200 8     the trainer's default batch: --max-frames 200, geometry (8, 42)
     python tools/bench_train_tpt.py 128 40 200 8 5 mfma   the same with model.set_train_kernels("mfma")
     python tools/bench_train_tpt.py 128 40 200 8 5 mfma mfma   and with model.set_train_linear("mfma") (section 19)
-    python tools/bench_train_tpt.py [B=128] [S=40] [T=100] [n_joints=12] [reps=5] [kernels=valu|mfma] [linear=valu|mfma]"""
+    python tools/bench_train_tpt.py 128 40 200 8 5 mfma mfma native   and with model.set_dropout_source("native") (section 20)
+    python tools/bench_train_tpt.py [B=128] [S=40] [T=100] [n_joints=12] [reps=5] [kernels=valu|mfma] [linear=valu|mfma]
+                                    [dropout_source=torch|native]"""
 import json
 import os
 import sys
@@ -33,6 +35,7 @@ J = int(sys.argv[4]) if len(sys.argv) > 4 else 12
 REPS = int(sys.argv[5]) if len(sys.argv) > 5 else 5
 KERNELS = sys.argv[6] if len(sys.argv) > 6 else "valu"
 LINEAR = sys.argv[7] if len(sys.argv) > 7 else None    # absent: the model's default, and no key in the record
+DROPOUT_SOURCE = sys.argv[8] if len(sys.argv) > 8 else None    # absent: the model's default, and no key in the record
 N_TOKENS, L, P, LR = 1000, 4, 0.1, 2e-4
 dev = torch.device("cuda:0")
 
@@ -83,6 +86,8 @@ with warnings.catch_warnings():
 m.set_train_kernels(KERNELS)
 if LINEAR is not None:
     m.set_train_linear(LINEAR)
+if DROPOUT_SOURCE is not None:
+    m.set_dropout_source(DROPOUT_SOURCE, seed=0)
 g = torch.Generator(device=dev).manual_seed(1)
 lengths = [T - (i * 37) % (T // 2 + 1) for i in range(B)]
 toks = torch.randint(0, N_TOKENS, (B, S), device=dev, generator=g)
@@ -109,6 +114,8 @@ out = {"B": B, "S": S, "T": T, "n_joints": J, "n_enc": L, "n_dec": L, "n_tokens"
        "kernels": KERNELS}
 if LINEAR is not None:
     out["linear"] = LINEAR
+if DROPOUT_SOURCE is not None:
+    out["dropout_source"] = DROPOUT_SOURCE
 out["reference_step_ms"], out["reference_step_ms_min"] = events_ms(make_step(m, list(m.parameters())), 10)
 out["reference_step_ms_max"] = SPREAD[0]
 tm = TorchTpt().to(dev).train()
