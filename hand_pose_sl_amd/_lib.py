@@ -102,6 +102,8 @@ SYMBOLS = {
                                          ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
     "b2h_tpt_mask_numel": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _i64p, ctypes.c_int]),
     "b2h_tenc_mask_numel": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int64, _i64p, ctypes.c_int]),
+    "b2h_adam_step": (ctypes.c_int, [ctypes.POINTER(_vp)] * 4 + [_i64p, ctypes.c_int, ctypes.c_float, _vp, ctypes.c_float,
+                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int64, _vp, _vp]),
     "b2h_model_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                       ctypes.POINTER(ctypes.c_int)]),
     "b2h_kernel_supported": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -24,6 +24,7 @@
 #include "kernel_tenc_train.h"
 #include "kernel_tpt.h"
 #include "kernel_attn_long.h"
+#include "kernel_adam.h"
 #include "kernel_dropout_masks.h"
 #include "kernel_train_attn_long.h"
 #include "kernel_train_attn_mfma.h"
@@ -2141,6 +2142,89 @@ int64_t b2h_tpt_mask_numel(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, in
     const int count = tpt_nmasks(m);
     for (int i = 0; numel && i < std::min(count, capacity); ++i) numel[i] = (int64_t)tpt_mask_bytes(m, i, B, S, T);
     return count;
+}
+
+} // extern "C"
+
+// ---- optimizer.step() (kernel_adam.h) ------------------------------------------------------------------------
+namespace {
+// The double a float hyper-parameter stands for: the shortest decimal that rounds to it, as a Python caller wrote it
+// (0.999f means 0.999, not 0.99900001287).  1 - beta2 needs this: taken from the float's exact value it would be off
+// by 1.3e-5 of itself, and exp_avg_sq with it.
+double shortest_decimal(float x) {
+    char buf[32];
+    for (int digits = 1; digits <= 9; ++digits) {
+        std::snprintf(buf, sizeof buf, "%.*g", digits, (double)x);
+        if (std::strtof(buf, nullptr) == x) break;
+    }
+    return std::strtod(buf, nullptr);
+}
+} // namespace
+
+extern "C" {
+
+int b2h_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                  const int64_t* numel, int n_tensors, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                  float weight_decay, int64_t step, const int64_t* step_dev, void* stream) {
+    if (n_tensors < 0) return fail(B2H_ERR_INVALID, "n_tensors must be >= 0");
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(B2H_ERR_INVALID, "betas must be in [0, 1)");
+    if (!(eps >= 0.f)) return fail(B2H_ERR_INVALID, "eps must be >= 0");
+    if (!(weight_decay >= 0.f)) return fail(B2H_ERR_INVALID, "weight_decay must be >= 0");
+    if (!lr_dev && !(lr >= 0.f)) return fail(B2H_ERR_INVALID, "lr must be >= 0");
+    if (step_dev ? step < 0 : step < 1)
+        return fail(B2H_ERR_INVALID, "step counts from 1 (from 0 with step_dev: step + *step_dev must be >= 1)");
+    if (misaligned(lr_dev, 4) || misaligned(step_dev, 8)) return fail(B2H_ERR_INVALID, "lr_dev / step_dev is misaligned");
+    if (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel))
+        return fail(B2H_ERR_INVALID, "params / grads / exp_avg / exp_avg_sq / numel is NULL");
+    for (int i = 0; i < n_tensors; ++i) {
+        const std::string at = "[" + std::to_string(i) + "]";
+        if (numel[i] < 0) return fail(B2H_ERR_INVALID, "numel" + at + " is negative");
+        if (numel[i] == 0) continue; // the pointers of an empty tensor are never looked at
+        if (numel[i] > (int64_t)1 << 40) return fail(B2H_ERR_INVALID, "numel" + at + " is too large");
+        const void* ptr[4] = {params[i], grads[i], exp_avg[i], exp_avg_sq[i]};
+        for (const void* q : ptr) {
+            if (!q) return fail(B2H_ERR_INVALID, "a pointer of tensor " + at + " is NULL");
+            if (misaligned(q, 4)) return fail(B2H_ERR_INVALID, "the pointers of tensor " + at + " must be 4-byte aligned");
+        }
+        const size_t bytes = (size_t)numel[i] * 4;
+        for (int x = 0; x < 4; ++x)
+            for (int y = x + 1; y < 4; ++y)
+                if (overlaps(ptr[x], bytes, ptr[y], bytes))
+                    return fail(B2H_ERR_INVALID, "params, grads, exp_avg and exp_avg_sq of tensor " + at + " overlap");
+    }
+    AdArgs a;
+    a.b1 = shortest_decimal(beta1);
+    a.b2 = shortest_decimal(beta2);
+    a.w1 = (float)(1.0 - a.b1);
+    a.b2f = beta2;
+    a.w2 = (float)(1.0 - a.b2);
+    a.eps = eps;
+    a.wd = weight_decay;
+    a.lr = lr;
+    a.step = step;
+    a.step_dev = step_dev;
+    a.lr_dev = lr_dev;
+    a.bc2s = a.step_size = 0.f;
+    if (!step_dev && !lr_dev) ad_bias(a.b1, a.b2, (double)lr, step, &a.bc2s, &a.step_size);
+    for (int base = 0; base < n_tensors; base += kAdMaxTensors) { // at most kAdMaxTensors tensors per launch
+        a.n = std::min(n_tensors - base, kAdMaxTensors);
+        a.first[0] = 0;
+        for (int i = 0; i < kAdMaxTensors; ++i) {
+            const bool used = i < a.n && numel[base + i] > 0;
+            a.p[i] = used ? params[base + i] : nullptr;
+            a.g[i] = used ? grads[base + i] : nullptr;
+            a.m[i] = used ? exp_avg[base + i] : nullptr;
+            a.v[i] = used ? exp_avg_sq[base + i] : nullptr;
+            a.numel[i] = used ? numel[base + i] : 0;
+            a.first[i + 1] = a.first[i] + (a.numel[i] + 3) / 4;
+        }
+        const int64_t chunks = a.first[a.n];
+        if (chunks == 0) continue;
+        const unsigned blocks = (unsigned)std::min<int64_t>((chunks + kAdThreads - 1) / kAdThreads, kAdMaxBlocks);
+        hipLaunchKernelGGL(b2h_adam_step_k, dim3(blocks), dim3(kAdThreads), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return B2H_OK;
 }
 
 } // extern "C"

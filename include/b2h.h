@@ -167,6 +167,7 @@ int b2h_weighted_l1_joints(const float* pred, const float* target, const float* 
  * whatever kernel the inference path uses.  They read the weights straight from the caller's eight
  * fp32 tensors, never from the model's packed buffers: b2h_load_weights is not needed (nor called),
  * and an optimizer may update the tensors in place between launches.
+ * b2h_adam_step below is that optimizer: torch.optim.Adam's update of every tensor in one launch.
  *   params: host array of the 8 device fp32 tensors in state_dict order (w1, b1, ..., w4, b4), layouts
  *           as b2h_load_weights.
  * Like b2h_forward they are stream-ordered and asynchronous: none synchronises, allocates or reads
@@ -266,6 +267,7 @@ int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, 
  * All arithmetic is exact fp32 on the vector ALU, whatever b2h_tenc_set_kernel selected.  The parameters are
  * read straight from the caller's tensors (b2h_tenc_load_weights is neither needed nor called), so an
  * optimizer may update them in place between launches.
+ * b2h_adam_step below is that optimizer: torch.optim.Adam's update of every tensor in one launch.
  *   params: host array of the 5 + 12*nlayers device fp32 tensors in the order of b2h_tenc_load_weights
  *           (pos_encoder.pe first), 4-byte aligned.
  *   p     : the dropout probability (the reference passes one value everywhere), 0 <= p <= 1.
@@ -419,6 +421,7 @@ int b2h_tpt_build_item(const float* body, const float* right_hand, float* item, 
  * hidden2pose_projection) and its backward, built like the TransformerEnc pair above: exact fp32 on the
  * vector ALU, one kernel per operation, the parameters read straight from the caller's tensors
  * (b2h_tpt_load_weights is neither needed nor called).
+ * b2h_adam_step below is that optimizer: torch.optim.Adam's update of every tensor in one launch.
  *   params: host array of the 9 + 12*n_enc_layers + 18*n_dec_layers device fp32 tensors in the order of
  *           b2h_tpt_load_weights, 4-byte aligned.
  *   tokens: device int64 (B, S), 8-byte aligned.  An id outside [0, n_tokens) never indexes anything: its
@@ -532,6 +535,41 @@ int b2h_dropout_masks(uint8_t* const* masks, const int64_t* numel, int n_masks, 
  * host functions: nothing is read from the device. */
 int64_t b2h_tpt_mask_numel(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int64_t* numel, int capacity);
 int64_t b2h_tenc_mask_numel(const b2h_tenc* m, int64_t B, int64_t T, int64_t* numel, int capacity);
+
+/* optimizer.step() --------------------------------------------------------------
+ * The last line of the reference's loop body (steps/traintest.py:121, torch.optim.Adam(model.parameters(), lr) at :48):
+ * Adam with amsgrad = False, maximize = False and classic L2 weight decay, for every tensor of a model from one HIP
+ * kernel (kernel_adam.h), so that a host applies the gradients of b2h_backward / b2h_tenc_backward / b2h_tpt_backward
+ * without an optimizer of its own.  Per element, fp32, every line one rounding or one fused multiply-add (marked F):
+ *   g' = g + wd * p                         F   only if wd != 0
+ *   m  = m + (g' - m) * (1 - b1)            F   after the subtraction
+ *   v  = v * b2 + ((1 - b2) * g') * g'      F   after the two products v * b2 and (1 - b2) * g'
+ *   den = sqrt(v) / bc2s + eps                  IEEE square root and division
+ *   p  = p + (-step_size) * (m / den)       F   after the division
+ * with t = step + *step_dev (without the *step_dev term when step_dev is NULL), bc2s = sqrt(1 - b2^t) and
+ * step_size = lr / (1 - b1^t) evaluated in double and rounded to float once; b^t by repeated squaring.
+ *   params, grads, exp_avg, exp_avg_sq, numel: HOST arrays of n_tensors device pointers (fp32, contiguous, 4-byte
+ *                 aligned; a tensor whose four pointers are all 16-byte aligned takes the 16-byte path) and element
+ *                 counts.  params, exp_avg and exp_avg_sq are updated in place; grads is only read.  exp_avg and
+ *                 exp_avg_sq start as zeros.  The pointers of a tensor with numel 0 are not looked at.
+ *   lr, lr_dev  : the learning rate, or when lr_dev is not NULL the device float that replaces it (only read), so a
+ *                 captured step follows a schedule (adjust_learning_rate, steps/utils.py:301-307).
+ *   beta1, beta2, eps, weight_decay: torch's betas, eps, weight_decay.  Each beta stands for the shortest decimal
+ *                 that rounds to the float given (0.999f means 0.999), because 1 - beta2 taken from the float's exact
+ *                 value would be off by 1e-5 of itself; lr, eps and weight_decay are taken as the floats they are.
+ *   step, step_dev: the first update is step 1.  A captured HIP graph passes the device word step_dev (read by the
+ *                 kernel, never written), e.g. the number of updates made so far with step = 1, and advances it
+ *                 itself between replays; step + *step_dev must be >= 1.
+ * One launch per 80 tensors, their pointers and sizes in the kernel arguments; the result does not depend on how the
+ * tensors are grouped into calls.  Stream-ordered and asynchronous: it does not synchronise, allocate or read device
+ * memory on the host, so it can be captured.  Nothing is written past numel[i] elements.  B2H_ERR_INVALID, before
+ * anything is launched: a NULL array with n_tensors > 0, n_tensors < 0, numel[i] < 0, a NULL or not 4-byte-aligned
+ * pointer of a tensor with numel[i] > 0, two of the four arrays of one tensor overlapping, a beta outside [0, 1),
+ * eps < 0, weight_decay < 0, lr < 0 with lr_dev NULL, NaN in any of these, step < 1 with step_dev NULL, step < 0
+ * otherwise.  n_tensors == 0 or all sizes 0 is a no-op (B2H_OK). */
+int b2h_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                  const int64_t* numel, int n_tensors, float lr, const float* lr_dev, float beta1, float beta2,
+                  float eps, float weight_decay, int64_t step, const int64_t* step_dev, void* stream);
 
 /* Introspection / measurement -------------------------------------------- */
 

@@ -6,7 +6,9 @@
   * one full step of the reference loop body (steps/traintest.py:94-121) at 128 x 200: forward,
     mask_output, maskedPoseL1, backward, torch.optim.Adam (lr 2e-4), steady state, HIP events;
   * the same step of the oracle's torch port on the host CPU -- context only, not a baseline.
-    python tools/bench_train.py [B=65536] [T=200]"""
+    python tools/bench_train.py [B=65536] [T=200] [optimizer=torch|native]
+The third argument selects the optimizer of the reference step, torch.optim.Adam or hps.Adam,
+and is recorded only when given."""
 import json
 import os
 import sys
@@ -21,6 +23,9 @@ PEAK = 157.3e12
 C = 30
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+OPTIMIZER = sys.argv[3] if len(sys.argv) > 3 else None    # absent: torch.optim.Adam, and no key in the record
+if OPTIMIZER not in (None, "torch", "native"):
+    sys.exit(f"optimizer must be torch or native, got {OPTIMIZER!r}")
 dev = torch.device("cuda:0")
 
 
@@ -97,7 +102,7 @@ SB, ST = 128, 200
 lengths = [ST - (i * 37) % 120 for i in range(SB)]
 xs = torch.rand((SB, ST, 12, 2), device=dev, generator=g) - 0.5
 ts = (torch.rand((SB, ST, 21, 2), device=dev, generator=g) - 0.5) * 0.2
-opt = torch.optim.Adam(m.parameters(), lr=2e-4)
+opt = (hps.Adam if OPTIMIZER == "native" else torch.optim.Adam)(m.parameters(), lr=2e-4)
 crit = hps.maskedPoseL1()
 
 
@@ -111,6 +116,8 @@ def step():
     opt.step()
 
 
+if OPTIMIZER is not None:
+    out["optimizer"] = OPTIMIZER
 out["reference_step_128x200_ms"] = events_ms(step, 20, warm=5)
 
 # context only: the oracle's torch port, same step on the host CPU

@@ -7,8 +7,9 @@ training kernels are plain per-operation fp32 kernels and carry no speed bar.
   * the same step with torch-ROCm's own nn.TransformerEncoder (the reference's model restated with torch
     modules) on the same GPU;
   * the same step of the tests' torch port (tests/tenc_train_ref.py) on the host CPU.
-    python tools/bench_train_tenc.py [B=128] [T=100] [dropout_source=torch|native]
-The third argument selects model.set_dropout_source and is recorded only when given."""
+    python tools/bench_train_tenc.py [B=128] [T=100] [dropout_source=torch|native] [optimizer=torch|native]
+The third argument selects model.set_dropout_source, the fourth the optimizer of the library's
+step, torch.optim.Adam or hps.Adam (section 21); each is recorded only when given."""
 import json
 import os
 import sys
@@ -27,6 +28,9 @@ from tenc_train_ref import leaf_state, param_keys, port_forward  # noqa: E402
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 DROPOUT_SOURCE = sys.argv[3] if len(sys.argv) > 3 else None    # absent: the model's default, and no key in the record
+OPTIMIZER = sys.argv[4] if len(sys.argv) > 4 else None    # absent: torch.optim.Adam, and no key in the record
+if OPTIMIZER not in (None, "torch", "native"):
+    sys.exit(f"optimizer must be torch or native, got {OPTIMIZER!r}")
 L, P, LR = 4, 0.1, 2e-4
 dev = torch.device("cuda:0")
 
@@ -77,8 +81,8 @@ ts = (torch.rand((B, T, 21, 2), device=dev, generator=g) - 0.5) * 0.2
 crit = hps.maskedPoseL1()
 
 
-def make_step(forward, params):
-    opt = torch.optim.Adam(params, lr=LR)
+def make_step(forward, params, optimizer=None):
+    opt = (hps.Adam if optimizer == "native" else torch.optim.Adam)(params, lr=LR)
 
     def step():
         prediction = forward(xs)
@@ -94,7 +98,9 @@ def make_step(forward, params):
 out = {"B": B, "T": T, "nlayers": L, "dropout": P}
 if DROPOUT_SOURCE is not None:
     out["dropout_source"] = DROPOUT_SOURCE
-out["reference_step_ms"] = events_ms(make_step(m, list(m.parameters())), 20)
+if OPTIMIZER is not None:
+    out["optimizer"] = OPTIMIZER
+out["reference_step_ms"] = events_ms(make_step(m, list(m.parameters()), OPTIMIZER), 20)
 tm = TorchEnc().to(dev).train()
 pe = m.pos_encoder.pe
 out["torch_rocm_nn_transformer_step_ms_context_only"] = events_ms(make_step(lambda x: tm(x, pe), list(tm.parameters())), 20)

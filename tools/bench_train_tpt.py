@@ -14,8 +14,10 @@ The two shapes of the record (DESIGN.md sections 13 and 16):
     python tools/bench_train_tpt.py 128 40 200 8 5 mfma   the same with model.set_train_kernels("mfma")
     python tools/bench_train_tpt.py 128 40 200 8 5 mfma mfma   and with model.set_train_linear("mfma") (section 19)
     python tools/bench_train_tpt.py 128 40 200 8 5 mfma mfma native   and with model.set_dropout_source("native") (section 20)
+    python tools/bench_train_tpt.py 128 40 200 8 5 mfma mfma native native   and with hps.Adam as the optimizer (section 21)
     python tools/bench_train_tpt.py [B=128] [S=40] [T=100] [n_joints=12] [reps=5] [kernels=valu|mfma] [linear=valu|mfma]
-                                    [dropout_source=torch|native]"""
+                                    [dropout_source=torch|native] [optimizer=torch|native]
+The optimizer argument concerns the library's step only; torch-ROCm's own model always steps with torch.optim.Adam."""
 import json
 import os
 import sys
@@ -36,6 +38,9 @@ REPS = int(sys.argv[5]) if len(sys.argv) > 5 else 5
 KERNELS = sys.argv[6] if len(sys.argv) > 6 else "valu"
 LINEAR = sys.argv[7] if len(sys.argv) > 7 else None    # absent: the model's default, and no key in the record
 DROPOUT_SOURCE = sys.argv[8] if len(sys.argv) > 8 else None    # absent: the model's default, and no key in the record
+OPTIMIZER = sys.argv[9] if len(sys.argv) > 9 else None    # absent: torch.optim.Adam, and no key in the record
+if OPTIMIZER not in (None, "torch", "native"):
+    sys.exit(f"optimizer must be torch or native, got {OPTIMIZER!r}")
 N_TOKENS, L, P, LR = 1000, 4, 0.1, 2e-4
 dev = torch.device("cuda:0")
 
@@ -96,8 +101,8 @@ ts = (torch.rand((B, T, 21, 2), device=dev, generator=g) - 0.5) * 0.2
 crit = hps.maskedPoseL1()
 
 
-def make_step(forward, params):
-    opt = torch.optim.Adam(params, lr=LR)
+def make_step(forward, params, optimizer=None):
+    opt = (hps.Adam if optimizer == "native" else torch.optim.Adam)(params, lr=LR)
 
     def step():
         prediction = forward(toks, xs)
@@ -116,7 +121,9 @@ if LINEAR is not None:
     out["linear"] = LINEAR
 if DROPOUT_SOURCE is not None:
     out["dropout_source"] = DROPOUT_SOURCE
-out["reference_step_ms"], out["reference_step_ms_min"] = events_ms(make_step(m, list(m.parameters())), 10)
+if OPTIMIZER is not None:
+    out["optimizer"] = OPTIMIZER
+out["reference_step_ms"], out["reference_step_ms_min"] = events_ms(make_step(m, list(m.parameters()), OPTIMIZER), 10)
 out["reference_step_ms_max"] = SPREAD[0]
 tm = TorchTpt().to(dev).train()
 out["torch_rocm_nn_transformer_step_ms_context_only"], out["torch_rocm_nn_transformer_step_ms_min"] = events_ms(
