@@ -1,8 +1,8 @@
 """The life cycle of the libb2h model handle behind a torch module, shared by ConvModel, TransformerEnc and
 TextPoseTransformer: created on the parameters' device, re-created when that device (or whatever else the
 handle was made for) changes, its weights repacked when a parameter is replaced or edited in place, destroyed
-with the module; plus the workspace that only grows and the two pointer helpers of the training paths, and the
-source of the two transformers' dropout masks (`NativeDropout`).
+with the module; plus the workspace that only grows and the two pointer helpers of the training paths, the
+source of the two transformers' dropout masks (`NativeDropout`) and their one autograd Function (`TrainFn`).
 """
 import ctypes
 import math
@@ -85,6 +85,102 @@ class NativeDropout:
                                              ctypes.c_void_p(step.data_ptr()), ctypes.c_void_p(st)))
             step.add_(1)
         return masks
+
+    def _drawn_masks(self, p, *dims):
+        """{key: mask} over `_mask_order(*dims)` from the selected source, drawn in that order; empty at p = 0."""
+        if p == 0.0:
+            return {}
+        order = self._mask_order(*dims)
+        if self.dropout_source == "native":
+            return self._native_dropout_masks(order, p)
+        dev = self._device()
+        return {key: (torch.rand(shape, device=dev) >= p).to(torch.uint8) for key, shape in order}
+
+    def _checked_masks(self, masks, p, dev, *dims):
+        """The given {key: mask} as the list a training entry point takes (`_mask_order(*dims)`), each one validated."""
+        if (p > 0.0) != bool(masks):
+            raise ValueError("masks must be given exactly when the dropout probability is > 0")
+        order = self._mask_order(*dims) if masks else []
+        for key, shape in order:
+            m = masks[key]
+            if m.shape != shape or m.dtype != torch.uint8 or m.device != dev or not m.is_contiguous():
+                raise RuntimeError(f"mask {key}: expected a contiguous uint8 tensor of shape {shape} on {dev}")
+        return [masks[k] for k, _ in order]
+
+
+class TrainFn(torch.autograd.Function):
+    """y = model(lead, x) of a transformer in training mode with its gradient, through the model's b2h_*_train_forward
+    / b2h_*_backward (exact fp32): `apply(model, p, masks, lead, x, *params)`.  `lead` is the model's leading tensor
+    without a gradient: TransformerEnc's `pe` or TextPoseTransformer's token ids.  The parameters go in as themselves (their own data_ptr, saved for backward, so autograd's version check
+    catches an in-place edit between forward and backward).  The context keeps the saved-activation buffer, `lead` and
+    the masks alive; the backward needs neither x nor y (the reference's loop overwrites the prediction's tail in place
+    before the loss).  The forward sets the handle to the model's route and records it, the backward sets it from
+    that record: a backward runs the kernels its forward ran, whatever the model says by then.
+
+    The model supplies what differs:
+        _TRAIN_FNS                  the names of its train_bytes, train_forward and backward entry points
+        _TRAIN_LEAD_IS_PARAM        whether `lead` travels in the parameter array and is checked like a parameter
+                                    (`pe`), or is an argument of its own that only has to be aligned (the token ids)
+        _train_shapes(lead, x)      the batch as the entry points take it, (B, T) or (B, S, T); y's shape; dx's shape
+        _train_head(lead, params)   the entry points' arguments between the handle and x (forward) / the masks (backward)
+        _train_route()              (setter entry point, value) pairs that select the kernels of a forward"""
+
+    @staticmethod
+    def _set_route(lib, model, route):
+        for setter, value in route:
+            _lib.check(getattr(lib, setter)(model._handle, value))
+
+    @staticmethod
+    def forward(ctx, model, p, masks, lead, x, *params):
+        for t in ((lead,) if model._TRAIN_LEAD_IS_PARAM else ()) + params:
+            if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("training needs contiguous float32 parameters on the input's device")
+        lib, dev = model._ensure_created()
+        x = _aligned(x)
+        if not model._TRAIN_LEAD_IS_PARAM:
+            lead = _aligned(lead)
+        dims, yshape, xshape = model._train_shapes(lead, x)
+        y = torch.empty(yshape, dtype=torch.float32, device=x.device)
+        nbytes = getattr(lib, model._TRAIN_FNS[0])(model._handle, *dims, 0)
+        saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
+        route = model._train_route()
+        with _lib.on_device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            TrainFn._set_route(lib, model, route)
+            _lib.check(getattr(lib, model._TRAIN_FNS[1])(
+                model._handle, *model._train_head(lead, params), ctypes.c_void_p(x.data_ptr()),
+                _ptrs(masks) if masks else None, p, ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(saved.data_ptr()), nbytes,
+                *dims, ctypes.c_void_p(st)))
+        ctx.model, ctx.p, ctx.masks, ctx.dims, ctx.xshape, ctx.route = model, p, masks, dims, xshape, route
+        ctx.save_for_backward(saved, lead, *params)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        saved, lead, *params = ctx.saved_tensors
+        model, masks, dims = ctx.model, ctx.masks, ctx.dims
+        need_dx = ctx.needs_input_grad[4]
+        dev = saved.device
+        if dims[0] == 0:
+            grads = [torch.zeros_like(t) for t in params]
+            dx = torch.zeros(ctx.xshape, dtype=torch.float32, device=dev) if need_dx else None
+        else:
+            lib, dev = model._ensure_created()
+            dy = _aligned(dy.to(torch.float32).contiguous())   # autograd may hand over an expanded / CopySlices gradient
+            grads = [torch.empty_like(t) for t in params]
+            dx = torch.empty(ctx.xshape, dtype=torch.float32, device=dev) if need_dx else None
+            nbytes = getattr(lib, model._TRAIN_FNS[0])(model._handle, *dims, 1)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            with _lib.on_device(dev):
+                st = torch.cuda.current_stream(dev).cuda_stream
+                TrainFn._set_route(lib, model, ctx.route)
+                _lib.check(getattr(lib, model._TRAIN_FNS[2])(
+                    model._handle, *model._train_head(lead, params), _ptrs(masks) if masks else None, ctx.p,
+                    ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(saved.data_ptr()), saved.numel(),
+                    ctypes.c_void_p(dx.data_ptr()) if dx is not None else None, _ptrs(grads), ctypes.c_void_p(ws.data_ptr()),
+                    nbytes, *dims, ctypes.c_void_p(st)))
+        return (None, None, None, None, dx) + tuple(g if ctx.needs_input_grad[5 + i] else None for i, g in enumerate(grads))
 
 
 class NativeModule:

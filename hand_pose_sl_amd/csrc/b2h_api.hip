@@ -1471,34 +1471,43 @@ const char* tt_shape_refusal(const b2h_tenc* m, int64_t B, int64_t T) {
     return nullptr;
 }
 
-// Checks shared by b2h_tenc_train_forward / b2h_tenc_backward, as tenc_launch makes them.
-int tt_check(const b2h_tenc* m, const float* const* params, const uint8_t* const* masks, float p, int64_t B, int64_t T) {
-    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+int tenc_nmasks(const b2h_tenc* m) { return 1 + 4 * m->nlayers; }
+
+// Elements of every keep-mask, in the order of `masks`: pos, then per layer attn, drop1, ff, drop2.
+std::vector<size_t> tenc_mask_bytes(const b2h_tenc* m, int64_t B, int64_t T) {
+    std::vector<size_t> n(tenc_nmasks(m), (size_t)B * T * kTtD);
+    n[0] = (size_t)B * T * kInCh;
+    for (size_t i = 1; i < n.size(); i += 4) n[i] = (size_t)B * kTtHeads * T * T;
+    return n;
+}
+
+// Checks shared by the train_forward and backward of both transformers (the model is not NULL), as tenc_launch makes
+// them.  shape_refusal: why the model refuses the batch, or nullptr.
+int tt_check(const char* shape_refusal, const float* const* params, size_t nparams, const uint8_t* const* masks, int nmasks,
+             float p) {
     if (!params) return fail(B2H_ERR_INVALID, "params is NULL");
     if (!(p >= 0.f && p <= 1.f)) return fail(B2H_ERR_INVALID, "dropout p must be in [0, 1]");
     if ((p > 0.f) != (masks != nullptr)) return fail(B2H_ERR_INVALID, "masks must be given exactly when p > 0");
-    if (const char* why = tt_shape_refusal(m, B, T)) return fail(B2H_ERR_SHAPE, why);
-    for (size_t i = 0; i < m->sizes.size(); ++i) {
+    if (shape_refusal) return fail(B2H_ERR_SHAPE, shape_refusal);
+    for (size_t i = 0; i < nparams; ++i) {
         if (!params[i]) return fail(B2H_ERR_INVALID, "params[" + std::to_string(i) + "] is NULL");
         if (misaligned(params[i], 4)) return fail(B2H_ERR_INVALID, "params must be 4-byte aligned fp32 tensors");
     }
     if (masks)
-        for (int i = 0; i < 1 + 4 * m->nlayers; ++i)
+        for (int i = 0; i < nmasks; ++i)
             if (!masks[i]) return fail(B2H_ERR_INVALID, "masks[" + std::to_string(i) + "] is NULL");
     return B2H_OK;
 }
 
-// The read-only operands of a training call for check_overlap: its plain inputs, the parameters and the masks.
-std::vector<Span> tt_read_only(const b2h_tenc* m, const float* const* params, const uint8_t* const* masks, int64_t N,
-                               int64_t T, std::vector<Span> ins) {
+// The read-only operands of a training call for check_overlap: its plain inputs, the parameters (floats each) and
+// the masks (bytes each).
+std::vector<Span> tt_read_only(const float* const* params, const std::vector<size_t>& floats, const uint8_t* const* masks,
+                               const std::vector<size_t>& mask_bytes, std::vector<Span> ins) {
+    ins.reserve(ins.size() + floats.size() + mask_bytes.size());
     for (Span& in : ins) in.what = "an input";
-    for (size_t i = 0; i < m->sizes.size(); ++i) ins.push_back({params[i], m->sizes[i] * 4, "a parameter"});
+    for (size_t i = 0; i < floats.size(); ++i) ins.push_back({params[i], floats[i] * 4, "a parameter"});
     if (masks)
-        for (int i = 0; i < 1 + 4 * m->nlayers; ++i) {
-            const int kind = i == 0 ? -1 : (i - 1) % 4;
-            const size_t n = kind < 0 ? (size_t)N * kInCh : (kind == 0 ? (size_t)N * kTtHeads * T : (size_t)N * kTtD);
-            ins.push_back({masks[i], n, "a mask"});
-        }
+        for (size_t i = 0; i < mask_bytes.size(); ++i) ins.push_back({masks[i], mask_bytes[i], "a mask"});
     return ins;
 }
 
@@ -1619,7 +1628,8 @@ size_t b2h_tenc_train_bytes(const b2h_tenc* m, int64_t B, int64_t T, int which) 
 
 int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float* x, const uint8_t* const* masks, float p,
                            float* y, void* saved, size_t saved_bytes, int64_t B, int64_t T, void* stream) {
-    if (int rc = tt_check(m, params, masks, p, B, T)) return rc;
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (int rc = tt_check(tt_shape_refusal(m, B, T), params, m->sizes.size(), masks, tenc_nmasks(m), p)) return rc;
     if (B == 0) return B2H_OK;
     if (!x || !y || !saved) return fail(B2H_ERR_INVALID, "NULL pointer");
     if (int rc = check_device(m->device)) return rc;
@@ -1630,7 +1640,7 @@ int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float*
     if (saved_bytes < need)
         return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tenc_train_bytes (" + std::to_string(need) + " B)");
     if (int rc = check_overlap({{y, (size_t)N * kOutCh * 4}, {saved, need}},
-                               tt_read_only(m, params, masks, N, T, {{x, (size_t)N * kInCh * 4}})))
+                               tt_read_only(params, m->sizes, masks, tenc_mask_bytes(m, B, T), {{x, (size_t)N * kInCh * 4}})))
         return rc;
     hipStream_t st = (hipStream_t)stream;
     const TtLin ln{st, false}; // TransformerEnc keeps the Linear kernels of kernel_tenc_train.h
@@ -1657,7 +1667,8 @@ int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float*
 int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* const* masks, float p, const float* dy,
                       const void* saved, size_t saved_bytes, float* dx, float* const* grads, void* scratch,
                       size_t scratch_bytes, int64_t B, int64_t T, void* stream) {
-    if (int rc = tt_check(m, params, masks, p, B, T)) return rc;
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (int rc = tt_check(tt_shape_refusal(m, B, T), params, m->sizes.size(), masks, tenc_nmasks(m), p)) return rc;
     if (B == 0) return fail(B2H_ERR_SHAPE, "b2h_tenc_backward needs B >= 1 (the gradients of an empty batch are not defined here)");
     if (!dy || !saved || !scratch) return fail(B2H_ERR_INVALID, "dy / saved / scratch is NULL");
     if (!grads) return fail(B2H_ERR_INVALID, "grads is NULL");
@@ -1678,7 +1689,8 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
     }
     if (dx) outs.push_back({dx, (size_t)N * kInCh * 4});
     outs.push_back({scratch, need});
-    if (int rc = check_overlap(outs, tt_read_only(m, params, masks, N, T, {{dy, (size_t)N * kOutCh * 4}, {saved, need_saved}})))
+    if (int rc = check_overlap(outs, tt_read_only(params, m->sizes, masks, tenc_mask_bytes(m, B, T),
+                                                  {{dy, (size_t)N * kOutCh * 4}, {saved, need_saved}})))
         return rc;
 
     hipStream_t st = (hipStream_t)stream;
@@ -1775,12 +1787,16 @@ size_t tpt_scratch_bytes(int64_t Ns, int64_t Nt, bool lng) {
 int tpt_nparams(const b2h_tpt* m) { return 9 + 12 * m->n_enc + 18 * m->n_dec; }
 int tpt_nmasks(const b2h_tpt* m) { return 4 * m->n_enc + 6 * m->n_dec; }
 
-// Elements of keep-mask i: per encoder layer attn, drop1, ff, drop2; per decoder layer self_attn, drop1,
-// cross_attn, drop2, ff, drop3.
-size_t tpt_mask_bytes(const b2h_tpt* m, int i, int64_t B, int64_t S, int64_t T) {
-    if (i < 4 * m->n_enc) return i % 4 == 0 ? (size_t)B * kTtHeads * S * S : (size_t)B * S * kTtD;
-    const int k = (i - 4 * m->n_enc) % 6;
-    return k == 0 ? (size_t)B * kTtHeads * T * T : (k == 2 ? (size_t)B * kTtHeads * T * S : (size_t)B * T * kTtD);
+// Elements of every keep-mask, in the order of `masks`: per encoder layer attn, drop1, ff, drop2; per decoder layer
+// self_attn, drop1, cross_attn, drop2, ff, drop3.
+std::vector<size_t> tpt_mask_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T) {
+    std::vector<size_t> n(tpt_nmasks(m), (size_t)B * T * kTtD);
+    for (int i = 0; i < 4 * m->n_enc; ++i) n[i] = i % 4 == 0 ? (size_t)B * kTtHeads * S * S : (size_t)B * S * kTtD;
+    for (size_t i = 4 * m->n_enc; i < n.size(); i += 6) {
+        n[i] = (size_t)B * kTtHeads * T * T;
+        n[i + 2] = (size_t)B * kTtHeads * T * S;
+    }
+    return n;
 }
 
 // Why the training calls refuse a (B, S, T) batch, or nullptr (b2h_tpt_mask_numel answers the same shapes).
@@ -1793,35 +1809,14 @@ const char* tptt_shape_refusal(int64_t B, int64_t S, int64_t T) {
     return nullptr;
 }
 
-// Checks shared by b2h_tpt_train_forward / b2h_tpt_backward, as tt_check makes them.
+// Checks shared by b2h_tpt_train_forward / b2h_tpt_backward: tt_check's, then the token ids.
 int tptt_check(const b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks, float p,
                int64_t B, int64_t S, int64_t T) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
-    if (!params) return fail(B2H_ERR_INVALID, "params is NULL");
-    if (!(p >= 0.f && p <= 1.f)) return fail(B2H_ERR_INVALID, "dropout p must be in [0, 1]");
-    if ((p > 0.f) != (masks != nullptr)) return fail(B2H_ERR_INVALID, "masks must be given exactly when p > 0");
-    if (const char* why = tptt_shape_refusal(B, S, T)) return fail(B2H_ERR_SHAPE, why);
-    for (int i = 0; i < tpt_nparams(m); ++i) {
-        if (!params[i]) return fail(B2H_ERR_INVALID, "params[" + std::to_string(i) + "] is NULL");
-        if (misaligned(params[i], 4)) return fail(B2H_ERR_INVALID, "params must be 4-byte aligned fp32 tensors");
-    }
-    if (masks)
-        for (int i = 0; i < tpt_nmasks(m); ++i)
-            if (!masks[i]) return fail(B2H_ERR_INVALID, "masks[" + std::to_string(i) + "] is NULL");
+    if (int rc = tt_check(tptt_shape_refusal(B, S, T), params, tpt_nparams(m), masks, tpt_nmasks(m), p)) return rc;
     if (B > 0 && !tokens) return fail(B2H_ERR_INVALID, "tokens is NULL");
     if (misaligned(tokens, 8)) return fail(B2H_ERR_INVALID, "tokens must be 8-byte aligned");
     return B2H_OK;
-}
-
-// The read-only operands of a training call for check_overlap: its plain inputs, the parameters and the masks.
-std::vector<Span> tptt_read_only(const b2h_tpt* m, const float* const* params, const uint8_t* const* masks, int64_t B,
-                                 int64_t S, int64_t T, std::vector<Span> ins) {
-    for (Span& in : ins) in.what = "an input";
-    const std::vector<size_t> sizes = tpt_param_floats(m);
-    for (size_t i = 0; i < sizes.size(); ++i) ins.push_back({params[i], sizes[i] * 4, "a parameter"});
-    if (masks)
-        for (int i = 0; i < tpt_nmasks(m); ++i) ins.push_back({masks[i], tpt_mask_bytes(m, i, B, S, T), "a mask"});
-    return ins;
 }
 
 void tt_layernorm(hipStream_t st, const float* X, const float* gamma, const float* beta, float* Y, float* stats, int64_t N) {
@@ -1912,8 +1907,8 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     if (saved_bytes < need)
         return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes (" + std::to_string(need) + " B)");
     if (int rc = check_overlap({{y, (size_t)Nt * m->nout * 4}, {saved, need}},
-                               tptt_read_only(m, params, masks, B, S, T,
-                                              {{tokens, (size_t)Ns * 8}, {x, (size_t)Nt * m->ninp * 4}})))
+                               tt_read_only(params, tpt_param_floats(m), masks, tpt_mask_bytes(m, B, S, T),
+                                            {{tokens, (size_t)Ns * 8}, {x, (size_t)Nt * m->ninp * 4}})))
         return rc;
     hipStream_t st = (hipStream_t)stream;
     const TtLin ln{st, tpt_train_linear(m) == TrainLinear::kMfma};
@@ -1999,8 +1994,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     }
     if (dx) outs.push_back({dx, (size_t)Nt * m->ninp * 4});
     outs.push_back({scratch, need});
-    if (int rc = check_overlap(outs, tptt_read_only(m, params, masks, B, S, T,
-                                                    {{tokens, (size_t)Ns * 8}, {dy, (size_t)Nt * m->nout * 4}, {saved, need_saved}})))
+    if (int rc = check_overlap(outs, tt_read_only(params, sizes, masks, tpt_mask_bytes(m, B, S, T),
+                                                  {{tokens, (size_t)Ns * 8}, {dy, (size_t)Nt * m->nout * 4}, {saved, need_saved}})))
         return rc;
 
     hipStream_t st = (hipStream_t)stream;
@@ -2131,17 +2126,16 @@ int b2h_dropout_masks(uint8_t* const* masks, const int64_t* numel, int n_masks, 
 
 int64_t b2h_tenc_mask_numel(const b2h_tenc* m, int64_t B, int64_t T, int64_t* numel, int capacity) {
     if (!m || tt_shape_refusal(m, B, T)) return 0;
-    const int count = 1 + 4 * m->nlayers;
-    for (int i = 0; numel && i < std::min(count, capacity); ++i)
-        numel[i] = i == 0 ? B * T * kInCh : ((i - 1) % 4 == 0 ? B * kTtHeads * T * T : B * T * kTtD);
-    return count;
+    const std::vector<size_t> n = tenc_mask_bytes(m, B, T);
+    for (int i = 0; numel && i < std::min((int)n.size(), capacity); ++i) numel[i] = (int64_t)n[i];
+    return (int64_t)n.size();
 }
 
 int64_t b2h_tpt_mask_numel(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, int64_t* numel, int capacity) {
     if (!m || tptt_shape_refusal(B, S, T)) return 0;
-    const int count = tpt_nmasks(m);
-    for (int i = 0; numel && i < std::min(count, capacity); ++i) numel[i] = (int64_t)tpt_mask_bytes(m, i, B, S, T);
-    return count;
+    const std::vector<size_t> n = tpt_mask_bytes(m, B, S, T);
+    for (int i = 0; numel && i < std::min((int)n.size(), capacity); ++i) numel[i] = (int64_t)n[i];
+    return (int64_t)n.size();
 }
 
 } // extern "C"

@@ -14,7 +14,7 @@ through the C ABI (`b2h_tpt_forward`).  Like the reference, the model passes no 
 like any other id) and never applies its two positional encodings, which exist only as `pe` buffers.
 
 Training: in training mode with autograd enabled and a parameter or `input_pose` requiring a gradient,
-`model(input_tokens, input_pose)` runs `_TptTrainFn` -- an exact-fp32 HIP forward and backward
+`model(input_tokens, input_pose)` runs `_native.TrainFn` -- an exact-fp32 HIP forward and backward
 (b2h_tpt_train_forward / b2h_tpt_backward, kernel_tpt_train.h) that read the parameters' own storage -- so the
 reference's loop body (steps/traintest.py:105-121) runs unchanged with any torch optimizer, at S <= 128 tokens and
 T <= 1024 frames (the trainer pads to `--max-frames 200`, run.py:28; beyond 128 frames the decoder's two attentions
@@ -36,7 +36,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import NativeDropout, NativeModule, _aligned, _ptrs
+from ._native import NativeDropout, NativeModule, TrainFn, _ptrs
 from .transformer_enc import TENC_KERNELS, PositionalEncoding
 
 
@@ -151,13 +151,7 @@ class TextPoseTransformer(NativeDropout, NativeModule, nn.Module):
         torch's layers: per encoder layer ("enc", l, name) with name = `attn` (B, 4, S, S), `drop1`, `ff`, `drop2`
         (B, S, 128 each); then per decoder layer ("dec", l, name) with name = `self_attn` (B, 4, T, T), `drop1`
         (B, T, 128), `cross_attn` (B, 4, T, S), `drop2`, `ff`, `drop3` (B, T, 128 each).  An empty dict at p = 0."""
-        p = self._dropout_p
-        if p == 0.0:
-            return {}
-        if self.dropout_source == "native":
-            return self._native_dropout_masks(self._mask_order(B, S, T), p)
-        dev = self._device()
-        return {key: (torch.rand(shape, device=dev) >= p).to(torch.uint8) for key, shape in self._mask_order(B, S, T)}
+        return self._drawn_masks(self._dropout_p, B, S, T)
 
     def _check_inputs(self, input_tokens, input_pose):
         if input_pose.dim() != 4 or input_pose.shape[2] * input_pose.shape[3] != self.ninp:
@@ -176,20 +170,29 @@ class TextPoseTransformer(NativeDropout, NativeModule, nn.Module):
                 raise IndexError("index out of range in self")  # nn.Embedding's message
 
     def _forward_train(self, input_tokens, input_pose, masks):
-        """The differentiable forward (`_TptTrainFn`) with the given keep-masks (`_draw_dropout_masks`)."""
+        """The differentiable forward (`_native.TrainFn`) with the given keep-masks (`_draw_dropout_masks`)."""
         self._check_inputs(input_tokens, input_pose)
         dev = self._device()
         tok = input_tokens.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
         x = input_pose.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
         p = self._dropout_p
-        if (p > 0.0) != bool(masks):
-            raise ValueError("masks must be given exactly when the dropout probability is > 0")
-        order = self._mask_order(tok.shape[0], tok.shape[1], x.shape[1]) if masks else []
-        for key, shape in order:
-            m = masks[key]
-            if m.shape != shape or m.dtype != torch.uint8 or m.device != x.device or not m.is_contiguous():
-                raise RuntimeError(f"mask {key}: expected a contiguous uint8 tensor of shape {shape} on {x.device}")
-        return _TptTrainFn.apply(self, p, [masks[k] for k, _ in order], tok, x, *self._tensors())
+        masks = self._checked_masks(masks, p, x.device, tok.shape[0], tok.shape[1], x.shape[1])
+        return TrainFn.apply(self, p, masks, tok, x, *self._tensors())
+
+    # what TrainFn asks of the model: the token ids are an argument of their own; the two routes travel to the backward
+    _TRAIN_FNS = ("b2h_tpt_train_bytes", "b2h_tpt_train_forward", "b2h_tpt_backward")
+    _TRAIN_LEAD_IS_PARAM = False
+
+    def _train_shapes(self, tok, x):
+        B, S, T = tok.shape[0], tok.shape[1], x.shape[1]
+        return (B, S, T), (B, T, self.nout // 2, 2), (B, T, self.ninp // 2, 2)
+
+    def _train_head(self, tok, params):
+        return _ptrs(params), ctypes.c_void_p(tok.data_ptr())
+
+    def _train_route(self):
+        return (("b2h_tpt_set_train_kernel", _lib.TRAIN_KERNELS[self.train_kernels]),
+                ("b2h_tpt_set_train_linear", _lib.TRAIN_KERNELS[self.train_linear]))
 
     def forward(self, input_tokens, input_pose):
         train = self._wants_grad(input_tokens, input_pose) and self._device().type == "cuda"
@@ -309,70 +312,4 @@ class TextPoseTransformer(NativeDropout, NativeModule, nn.Module):
         return self._run(input_tokens, body, (flags, float(factor), n_frames if mask_tail else None))
 
 
-class _TptTrainFn(torch.autograd.Function):
-    """y = TextPoseTransformer(tokens, x) in training mode with its gradient: b2h_tpt_train_forward /
-    b2h_tpt_backward (exact fp32, kernel_tpt_train.h; kernel_train_attn_long.h for the decoder's attentions at
-    128 < T <= 1024, or kernel_train_attn_mfma.h when the model's `train_kernels` is "mfma": the forward sets the
-    handle's train kernel from the model and records it, the backward sets it from that record; the Linear kernels
-    of `train_linear`, kernel_tenc_train.h or kernel_train_linear_mfma.h, travel the same way), after
-    transformer_enc._TencTrainFn.  The parameters go in
-    as themselves (their own data_ptr, saved for backward, so autograd's version check catches an in-place edit
-    between forward and backward).  The context keeps the saved-activation buffer, the token ids and the masks
-    alive; the backward needs neither x nor y (the reference's loop overwrites the prediction's tail in place
-    before the loss).  The token ids get no gradient; token_embedding.weight's is dense."""
-
-    @staticmethod
-    def forward(ctx, model, p, masks, tok, x, *params):
-        for t in params:
-            if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError("training needs contiguous float32 parameters on the input's device")
-        lib, dev = model._ensure_created()
-        x = _aligned(x)
-        tok = _aligned(tok)
-        B, S, T = tok.shape[0], tok.shape[1], x.shape[1]
-        y = torch.empty((B, T, model.nout // 2, 2), dtype=torch.float32, device=x.device)
-        nbytes = lib.b2h_tpt_train_bytes(model._handle, B, S, T, 0)
-        saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
-        kernels, linear = model.train_kernels, model.train_linear
-        with _lib.on_device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.b2h_tpt_set_train_kernel(model._handle, _lib.TRAIN_KERNELS[kernels]))
-            _lib.check(lib.b2h_tpt_set_train_linear(model._handle, _lib.TRAIN_KERNELS[linear]))
-            _lib.check(lib.b2h_tpt_train_forward(model._handle, _ptrs(params), ctypes.c_void_p(tok.data_ptr()),
-                                                 ctypes.c_void_p(x.data_ptr()), _ptrs(masks) if masks else None, p,
-                                                 ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(saved.data_ptr()), nbytes,
-                                                 B, S, T, ctypes.c_void_p(st)))
-        ctx.model, ctx.p, ctx.masks, ctx.shape, ctx.kernels = model, p, masks, (B, S, T), kernels
-        ctx.linear = linear
-        ctx.save_for_backward(saved, tok, *params)
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        saved, tok, *params = ctx.saved_tensors
-        model, masks = ctx.model, ctx.masks
-        need_dx = ctx.needs_input_grad[4]
-        B, S, T = ctx.shape
-        dev = saved.device
-        xshape = (B, T, model.ninp // 2, 2)
-        if B == 0:
-            grads = [torch.zeros_like(t) for t in params]
-            dx = torch.zeros(xshape, dtype=torch.float32, device=dev) if need_dx else None
-        else:
-            lib, dev = model._ensure_created()
-            dy = _aligned(dy.to(torch.float32).contiguous())   # autograd may hand over an expanded / CopySlices gradient
-            grads = [torch.empty_like(t) for t in params]
-            dx = torch.empty(xshape, dtype=torch.float32, device=dev) if need_dx else None
-            nbytes = lib.b2h_tpt_train_bytes(model._handle, B, S, T, 1)
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            with _lib.on_device(dev):
-                st = torch.cuda.current_stream(dev).cuda_stream
-                _lib.check(lib.b2h_tpt_set_train_kernel(model._handle, _lib.TRAIN_KERNELS[ctx.kernels]))
-                _lib.check(lib.b2h_tpt_set_train_linear(model._handle, _lib.TRAIN_KERNELS[ctx.linear]))
-                _lib.check(lib.b2h_tpt_backward(model._handle, _ptrs(params), ctypes.c_void_p(tok.data_ptr()),
-                                                _ptrs(masks) if masks else None, ctx.p, ctypes.c_void_p(dy.data_ptr()),
-                                                ctypes.c_void_p(saved.data_ptr()), saved.numel(),
-                                                ctypes.c_void_p(dx.data_ptr()) if dx is not None else None, _ptrs(grads),
-                                                ctypes.c_void_p(ws.data_ptr()), nbytes, B, S, T, ctypes.c_void_p(st)))
-        return (None, None, None, None, dx) + tuple(g if ctx.needs_input_grad[5 + i] else None for i, g in enumerate(grads))
+_TptTrainFn = TrainFn   # the name earlier documents and tests' docstrings use

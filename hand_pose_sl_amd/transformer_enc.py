@@ -9,7 +9,7 @@ runs through the C ABI (`b2h_tenc_forward`).  Only the geometry the reference's 
 (ninp=24, nhead=4, nhid=128, nout=42; infer_utterance.py:99-101) is implemented.
 
 Training: in training mode with autograd enabled and a parameter or the input requiring a gradient,
-`model(src)` runs `_TencTrainFn` -- an exact-fp32 HIP forward and backward (b2h_tenc_train_forward /
+`model(src)` runs `_native.TrainFn` -- an exact-fp32 HIP forward and backward (b2h_tenc_train_forward /
 b2h_tenc_backward, kernel_tenc_train.h) that read the parameters' own storage -- so the reference's loop
 body (steps/traintest.py:87-121) runs unchanged with any torch optimizer.  The dropout keep-masks are
 drawn by torch on the model's device (`_draw_dropout_masks`; they follow torch.manual_seed) and handed
@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import NativeDropout, NativeModule, _aligned, _ptrs
+from ._native import NativeDropout, NativeModule, TrainFn, _ptrs
 
 
 class PositionalEncoding(nn.Module):
@@ -131,38 +131,29 @@ class TransformerEnc(NativeDropout, NativeModule, nn.Module):
         case in this fixed order: `pos` (B, T, 24);
         then layer by layer `attn` (B, 4, T, T), `drop1`, `ff`, `drop2` (B, T, 128 each), keyed (layer, name).
         An empty dict at p = 0."""
-        p = float(self._modules["pos_encoder"]._modules["dropout"].p)
-        if p == 0.0:
-            return {}
-        if self.dropout_source == "native":
-            return self._native_dropout_masks(self._mask_order(B, T), p)
-        dev = self._device()
-
-        def draw(*shape):
-            return (torch.rand(shape, device=dev) >= p).to(torch.uint8)
-
-        masks = {"pos": draw(B, T, self.ninp)}
-        nhead, nhid = self._geom[1], self._geom[2]
-        for l in range(self._geom[4]):
-            masks[(l, "attn")] = draw(B, nhead, T, T)
-            for name in ("drop1", "ff", "drop2"):
-                masks[(l, name)] = draw(B, T, nhid)
-        return masks
+        return self._drawn_masks(float(self._modules["pos_encoder"]._modules["dropout"].p), B, T)
 
     def _forward_train(self, src, masks):
-        """The differentiable forward (`_TencTrainFn`) with the given keep-masks (`_draw_dropout_masks`)."""
+        """The differentiable forward (`_native.TrainFn`) with the given keep-masks (`_draw_dropout_masks`)."""
         x = self._check_input(src)
         p = float(self._modules["pos_encoder"]._modules["dropout"].p)
-        if (p > 0.0) != bool(masks):
-            raise ValueError("masks must be given exactly when the dropout probability is > 0")
-        order = self._mask_order(x.shape[0], x.shape[1]) if masks else []
-        if masks:
-            for key, shape in order:
-                m = masks[key]
-                if m.shape != shape or m.dtype != torch.uint8 or m.device != x.device or not m.is_contiguous():
-                    raise RuntimeError(f"mask {key}: expected a contiguous uint8 tensor of shape {shape} on {x.device}")
         tensors = self._tensors()
-        return _TencTrainFn.apply(self, p, [masks[k] for k, _ in order], x, tensors[0], *tensors[1:])
+        return TrainFn.apply(self, p, self._checked_masks(masks, p, x.device, x.shape[0], x.shape[1]), tensors[0], x,
+                             *tensors[1:])
+
+    # what TrainFn asks of the model: pe travels as params[0] of the entry points and has no gradient
+    _TRAIN_FNS = ("b2h_tenc_train_bytes", "b2h_tenc_train_forward", "b2h_tenc_backward")
+    _TRAIN_LEAD_IS_PARAM = True
+
+    def _train_shapes(self, pe, x):
+        B, T = x.shape[0], x.shape[1]
+        return (B, T), (B, T, 21, 2), (B, T, 12, 2)
+
+    def _train_head(self, pe, params):
+        return (_ptrs((pe, *params)),)
+
+    def _train_route(self):
+        return ()
 
     def _run(self, src, flags, factor, n_frames):
         lib = self._ensure_handle()
@@ -215,56 +206,4 @@ class TransformerEnc(NativeDropout, NativeModule, nn.Module):
         return self._run(body, flags, factor, n_frames)
 
 
-class _TencTrainFn(torch.autograd.Function):
-    """y = TransformerEnc(x) in training mode with its gradient: b2h_tenc_train_forward / b2h_tenc_backward
-    (exact fp32, kernel_tenc_train.h).  The parameters go in as themselves (their own data_ptr, saved for
-    backward, so autograd's version check catches an in-place edit between forward and backward).  The context
-    keeps the saved-activation buffer and the masks alive; the backward needs neither x nor y (the reference's
-    loop overwrites the prediction's tail in place before the loss)."""
-
-    @staticmethod
-    def forward(ctx, model, p, masks, x, pe, *params):
-        for t in (pe,) + params:
-            if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError("training needs contiguous float32 parameters on the input's device")
-        lib, dev = model._ensure_created()
-        x = _aligned(x)
-        B, T = x.shape[0], x.shape[1]
-        y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=x.device)
-        nbytes = lib.b2h_tenc_train_bytes(model._handle, B, T, 0)
-        saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
-        with _lib.on_device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.b2h_tenc_train_forward(model._handle, _ptrs((pe,) + params), ctypes.c_void_p(x.data_ptr()),
-                                                  _ptrs(masks) if masks else None, p, ctypes.c_void_p(y.data_ptr()),
-                                                  ctypes.c_void_p(saved.data_ptr()), nbytes, B, T, ctypes.c_void_p(st)))
-        ctx.model, ctx.p, ctx.masks, ctx.shape = model, p, masks, (B, T)
-        ctx.save_for_backward(saved, pe, *params)
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        saved, pe, *params = ctx.saved_tensors
-        model, masks = ctx.model, ctx.masks
-        need_dx = ctx.needs_input_grad[3]
-        B, T = ctx.shape
-        dev = saved.device
-        if B == 0:
-            grads = [torch.zeros_like(t) for t in params]
-            dx = torch.zeros((B, T, 12, 2), dtype=torch.float32, device=dev) if need_dx else None
-        else:
-            lib, dev = model._ensure_created()
-            dy = _aligned(dy.to(torch.float32).contiguous())   # autograd may hand over an expanded / CopySlices gradient
-            grads = [torch.empty_like(t) for t in params]
-            dx = torch.empty((B, T, 12, 2), dtype=torch.float32, device=dev) if need_dx else None
-            nbytes = lib.b2h_tenc_train_bytes(model._handle, B, T, 1)
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            with _lib.on_device(dev):
-                st = torch.cuda.current_stream(dev).cuda_stream
-                _lib.check(lib.b2h_tenc_backward(model._handle, _ptrs([pe] + params), _ptrs(masks) if masks else None,
-                                                 ctx.p, ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(saved.data_ptr()),
-                                                 saved.numel(), ctypes.c_void_p(dx.data_ptr()) if dx is not None else None,
-                                                 _ptrs(grads), ctypes.c_void_p(ws.data_ptr()), nbytes, B, T,
-                                                 ctypes.c_void_p(st)))
-        return (None, None, None, dx, None) + tuple(g if ctx.needs_input_grad[5 + i] else None for i, g in enumerate(grads))
+_TencTrainFn = TrainFn   # the name earlier documents and tests' docstrings use
