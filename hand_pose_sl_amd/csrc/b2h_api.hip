@@ -22,6 +22,7 @@
 #include "kernel_mfma3w.h"
 #include "kernel_tenc.h"
 #include "kernel_tenc_train.h"
+#include "kernel_train_attn.h"
 #include "kernel_tpt.h"
 #include "kernel_attn_long.h"
 #include "kernel_adam.h"
@@ -792,9 +793,7 @@ int set_tenc_kernel_attributes() {
                 (rc = raise_lds_cap(kAttnLongF32[nt - 1], attn_long_f32_lds_bytes(nt))) ||
                 (rc = raise_lds_cap(kAttnLongH3[nt - 1], attn_long_h3_lds_bytes(nt))))
                 return rc;
-        if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd)) ||
-            (rc = raise_lds_cap(b2h_tptt_xsdpa)) || (rc = raise_lds_cap(b2h_tptt_xsdpa_bwd)))
-            return rc;
+        if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd))) return rc;
         if ((rc = raise_lds_cap(b2h_lt_sdpa, (int)kLtFwdLds)) || (rc = raise_lds_cap(b2h_lt_sdpa_bwd_kv, (int)kLtBwdKvLds)) ||
             (rc = raise_lds_cap(b2h_lt_sdpa_bwd_q, (int)kLtBwdQLds)))
             return rc;
@@ -1567,6 +1566,46 @@ void tt_layernorm_bwd(hipStream_t st, const float* dY, const float* X, const flo
 
 float tt_scale(float p) { return p < 1.f ? 1.f / (1.f - p) : 0.f; }
 
+// Which kernels run an attention in training: the whole-matrix pair (kernel_train_attn.h) up to 128 x 128, beyond
+// that the blocked ones, on the vector ALU (kernel_train_attn_long.h) or on the matrix cores
+// (kernel_train_attn_mfma.h).
+enum class TrainAttn { kWhole, kBlockedValu, kBlockedMfma };
+
+// Self-attention over [Q | K | V] rows (N, 384), and its gradients [dQ | dK | dV] in the same layout.
+XsdpaSrc self_src(const float* qkv) { return XsdpaSrc{qkv, 3 * kTtD, 0, qkv, 3 * kTtD, kTtD, 2 * kTtD}; }
+LtGradDst self_dst(float* gQ) { return LtGradDst{gQ, 3 * kTtD, 0, gQ, 3 * kTtD, kTtD, 2 * kTtD}; }
+
+// Attention of B sequences of Tq query rows over Tk key rows in training: O (B*Tq, 128) and, from the blocked kernels
+// only, the rows' log-sum-exp (B, 4, Tq).
+void train_sdpa(hipStream_t st, TrainAttn route, const XsdpaSrc& src, const uint8_t* mask, float sc, float* O, float* lse,
+                int64_t B, int Tq, int Tk) {
+    const unsigned heads = (unsigned)(B * kTtHeads);
+    const dim3 grid(heads, lt_blocks(Tq, kLtQb));
+    if (route == TrainAttn::kWhole)
+        hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes(Tq, Tk, false), st, src, mask, sc, O, Tq, Tk);
+    else if (route == TrainAttn::kBlockedMfma)
+        hipLaunchKernelGGL(b2h_mt_sdpa, grid, dim3(256), kMtFwdLds, st, src, mask, sc, O, lse, Tq, Tk);
+    else
+        hipLaunchKernelGGL(b2h_lt_sdpa, grid, dim3(256), kLtFwdLds, st, src, mask, sc, O, lse, Tq, Tk);
+}
+
+// Its backward.  Blocked: the query owner (dQ, and the row terms D for the key owner), then the key owner (dK, dV).
+void train_sdpa_bwd(hipStream_t st, TrainAttn route, const XsdpaSrc& src, const float* dO, const float* lse, float* D,
+                    const uint8_t* mask, float sc, const LtGradDst& dst, int64_t B, int Tq, int Tk) {
+    const unsigned heads = (unsigned)(B * kTtHeads);
+    const dim3 gq(heads, lt_blocks(Tq, kLtQb)), gkv(heads, lt_blocks(Tk, kLtKb));
+    if (route == TrainAttn::kWhole) {
+        hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3(heads), dim3(256), tt_sdpa_lds_bytes(Tq, Tk, true), st, src, dO, mask, sc, dst,
+                           Tq, Tk);
+    } else if (route == TrainAttn::kBlockedMfma) {
+        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_q, gq, dim3(256), kMtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_kv, gkv, dim3(256), kMtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+    } else {
+        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_q, gq, dim3(256), kLtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_kv, gkv, dim3(256), kLtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+    }
+}
+
 // One torch.nn.TransformerEncoderLayer (post-norm, ReLU) over N = B * T rows in training mode: H -> L.H2.
 // w: its twelve tensors in state_dict order; mk: its four keep-masks attn, drop1, ff, drop2, or nullptr.
 void tt_enc_layer_forward(const TtLin& ln, const float* const* w, const TtLayer& L, const float* H, int64_t B, int T,
@@ -1575,8 +1614,7 @@ void tt_enc_layer_forward(const TtLin& ln, const float* const* w, const TtLayer&
     const int64_t N = B * T;
     const auto mask = [&](int i) { return mk ? mk[i] : nullptr; };
     tt_linear(ln, H, w[0], w[1], L.QKV, N, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
-    hipLaunchKernelGGL(b2h_tt_sdpa, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes(T, false), st, L.QKV,
-                       mask(0), sc, L.O, T);
+    train_sdpa(st, TrainAttn::kWhole, self_src(L.QKV), mask(0), sc, L.O, nullptr, B, T, T);
     tt_linear(ln, L.O, w[2], w[3], L.R1, N, kTtD, kTtD, 0, mask(1), sc, H);
     hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R1, w[8], w[9], L.H1, L.ST, 4, N);
     tt_linear(ln, L.H1, w[4], w[5], L.F1, N, kTtD, kTtD, 1, mask(2), sc, nullptr);
@@ -1611,8 +1649,7 @@ void tt_enc_layer_backward(const TtLin& ln, const float* const* w, float* const*
     const float* dA = mk ? G.gBm : G.gB;
     tt_linear_dw(ln, dA, L.O, G.slabs, N, kTtD, kTtD, g[2], g[3]);
     tt_linear_dx(ln, dA, w[2], G.gC, N, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);             // gC = dO
-    hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3((unsigned)(B * kTtHeads)), dim3(256), tt_sdpa_lds_bytes(T, true), st, L.QKV,
-                       G.gC, mask(0), sc, G.gQ, T);
+    train_sdpa_bwd(st, TrainAttn::kWhole, self_src(L.QKV), G.gC, nullptr, nullptr, mask(0), sc, self_dst(G.gQ), B, T, T);
     tt_linear_dw(ln, G.gQ, Hin, G.slabs, N, kTtD, 3 * kTtD, g[0], g[1]);
     tt_linear_dx(ln, G.gQ, w[0], G.gA, N, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);          // gA = dH_in
 }
@@ -1825,13 +1862,9 @@ void tt_layernorm(hipStream_t st, const float* X, const float* gamma, const floa
 
 // The cross-attention operands of decoder layer L: queries QC (Nt, 128), [K | V] rows (Ns, 256).
 XsdpaSrc tpt_xsrc(const TptDecLayer& L) { return XsdpaSrc{L.QC, kTtD, 0, L.KV, 2 * kTtD, 0, kTtD}; }
-// The self-attention operands as the long kernels take them: [Q | K | V] rows (Nt, 384).
-XsdpaSrc tpt_ssrc(const TptDecLayer& L) { return XsdpaSrc{L.QKV, 3 * kTtD, 0, L.QKV, 3 * kTtD, kTtD, 2 * kTtD}; }
-
-// Which kernels run the decoder's two attentions in training: the whole-matrix kernels up to 128 frames, beyond them
-// the blocked ones, on the vector ALU (kernel_train_attn_long.h) or on the matrix cores (kernel_train_attn_mfma.h) as
-// b2h_tpt_set_train_kernel chose.  The one place that decides: the dispatch and b2h_tpt_train_attn_name both ask it.
-enum class TrainAttn { kWhole, kBlockedValu, kBlockedMfma };
+// Which kernels run the decoder's two attentions in training: the whole-matrix pair up to 128 frames, beyond them the
+// blocked ones as b2h_tpt_set_train_kernel chose.  The one place that decides: the dispatch and
+// b2h_tpt_train_attn_name both ask it.
 TrainAttn tpt_train_attn(const b2h_tpt* m, int64_t T) {
     if (!tpt_long(T)) return TrainAttn::kWhole;
     return m->train_kernel == B2H_TRAIN_MFMA ? TrainAttn::kBlockedMfma : TrainAttn::kBlockedValu;
@@ -1842,31 +1875,6 @@ TrainAttn tpt_train_attn(const b2h_tpt* m, int64_t T) {
 enum class TrainLinear { kValu, kMfma };
 TrainLinear tpt_train_linear(const b2h_tpt* m) {
     return m->train_linear == B2H_TRAIN_MFMA ? TrainLinear::kMfma : TrainLinear::kValu;
-}
-
-// Attention of B sequences of Tq > 128 query rows over Tk key rows in training (kernel_train_attn_long.h, or
-// kernel_train_attn_mfma.h with mfma): O (B*Tq, 128) and the rows' log-sum-exp (B, 4, Tq).
-void lt_sdpa(hipStream_t st, bool mfma, const XsdpaSrc& src, const uint8_t* mask, float sc, float* O, float* lse, int64_t B,
-             int Tq, int Tk) {
-    const dim3 grid((unsigned)(B * kTtHeads), lt_blocks(Tq, kLtQb));
-    if (mfma)
-        hipLaunchKernelGGL(b2h_mt_sdpa, grid, dim3(256), kMtFwdLds, st, src, mask, sc, O, lse, Tq, Tk);
-    else
-        hipLaunchKernelGGL(b2h_lt_sdpa, grid, dim3(256), kLtFwdLds, st, src, mask, sc, O, lse, Tq, Tk);
-}
-
-// Its backward: the query owner (dQ, and the row terms D for the key owner), then the key owner ([dK | dV]).
-void lt_sdpa_bwd(hipStream_t st, bool mfma, const XsdpaSrc& src, const float* dO, const float* lse, float* D,
-                 const uint8_t* mask, float sc, const LtGradDst& dst, int64_t B, int Tq, int Tk) {
-    const unsigned heads = (unsigned)(B * kTtHeads);
-    const dim3 gq(heads, lt_blocks(Tq, kLtQb)), gkv(heads, lt_blocks(Tk, kLtKb));
-    if (mfma) {
-        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_q, gq, dim3(256), kMtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
-        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_kv, gkv, dim3(256), kMtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
-    } else {
-        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_q, gq, dim3(256), kLtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
-        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_kv, gkv, dim3(256), kLtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
-    }
 }
 
 } // namespace
@@ -1902,7 +1910,8 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     if (misaligned(x, 16) || misaligned(y, 16) || misaligned(saved, 16))
         return fail(B2H_ERR_INVALID, "x, y and the saved buffer must be 16-byte aligned");
     const int64_t Ns = B * S, Nt = B * T;
-    const bool lng = tpt_long(T), mfma = tpt_train_attn(m, T) == TrainAttn::kBlockedMfma;
+    const bool lng = tpt_long(T);
+    const TrainAttn route = tpt_train_attn(m, T);
     const size_t need = tpt_saved_bytes(m, Ns, Nt, lng);
     if (saved_bytes < need)
         return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes (" + std::to_string(need) + " B)");
@@ -1933,28 +1942,19 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     HIP_TRY(hipMemcpyAsync(sv.X0, x, (size_t)Nt * m->ninp * 4, hipMemcpyDeviceToDevice, st));
     tt_linear(ln, sv.X0, wt[3], wt[4], sv.XT0, Nt, m->ninp, kTtD, 0, nullptr, 1.f, nullptr);
     H = sv.XT0;
-    const unsigned heads = (unsigned)(B * kTtHeads);
     for (int l = 0; l < m->n_dec; ++l) { // torch.nn.TransformerDecoderLayer, post-norm, ReLU
         const float* const* w = params + 12 * m->n_enc + 2 + 18 * l;
         const int mi = 4 * m->n_enc + 6 * l;
         const TptDecLayer L = sv.dec_layer(l);
         tt_linear(ln, H, w[0], w[1], L.QKV, Nt, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
         float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
-        if (lng)
-            lt_sdpa(st, mfma, tpt_ssrc(L), mk(mi), sc, L.O, lse, B, (int)T, (int)T);
-        else
-            hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, false), st, L.QKV, mk(mi), sc,
-                               L.O, (int)T);
+        train_sdpa(st, route, self_src(L.QKV), mk(mi), sc, L.O, lse, B, (int)T, (int)T);
         tt_linear(ln, L.O, w[2], w[3], L.R1, Nt, kTtD, kTtD, 0, mk(mi + 1), sc, H);
         tt_layernorm(st, L.R1, w[12], w[13], L.H1, L.ST12, Nt);
         // multihead_attn: the query of H1 (in_proj rows 0..127), [K | V] of the memory (rows 128..383)
         tt_linear(ln, L.H1, w[4], w[5], L.QC, Nt, kTtD, kTtD, 0, nullptr, 1.f, nullptr);
         tt_linear(ln, sv.MEM, w[4] + kDD, w[5] + kTtD, L.KV, Ns, kTtD, 2 * kTtD, 0, nullptr, 1.f, nullptr);
-        if (lng)
-            lt_sdpa(st, mfma, tpt_xsrc(L), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S);
-        else
-            hipLaunchKernelGGL(b2h_tptt_xsdpa, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, false), st,
-                               tpt_xsrc(L), mk(mi + 2), sc, L.OC, (int)T, (int)S);
+        train_sdpa(st, route, tpt_xsrc(L), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S);
         tt_linear(ln, L.OC, w[6], w[7], L.R2, Nt, kTtD, kTtD, 0, mk(mi + 3), sc, L.H1);
         tt_layernorm(st, L.R2, w[14], w[15], L.H2, L.ST12 + 2, Nt);
         tt_linear(ln, L.H2, w[8], w[9], L.F1, Nt, kTtD, kTtD, 1, mk(mi + 4), sc, nullptr);
@@ -1980,7 +1980,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     if (misaligned(dy, 16) || misaligned(saved, 16) || misaligned(scratch, 16) || (dx && misaligned(dx, 16)))
         return fail(B2H_ERR_INVALID, "dy, dx, the saved buffer and the scratch must be 16-byte aligned");
     const int64_t Ns = B * S, Nt = B * T;
-    const bool lng = tpt_long(T), mfma = tpt_train_attn(m, T) == TrainAttn::kBlockedMfma;
+    const bool lng = tpt_long(T);
+    const TrainAttn route = tpt_train_attn(m, T);
     const size_t need_saved = tpt_saved_bytes(m, Ns, Nt, lng), need = tpt_scratch_bytes(Ns, Nt, lng);
     if (saved_bytes < need_saved) return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes");
     if (scratch_bytes < need)
@@ -2010,7 +2011,6 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     TtGrad G = tt_grad(scr, Nt); // the frame rows first; the slabs lie behind both row sets
     G.slabs = dM[1] + Ns * kTtD;
     float* Drow = G.slabs + (int64_t)tt_nslabs(Nmax) * kTtSlab; // long T only
-    const unsigned heads = (unsigned)(B * kTtHeads);
     const int od = 12 * m->n_enc + 2, ot = od + 18 * m->n_dec + 2; // the first decoder layer; token_embedding
 
     // hidden2pose_projection (:213) and decoder.norm
@@ -2038,12 +2038,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         tt_linear_dw(ln, dC, L.OC, G.slabs, Nt, kTtD, kTtD, g[6], g[7]);
         tt_linear_dx(ln, dC, w[6], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dOC
         const float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
-        if (lng)
-            lt_sdpa_bwd(st, mfma, tpt_xsrc(L), G.gC, lse + Nt * kTtHeads, Drow, mk(mi + 2), sc,
-                        LtGradDst{G.gA, kTtD, 0, dKV, 2 * kTtD, 0, kTtD}, B, (int)T, (int)S);
-        else
-            hipLaunchKernelGGL(b2h_tptt_xsdpa_bwd, dim3(heads), dim3(256), tptt_xsdpa_lds_bytes((int)T, (int)S, true), st,
-                               tpt_xsrc(L), G.gC, mk(mi + 2), sc, G.gA, dKV, (int)T, (int)S);        // gA = dQC
+        train_sdpa_bwd(st, route, tpt_xsrc(L), G.gC, lse + Nt * kTtHeads, Drow, mk(mi + 2), sc,
+                       LtGradDst{G.gA, kTtD, 0, dKV, 2 * kTtD, 0, kTtD}, B, (int)T, (int)S);          // gA = dQC, dKV
         // multihead_attn.in_proj: rows 0..127 from (dQC, H1) over the frames, rows 128..383 from ([dK | dV], MEM)
         // over the tokens, each with the slab count of its own row set
         tt_linear_dw(ln, G.gA, L.H1, G.slabs, Nt, kTtD, kTtD, g[4], g[5]);
@@ -2057,12 +2053,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         const float* dA = masks ? G.gBm : G.gB;
         tt_linear_dw(ln, dA, L.O, G.slabs, Nt, kTtD, kTtD, g[2], g[3]);
         tt_linear_dx(ln, dA, w[2], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dO
-        if (lng)
-            lt_sdpa_bwd(st, mfma, tpt_ssrc(L), G.gC, lse, Drow, mk(mi), sc,
-                        LtGradDst{G.gQ, 3 * kTtD, 0, G.gQ, 3 * kTtD, kTtD, 2 * kTtD}, B, (int)T, (int)T);
-        else
-            hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3(heads), dim3(256), tt_sdpa_lds_bytes((int)T, true), st, L.QKV, G.gC,
-                               mk(mi), sc, G.gQ, (int)T);
+        train_sdpa_bwd(st, route, self_src(L.QKV), G.gC, lse, Drow, mk(mi), sc, self_dst(G.gQ), B, (int)T, (int)T);
         tt_linear_dw(ln, G.gQ, Hin, G.slabs, Nt, kTtD, 3 * kTtD, g[0], g[1]);
         tt_linear_dx(ln, G.gQ, w[0], G.gA, Nt, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);         // gA = dH_in
     }

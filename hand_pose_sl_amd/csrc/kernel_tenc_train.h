@@ -12,9 +12,10 @@
 //   b2h_tt_linear_dw     slab partials of dW = dY^T X and db = sum dY
 //   b2h_tt_layernorm     y = (x - mean) rstd gamma + beta, saves mean / rstd (eps 1e-5, biased variance)
 //   b2h_tt_layernorm_bwd dx [and dx through a keep-mask], slab partials of dgamma / dbeta
-//   b2h_tt_sdpa          O = drop(softmax(Q K^T / sqrt(32))) V, one workgroup per (sequence, head)
-//   b2h_tt_sdpa_bwd      recomputes the probabilities from Q, K; dQ, dK, dV
 //   b2h_tt_reduce        sums the slabs in ascending order into the gradient tensors
+//
+// The attention pair b2h_tt_sdpa / b2h_tt_sdpa_bwd is in kernel_train_attn.h, which builds on this header's
+// constants and wave reductions.
 //
 // Parameter gradients are bitwise deterministic: workgroup s of a *_dw / *_bwd launch owns the row tiles
 // s, s + S, s + 2S, ... (S = tt_nslabs(N), a function of (B, T) only), sums them in that order in
@@ -37,10 +38,6 @@ constexpr float kTtQkScale = 0.17677669529663687f;  // 1 / sqrt(32)
 __host__ __device__ inline int tt_nslabs(int64_t N) {
     const int64_t t = (N + 2 * kTtDwRows - 1) / (2 * kTtDwRows);
     return (int)(t < 1 ? 1 : (t > kTtMaxSlabs ? kTtMaxSlabs : t));
-}
-__host__ __device__ inline int tt_ps(int T) { return T | 1; } // LDS row stride of the (T, T) probabilities
-__host__ __device__ inline size_t tt_sdpa_lds_bytes(int T, bool bwd) {
-    return (size_t)4 * ((bwd ? 4 : 3) * T * kTtQs + T * tt_ps(T)) + (bwd ? (size_t)(T * T + 3) / 4 * 4 : 0);
 }
 
 __device__ inline float tt_wave_sum(float v) {
@@ -301,152 +298,6 @@ __global__ __launch_bounds__(256) void b2h_tt_layernorm_bwd(const float* __restr
     __syncthreads();
     const int e = threadIdx.x; // 256 threads, 256 slab elements
     slabs[(int64_t)blockIdx.x * slab + e] = ((part[0][e] + part[1][e]) + part[2][e]) + part[3][e];
-}
-
-// Shared by the attention kernels: Q, K, V (and dO) rows of one (sequence, head) into LDS, then
-// P[i][j] = softmax_j(Q_i . K_j / sqrt(32)), one wave per row, PRE-dropout.
-__device__ inline void tt_load_head(const float* __restrict__ src, int ld, float* dst, int T) {
-    for (int e = threadIdx.x; e < T * kTtHd; e += blockDim.x) {
-        const int i = e >> 5, d = e & 31;
-        dst[i * kTtQs + d] = src[(int64_t)i * ld + d];
-    }
-}
-
-__device__ inline void tt_softmax_rows(const float* Q, const float* K, float* P, int T) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6, ps = tt_ps(T);
-    for (int i = w; i < T; i += nw) {
-        float s[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int j = lane + 64 * u;
-            float a = 0.f;
-            if (j < T)
-#pragma unroll
-                for (int d = 0; d < kTtHd; ++d) a = fmaf(Q[i * kTtQs + d], K[j * kTtQs + d], a);
-            s[u] = j < T ? a * kTtQkScale : -INFINITY;
-        }
-        const float mx = tt_wave_max(fmaxf(s[0], s[1]));
-        const float e0 = expf(s[0] - mx), e1 = lane + 64 < T ? expf(s[1] - mx) : 0.f; // lane 0 < T always; e0 = 0 past T
-        const float sum = tt_wave_sum((lane < T ? e0 : 0.f) + e1);
-        if (lane < T) P[i * ps + lane] = e0 / sum;
-        if (lane + 64 < T) P[i * ps + lane + 64] = e1 / sum;
-    }
-}
-
-// O[i][32 h + d] = sum_j drop(P)[i][j] V[j][d].  qkv (N, 384) = [Q | K | V] rows of in_proj; mask (B, 4, T, T).
-// grid B * 4, 256 threads, tt_sdpa_lds_bytes(T, false) of dynamic LDS.  T <= 128.
-__global__ __launch_bounds__(256) void b2h_tt_sdpa(const float* __restrict__ qkv, const uint8_t* __restrict__ mask,
-                                                   float scale, float* __restrict__ O, int T) {
-    extern __shared__ __attribute__((aligned(16))) float smem_tt[];
-    float* Q = smem_tt;
-    float* K = Q + T * kTtQs;
-    float* V = K + T * kTtQs;
-    float* P = V + T * kTtQs;
-    const int64_t b = blockIdx.x / kTtHeads;
-    const int h = blockIdx.x % kTtHeads, ps = tt_ps(T);
-    const float* base = qkv + b * T * (3 * kTtD) + h * kTtHd;
-    tt_load_head(base, 3 * kTtD, Q, T);
-    tt_load_head(base + kTtD, 3 * kTtD, K, T);
-    tt_load_head(base + 2 * kTtD, 3 * kTtD, V, T);
-    __syncthreads();
-    tt_softmax_rows(Q, K, P, T);
-    __syncthreads();
-    if (mask) {
-        const uint8_t* mk = mask + (int64_t)blockIdx.x * T * T;
-        for (int e = threadIdx.x; e < T * T; e += 256) {
-            const int i = e / T, j = e % T;
-            P[i * ps + j] = mk[e] ? P[i * ps + j] * scale : 0.f;
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < T * kTtHd; e += 256) {
-        const int i = e >> 5, d = e & 31;
-        float a = 0.f;
-        for (int j = 0; j < T; ++j) a = fmaf(P[i * ps + j], V[j * kTtQs + d], a);
-        O[(b * T + i) * kTtD + h * kTtHd + d] = a;
-    }
-}
-
-// Backward of b2h_tt_sdpa for one (sequence, head).  S = softmax (recomputed), Pd = drop(S):
-//   dV = Pd^T dO;  dP = dO V^T;  dSd = keep ? dP * scale : 0;  dZ = S o (dSd - rowsum(dSd o S));
-//   dQ = dZ K / sqrt(32);  dK = dZ^T Q / sqrt(32).
-// dO (N, 128) is the gradient of the concatenated heads; dqkv (N, 384) receives [dQ | dK | dV].
-// tt_sdpa_lds_bytes(T, true) of dynamic LDS: Q, K, V, dO, the (T, T) matrix and the mask bytes.
-__global__ __launch_bounds__(256) void b2h_tt_sdpa_bwd(const float* __restrict__ qkv, const float* __restrict__ dO,
-                                                       const uint8_t* __restrict__ mask, float scale,
-                                                       float* __restrict__ dqkv, int T) {
-    extern __shared__ __attribute__((aligned(16))) float smem_tt[];
-    float* Q = smem_tt;
-    float* K = Q + T * kTtQs;
-    float* V = K + T * kTtQs;
-    float* G = V + T * kTtQs;
-    float* P = G + T * kTtQs;
-    uint8_t* Mk = reinterpret_cast<uint8_t*>(P + T * tt_ps(T));
-    const int64_t b = blockIdx.x / kTtHeads;
-    const int h = blockIdx.x % kTtHeads, ps = tt_ps(T);
-    const float* base = qkv + b * T * (3 * kTtD) + h * kTtHd;
-    tt_load_head(base, 3 * kTtD, Q, T);
-    tt_load_head(base + kTtD, 3 * kTtD, K, T);
-    tt_load_head(base + 2 * kTtD, 3 * kTtD, V, T);
-    tt_load_head(dO + b * T * kTtD + h * kTtHd, kTtD, G, T);
-    if (mask) {
-        const uint8_t* mk = mask + (int64_t)blockIdx.x * T * T;
-        for (int e = threadIdx.x; e < T * T; e += 256) Mk[e] = mk[e];
-    }
-    __syncthreads();
-    tt_softmax_rows(Q, K, P, T);
-    __syncthreads();
-    float* out = dqkv + b * T * (3 * kTtD) + h * kTtHd;
-    for (int e = threadIdx.x; e < T * kTtHd; e += 256) { // dV[j][d] = sum_i Pd[i][j] dO[i][d]
-        const int j = e >> 5, d = e & 31;
-        float a = 0.f;
-        for (int i = 0; i < T; ++i) {
-            float pd = P[i * ps + j];
-            if (mask) pd = Mk[i * T + j] ? pd * scale : 0.f;
-            a = fmaf(pd, G[i * kTtQs + d], a);
-        }
-        out[(int64_t)j * (3 * kTtD) + 2 * kTtD + d] = a;
-    }
-    __syncthreads();
-    {   // P <- dZ / sqrt(32), one wave per row
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        for (int i = w; i < T; i += 4) {
-            float sv[2], dsd[2];
-            float rs = 0.f;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int j = lane + 64 * u;
-                sv[u] = 0.f;
-                dsd[u] = 0.f;
-                if (j < T) {
-                    float a = 0.f;
-#pragma unroll
-                    for (int d = 0; d < kTtHd; ++d) a = fmaf(G[i * kTtQs + d], V[j * kTtQs + d], a);
-                    if (mask) a = Mk[i * T + j] ? a * scale : 0.f;
-                    sv[u] = P[i * ps + j];
-                    dsd[u] = a;
-                    rs = fmaf(a, sv[u], rs);
-                }
-            }
-            rs = tt_wave_sum(rs);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int j = lane + 64 * u;
-                if (j < T) P[i * ps + j] = sv[u] * (dsd[u] - rs) * kTtQkScale;
-            }
-        }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < T * kTtHd; e += 256) {
-        const int i = e >> 5, d = e & 31;
-        float aq = 0.f, ak = 0.f;
-        for (int j = 0; j < T; ++j) {
-            aq = fmaf(P[i * ps + j], K[j * kTtQs + d], aq); // dQ[i][d] = sum_j dZ[i][j] K[j][d]
-            ak = fmaf(P[j * ps + i], Q[j * kTtQs + d], ak); // dK[i][d] = sum_j dZ[j][i] Q[j][d]
-        }
-        out[(int64_t)i * (3 * kTtD) + d] = aq;
-        out[(int64_t)i * (3 * kTtD) + kTtD + d] = ak;
-    }
 }
 
 } // namespace b2h

@@ -1,7 +1,7 @@
 // Blocked attention for training at more than 128 frames: the two attentions of TextPoseTransformer's decoder,
 // self (Tq = Tk = T) and cross (Tq = T, Tk = S <= 128), forward and backward, where one (sequence, head) no longer
-// fits LDS (b2h_tt_sdpa / b2h_tptt_xsdpa keep the whole (Tq, Tk) matrix there and stop at 128 x 128).  Same style as
-// kernel_tenc_train.h / kernel_tpt_train.h: exact fp32 on the vector ALU, one kernel per operation, keep-masks
+// fits LDS (kernel_train_attn.h's b2h_tt_sdpa keeps the whole (Tq, Tk) matrix there and stops at 128 x 128).  Same style
+// as kernel_tenc_train.h / kernel_train_attn.h: exact fp32 on the vector ALU, one kernel per operation, keep-masks
 // (uint8, 1 = keep) as inputs -- read from global memory here, Tq x Tk bytes do not fit LDS either --, `scale` =
 // 1 / (1 - p), a NULL mask means p = 0, fmaf over d and 1 / sqrt(32) applied after the dot product.
 //
@@ -11,7 +11,7 @@
 //                      sigma_i = rowsum(P) and D_i = rowsum(dSd o P) / sigma_i, then for dQ, which it writes once
 //   b2h_lt_sdpa_bwd_kv the key owner: one workgroup per key block walks the query blocks and writes dK, dV once
 //
-// The operands are described by XsdpaSrc (kernel_tpt_train.h) and the gradients' destinations by LtGradDst, so the
+// The operands are described by XsdpaSrc and the gradients' destinations by LtGradDst (kernel_train_attn.h), so the
 // same three kernels serve [Q | K | V] rows at ld 384 and QC at ld 128 against the memory's [K | V] rows at ld 256.
 // The backward recomputes P_ij = exp(s_ij - LSE_i) / sigma_i block by block.  With dSd = keep ? dP * scale : 0 and
 // dZ = P o (dSd - D):  dV_j = sum_i Pd_ij dO_i,  dK_j = sum_i dZ_ij Q_i / sqrt(32),  dQ_i = sum_j dZ_ij K_j / sqrt(32).
@@ -20,7 +20,7 @@
 // its terms in registers in ascending block and row order, an order fixed by (Tq, Tk) alone.  No atomics, no
 // handoff between workgroups, nothing read from another sequence.
 #pragma once
-#include "kernel_tpt_train.h"
+#include "kernel_train_attn.h"
 
 namespace b2h {
 
@@ -36,23 +36,6 @@ constexpr size_t kLtBwdKvLds = (size_t)4 * ((2 * kLtQb + 2 * kLtKb) * kTtQs + 2 
 constexpr size_t kLtBwdQLds = (size_t)4 * ((2 * kLtQb + 2 * kLtKb) * kTtQs + kLtQb * kLtPs + 2 * kLtQb);
 
 __host__ __device__ inline int lt_blocks(int n, int per) { return (n + per - 1) / per; }
-
-// Where the gradients of one attention go: dQ rows (B*Tq, lddq) from column coldq + 32 h; dK and dV rows
-// (B*Tk, lddkv) from coldk + 32 h and coldv + 32 h.
-struct LtGradDst {
-    float* dq;
-    int lddq, coldq;
-    float* dkv;
-    int lddkv, coldk, coldv;
-};
-
-// n rows of 32 floats from src (leading dimension ld) into LDS at stride 33
-__device__ inline void lt_load_rows(const float* __restrict__ src, int ld, float* dst, int n) {
-    for (int e = threadIdx.x; e < n * kTtHd; e += 256) {
-        const int i = e >> 5, d = e & 31;
-        dst[i * kTtQs + d] = src[(int64_t)i * ld + d];
-    }
-}
 
 __device__ inline float lt_dot(const float* a, const float* b) {
     float s = 0.f;
@@ -83,15 +66,15 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa(XsdpaSrc src, const uint8_t* 
     const int d = threadIdx.x & 31, r0 = threadIdx.x >> 5;
     const float* kv = src.kv + b * Tk * src.ldkv + h * kTtHd;
     const uint8_t* mk = mask ? mask + ((int64_t)blockIdx.x * Tq + i0) * Tk : nullptr;
-    lt_load_rows(src.q + (b * Tq + i0) * src.ldq + src.colq + h * kTtHd, src.ldq, Q, nq);
+    tt_load_head(src.q + (b * Tq + i0) * src.ldq + src.colq + h * kTtHd, src.ldq, Q, nq);
     float acc[kLtQb / 8];
 #pragma unroll
     for (int r = 0; r < kLtQb / 8; ++r) acc[r] = 0.f;
     for (int j0 = 0; j0 < Tk; j0 += kLtKb) {
         const int nk = min(kLtKb, Tk - j0); // < 128 only in the last block
         __syncthreads();                    // the previous block is done with K, V, P
-        lt_load_rows(kv + (int64_t)j0 * src.ldkv + src.colk, src.ldkv, K, nk);
-        lt_load_rows(kv + (int64_t)j0 * src.ldkv + src.colv, src.ldkv, V, nk);
+        tt_load_head(kv + (int64_t)j0 * src.ldkv + src.colk, src.ldkv, K, nk);
+        tt_load_head(kv + (int64_t)j0 * src.ldkv + src.colv, src.ldkv, V, nk);
         __syncthreads();
         for (int i = w; i < nq; i += 4) {
             float s[2];
@@ -182,16 +165,16 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_kv(XsdpaSrc src, const fl
     const int j0 = blockIdx.y * kLtKb, nk = min(kLtKb, Tk - j0);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, d = threadIdx.x & 31, r0 = threadIdx.x >> 5;
     const float* kv = src.kv + (b * Tk + j0) * src.ldkv + h * kTtHd;
-    lt_load_rows(kv + src.colk, src.ldkv, K, nk);
-    lt_load_rows(kv + src.colv, src.ldkv, V, nk);
+    tt_load_head(kv + src.colk, src.ldkv, K, nk);
+    tt_load_head(kv + src.colv, src.ldkv, V, nk);
     float av[kLtKb / 8], ak[kLtKb / 8];
 #pragma unroll
     for (int r = 0; r < kLtKb / 8; ++r) av[r] = ak[r] = 0.f;
     for (int i0 = 0; i0 < Tq; i0 += kLtQb) {
         const int nq = min(kLtQb, Tq - i0);
         __syncthreads(); // the previous block is done with Q, G, Pd, dZ
-        lt_load_rows(src.q + (b * Tq + i0) * src.ldq + src.colq + h * kTtHd, src.ldq, Q, nq);
-        lt_load_rows(dO + (b * Tq + i0) * kTtD + h * kTtHd, kTtD, G, nq);
+        tt_load_head(src.q + (b * Tq + i0) * src.ldq + src.colq + h * kTtHd, src.ldq, Q, nq);
+        tt_load_head(dO + (b * Tq + i0) * kTtD + h * kTtHd, kTtD, G, nq);
         __syncthreads();
         const int64_t row0 = (int64_t)blockIdx.x * Tq + i0;
         for (int i = w; i < nq; i += 4) {
@@ -258,8 +241,8 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_q(XsdpaSrc src, const flo
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, d = threadIdx.x & 31, r0 = threadIdx.x >> 5;
     const float* kv = src.kv + b * Tk * src.ldkv + h * kTtHd;
     const int64_t row0 = (int64_t)blockIdx.x * Tq + i0;
-    lt_load_rows(src.q + (b * Tq + i0) * src.ldq + src.colq + h * kTtHd, src.ldq, Q, nq);
-    lt_load_rows(dO + (b * Tq + i0) * kTtD + h * kTtHd, kTtD, G, nq);
+    tt_load_head(src.q + (b * Tq + i0) * src.ldq + src.colq + h * kTtHd, src.ldq, Q, nq);
+    tt_load_head(dO + (b * Tq + i0) * kTtD + h * kTtHd, kTtD, G, nq);
     float aq[kLtQb / 8];
 #pragma unroll
     for (int r = 0; r < kLtQb / 8; ++r) aq[r] = 0.f;
@@ -268,8 +251,8 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_q(XsdpaSrc src, const flo
             const int nk = min(kLtKb, Tk - j0);
             __syncthreads(); // the previous block is done with K, V, dZ; the first walk's Ds is complete
             if (walk == 0 || Tk > kLtKb) { // a single key block is still there
-                lt_load_rows(kv + (int64_t)j0 * src.ldkv + src.colk, src.ldkv, K, nk);
-                lt_load_rows(kv + (int64_t)j0 * src.ldkv + src.colv, src.ldkv, V, nk);
+                tt_load_head(kv + (int64_t)j0 * src.ldkv + src.colk, src.ldkv, K, nk);
+                tt_load_head(kv + (int64_t)j0 * src.ldkv + src.colv, src.ldkv, V, nk);
                 __syncthreads();
             }
             for (int i = w; i < nq; i += 4) {

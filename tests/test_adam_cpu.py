@@ -6,7 +6,6 @@ and the structure of its state_dict; the C host that trains compiles and links l
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -18,6 +17,7 @@ import hand_pose_sl_amd as hps
 from conftest import ROOT
 from hand_pose_sl_amd import _lib
 from hand_pose_sl_amd import build as b2h_build
+from kernel_remarks import kernel_remarks
 
 
 def test_entry_point_declared_typed_and_exported():
@@ -97,34 +97,15 @@ def test_refusals_launch_nothing_and_no_ops_return_ok():
     assert _call(lib, p=[0x10000] * 200, g=[0x10000] * 200, m=[0x10000] * 200, v=[0x10000] * 200, sizes=[0] * 200) == _lib.OK
 
 
-def test_kernel_has_no_scratch_spills_or_lds(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "hand_pose_sl_amd", "csrc", "b2h_api.hip")
-    r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-                        "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", "x.so", src],
-                       cwd=tmp_path, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():                  # parsed as test_dropout_masks_cpu.py does
-        m = re.search(r"remark: [^ ]*\s+(.*?) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            cur = kernels.setdefault(t.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in t:
-            k, v = t.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+def test_kernel_has_no_scratch_spills_or_lds():
+    kernels, listing = kernel_remarks()
     new = {n: res for n, res in kernels.items() if "b2h_adam_step_k" in n}
     assert len(new) == 1, sorted(new)
     for name, res in new.items():
         print(name, "VGPRs", res["VGPRs"], "SGPRs", res["TotalSGPRs"], "occupancy", res["Occupancy [waves/SIMD]"])
         assert res["ScratchSize [bytes/lane]"] == "0" and res["VGPRs Spill"] == "0" and res["SGPRs Spill"] == "0", (name, res)
         assert int(res["LDS Size [bytes/block]"]) == 0, (name, res)
-    listing = [f for f in os.listdir(tmp_path) if f.endswith("gfx950.s")]
-    text = open(os.path.join(tmp_path, listing[0])).read()
+    text = open(listing).read()
     body = text[text.index("b2h_adam_step_kENS_6AdArgsE:"):]
     body = body[:body.index("s_endpgm")]
     # the whole chunks: four 16-byte loads (g, m, v, p) and three 16-byte stores (p, m, v); the dword path: four loads

@@ -6,8 +6,6 @@ counts are printed: pytest -s; DESIGN.md section 20 quotes them)."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 import warnings
 
 import numpy as np
@@ -17,6 +15,7 @@ import hand_pose_sl_amd as hps
 import philox_ref
 from conftest import ROOT
 from hand_pose_sl_amd import _lib
+from kernel_remarks import kernel_remarks
 
 
 def _hex(words):
@@ -140,34 +139,15 @@ def test_mask_orders_of_the_two_models():
                                       ((0, "ff"), (2, 9, 128)), ((0, "drop2"), (2, 9, 128))]
 
 
-def test_kernel_has_no_scratch_or_spills(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "hand_pose_sl_amd", "csrc", "b2h_api.hip")
-    r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-                        "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", "x.so", src],
-                       cwd=tmp_path, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():                  # parsed as test_tpt_train_linear_mfma_cpu.py does
-        m = re.search(r"remark: [^ ]*\s+(.*?) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            cur = kernels.setdefault(t.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in t:
-            k, v = t.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+def test_kernel_has_no_scratch_or_spills():
+    kernels, listing = kernel_remarks()
     new = {n: res for n, res in kernels.items() if "b2h_dropout_masks_k" in n}
     assert len(new) == 1, sorted(new)
     for name, res in new.items():
         print(name, "VGPRs", res["VGPRs"], "SGPRs", res["TotalSGPRs"], "occupancy", res["Occupancy [waves/SIMD]"])
         assert res["ScratchSize [bytes/lane]"] == "0" and res["VGPRs Spill"] == "0" and res["SGPRs Spill"] == "0", (name, res)
         assert int(res["LDS Size [bytes/block]"]) == 0, (name, res)
-    listing = [f for f in os.listdir(tmp_path) if f.endswith("gfx950.s")]
-    text = open(os.path.join(tmp_path, listing[0])).read()
+    text = open(listing).read()
     body = text[text.index("b2h_dropout_masks_kENS_6DmArgsE:"):]
     body = body[:body.index("s_endpgm")]
     # one 16-byte store for the whole chunks, byte stores for the tail, no atomics; the round products are v_mad_u64_u32

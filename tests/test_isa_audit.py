@@ -1,5 +1,5 @@
-"""Static checks of the compiled gfx950 kernels (no GPU needed), from ONE compile of b2h_api.hip with
---save-temps and hipcc's resource-usage remarks (about a minute):
+"""Static checks of the compiled gfx950 kernels (no GPU needed), from the one compile of b2h_api.hip with
+--save-temps and hipcc's resource-usage remarks that tests/kernel_remarks.py makes per pytest process:
 * no buffer/global store may have its data registers rewritten within two wait states
   (tools/store_war_audit.py) -- the store-data write-after-read hazard that produced wrong frames in
   the fused 16-bit kernel;
@@ -7,29 +7,20 @@
   refactor once left the wide 16-bit kernel with 24 spilled VGPRs and serialised weight loads (-22 %),
   visible only in a width sweep on the GPU."""
 import os
-import shutil
 import subprocess
 import sys
 
 import pytest
 
+from kernel_remarks import kernel_remarks
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
-def compiled(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    tmp = tmp_path_factory.mktemp("isa")
-    src = os.path.join(ROOT, "hand_pose_sl_amd", "csrc", "b2h_api.hip")
-    r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-                        "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", "x.so", src],
-                       cwd=tmp, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    listing = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
-    assert listing, os.listdir(tmp)
-    return os.path.join(tmp, listing[0]), r.stderr
+def compiled():
+    kernels, listing = kernel_remarks()
+    return listing, kernels
 
 
 def test_no_close_store_data_overwrite(compiled):
@@ -40,18 +31,7 @@ def test_no_close_store_data_overwrite(compiled):
 
 
 def test_no_kernel_spills_and_promised_occupancy(compiled):
-    import re
-    kernels, cur = {}, None
-    for line in compiled[1].splitlines():
-        m = re.search(r"remark: [^ ]*\s+(.*?) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            cur = kernels.setdefault(t.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in t:
-            k, v = t.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+    kernels = compiled[1]
     conv = {n: r for n, r in kernels.items() if "b2h_fwd" in n or "b2h_tenc_chain" in n or "b2h_attn" in n}
     assert len(conv) >= 25, sorted(kernels)             # every instantiation of every kernel family was seen
     for name, r in conv.items():

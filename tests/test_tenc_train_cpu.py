@@ -5,14 +5,13 @@ dropout follows torch's definition; the new kernels compile without scratch or s
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from conftest import GOLDEN, ROOT
+from kernel_remarks import kernel_remarks
 from tenc_train_ref import (NAMES, leaf_state, load_tenc, masked_l1, param_keys, port_forward, seeded_state,
                             tenc_cases)
 
@@ -121,26 +120,8 @@ def test_port_dropout_semantics():
     assert torch.isfinite(y1).all() and torch.equal(y1, port_forward(x * 3, state, z, 1.0, torch.float64))
 
 
-def test_new_kernels_have_no_scratch_or_spills(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "hand_pose_sl_amd", "csrc", "b2h_api.hip")
-    r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-                        "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", "x.so", src],
-                       cwd=tmp_path, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: [^ ]*\s+(.*?) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            cur = kernels.setdefault(t.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in t:
-            k, v = t.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+def test_new_kernels_have_no_scratch_or_spills():
+    kernels, _ = kernel_remarks()
     new = {n: r for n, r in kernels.items() if "b2h_tt_" in n}
     # posenc, linear, linear_dx, linear_dw, reduce, layernorm, layernorm_bwd, sdpa, sdpa_bwd
     assert len(new) == 9, sorted(new)

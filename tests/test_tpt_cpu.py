@@ -6,7 +6,6 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -16,6 +15,7 @@ import torch
 
 from conftest import ROOT
 from tpt_ref import CASES, Checker, build, case_model, load_case, recipe_model
+from kernel_remarks import kernel_remarks
 
 NEW = ["b2h_tpt_create", "b2h_tpt_destroy", "b2h_tpt_load_weights", "b2h_tpt_workspace_bytes", "b2h_tpt_forward"]
 
@@ -152,26 +152,8 @@ def test_checker_reproduces_reference_fixture(name):
     assert 1.0 < np.abs(r["y64"]).max() < 4.0                # outputs of order 2: absolute bounds mean something
 
 
-def test_new_kernels_have_no_scratch_or_spills(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "hand_pose_sl_amd", "csrc", "b2h_api.hip")
-    r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-                        "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", "x.so", src],
-                       cwd=tmp_path, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: [^ ]*\s+(.*?) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            cur = kernels.setdefault(t.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in t:
-            k, v = t.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+def test_new_kernels_have_no_scratch_or_spills():
+    kernels, _ = kernel_remarks()
     new = {n: r for n, r in kernels.items() if "b2h_tpt_" in n or "b2h_attn_cross_f32" in n}
     # embed, layernorm, and the cross-attention by key tiles 1..8 (not 8 x 8: the query tiles are the block size)
     assert len(new) == 10, sorted(new)

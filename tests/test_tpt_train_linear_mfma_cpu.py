@@ -4,9 +4,6 @@ and exported and answer a NULL model; the Python switch, independent of set_trai
 compile for gfx950 without scratch, spills or static LDS (their register counts are printed: pytest -s; DESIGN.md
 section 19 quotes them)."""
 import os
-import re
-import shutil
-import subprocess
 import warnings
 
 import pytest
@@ -14,6 +11,7 @@ import pytest
 import hand_pose_sl_amd as hps
 from conftest import ROOT
 from hand_pose_sl_amd import _lib
+from kernel_remarks import kernel_remarks
 
 ML_KERNELS = ["b2h_ml_linearE", "b2h_ml_linear_dxE", "b2h_ml_linear_dwE"]    # as the mangled names spell them
 
@@ -49,26 +47,8 @@ def test_python_switch_is_independent_of_train_kernels():
     assert m.train_linear == "mfma"
 
 
-def test_ml_kernels_have_no_scratch_spills_or_static_lds(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "hand_pose_sl_amd", "csrc", "b2h_api.hip")
-    r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-                        "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", "x.so", src],
-                       cwd=tmp_path, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():                  # parsed as test_tpt_train_mfma_cpu.py does
-        m = re.search(r"remark: [^ ]*\s+(.*?) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            cur = kernels.setdefault(t.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in t:
-            k, v = t.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+def test_ml_kernels_have_no_scratch_spills_or_static_lds():
+    kernels, _ = kernel_remarks()
     new = {n: r for n, r in kernels.items() if "b2h_ml_" in n}
     assert len(new) == 3 and all(any(k in n for n in new) for k in ML_KERNELS), sorted(new)
     for name, res in sorted(new.items()):

@@ -5,17 +5,14 @@ T = 200; the blocked attention kernels (kernel_train_attn_long.h) compile for gf
 the C ABI answers without a device at T = 200."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 import torch
 
 import tpt_ref
 from conftest import ROOT
 from tpt_train_ref import leaf_state, load_train, masked_l1, param_keys, port_forward
+from kernel_remarks import kernel_remarks
 
 LONG_CASE = "long_train_e2_d2_b2_s40_t200"
 LONG_KERNELS = ["b2h_lt_sdpaE", "b2h_lt_sdpa_bwd_kvE", "b2h_lt_sdpa_bwd_qE"]   # as the mangled names spell them
@@ -58,26 +55,8 @@ def test_port_reproduces_reference_fixture_at_200_frames():
     np.testing.assert_allclose(x.grad.numpy(), r["dx64"], rtol=1e-9, atol=1e-12 * np.abs(r["dx64"]).max())
 
 
-def test_long_kernels_have_no_scratch_or_spills(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "hand_pose_sl_amd", "csrc", "b2h_api.hip")
-    r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-                        "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", "x.so", src],
-                       cwd=tmp_path, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: [^ ]*\s+(.*?) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            cur = kernels.setdefault(t.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in t:
-            k, v = t.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+def test_long_kernels_have_no_scratch_or_spills():
+    kernels, _ = kernel_remarks()
     new = {n: r for n, r in kernels.items() if "b2h_lt_" in n}
     assert len(new) == 3 and all(any(k in n for n in new) for k in LONG_KERNELS), sorted(new)
     for name, res in new.items():

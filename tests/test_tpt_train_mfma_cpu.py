@@ -3,9 +3,6 @@ TextPoseTransformer.set_train_kernels) without a GPU: the two entry points are d
 answer a NULL model; the Python switch; the three b2h_mt_* kernels compile for gfx950 without scratch, spills or
 static LDS (their VGPR counts are printed: pytest -s; DESIGN.md section 17 quotes them)."""
 import os
-import re
-import shutil
-import subprocess
 import warnings
 
 import pytest
@@ -13,6 +10,7 @@ import pytest
 import hand_pose_sl_amd as hps
 from conftest import ROOT
 from hand_pose_sl_amd import _lib
+from kernel_remarks import kernel_remarks
 
 MFMA_KERNELS = ["b2h_mt_sdpaE", "b2h_mt_sdpa_bwd_kvE", "b2h_mt_sdpa_bwd_qE"]    # as the mangled names spell them
 
@@ -45,26 +43,8 @@ def test_python_switch():
     assert m.train_kernels == "valu"                    # a refused name changes nothing
 
 
-def test_mfma_kernels_have_no_scratch_spills_or_static_lds(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "hand_pose_sl_amd", "csrc", "b2h_api.hip")
-    r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-                        "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", "x.so", src],
-                       cwd=tmp_path, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():                  # parsed as test_tpt_train_long_cpu.py does
-        m = re.search(r"remark: [^ ]*\s+(.*?) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            cur = kernels.setdefault(t.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in t:
-            k, v = t.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+def test_mfma_kernels_have_no_scratch_spills_or_static_lds():
+    kernels, _ = kernel_remarks()
     new = {n: r for n, r in kernels.items() if "b2h_mt_" in n}
     assert len(new) == 3 and all(any(k in n for n in new) for k in MFMA_KERNELS), sorted(new)
     for name, res in sorted(new.items()):

@@ -3,8 +3,6 @@ training fixtures (tests/golden/train/) reproduce through float64 autograd of th
 which pins the checker the GPU tests use; the new kernels compile without scratch or spills."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +10,7 @@ import torch
 
 from conftest import ROOT
 from train_ref import KEYS, load_train, port_grads, reference_loss, train_cases
+from kernel_remarks import kernel_remarks
 
 NEW = ["b2h_train_forward", "b2h_backward_workspace_bytes", "b2h_backward", "b2h_masked_l1_backward",
        "b2h_weighted_l1_backward"]
@@ -88,26 +87,8 @@ def test_trajectory_fixture_reproduces_through_torch_port():
         np.testing.assert_allclose(st[k].detach().numpy(), r["final64_" + k.replace(".", "_")], rtol=0, atol=1e-10)
 
 
-def test_new_kernels_have_no_scratch_or_spills(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "hand_pose_sl_amd", "csrc", "b2h_api.hip")
-    r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-                        "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", "x.so", src],
-                       cwd=tmp_path, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: [^ ]*\s+(.*?) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            cur = kernels.setdefault(t.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in t:
-            k, v = t.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+def test_new_kernels_have_no_scratch_or_spills():
+    kernels, _ = kernel_remarks()
     new = {n: r for n, r in kernels.items() if "b2h_train_" in n or "b2h_l1_backward" in n}
     assert len(new) == 6, sorted(new)    # b2h_train_conv<0|1|2>, b2h_train_reduce, b2h_l1_backward_kernel<2>
     for name, res in new.items():

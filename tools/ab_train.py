@@ -3,7 +3,7 @@
 backward) of TransformerEnc or TextPoseTransformer through the C ABI, after tools/ab_lib.py and tools/ab_tpt.py.
     python tools/ab_train.py <libA.so> <libB.so> [...] --model tpt --shape 128 40 200 --layers 4 --p 0.1 \
         [--attn valu|mfma] [--linear valu|mfma] [--geometry 8 42] [--rounds 7] [--iters 10] [--host-calls 0] \
-        [--refused-calls 0]
+        [--refused-calls 0] [--max-len 100]
 Each library is loaded under its own ctypes handle (only the symbols it has are typed) and gets its own model handle;
 all of them run on the same inputs, parameters, masks and the same output, saved and scratch buffers.  Naming the same
 file twice (or a copy of it) gives the spread of a build against itself, which a difference between two builds has to
@@ -29,6 +29,7 @@ ap.add_argument("--p", type=float, default=0.1)
 ap.add_argument("--attn", choices=sorted(_lib.TRAIN_KERNELS), default="valu")
 ap.add_argument("--linear", choices=sorted(_lib.TRAIN_KERNELS), default="valu")
 ap.add_argument("--geometry", type=int, nargs=2, default=(8, 42), metavar=("N_JOINTS", "NOUT"), help="tpt only")
+ap.add_argument("--max-len", type=int, default=100, help="tenc only: rows of the positional table (T <= max_len)")
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--host-calls", type=int, default=0)
@@ -59,6 +60,8 @@ with warnings.catch_warnings():
         create, ninp, nout = "b2h_tpt_create", model.ninp, model.nout
     else:
         model = hps.TransformerEnc(24, 4, 128, 42, a.layers, dropout=a.p)
+        if a.max_len != 100:  # the class builds the reference's table of 100 rows; the handle takes any length
+            model.pos_encoder = type(model.pos_encoder)(24, a.p, max_len=a.max_len)
         create, ninp, nout = "b2h_tenc_create", 24, 42
 tensors = [t.detach().to(dev).contiguous() for t in model._tensors()]
 g = torch.Generator().manual_seed(1)
