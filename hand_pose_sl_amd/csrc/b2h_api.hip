@@ -753,8 +753,7 @@ struct Chain {
     }
 };
 
-// Attention kernels by query tiles, [nt - 1] with nt = ceil(T / 16) <= 8.  f16x3: b2h_attn_qkv_h3 projects Q, K, V
-// itself.  fp32: b2h_attn_mfma_f32 reads them from the chain's QKV rows.
+// f16x3 self-attention by query tiles, [nt - 1] with nt = ceil(T / 16) <= 8: b2h_attn_qkv_h3 projects Q, K, V itself
 using AttnQkvKernel = void (*)(AttnQkvArgs);
 constexpr AttnQkvKernel kAttnQkvH3[kAttnMaxTiles] = {b2h_attn_qkv_h3<1>, b2h_attn_qkv_h3<2>, b2h_attn_qkv_h3<3>,
                                                      b2h_attn_qkv_h3<4>, b2h_attn_qkv_h3<5>, b2h_attn_qkv_h3<6>,
@@ -765,17 +764,19 @@ using AttnCrossH3Kernel = void (*)(AttnCrossArgs);
 constexpr AttnCrossH3Kernel kAttnCrossH3[kAttnMaxTiles] = {b2h_attn_cross_h3<1>, b2h_attn_cross_h3<2>, b2h_attn_cross_h3<3>,
                                                            b2h_attn_cross_h3<4>, b2h_attn_cross_h3<5>, b2h_attn_cross_h3<6>,
                                                            b2h_attn_cross_h3<7>, b2h_attn_cross_h3<8>};
-using AttnKernel = void (*)(const float*, float*, int);
-constexpr AttnKernel kAttn[kAttnMaxTiles] = {b2h_attn_mfma_f32<1>, b2h_attn_mfma_f32<2>, b2h_attn_mfma_f32<3>,
-                                             b2h_attn_mfma_f32<4>, b2h_attn_mfma_f32<5>, b2h_attn_mfma_f32<6>,
-                                             b2h_attn_mfma_f32<7>, b2h_attn_mfma_f32<8>};
-
-// Attention over more than 128 query rows (kernel_attn_long.h) by key tiles per key block, [nk - 1]
-using AttnLongKernel = void (*)(const float*, int, int, const float*, int, int, int, float*, int, int);
-constexpr AttnLongKernel kAttnLongF32[kAttnMaxTiles] = {b2h_attn_long_f32<1>, b2h_attn_long_f32<2>, b2h_attn_long_f32<3>,
+// Attention over described rows (AttnSrc) by key tiles, [nk - 1]: fp32 up to 128 query rows with nk = ceil(Tk / 16) (the
+// block size carries the query tiles; row [1] for launches with as many query tiles as key tiles); beyond
+// (kernel_attn_long.h), both arithmetics, nk = key tiles per key block
+using AttnRowsKernel = void (*)(AttnSrc, float*, int, int);
+constexpr AttnRowsKernel kAttnF32[2][kAttnMaxTiles] = {
+    {b2h_attn_f32<1, false>, b2h_attn_f32<2, false>, b2h_attn_f32<3, false>, b2h_attn_f32<4, false>, b2h_attn_f32<5, false>,
+     b2h_attn_f32<6, false>, b2h_attn_f32<7, false>, b2h_attn_f32<8, false>},
+    {b2h_attn_f32<1, true>, b2h_attn_f32<2, true>, b2h_attn_f32<3, true>, b2h_attn_f32<4, true>, b2h_attn_f32<5, true>,
+     b2h_attn_f32<6, true>, b2h_attn_f32<7, true>, b2h_attn_f32<8, true>}};
+constexpr AttnRowsKernel kAttnLongF32[kAttnMaxTiles] = {b2h_attn_long_f32<1>, b2h_attn_long_f32<2>, b2h_attn_long_f32<3>,
                                                         b2h_attn_long_f32<4>, b2h_attn_long_f32<5>, b2h_attn_long_f32<6>,
                                                         b2h_attn_long_f32<7>, b2h_attn_long_f32<8>};
-constexpr AttnLongKernel kAttnLongH3[kAttnMaxTiles] = {b2h_attn_long_h3<1>, b2h_attn_long_h3<2>, b2h_attn_long_h3<3>,
+constexpr AttnRowsKernel kAttnLongH3[kAttnMaxTiles] = {b2h_attn_long_h3<1>, b2h_attn_long_h3<2>, b2h_attn_long_h3<3>,
                                                        b2h_attn_long_h3<4>, b2h_attn_long_h3<5>, b2h_attn_long_h3<6>,
                                                        b2h_attn_long_h3<7>, b2h_attn_long_h3<8>};
 
@@ -820,23 +821,28 @@ void self_attn_h3(const TencBlob (&heads)[kTencHeads], const float* x, float* OC
     hipLaunchKernelGGL(kAttnQkvH3[nt - 1], dim3(attn_h3_grid(num_cus)), dim3(64 * nt), (size_t)attn_qkv_lds_bytes(nt), st, qa);
 }
 
-// fp32 self-attention of B sequences of T <= 128 rows: Q | K | V rows (B*T, 384) -> OC (B*T, 128)
-void self_attn_f32(const float* QKV, float* OC, int64_t B, int T, hipStream_t st) {
-    const int nt = (T + 15) / 16;
-    hipLaunchKernelGGL(kAttn[nt - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nt), (size_t)attn_f32_lds_bytes(nt), st,
-                       QKV, OC, T);
-}
+// The operands of the two attentions, inference and training: the chain's [Q | K | V] rows against themselves, and
+// the decoder's cross-query rows against the memory's [K | V] rows
+AttnSrc self_src(const float* qkv) { return AttnSrc{qkv, 3 * kTencD, 0, qkv, 3 * kTencD, kTencD, 2 * kTencD}; }
+AttnSrc cross_src(const float* qc, const float* kv) { return AttnSrc{qc, kTencD, 0, kv, 2 * kTencD, 0, kTencD}; }
 
-// Attention of B sequences of Tq > 128 query rows over Tk key rows, both arithmetics (kernel_attn_long.h has the
-// operand description).  The query tiles are cut into ceil(tiles / 8) blocks of equal tile count (>= 5 for Tq > 128,
-// which the kernels' staging rounds count on), the key tiles likewise into blocks of nk tiles.
-void attn_long(bool h3, const float* q, int ldq, int colq, const float* kv, int ldkv, int colk, int colv, float* out,
-               int64_t B, int Tq, int Tk, hipStream_t st) {
-    const int ntq = (Tq + 15) / 16, nqb = (ntq + kAttnMaxTiles - 1) / kAttnMaxTiles, wpb = (ntq + nqb - 1) / nqb;
-    const int ntk = (Tk + 15) / 16, nkb = (ntk + kAttnMaxTiles - 1) / kAttnMaxTiles, nk = (ntk + nkb - 1) / nkb;
+// Inference attention of B sequences of Tq query rows over Tk key rows, out (B*Tq, 128).  Tq <= 128 (and Tk <= 128):
+// the whole-matrix b2h_attn_f32, one wave per query tile.  That arm is exact fp32 ONLY: f16x3 at T <= 128 keeps its
+// fused kernels (self_attn_h3, b2h_attn_cross_h3) and never gets here.  Beyond, both arithmetics (kernel_attn_long.h):
+// the query tiles are cut into ceil(tiles / 8) blocks of equal tile count (>= 5 for Tq > 128, which the kernels'
+// staging rounds count on), the key tiles likewise into blocks of nk tiles.
+void attn_rows(hipStream_t st, bool h3, const AttnSrc& src, float* out, int64_t B, int Tq, int Tk) {
+    const int ntq = (Tq + 15) / 16, ntk = (Tk + 15) / 16;
+    if (ntq <= kAttnMaxTiles) {
+        hipLaunchKernelGGL(kAttnF32[ntq == ntk][ntk - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * ntq),
+                           (size_t)attn_f32_lds_bytes(ntk), st, src, out, Tq, Tk);
+        return;
+    }
+    const int nqb = (ntq + kAttnMaxTiles - 1) / kAttnMaxTiles, wpb = (ntq + nqb - 1) / nqb;
+    const int nkb = (ntk + kAttnMaxTiles - 1) / kAttnMaxTiles, nk = (ntk + nkb - 1) / nkb;
     hipLaunchKernelGGL(h3 ? kAttnLongH3[nk - 1] : kAttnLongF32[nk - 1], dim3((unsigned)(B * kTencHeads), (unsigned)nqb),
-                       dim3(64 * wpb), (size_t)(h3 ? attn_long_h3_lds_bytes(nk) : attn_long_f32_lds_bytes(nk)), st, q, ldq,
-                       colq, kv, ldkv, colk, colv, out, Tq, Tk);
+                       dim3(64 * wpb), (size_t)(h3 ? attn_long_h3_lds_bytes(nk) : attn_long_f32_lds_bytes(nk)), st, src, out,
+                       Tq, Tk);
 }
 
 // Residual stream XA, attention output OC and (fp32 path) the Q, K, V rows of the next attention; QKV is
@@ -901,11 +907,8 @@ int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, con
     const TencWs ws{XA, XA + n * kTencD, h3 ? nullptr : XA + 2 * n * kTencD};
     chain_in(m, x, n, (int)T, fa, ws, st);
     for (int l = 0; l < m->nlayers; ++l) { // torch.nn.TransformerEncoderLayer, post-norm, ReLU
-        if (h3) {
-            self_attn_h3(m->layers[l].qkv_head, ws.XA, ws.OC, B, (int)T, m->num_cus, st);
-        } else {
-            self_attn_f32(ws.QKV, ws.OC, B, (int)T, st);
-        }
+        if (h3) self_attn_h3(m->layers[l].qkv_head, ws.XA, ws.OC, B, (int)T, m->num_cus, st);
+        else attn_rows(st, false, self_src(ws.QKV), ws.OC, B, (int)T, (int)T);
         chain_tail(m, l, y, n, (int)T, fa, ws, st);
     }
     HIP_TRY(hipGetLastError());
@@ -1064,11 +1067,6 @@ TptWs tpt_ws(void* workspace, int64_t Ns, int64_t Nt, int n_dec) {
     w.XP = w.QKVt + Nt * 3 * kTencD;
     return w;
 }
-
-using AttnCrossKernel = void (*)(const float*, int, int, const float*, int, int, int, float*, int, int);
-constexpr AttnCrossKernel kAttnCross[kAttnMaxTiles] = {b2h_attn_cross_f32<1>, b2h_attn_cross_f32<2>, b2h_attn_cross_f32<3>,
-                                                       b2h_attn_cross_f32<4>, b2h_attn_cross_f32<5>, b2h_attn_cross_f32<6>,
-                                                       b2h_attn_cross_f32<7>, b2h_attn_cross_f32<8>};
 
 // A chain without the item transforms: (n, ldx) rows, optional (n, 128) residual rows
 Chain tpt_rows(const float* x, int ldx, const float* res, int64_t n, bool h3 = false) {
@@ -1324,7 +1322,7 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
         }
         for (int l = 0; l < m->n_enc; ++l) {
             const EncLayer& L = m->enc[l];
-            self_attn_f32(ws.QKVs, ws.OCs, B, (int)S, st);
+            attn_rows(st, false, self_src(ws.QKVs), ws.OCs, B, (int)S, (int)S);
             Chain c = tpt_rows(ws.OCs, kTencD, ws.MEM, Ns);
             c.add_layer_tail(L.attn_out, L.ff1, L.ff2, ws.MEM, l + 1 < m->n_enc ? &m->enc[l + 1] : nullptr, ws.QKVs);
             c.launch(m->num_cus, st);
@@ -1353,21 +1351,15 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
     }
     for (int l = 0; l < m->n_dec; ++l) {
         const auto& L = m->dec[l];
-        if (long_t) attn_long(h3, ws.QKVt, 3 * kTencD, 0, ws.QKVt, 3 * kTencD, kTencD, 2 * kTencD, ws.OCt, B, (int)T, (int)T, st);
-        else self_attn_f32(ws.QKVt, ws.OCt, B, (int)T, st);
+        attn_rows(st, h3, self_src(ws.QKVt), ws.OCt, B, (int)T, (int)T);
         {   // self out_proj + x -> norm1 -> X1; the cross-attention query of X1
             Chain c = tpt_rows(ws.OCt, kTencD, ws.XT, Nt, h3);
             c.add(L.attn_out, ST_RESLN_GLOBAL, ws.X1);
             c.add(L.cq, ST_STORE, ws.QC);
             c.launch(m->num_cus, st);
         }
-        const float* mkv = ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats;
-        if (long_t) // one key block: S <= 128
-            attn_long(h3, ws.QC, kTencD, 0, mkv, 2 * kTencD, 0, kTencD, ws.OCt, B, (int)T, (int)S, st);
-        else
-            hipLaunchKernelGGL(kAttnCross[nk - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * nq),
-                               (size_t)attn_f32_lds_bytes(nk), st, ws.QC, kTencD, 0, mkv, 2 * kTencD, 0, kTencD, ws.OCt, (int)T,
-                               (int)S);
+        // S <= 128: one key block at any T
+        attn_rows(st, h3, cross_src(ws.QC, ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats), ws.OCt, B, (int)T, (int)S);
         // cross out_proj + X1 -> norm2 -> linear1 ReLU -> linear2 + res -> norm3 -> XT [+ the next layer's Q, K, V]
         Chain c = tpt_rows(ws.OCt, kTencD, ws.X1, Nt, h3);
         c.add_layer_tail(L.cross_out, L.ff1, L.ff2, ws.XT, l + 1 < m->n_dec ? &m->dec[l + 1] : nullptr, ws.QKVt);
@@ -1571,13 +1563,12 @@ float tt_scale(float p) { return p < 1.f ? 1.f / (1.f - p) : 0.f; }
 // (kernel_train_attn_mfma.h).
 enum class TrainAttn { kWhole, kBlockedValu, kBlockedMfma };
 
-// Self-attention over [Q | K | V] rows (N, 384), and its gradients [dQ | dK | dV] in the same layout.
-XsdpaSrc self_src(const float* qkv) { return XsdpaSrc{qkv, 3 * kTtD, 0, qkv, 3 * kTtD, kTtD, 2 * kTtD}; }
+// The gradients of self-attention over [Q | K | V] rows (N, 384): [dQ | dK | dV] in the same layout (self_src's counterpart).
 LtGradDst self_dst(float* gQ) { return LtGradDst{gQ, 3 * kTtD, 0, gQ, 3 * kTtD, kTtD, 2 * kTtD}; }
 
 // Attention of B sequences of Tq query rows over Tk key rows in training: O (B*Tq, 128) and, from the blocked kernels
 // only, the rows' log-sum-exp (B, 4, Tq).
-void train_sdpa(hipStream_t st, TrainAttn route, const XsdpaSrc& src, const uint8_t* mask, float sc, float* O, float* lse,
+void train_sdpa(hipStream_t st, TrainAttn route, const AttnSrc& src, const uint8_t* mask, float sc, float* O, float* lse,
                 int64_t B, int Tq, int Tk) {
     const unsigned heads = (unsigned)(B * kTtHeads);
     const dim3 grid(heads, lt_blocks(Tq, kLtQb));
@@ -1590,7 +1581,7 @@ void train_sdpa(hipStream_t st, TrainAttn route, const XsdpaSrc& src, const uint
 }
 
 // Its backward.  Blocked: the query owner (dQ, and the row terms D for the key owner), then the key owner (dK, dV).
-void train_sdpa_bwd(hipStream_t st, TrainAttn route, const XsdpaSrc& src, const float* dO, const float* lse, float* D,
+void train_sdpa_bwd(hipStream_t st, TrainAttn route, const AttnSrc& src, const float* dO, const float* lse, float* D,
                     const uint8_t* mask, float sc, const LtGradDst& dst, int64_t B, int Tq, int Tk) {
     const unsigned heads = (unsigned)(B * kTtHeads);
     const dim3 gq(heads, lt_blocks(Tq, kLtQb)), gkv(heads, lt_blocks(Tk, kLtKb));
@@ -1860,8 +1851,6 @@ void tt_layernorm(hipStream_t st, const float* X, const float* gamma, const floa
     hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, X, gamma, beta, Y, stats, 4, N);
 }
 
-// The cross-attention operands of decoder layer L: queries QC (Nt, 128), [K | V] rows (Ns, 256).
-XsdpaSrc tpt_xsrc(const TptDecLayer& L) { return XsdpaSrc{L.QC, kTtD, 0, L.KV, 2 * kTtD, 0, kTtD}; }
 // Which kernels run the decoder's two attentions in training: the whole-matrix pair up to 128 frames, beyond them the
 // blocked ones as b2h_tpt_set_train_kernel chose.  The one place that decides: the dispatch and
 // b2h_tpt_train_attn_name both ask it.
@@ -1954,7 +1943,7 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
         // multihead_attn: the query of H1 (in_proj rows 0..127), [K | V] of the memory (rows 128..383)
         tt_linear(ln, L.H1, w[4], w[5], L.QC, Nt, kTtD, kTtD, 0, nullptr, 1.f, nullptr);
         tt_linear(ln, sv.MEM, w[4] + kDD, w[5] + kTtD, L.KV, Ns, kTtD, 2 * kTtD, 0, nullptr, 1.f, nullptr);
-        train_sdpa(st, route, tpt_xsrc(L), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S);
+        train_sdpa(st, route, cross_src(L.QC, L.KV), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S);
         tt_linear(ln, L.OC, w[6], w[7], L.R2, Nt, kTtD, kTtD, 0, mk(mi + 3), sc, L.H1);
         tt_layernorm(st, L.R2, w[14], w[15], L.H2, L.ST12 + 2, Nt);
         tt_linear(ln, L.H2, w[8], w[9], L.F1, Nt, kTtD, kTtD, 1, mk(mi + 4), sc, nullptr);
@@ -2038,7 +2027,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         tt_linear_dw(ln, dC, L.OC, G.slabs, Nt, kTtD, kTtD, g[6], g[7]);
         tt_linear_dx(ln, dC, w[6], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dOC
         const float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
-        train_sdpa_bwd(st, route, tpt_xsrc(L), G.gC, lse + Nt * kTtHeads, Drow, mk(mi + 2), sc,
+        train_sdpa_bwd(st, route, cross_src(L.QC, L.KV), G.gC, lse + Nt * kTtHeads, Drow, mk(mi + 2), sc,
                        LtGradDst{G.gA, kTtD, 0, dKV, 2 * kTtD, 0, kTtD}, B, (int)T, (int)S);          // gA = dQC, dKV
         // multihead_attn.in_proj: rows 0..127 from (dQC, H1) over the frames, rows 128..383 from ([dK | dV], MEM)
         // over the tokens, each with the slab count of its own row set

@@ -58,6 +58,19 @@ struct MfmaParams {
     int pos_emb;          // layer-1 in-channel 24 carries t/100 (weights permuted)
 };
 
+// ---- transformer attention (inference and training) -------------------------
+// Where the operands of one attention live: q rows (B*Tq, ldq), the head's 32 columns from colq + 32 h;
+// kv rows (B*Tk, ldkv), K from colk + 32 h and V from colv + 32 h.  Self-attention: q = kv = the [Q | K | V] rows
+// at ld 384, columns 0 / 128 / 256, Tq = Tk; cross-attention: the query rows at ld 128 against the memory's
+// [K | V] rows at ld 256.  Nothing reached through it is __restrict__.
+struct AttnSrc {
+    const float* q;
+    int ldq, colq;
+    const float* kv;
+    int ldkv, colk, colv;
+};
+constexpr float kAttnQkScale = 0.17677669529663687f; // head_dim^-0.5 = 1 / sqrt(32)
+
 __host__ __device__ inline int hidden_chan_of(int mt, int row) { return 8 * (row >> 2) + 4 * mt + (row & 3); }
 __host__ __device__ inline int last_chan_of(int mt, int row) { return 16 * mt + row; }
 

@@ -1,15 +1,13 @@
 // Attention over more than 128 query rows (TextPoseTransformer's decoder at T > 128, b2h_tpt_forward_fused): the
 // keys no longer fit one workgroup's LDS and a query's scores no longer fit its registers, so the keys are walked
-// in blocks with an online softmax.  Two kernels, one per arithmetic, with the operand description of
-// b2h_attn_cross_f32 (kernel_tpt.h), so that each serves both uses:
-//   q   : (B*Tq, ldq)  rows, the head's 32 columns start at colq + 32 h
-//   kv  : (B*Tk, ldkv) rows, K at colk + 32 h and V at colv + 32 h
+// in blocks with an online softmax.  Two kernels, one per arithmetic, on described operands (AttnSrc, b2h_common.h)
+// like b2h_attn_f32 (kernel_tenc.h), so that each serves both uses:
 //   out : (B*Tq, 128), head h -> columns 32 h ..
 //   self-attention : q = kv = the chain's Q | K | V rows (ld 384, columns 0 / 128 / 256), Tk = Tq = T
 //   cross-attention: q = the chain's QC rows (ld 128), kv = the memory's K | V rows (ld 256), Tk = S <= 128: one block
 //
 //   b2h_attn_long_f32<NK>  exact fp32 (v_mfma_f32_16x16x4_f32): K, V rows in LDS at the kAttnRow pitch, the score
-//                          tile is the B operand of P.V, as in attn_core_f32 (kernel_tenc.h).
+//                          tile is the B operand of P.V: the tile products of b2h_attn_f32 (kernel_tenc.h).
 //   b2h_attn_long_h3<NK>   B2H_TENC_F16X3: reads the same fp32 rows and splits them into f16 hi + lo as it stages
 //                          them -- K rows at the kKRow pitch in the chain's k-slot order, V^T in vt_slot order --
 //                          then split8 of the probabilities and three v_mfma_f32_16x16x32_f16 per product, as in
@@ -39,16 +37,15 @@ constexpr int attn_long_f32_lds_bytes(int nk) { return 2 * attn_f32_lds_bytes(nk
 constexpr int attn_long_h3_lds_bytes(int nk) { return 2 * attn_kv_bytes(nk); }
 
 template <int NK>
-__global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(const float* __restrict__ qm, int ldq, int colq,
-                                                                        const float* __restrict__ kv, int ldkv, int colk,
-                                                                        int colv, float* __restrict__ out, int Tq, int Tk) {
+__global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(AttnSrc src, float* __restrict__ out, int Tq,
+                                                                        int Tk) {
     extern __shared__ __attribute__((aligned(16))) char smem_al[];
     constexpr int kBuf = attn_f32_lds_bytes(NK);      // K, then V of one key block
     constexpr int kChunks = NK * 16 * 8;              // float4 of a block's K (and of its V)
     constexpr int R = (kChunks + 64 * kLongMinWaves - 1) / (64 * kLongMinWaves); // staging rounds: <= 4
     const int b = blockIdx.x / kTencHeads, h = blockIdx.x % kTencHeads;
-    const __amdgpu_buffer_rsrc_t krs = make_rsrc(kv + (int64_t)b * Tk * ldkv, Tk * ldkv * 4);
-    const __amdgpu_buffer_rsrc_t qrs = make_rsrc(qm + (int64_t)b * Tq * ldq, Tq * ldq * 4);
+    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + (int64_t)b * Tk * src.ldkv, Tk * src.ldkv * 4);
+    const __amdgpu_buffer_rsrc_t qrs = make_rsrc(src.q + (int64_t)b * Tq * src.ldq, Tq * src.ldq * 4);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nthreads = __builtin_amdgcn_readfirstlane(blockDim.x);
     const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
@@ -59,9 +56,9 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(const fl
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int i = threadIdx.x + r * nthreads, t = jb * 16 * NK + (i >> 3), c = i & 7;
-            const int off = i < kChunks ? (t * ldkv + h * kTencHd + 4 * c) * 4 : (int)kOob;
-            k4[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, colk * 4, 0));
-            v4[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, colv * 4, 0));
+            const int off = i < kChunks ? (t * src.ldkv + h * kTencHd + 4 * c) * 4 : (int)kOob;
+            k4[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, src.colk * 4, 0));
+            v4[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, src.colv * 4, 0));
         }
     };
     auto put = [&](int buf, const f32x4 (&k4)[R], const f32x4 (&v4)[R]) {
@@ -80,11 +77,10 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(const fl
     fetch(0, kr, vr);
 #pragma unroll
     for (int g = 0; g < 2; ++g) // B operand of S^T: d = 16g + 4q + j
-        qb[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            qrs, (tq * ldq + colq + h * kTencHd + 16 * g + 4 * q) * 4, 0, 0));
+        qb[g] = buf_load4(qrs, tq * src.ldq + src.colq + h * kTencHd + 16 * g + 4 * q);
     put(0, kr, vr);
-    qb[0] *= 0.17677669529663687f; // pre-scaled query (torch scales q, not the scores)
-    qb[1] *= 0.17677669529663687f;
+    qb[0] *= kAttnQkScale; // pre-scaled query (torch scales q, not the scores)
+    qb[1] *= kAttnQkScale;
     __syncthreads();
     float m = -INFINITY, l = 0.f;
     f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -99,13 +95,7 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(const fl
         float bm = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < NK; ++kt) {
-            sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                const f32x4 ka = *reinterpret_cast<const f32x4*>(Ks + (kt * 16 + col) * kAttnRow + 16 * g + 4 * q);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[j], qb[g][j], sc[kt], 0, 0, 0);
-            }
+            sc[kt] = tile_rows_dot(Ks, kt, qb, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
             for (int r = 0; r < 4; ++r) { // D row 4q + r = key index within the tile
                 if (kt * 16 + 4 * q + r >= left) sc[kt][r] = -INFINITY;
@@ -128,38 +118,26 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(const fl
         o[0] *= alpha;
         o[1] *= alpha;
 #pragma unroll
-        for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float* vrow = Vs + (kt * 16 + 4 * q + r) * kAttnRow + col;
-                o[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[0], sc[kt][r], o[0], 0, 0, 0);
-                o[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[16], sc[kt][r], o[1], 0, 0, 0);
-            }
+        for (int kt = 0; kt < NK; ++kt) tile_cols_acc(Vs, kt, sc[kt], o);
         if (more) { // (workgroup-uniform)
             put((jb + 1) & 1, kr, vr);
             __syncthreads();
         }
     }
-    // D rows 16mt + 4q + r = d; queries >= Tq fall outside the descriptor
-    const float inv = 1.0f / l;
-    const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + (int64_t)b * Tq * kTencD, Tq * kTencD * 4);
-    const int ooff = (tq * kTencD + h * kTencHd + 4 * q) * 4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0] * inv), ors, ooff, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
+    attn_store_out(out, b, Tq, tq, h, o, l);
 }
 
 template <int NK>
-__global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_h3(const float* __restrict__ qm, int ldq, int colq,
-                                                                       const float* __restrict__ kv, int ldkv, int colk,
-                                                                       int colv, float* __restrict__ out, int Tq, int Tk) {
+__global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_h3(AttnSrc src, float* __restrict__ out, int Tq,
+                                                                       int Tk) {
     extern __shared__ __attribute__((aligned(16))) char smem_alh[];
     constexpr int KS = (NK + 1) / 2;                  // k-steps of 32 keys
     constexpr int kKBytes = attn_k_bytes(NK), kKV = attn_kv_bytes(NK);
     constexpr int kItems = NK * 16 * 4;               // (key, lane quarter): 8 of the key's 32 K dims and 8 of its V dims
     constexpr int R = (kItems + 64 * kLongMinWaves - 1) / (64 * kLongMinWaves); // staging rounds: <= 2
     const int b = blockIdx.x / kTencHeads, h = blockIdx.x % kTencHeads;
-    const __amdgpu_buffer_rsrc_t krs = make_rsrc(kv + (int64_t)b * Tk * ldkv, Tk * ldkv * 4);
-    const __amdgpu_buffer_rsrc_t qrs = make_rsrc(qm + (int64_t)b * Tq * ldq, Tq * ldq * 4);
+    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + (int64_t)b * Tk * src.ldkv, Tk * src.ldkv * 4);
+    const __amdgpu_buffer_rsrc_t qrs = make_rsrc(src.q + (int64_t)b * Tq * src.ldq, Tq * src.ldq * 4);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nthreads = __builtin_amdgcn_readfirstlane(blockDim.x);
     const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
@@ -170,11 +148,11 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_h3(const flo
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int i = threadIdx.x + r * nthreads, t = jb * 16 * NK + (i >> 2), qq = i & 3;
-            const int off = i < kItems ? (t * ldkv + h * kTencHd + 4 * qq) * 4 : (int)kOob;
+            const int off = i < kItems ? (t * src.ldkv + h * kTencHd + 4 * qq) * 4 : (int)kOob;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                k4[r][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, (colk + 16 * u) * 4, 0));
-                v4[r][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, (colv + 16 * u) * 4, 0));
+                k4[r][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, (src.colk + 16 * u) * 4, 0));
+                v4[r][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, (src.colv + 16 * u) * 4, 0));
             }
         }
     };
@@ -215,11 +193,10 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_h3(const flo
         f32x4 q4[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-            q4[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                qrs, (tq * ldq + colq + h * kTencHd + 16 * u + 4 * q) * 4, 0, 0));
+            q4[u] = buf_load4(qrs, tq * src.ldq + src.colq + h * kTencHd + 16 * u + 4 * q);
         float vq[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) vq[j] = q4[j >> 2][j & 3] * 0.17677669529663687f; // torch scales q, not the scores
+        for (int j = 0; j < 8; ++j) vq[j] = q4[j >> 2][j & 3] * kAttnQkScale; // torch scales q, not the scores
         split8(vq, qh, ql);
     }
     if (KS * 32 > NK * 16) { // odd NK: the last k-step's upper 16 key slots of V^T have no writer (both buffers)
@@ -298,11 +275,7 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_h3(const flo
             __syncthreads();
         }
     }
-    const float inv = 1.0f / l;
-    const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + (int64_t)b * Tq * kTencD, Tq * kTencD * 4);
-    const int ooff = (tq * kTencD + h * kTencHd + 4 * q) * 4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0] * inv), ors, ooff, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
+    attn_store_out(out, b, Tq, tq, h, o, l);
 }
 
 } // namespace b2h

@@ -1,11 +1,12 @@
 // TransformerEnc (body2hand/src/models/HandPoseModels.py:118-178) on gfx950.
 // Two kernels per precision:
 //
-//   b2h_attn_mfma_f32 / b2h_attn_qkv_h3
+//   b2h_attn_f32 / b2h_attn_qkv_h3
 //                       self-attention, wave = 16 query frames of one (sequence, head): scores and
 //                       P.V on the matrix cores, softmax in registers over all T keys (the
 //                       reference passes no mask, HandPoseModels.py:170).  The fp32 kernel reads
-//                       Q, K, V rows; the f16x3 kernel projects them itself from the residual stream.
+//                       described Q, K, V rows (AttnSrc: TextPoseTransformer's cross-attention is the
+//                       same kernel); the f16x3 kernel projects them itself from the residual stream.
 //   b2h_tenc_chain<H3>  everything between two attention calls, which is all per-frame: a wave
 //                       carries 16 frames through a chain of Linear layers in registers (the
 //                       accumulator layout IS the next GEMM's operand layout), with bias, ReLU,
@@ -66,26 +67,123 @@ constexpr int kAttnMaxTiles = 8; // T <= 128
 constexpr int kAttnRow = 36;
 constexpr int attn_f32_lds_bytes(int nt) { return 2 * nt * 16 * kAttnRow * (int)sizeof(float); } // K, then V
 
-// The core of both exact-fp32 attention kernels (b2h_attn_mfma_f32 here, b2h_attn_cross_f32 in kernel_tpt.h), from
-// the staged operands to the output stores: score tiles S^T = K . Q^T, the mask of keys >= Tk, softmax over the keys
-// inside the lane quartet, O^T = V^T . P^T, the normalisation and the two stores of query row tq.  Ks / Vs hold the
-// head's 16 NK key / value rows at the kAttnRow pitch (rows >= Tk zero), qb this lane's pre-scaled query fragments
-// (d = 16g + 4q + j); out is (B*Tq, 128).  The kernels differ only in where they load Ks, Vs and qb from.
-template <int NK>
-__device__ __forceinline__ void attn_core_f32(const float* Ks, const float* Vs, const f32x4 (&qb)[2], int Tk,
-                                              float* __restrict__ out, int Tq, int b, int h, int tq, int col, int q) {
+// A float4 of a row set through its descriptor: offsets in floats; past the end a load returns 0 and a store is dropped
+constexpr uint32_t kOob = 0x7ffffff0u; // byte offset no descriptor here reaches
+__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t rs, int float_off) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, float_off * 4, 0, 0));
+}
+__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t rs, int float_off, f32x4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, float_off * 4, 0, 0);
+}
+
+// The two fp32 tile products (v_mfma_f32_16x16x4_f32) of every attention kernel that keeps its rows in LDS at the
+// kAttnRow pitch -- b2h_attn_f32 below, b2h_attn_long_f32 (kernel_attn_long.h), b2h_mt_* (kernel_train_attn_mfma.h).
+// lane = (col, q) = (lane % 16, lane / 16); the first product's accumulator (row 4 q + r of column col in register r)
+// is the second one's B operand without leaving its registers.
+// acc += rows[16 kt + col][:] . frag: the A operand is the tile's rows from LDS, d = 16 g + 4 q + j in k-step
+// (g, j); frag holds the B operand's same d for the lane's column
+__device__ __forceinline__ f32x4 tile_rows_dot(const float* rows, int kt, const f32x4 (&frag)[2], f32x4 acc) {
+    const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(rows + (kt * 16 + col) * kAttnRow + 16 * g + 4 * q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], frag[g][j], acc, 0, 0, 0);
+    }
+    return acc;
+}
+// out^T[16 mt + ..][col] += sum over the tile's rows 4 q + r of rows[16 kt + 4 q + r][16 mt + col] * w[r]
+__device__ __forceinline__ void tile_cols_acc(const float* rows, int kt, f32x4 w, f32x4 (&out)[2]) {
+    const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float* row = rows + (kt * 16 + 4 * q + r) * kAttnRow + col;
+        out[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[0], w[r], out[0], 0, 0, 0);
+        out[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[16], w[r], out[1], 0, 0, 0);
+    }
+}
+
+// The inference attention kernels' last step: O^T / l of query row tq of sequence b into out (B*Tq, 128), head h ->
+// columns 32 h ..  o[mt][r] is d = 16 mt + 4 q + r; queries >= Tq fall outside the descriptor.
+__device__ __forceinline__ void attn_store_out(float* out, int64_t b, int Tq, int tq, int h, const f32x4 (&o)[2], float l) {
+    const int q = (threadIdx.x & 63) >> 4;
+    const float inv = 1.0f / l;
+    const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + b * Tq * kTencD, Tq * kTencD * 4);
+    const int ooff = (tq * kTencD + h * kTencHd + 4 * q) * 4;
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0] * inv), ors, ooff, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
+}
+
+// Attention over described rows (AttnSrc, b2h_common.h) on the matrix cores, exact fp32 (v_mfma_f32_16x16x4_f32), up
+// to 128 query rows and 128 key rows: softmax(q k^T) v with q pre-scaled by head_dim^-0.5
+// (torch.nn.MultiheadAttention), no mask (the reference passes none, HandPoseModels.py:170, :211).  Every fp32
+// self-attention (q = kv = the chain's [Q | K | V] rows, Tq = Tk) and TextPoseTransformer's cross-attention
+// (frames' QC rows against the memory's [K | V] rows, every memory row attended, padded token ids included).
+//   out : (B*Tq, 128), head h -> columns 32 h ..
+// Workgroup = (sequence, head); wave w owns query tile w (16 rows) against all key tiles, so the block size is
+// 64 * ceil(Tq / 16) (<= 512) and only the key-tile count NK = ceil(Tk / 16) is a template parameter (the loops over
+// it are branch-free), not 8 x 8 pairs.  SQ says that the launch has as many query tiles as key tiles (every
+// self-attention): the block size 64 NK is then a constant, the staging loop below is its one round without a
+// branch, and a one-wave workgroup needs no barrier.  Without it TransformerEnc at T = 16 ran 0.2 % slower than
+// with the self-attention kernel this one replaced; the results are the same bit for bit.
+//   S^T[key][query] = K[key][d] . (Q[query][d] * 32^-0.5)      8 MFMAs per 16x16 tile
+//   softmax over keys: the 4*NK scores of a query sit in ONE lane quartet
+//                      (registers + lanes l, l^16, l^32), keys >= Tk masked to -inf
+//   O^T[d][query] = V^T[d][key] . P^T[key][query]: the score tile's accumulator IS the B operand
+//                      (D row 4q+r  <->  B k-index q for fixed r): no shuffle, no LDS round trip
+// K and V of the head live in LDS as [key][kAttnRow] fp32 with kAttnRow = 36: the 4-float pad
+// spreads the 16 key rows of a fragment read (ds_read_b128, K) and the 4 row groups of a V column
+// read (ds_read_b32) over all banks (a 32-float row puts them on the same ones).  All global accesses are buffer
+// instructions over the sequence's rows: key rows >= Tk read 0 and are masked to -inf, query rows >= Tq read 0 (a
+// uniform softmax over the valid keys, finite) and their stores are dropped by the range check; nothing is
+// predicated and all loads of a staging round are in flight together.
+template <int NK, bool SQ>
+__global__ __launch_bounds__(SQ ? 64 * NK : 64 * kAttnMaxTiles) void b2h_attn_f32(AttnSrc src, float* __restrict__ out,
+                                                                                   int Tq, int Tk) {
+    extern __shared__ __attribute__((aligned(16))) char smem_attn[];
+    float* Ks = reinterpret_cast<float*>(smem_attn);
+    float* Vs = reinterpret_cast<float*>(smem_attn + attn_f32_lds_bytes(NK) / 2);
+    const int b = blockIdx.x / kTencHeads, h = blockIdx.x % kTencHeads;
+    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + (int64_t)b * Tk * src.ldkv, Tk * src.ldkv * 4);
+    const __amdgpu_buffer_rsrc_t qrs = make_rsrc(src.q + (int64_t)b * Tq * src.ldq, Tq * src.ldq * 4);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nthreads = SQ ? 64 * NK : __builtin_amdgcn_readfirstlane(blockDim.x);
+    const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
+    const int tq = wave * 16 + col;
+    f32x4 qb[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) // B operand of S^T: d = 16g + 4q + j
+        qb[g] = buf_load4(qrs, tq * src.ldq + src.colq + h * kTencHd + 16 * g + 4 * q);
+    // K, V rows of the head: NK*16 rows x 8 float4 each, two per thread and round (one round when Tq and Tk
+    // have the same tile count); every LDS row below 16 NK is written, rows >= Tk with the zeros of the range check
+    constexpr int kChunks = NK * 16 * 8;
+#pragma unroll 1
+    for (int i0 = threadIdx.x; i0 < kChunks; i0 += 2 * nthreads) {
+        f32x4 k4[2], v4[2];
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int i = i0 + it * nthreads, t = i >> 3, c = i & 7;
+            const int off = i < kChunks ? (t * src.ldkv + h * kTencHd + 4 * c) * 4 : (int)kOob;
+            k4[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, src.colk * 4, 0));
+            v4[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, src.colv * 4, 0));
+        }
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int i = i0 + it * nthreads, t = i >> 3, c = i & 7;
+            if (i < kChunks) {
+                *reinterpret_cast<f32x4*>(Ks + t * kAttnRow + 4 * c) = k4[it];
+                *reinterpret_cast<f32x4*>(Vs + t * kAttnRow + 4 * c) = v4[it];
+            }
+        }
+    }
+    qb[0] *= kAttnQkScale; // pre-scaled query (torch scales q, not the scores)
+    qb[1] *= kAttnQkScale;
+    __syncthreads();
     f32x4 sc[NK];
     float mx = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NK; ++kt) {
-        sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            // A operand: key row kt*16 + col, d = 16g + 4q + j
-            const f32x4 ka = *reinterpret_cast<const f32x4*>(Ks + (kt * 16 + col) * kAttnRow + 16 * g + 4 * q);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) sc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[j], qb[g][j], sc[kt], 0, 0, 0);
-        }
+        sc[kt] = tile_rows_dot(Ks, kt, qb, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
         for (int r = 0; r < 4; ++r) { // D row 4q + r = key index within the tile
             if (kt * 16 + 4 * q + r >= Tk) sc[kt][r] = -INFINITY;
@@ -102,75 +200,10 @@ __device__ __forceinline__ void attn_core_f32(const float* Ks, const float* Vs, 
             l += sc[kt][r];
         }
     l = quad_sum(l);
-    // O^T[d][query]: for step (kt, r) lane q supplies P^T[kt*16 + 4q + r][query] = sc[kt][r];
-    // the A operand is V[kt*16 + 4q + r][16mt + col]
     f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-    for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* vrow = Vs + (kt * 16 + 4 * q + r) * kAttnRow + col;
-            o[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[0], sc[kt][r], o[0], 0, 0, 0);
-            o[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[16], sc[kt][r], o[1], 0, 0, 0);
-        }
-    // D rows 16mt + 4q + r = d; queries >= Tq fall outside the descriptor
-    const float inv = 1.0f / l;
-    const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + (int64_t)b * Tq * kTencD, Tq * kTencD * 4);
-    const int ooff = (tq * kTencD + h * kTencHd + 4 * q) * 4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0] * inv), ors, ooff, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
-}
-
-// Self-attention on the matrix cores, exact fp32 (v_mfma_f32_16x16x4_f32): softmax(q k^T) v with
-// q pre-scaled by head_dim^-0.5 (torch.nn.MultiheadAttention).
-//   qkv : (B*T, 384) = [q | k | v] x 128, head h = columns h*32 .. h*32+31 of each third
-//   out : (B*T, 128), head h -> columns h*32 ..  Workgroup = (sequence,
-// head); wave w owns query tile w (16 frames) against all key tiles:
-//   S^T[key][query] = K[key][d] . (Q[query][d] * 32^-0.5)      8 MFMAs per 16x16 tile
-//   softmax over keys: the 4*ntiles scores of a query sit in ONE lane quartet
-//                      (registers + lanes l, l^16, l^32), keys >= T masked to -inf
-//   O^T[d][query] = V^T[d][key] . P^T[key][query]: the score tile's accumulator IS the B operand
-//                      (D row 4q+r  <->  B k-index q for fixed r): no shuffle, no LDS round trip
-// K and V of the head live in LDS as [key][kAttnRow] fp32 with kAttnRow = 36: the 4-float pad
-// spreads the 16 key rows of a fragment read (ds_read_b128, K) and the 4 row groups of a V column
-// read (ds_read_b32) over all banks (a 32-float row puts them on the same ones).  Rows T..16*NT
-// are zero: every global access is a buffer instruction over the sequence's rows, whose range
-// check returns 0 past T and drops stores, so nothing is predicated and all loads of the
-// workgroup are in flight together.
-template <int NT> // number of 16-frame tiles = ceil(T / 16): compile-time so that the loops are branch-free
-__global__ __launch_bounds__(64 * NT) void b2h_attn_mfma_f32(const float* __restrict__ qkv,
-                                                          float* __restrict__ out, int T) {
-    extern __shared__ __attribute__((aligned(16))) char smem_attn2[];
-    float* Ks = reinterpret_cast<float*>(smem_attn2);
-    float* Vs = reinterpret_cast<float*>(smem_attn2 + attn_f32_lds_bytes(NT) / 2);
-    const int b = blockIdx.x / kTencHeads, h = blockIdx.x % kTencHeads;
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(qkv + (int64_t)b * T * (3 * kTencD), T * 3 * kTencD * 4);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
-    const int tq = wave * 16 + col;
-    // K, V rows of the head: NT*16 rows x 8 float4 = two per thread each; and this lane's query
-    f32x4 k4[2], v4[2], qb[2];
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int i = threadIdx.x + it * 64 * NT, t = i >> 3, c = i & 7;
-        const int off = (t * 3 * kTencD + h * kTencHd + 4 * c) * 4;
-        k4[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, kTencD * 4, 0));
-        v4[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 2 * kTencD * 4, 0));
-    }
-#pragma unroll
-    for (int g = 0; g < 2; ++g) // B operand of S^T: d = 16g + 4q + j
-        qb[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            rs, (tq * 3 * kTencD + h * kTencHd + 16 * g + 4 * q) * 4, 0, 0));
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int i = threadIdx.x + it * 64 * NT, t = i >> 3, c = i & 7;
-        *reinterpret_cast<f32x4*>(Ks + t * kAttnRow + 4 * c) = k4[it];
-        *reinterpret_cast<f32x4*>(Vs + t * kAttnRow + 4 * c) = v4[it];
-    }
-    qb[0] *= 0.17677669529663687f; // pre-scaled query (torch scales q, not the scores)
-    qb[1] *= 0.17677669529663687f;
-    __syncthreads();
-    attn_core_f32<NT>(Ks, Vs, qb, T, out, T, b, h, tq, col, q);
+    for (int kt = 0; kt < NK; ++kt) tile_cols_acc(Vs, kt, sc[kt], o);
+    attn_store_out(out, b, Tq, tq, h, o, l);
 }
 
 // ---- per-frame chain ---------------------------------------------------------------------
@@ -344,8 +377,7 @@ __device__ __forceinline__ void chain_gemm_h3_db(const f32x4* __restrict__ wl, i
 // have, a missing output), so the loop has no branch around a load or store and the compiler can
 // count outstanding operations instead of draining them (with predicated global_load/store it
 // waited vmcnt(0) before the first MFMA of every stage and before every store).
-constexpr uint32_t kOob = 0x7ffffff0u; // byte offset no descriptor here reaches
-
+// (kOob, the offset that stands for "no access", is defined with buf_load4 above.)
 __device__ __forceinline__ f32x4 chain_ld(__amdgpu_buffer_rsrc_t rs, uint32_t off) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0));
 }
@@ -361,7 +393,7 @@ __device__ __forceinline__ f32x4 chain_ld(__amdgpu_buffer_rsrc_t rs, uint32_t of
 //     Q_h stays in registers: with the chain's k-slot order (slot (q, j) = dim 16(j>>2) + 4q + (j&3)) a lane's
 //         eight accumulators ARE its query fragment; K_h goes to LDS as the lane's one 16-byte chunk of its
 //         key row in the same slot order, V_h as V^T[dim][key slot]
-//     barrier, then the same wave mapping and softmax as b2h_attn_mfma_f32, both products on
+//     barrier, then the same wave mapping and softmax as b2h_attn_f32, both products on
 //     v_mfma_f32_16x16x32_f16 as lo.hi + hi.lo + hi.hi with fp32 accumulation:
 //       S^T tile = K[16 keys][32 dims] . Q^T     one k-step (k = dims): A from the LDS rows of K (f16 hi / lo),
 //                  B = this lane's query fragment
@@ -453,7 +485,7 @@ __global__ __launch_bounds__(64 * NT) void b2h_attn_qkv_h3(AttnQkvArgs a) {
             float vq[8], vk[8], vv[8]; // slot (q, j) = dim 16 (j >> 2) + 4q + (j & 3) = accumulator (j >> 2, j & 3)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                vq[j] = acc[j >> 2][j & 3] * 0.17677669529663687f; // torch scales q, not the scores
+                vq[j] = acc[j >> 2][j & 3] * kAttnQkScale; // torch scales q, not the scores
                 vk[j] = acc[2 + (j >> 2)][j & 3];
                 vv[j] = acc[4 + (j >> 2)][j & 3];
             }

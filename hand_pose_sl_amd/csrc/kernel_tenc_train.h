@@ -33,7 +33,7 @@ constexpr int kTtDwRows = 64, kTtDwM = 32;          // row tile and output-row t
 constexpr int kTtMaxSlabs = 64;
 constexpr int kTtQs = kTtHd + 1;                    // LDS row stride of Q, K, V, dO (odd: conflict-free columns)
 constexpr float kTtLnEps = 1e-5f;
-constexpr float kTtQkScale = 0.17677669529663687f;  // 1 / sqrt(32)
+constexpr float kTtQkScale = kAttnQkScale;          // 1 / sqrt(32)
 
 __host__ __device__ inline int tt_nslabs(int64_t N) {
     const int64_t t = (N + 2 * kTtDwRows - 1) / (2 * kTtDwRows);

@@ -3,17 +3,17 @@
 //
 //   b2h_tpt_embed        token_embedding(input_tokens) (:206): row n of the (B*S, 128) encoder input is
 //                        table[tokens[n]], not scaled.
-//   b2h_attn_cross_f32   the decoder's multihead_attn: queries are the Tq target frames of a sequence, keys and
-//                        values the Tk rows of the encoder memory of the same sequence.  The reference passes no
-//                        mask (:211), so every memory row is attended, padded token ids included.
-//   b2h_attn_cross_h3    the same attention for B2H_TENC_F16X3, with its Q, K and V projections inside: it reads the
-//                        frames' norm1 rows and the memory rows, so neither Q nor the memory's K | V cross HBM.
+//   b2h_attn_cross_h3    the decoder's multihead_attn for B2H_TENC_F16X3, with its Q, K and V projections inside:
+//                        queries are the T target frames of a sequence (their norm1 rows), keys and values the S rows
+//                        of the encoder memory of the same sequence, so neither Q nor the memory's K | V cross HBM.
+//                        The reference passes no mask (:211): every memory row is attended, padded token ids included.
+//                        (In exact fp32 that attention is b2h_attn_f32, kernel_tenc.h, on the QC and memory K | V rows.)
 //   b2h_tpt_layernorm    encoder.norm / decoder.norm, the LayerNorm that ends each stack of torch.nn.Transformer.
 //   b2h_item_pad_rows     42- and 58-float pose rows -> zero-padded 64-float rows for the chain's front.
 //   b2h_item_build_kernel  the composite input rows of `--predict right_index` / `right_3fingers`.
 //
 // Everything else of the model is per-frame and runs as descriptors of b2h_tenc_chain<H3>; the self-attention of
-// both stacks is b2h_attn_mfma_f32 or b2h_attn_qkv_h3 (b2h_api.hip: tpt_launch has the launch lists).  Targets of
+// both stacks is b2h_attn_f32 or b2h_attn_qkv_h3 (b2h_api.hip: tpt_launch has the launch lists).  Targets of
 // more than 128 frames (b2h_tpt_forward_fused) run the decoder's two attentions on kernel_attn_long.h instead.
 #pragma once
 #include "kernel_tenc.h"
@@ -101,64 +101,6 @@ __global__ __launch_bounds__(256) void b2h_tpt_layernorm(const float* X, const f
         make_float4(dx * rstd * g.x + b.x, dy * rstd * g.y + b.y, dz * rstd * g.z + b.z, dw * rstd * g.w + b.w);
 }
 
-// Cross-attention on the matrix cores, exact fp32 (v_mfma_f32_16x16x4_f32).  Everything after the operands are
-// staged is attn_core_f32 (kernel_tenc.h), which b2h_attn_mfma_f32 runs too: q pre-scaled by 32^-0.5, K and V rows
-// in LDS at the 36-float pitch.  What differs is where the operands come from:
-//   q   : (B*Tq, ldq)  rows, the head's 32 columns start at colq + 32 h
-//   kv  : (B*Tk, ldkv) rows of ANOTHER row set, K at colk + 32 h and V at colv + 32 h
-//   out : (B*Tq, 128), head h -> columns 32 h ..
-// Workgroup = (sequence, head); wave w owns query tile w, so the block size is 64 * ceil(Tq / 16) (<= 512) and
-// only the key-tile count NK = ceil(Tk / 16) is a template parameter: 8 instantiations, not 8 x 8.  All global
-// accesses are buffer instructions over the sequence's rows: key rows >= Tk read 0 and are masked to -inf,
-// query rows >= Tq read 0 (a uniform softmax over the valid keys, finite) and their stores are dropped by the
-// range check; nothing is predicated.
-template <int NK>
-__global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_cross_f32(const float* __restrict__ qm, int ldq, int colq,
-                                                                         const float* __restrict__ kv, int ldkv, int colk,
-                                                                         int colv, float* __restrict__ out, int Tq, int Tk) {
-    extern __shared__ __attribute__((aligned(16))) char smem_attnx[];
-    float* Ks = reinterpret_cast<float*>(smem_attnx);
-    float* Vs = reinterpret_cast<float*>(smem_attnx + attn_f32_lds_bytes(NK) / 2);
-    const int b = blockIdx.x / kTencHeads, h = blockIdx.x % kTencHeads;
-    const __amdgpu_buffer_rsrc_t krs = make_rsrc(kv + (int64_t)b * Tk * ldkv, Tk * ldkv * 4);
-    const __amdgpu_buffer_rsrc_t qrs = make_rsrc(qm + (int64_t)b * Tq * ldq, Tq * ldq * 4);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nthreads = __builtin_amdgcn_readfirstlane(blockDim.x);
-    const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
-    const int tq = wave * 16 + col;
-    f32x4 qb[2];
-#pragma unroll
-    for (int g = 0; g < 2; ++g) // B operand of S^T: d = 16g + 4q + j
-        qb[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            qrs, (tq * ldq + colq + h * kTencHd + 16 * g + 4 * q) * 4, 0, 0));
-    // K, V rows of the head: NK*16 rows x 8 float4 each, two per thread and round (one round when Tq and Tk
-    // have the same tile count); every LDS row below 16 NK is written, rows >= Tk with the zeros of the range check
-    constexpr int kChunks = NK * 16 * 8;
-#pragma unroll 1
-    for (int i0 = threadIdx.x; i0 < kChunks; i0 += 2 * nthreads) {
-        f32x4 k4[2], v4[2];
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int i = i0 + it * nthreads, t = i >> 3, c = i & 7;
-            const int off = i < kChunks ? (t * ldkv + h * kTencHd + 4 * c) * 4 : (int)kOob;
-            k4[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, colk * 4, 0));
-            v4[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, colv * 4, 0));
-        }
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int i = i0 + it * nthreads, t = i >> 3, c = i & 7;
-            if (i < kChunks) {
-                *reinterpret_cast<f32x4*>(Ks + t * kAttnRow + 4 * c) = k4[it];
-                *reinterpret_cast<f32x4*>(Vs + t * kAttnRow + 4 * c) = v4[it];
-            }
-        }
-    }
-    qb[0] *= 0.17677669529663687f; // pre-scaled query (torch scales q, not the scores)
-    qb[1] *= 0.17677669529663687f;
-    __syncthreads();
-    attn_core_f32<NK>(Ks, Vs, qb, Tk, out, Tq, b, h, tq, col, q);
-}
-
 // ---- Q, K, V projection + cross-attention in one kernel (B2H_TENC_F16X3) ------------------------------------------
 // The two-row-set sibling of b2h_attn_qkv_h3 (kernel_tenc.h; its comment has the fragment layouts, all reused here):
 // queries come from the T frame rows `x` (the decoder's norm1 output), keys and values from the S rows `mem` of the
@@ -166,7 +108,7 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_cross_f32(const f
 // v_mfma_f32_16x16x32_f16 per product, so that Q and the memory's K | V never cross HBM.
 //   Launch : persistent and bound to a head like the sibling (blockIdx = 8 (4 slot + head) + xcd, b += 8 nslots);
 //            block = 64 ceil(T / 16) threads, wave w owns query tile w; only NK = ceil(S / 16) is a template
-//            parameter (8 instantiations, as b2h_attn_cross_f32).
+//            parameter (8 instantiations, as b2h_attn_f32).
 //   Weights: the head's blob is the one b2h_attn_qkv_h3 takes -- [hi: mt(6)][g(4)][lane] f16x8, [lo] the same, 384
 //            fp32 with the 96 biases first; M-tiles 0-1 = Q_h, 2-3 = K_h, 4-5 = V_h -- copied to LDS once per
 //            workgroup.  The two projections address their M-tiles inside it with chain_gemm_h3_at: Q at (hi, lo),
@@ -197,8 +139,9 @@ struct AttnCrossArgs {
 
 // From "K and V of the sequence complete in LDS" to the output stores: score tiles S^T = K . Q^T (lo.hi + hi.lo +
 // hi.hi), the mask of keys >= Tk, softmax over the keys inside the lane quartet (v_exp_f32), O^T = V^T . P^T with
-// the score registers as the B operand, the normalisation and the two stores of query row tq.  This is the tail of
-// b2h_attn_qkv_h3 (kernel_tenc.h) line for line, with the key count Tk apart from the query count Tq.  It is a copy
+// the score registers as the B operand, the normalisation and the two stores of query row tq (attn_store_out).  Up to
+// the stores this is the tail of b2h_attn_qkv_h3 (kernel_tenc.h) line for line, with the key count Tk apart from the
+// query count Tq.  It is a copy
 // and not one function for both kernels because sharing it changed the sibling's code: with the tail moved into a
 // force-inlined function, b2h_attn_qkv_h3<1> came out with 134 instead of 130 VGPRs and 7 more instructions and
 // <5> with another register count, and TransformerEnc's kernels are not to change for this model (DESIGN.md
@@ -253,11 +196,7 @@ __device__ __forceinline__ void attn_core_h3(const _Float16* Kh, const _Float16*
             o[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, ph, o[mt], 0, 0, 0);
         }
     }
-    const float inv = 1.0f / l;
-    const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + b * Tq * kTencD, Tq * kTencD * 4);
-    const int ooff = (tq * kTencD + h * kTencHd + 4 * q) * 4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0] * inv), ors, ooff, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1] * inv), ors, ooff, 64, 0);
+    attn_store_out(out, b, Tq, tq, h, o, l);
 }
 
 template <int NK>
@@ -321,7 +260,7 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_cross_h3(AttnCros
         {
             float vq[8]; // slot (q, j) = dim 16 (j >> 2) + 4q + (j & 3) = accumulator (j >> 2, j & 3)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) vq[j] = acc[j >> 2][j & 3] * 0.17677669529663687f; // torch scales q, not the scores
+            for (int j = 0; j < 8; ++j) vq[j] = acc[j >> 2][j & 3] * kAttnQkScale; // torch scales q, not the scores
             split8(vq, qh, ql);
         }
         // K_h | V_h of this wave's key tiles: M-tiles 2-5

@@ -7,7 +7,7 @@
 //                    (sequence, head), the whole (Tq, Tk) matrix in LDS
 //   b2h_tt_sdpa_bwd  recomputes the probabilities from Q, K; dQ for the query rows, dK and dV for the key rows
 //
-// The operands are described by XsdpaSrc and the gradients' destinations by LtGradDst, so the one pair serves
+// The operands are described by AttnSrc (b2h_common.h) and the gradients' destinations by LtGradDst, so the one pair serves
 // self-attention ([Q | K | V] rows at ld 384, Tq = Tk) and cross-attention (QC at ld 128 against the memory's [K | V]
 // rows at ld 256), as the blocked kernels beyond 128 rows do (kernel_train_attn_long.h, kernel_train_attn_mfma.h).
 // In self-attention q and kv are one buffer, and so are dq and dkv: nothing reached through the two structs is
@@ -17,16 +17,7 @@
 
 namespace b2h {
 
-// Where the operands of one attention live: q rows (B*Tq, ldq), the head's 32 columns from colq + 32 h;
-// kv rows (B*Tk, ldkv), K from colk + 32 h and V from colv + 32 h.
-struct XsdpaSrc {
-    const float* q;
-    int ldq, colq;
-    const float* kv;
-    int ldkv, colk, colv;
-};
-
-// Where the gradients of one attention go: dQ rows (B*Tq, lddq) from column coldq + 32 h; dK and dV rows
+// Where the gradients of one attention go (AttnSrc's counterpart, b2h_common.h): dQ rows (B*Tq, lddq) from column coldq + 32 h; dK and dV rows
 // (B*Tk, lddkv) from coldk + 32 h and coldv + 32 h.
 struct LtGradDst {
     float* dq;
@@ -76,7 +67,7 @@ __device__ inline void tt_softmax_rows(const float* Q, const float* K, float* P,
 
 // O[i][32 h + d] = sum_j drop(P)[i][j] V[j][d], O (B*Tq, 128); mask (B, 4, Tq, Tk).
 // grid B * 4, 256 threads, tt_sdpa_lds_bytes(Tq, Tk, false) of dynamic LDS.  1 <= Tq, Tk <= 128.
-__global__ __launch_bounds__(256) void b2h_tt_sdpa(XsdpaSrc src, const uint8_t* __restrict__ mask, float scale,
+__global__ __launch_bounds__(256) void b2h_tt_sdpa(AttnSrc src, const uint8_t* __restrict__ mask, float scale,
                                                    float* __restrict__ O, int Tq, int Tk) {
     extern __shared__ __attribute__((aligned(16))) float smem_tt[];
     float* Q = smem_tt;
@@ -113,7 +104,7 @@ __global__ __launch_bounds__(256) void b2h_tt_sdpa(XsdpaSrc src, const uint8_t* 
 //   dQ[i] = sum_j dZ[i][j] K[j] / sqrt(32);  dK[j] = sum_i dZ[i][j] Q[i] / sqrt(32).
 // dO (B*Tq, 128) is the gradient of the concatenated heads.  tt_sdpa_lds_bytes(Tq, Tk, true) of dynamic LDS: Q, dO,
 // K, V, the (Tq, Tk) matrix and the mask bytes.
-__global__ __launch_bounds__(256) void b2h_tt_sdpa_bwd(XsdpaSrc src, const float* __restrict__ dO,
+__global__ __launch_bounds__(256) void b2h_tt_sdpa_bwd(AttnSrc src, const float* __restrict__ dO,
                                                        const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
                                                        int Tq, int Tk) {
     extern __shared__ __attribute__((aligned(16))) float smem_tt[];

@@ -11,7 +11,7 @@
 //                      sigma_i = rowsum(P) and D_i = rowsum(dSd o P) / sigma_i, then for dQ, which it writes once
 //   b2h_lt_sdpa_bwd_kv the key owner: one workgroup per key block walks the query blocks and writes dK, dV once
 //
-// The operands are described by XsdpaSrc and the gradients' destinations by LtGradDst (kernel_train_attn.h), so the
+// The operands are described by AttnSrc and the gradients' destinations by LtGradDst (kernel_train_attn.h), so the
 // same three kernels serve [Q | K | V] rows at ld 384 and QC at ld 128 against the memory's [K | V] rows at ld 256.
 // The backward recomputes P_ij = exp(s_ij - LSE_i) / sigma_i block by block.  With dSd = keep ? dP * scale : 0 and
 // dZ = P o (dSd - D):  dV_j = sum_i Pd_ij dO_i,  dK_j = sum_i dZ_ij Q_i / sqrt(32),  dQ_i = sum_j dZ_ij K_j / sqrt(32).
@@ -49,7 +49,7 @@ __device__ inline float lt_dot(const float* a, const float* b) {
 // A wave owns the rows w, w + 4, .. of the query block for the scores; a thread owns column d = tid % 32 of the
 // rows tid / 32 + 8 r for the output.  The row state lives in LDS: running maximum, running sum and the factor
 // alpha = exp(m_old - m_new) of the current key block (0 on the first block, where m_old is not formed).
-__global__ __launch_bounds__(256) void b2h_lt_sdpa(XsdpaSrc src, const uint8_t* __restrict__ mask, float scale,
+__global__ __launch_bounds__(256) void b2h_lt_sdpa(AttnSrc src, const uint8_t* __restrict__ mask, float scale,
                                                    float* __restrict__ O, float* __restrict__ lse, int Tq, int Tk) {
     extern __shared__ __attribute__((aligned(16))) float smem_lt[];
     float* Q = smem_lt;
@@ -149,7 +149,7 @@ __device__ inline void lt_bwd_terms(const float* q, const float* g, const float*
 // The key owner: dK[j] and dV[j] of the key rows j0 .. j0 + 127 of one (sequence, head), summed over the query blocks
 // in ascending order, rows ascending inside a block.  grid (B * 4, ceil(Tk / 128)), 256 threads, kLtBwdKvLds.
 // A thread owns column d = tid % 32 of the key rows tid / 32 + 8 r, r < 16: 32 sums in registers, stored once.
-__global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_kv(XsdpaSrc src, const float* __restrict__ dO,
+__global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_kv(AttnSrc src, const float* __restrict__ dO,
                                                           const float* __restrict__ lse, const float* __restrict__ D,
                                                           const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
                                                           int Tq, int Tk) {
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_kv(XsdpaSrc src, const fl
 // fp32 reference 1.5e-6.  Dividing by sigma_i makes the row sum 1 to the rounding of its own
 // terms, as in b2h_tt_sdpa_bwd.
 // A thread owns column d = tid % 32 of the rows tid / 32 + 8 r, r < 8.
-__global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_q(XsdpaSrc src, const float* __restrict__ dO,
+__global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_q(AttnSrc src, const float* __restrict__ dO,
                                                          const float* __restrict__ lse, float* __restrict__ D,
                                                          const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
                                                          int Tq, int Tk) {

@@ -1,6 +1,6 @@
 // The blocked training attention of kernel_train_attn_long.h on the matrix cores: b2h_mt_sdpa, b2h_mt_sdpa_bwd_q and
 // b2h_mt_sdpa_bwd_kv are drop-in counterparts of b2h_lt_sdpa, b2h_lt_sdpa_bwd_q and b2h_lt_sdpa_bwd_kv -- the same
-// arguments (XsdpaSrc operands, a uint8 keep-mask (B, 4, Tq, Tk) in global memory or NULL, `scale` = 1 / (1 - p)), the
+// arguments (AttnSrc operands, a uint8 keep-mask (B, 4, Tq, Tk) in global memory or NULL, `scale` = 1 / (1 - p)), the
 // same O (B*Tq, 128), LSE (B, 4, Tq) and {D, sigma} (B, 4, Tq, 2) layouts, the same grids (64 query rows or 128 key
 // rows per workgroup of 256 threads) and the same mathematics (DESIGN.md sections 16 and 17): an online softmax whose
 // first block sets alpha = 0 and reads no state, mask and scale on the numerator only, a backward that recomputes
@@ -11,7 +11,8 @@
 // the workgroup's rows as the COLUMNS of every product it forms, so a row of that tile never meets another row's
 // numbers, and the first product's accumulator is the B operand of the second without leaving its registers
 // (lane = (col, q): the 16 x 16 result holds row 4 q + r of column col in register r, and B[k = q][col] of the k-step
-// r of the next product is that very register -- the order of b2h_attn_long_f32, kernel_attn_long.h):
+// r of the next product is that very register -- tile_rows_dot and tile_cols_acc of kernel_tenc.h, which the inference
+// kernels b2h_attn_f32 and b2h_attn_long_f32 run too):
 //
 //   forward, query owner   columns = the wave's 16 queries.  S^T = K Q^T and dP^T = V dO^T (A = the key block's rows
 //                          from LDS, B = Q / dO fragments in registers), then O^T += V^T Pd^T, dQ^T += K^T dZ^T
@@ -51,21 +52,15 @@ struct MtRows {
     f32x4 a[4], b[4];
 };
 
-__device__ __forceinline__ f32x4 mt_load4(__amdgpu_buffer_rsrc_t rs, int float_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, float_off * 4, 0, 0));
-}
-__device__ __forceinline__ void mt_store4(__amdgpu_buffer_rsrc_t rs, int float_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, float_off * 4, 0, 0);
-}
 __device__ __forceinline__ f32x4 mt_zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
 // K and V rows j0 .. j0 + 127 of head h -> registers; rows >= Tk lie outside krs and read 0
-__device__ __forceinline__ void mt_fetch_kv(__amdgpu_buffer_rsrc_t krs, const XsdpaSrc& src, int h, int j0, MtRows& x) {
+__device__ __forceinline__ void mt_fetch_kv(__amdgpu_buffer_rsrc_t krs, const AttnSrc& src, int h, int j0, MtRows& x) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int i = threadIdx.x + 256 * r, off = (j0 + (i >> 3)) * src.ldkv + h * kTtHd + 4 * (i & 7);
-        x.a[r] = mt_load4(krs, off + src.colk);
-        x.b[r] = mt_load4(krs, off + src.colv);
+        x.a[r] = buf_load4(krs, off + src.colk);
+        x.b[r] = buf_load4(krs, off + src.colv);
     }
 }
 __device__ __forceinline__ void mt_put_kv(char* buf, const MtRows& x) {
@@ -79,34 +74,10 @@ __device__ __forceinline__ void mt_put_kv(char* buf, const MtRows& x) {
     }
 }
 
-// acc += rows[16 kt + lane % 16][:] . frag: the A operand is the tile's rows from LDS, d = 16 g + 4 q + j in k-step
-// (g, j); frag holds the B operand's same d for the lane's column
-__device__ __forceinline__ f32x4 mt_rows_dot(const float* rows, int kt, const f32x4 (&frag)[2], f32x4 acc) {
-    const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(rows + (kt * 16 + col) * kAttnRow + 16 * g + 4 * q);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], frag[g][j], acc, 0, 0, 0);
-    }
-    return acc;
-}
-
-// out^T[16 mt + ..][col] += sum over the tile's rows 4 q + r of rows[16 kt + 4 q + r][16 mt + lane % 16] * w[r]
-__device__ __forceinline__ void mt_cols_acc(const float* rows, int kt, f32x4 w, f32x4 (&out)[2]) {
-    const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float* row = rows + (kt * 16 + 4 * q + r) * kAttnRow + col;
-        out[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[0], w[r], out[0], 0, 0, 0);
-        out[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[16], w[r], out[1], 0, 0, 0);
-    }
-}
-
 // O[i][32 h + d] = sum_j keep_ij scale e_ij V[j][d] / l_i with e_ij = exp(s_ij - m_i), l_i = sum_j e_ij (unmasked);
 // lse_i = m_i + log l_i.  grid (B * 4, ceil(Tq / 64)), 256 threads, kMtFwdLds.  Wave w owns the queries i0 + 16 w ..;
 // the row state (m, l) lives in the registers of the four lanes of a column.
-__global__ __launch_bounds__(256) void b2h_mt_sdpa(XsdpaSrc src, const uint8_t* __restrict__ mask, float scale,
+__global__ __launch_bounds__(256) void b2h_mt_sdpa(AttnSrc src, const uint8_t* __restrict__ mask, float scale,
                                                    float* __restrict__ O, float* __restrict__ lse, int Tq, int Tk) {
     extern __shared__ __attribute__((aligned(16))) char smem_mt[];
     const int64_t b = blockIdx.x / kTtHeads;
@@ -123,7 +94,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa(XsdpaSrc src, const uint8_t* 
     mt_fetch_kv(krs, src, h, 0, nx);
     f32x4 qb[2];
 #pragma unroll
-    for (int g = 0; g < 2; ++g) qb[g] = mt_load4(qrs, tq * src.ldq + src.colq + h * kTtHd + 16 * g + 4 * q);
+    for (int g = 0; g < 2; ++g) qb[g] = buf_load4(qrs, tq * src.ldq + src.colq + h * kTtHd + 16 * g + 4 * q);
     mt_put_kv(smem_mt, nx);
     __syncthreads();
     float m = -INFINITY, l = 0.f;
@@ -141,7 +112,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa(XsdpaSrc src, const uint8_t* 
 #pragma unroll
             for (int kt = 0; kt < kMtKb / 16; ++kt) {
                 if (kt * 16 < left) {
-                    sc[kt] = mt_rows_dot(Ks, kt, qb, mt_zero4());
+                    sc[kt] = tile_rows_dot(Ks, kt, qb, mt_zero4());
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         sc[kt][r] = kt * 16 + 4 * q + r < left ? sc[kt][r] * kTtQkScale : -INFINITY;
@@ -173,7 +144,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa(XsdpaSrc src, const uint8_t* 
             o[1] *= alpha;
 #pragma unroll
             for (int kt = 0; kt < kMtKb / 16; ++kt)
-                if (kt * 16 < left) mt_cols_acc(Vs, kt, sc[kt], o);
+                if (kt * 16 < left) tile_cols_acc(Vs, kt, sc[kt], o);
         }
         if (more) { // (workgroup-uniform)
             mt_put_kv(smem_mt + ((jb + 1) & 1) * kMtKvBuf, nx);
@@ -183,8 +154,8 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa(XsdpaSrc src, const uint8_t* 
     if (!live) return;
     // D rows 16 mt + 4 q + r = d of query tq; queries >= Tq fall outside the descriptor
     const __amdgpu_buffer_rsrc_t ors = make_rsrc(O + b * Tq * kTtD, Tq * kTtD * 4);
-    mt_store4(ors, tq * kTtD + h * kTtHd + 4 * q, o[0] / l);
-    mt_store4(ors, tq * kTtD + h * kTtHd + 16 + 4 * q, o[1] / l);
+    buf_store4(ors, tq * kTtD + h * kTtHd + 4 * q, o[0] / l);
+    buf_store4(ors, tq * kTtD + h * kTtHd + 16 + 4 * q, o[1] / l);
     if (q == 0 && tq < Tq) lse[(int64_t)blockIdx.x * Tq + tq] = m + logf(l);
 }
 
@@ -194,7 +165,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa(XsdpaSrc src, const uint8_t* 
 // D_i = sum_j dSd_ij exp(s_ij - LSE_i) / sigma_i -- a lane adds its keys of a block, the column's four lanes are added,
 // the blocks are added in ascending order --, then for dZ = P o (dSd - D) / sqrt(32) and dQ^T += K^T dZ^T.  A single key
 // block (cross-attention) is staged once.
-__global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(XsdpaSrc src, const float* __restrict__ dO,
+__global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(AttnSrc src, const float* __restrict__ dO,
                                                          const float* __restrict__ lse, float* __restrict__ D,
                                                          const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
                                                          int Tq, int Tk) {
@@ -216,8 +187,8 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(XsdpaSrc src, const flo
     f32x4 qb[2], gb[2];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-        qb[g] = mt_load4(qrs, tq * src.ldq + src.colq + h * kTtHd + 16 * g + 4 * q);
-        gb[g] = mt_load4(grs, tq * kTtD + h * kTtHd + 16 * g + 4 * q);
+        qb[g] = buf_load4(qrs, tq * src.ldq + src.colq + h * kTtHd + 16 * g + 4 * q);
+        gb[g] = buf_load4(grs, tq * kTtD + h * kTtHd + 16 * g + 4 * q);
     }
     const float lse_i = tq < Tq ? lse[row] : 0.f;
     mt_put_kv(smem_mt, nx);
@@ -241,7 +212,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(XsdpaSrc src, const flo
 #pragma unroll
             for (int kt = 0; kt < kMtKb / 16; ++kt) {
                 if (kt * 16 < left) {
-                    const f32x4 s = mt_rows_dot(Ks, kt, qb, mt_zero4()), dp = mt_rows_dot(Vs, kt, gb, mt_zero4());
+                    const f32x4 s = tile_rows_dot(Ks, kt, qb, mt_zero4()), dp = tile_rows_dot(Vs, kt, gb, mt_zero4());
                     f32x4 dz;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -254,7 +225,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(XsdpaSrc src, const flo
                         sg += p;
                         dz[r] = p * (dsd - Di) * kTtQkScale;
                     }
-                    if (walk) mt_cols_acc(Ks, kt, dz, aq);
+                    if (walk) tile_cols_acc(Ks, kt, dz, aq);
                 }
             }
             if (!walk) {
@@ -275,8 +246,8 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(XsdpaSrc src, const flo
         D[2 * row + 1] = Sg;
     }
     const __amdgpu_buffer_rsrc_t ors = make_rsrc(dst.dq + b * Tq * dst.lddq, Tq * dst.lddq * 4);
-    mt_store4(ors, tq * dst.lddq + dst.coldq + h * kTtHd + 4 * q, aq[0]);
-    mt_store4(ors, tq * dst.lddq + dst.coldq + h * kTtHd + 16 + 4 * q, aq[1]);
+    buf_store4(ors, tq * dst.lddq + dst.coldq + h * kTtHd + 4 * q, aq[0]);
+    buf_store4(ors, tq * dst.lddq + dst.coldq + h * kTtHd + 16 + 4 * q, aq[1]);
 }
 
 // The key owner: dK[j] and dV[j] of the key rows j0 .. j0 + 127 of one (sequence, head), summed over the query blocks
@@ -284,7 +255,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(XsdpaSrc src, const flo
 // of the block (so that a short block, cross-attention's S keys, spreads over the waves); its K and V rows are B
 // fragments in registers for the whole kernel.  Per query tile P and dP come out with the queries 4 q + r in the
 // lane's four registers; Pd and dZ of queries >= Tq are forced to 0, since the queries are what dV and dK sum over.
-__global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(XsdpaSrc src, const float* __restrict__ dO,
+__global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(AttnSrc src, const float* __restrict__ dO,
                                                           const float* __restrict__ lse, const float* __restrict__ D,
                                                           const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
                                                           int Tq, int Tk) {
@@ -307,8 +278,8 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(XsdpaSrc src, const fl
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int i = threadIdx.x + 256 * r, t = i0 + (i >> 3), c = 4 * (i & 7);
-            nq4[r] = mt_load4(qrs, t * src.ldq + src.colq + h * kTtHd + c);
-            ng4[r] = mt_load4(grs, t * kTtD + h * kTtHd + c);
+            nq4[r] = buf_load4(qrs, t * src.ldq + src.colq + h * kTtHd + c);
+            ng4[r] = buf_load4(grs, t * kTtD + h * kTtHd + c);
         }
         const int t = i0 + (int)threadIdx.x;
         const bool have = threadIdx.x < kMtQb && t < Tq;
@@ -339,8 +310,8 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(XsdpaSrc src, const fl
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             const int off = (j0 + (wave + 4 * u) * 16 + col) * src.ldkv + h * kTtHd + 16 * g + 4 * q; // keys >= Tk read 0
-            kb[u][g] = mt_load4(krs, off + src.colk);
-            vb[u][g] = mt_load4(krs, off + src.colv);
+            kb[u][g] = buf_load4(krs, off + src.colk);
+            vb[u][g] = buf_load4(krs, off + src.colv);
             ak[u][g] = av[u][g] = mt_zero4();
         }
     put(smem_mt);
@@ -363,7 +334,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(XsdpaSrc src, const fl
                 for (int u = 0; u < 2; ++u) {
                     const int kt = wave + 4 * u, j = j0 + kt * 16 + col;
                     if (kt * 16 < left) {
-                        const f32x4 s = mt_rows_dot(Qs, qt, kb[u], mt_zero4()), dp = mt_rows_dot(Gs, qt, vb[u], mt_zero4());
+                        const f32x4 s = tile_rows_dot(Qs, qt, kb[u], mt_zero4()), dp = tile_rows_dot(Gs, qt, vb[u], mt_zero4());
                         f32x4 pd, dz;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -378,8 +349,8 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(XsdpaSrc src, const fl
                             pd[r] = i < nq ? w : 0.f;
                             dz[r] = i < nq ? p * (dsd - d4[r]) * kTtQkScale : 0.f;
                         }
-                        mt_cols_acc(Gs, qt, pd, av[u]);
-                        mt_cols_acc(Qs, qt, dz, ak[u]);
+                        tile_cols_acc(Gs, qt, pd, av[u]);
+                        tile_cols_acc(Qs, qt, dz, ak[u]);
                     }
                 }
             }
@@ -397,8 +368,8 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(XsdpaSrc src, const fl
         if (kt * 16 < left) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
-                mt_store4(ors, off + dst.coldk + 16 * mt, ak[u][mt]);
-                mt_store4(ors, off + dst.coldv + 16 * mt, av[u][mt]);
+                buf_store4(ors, off + dst.coldk + 16 * mt, ak[u][mt]);
+                buf_store4(ors, off + dst.coldv + 16 * mt, av[u][mt]);
             }
         }
     }

@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void b2h_ml_linear(const float* __restrict__ X
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = (k4[u] >> (8 * r)) & 0xff ? v[r] * scale : 0.f;
                     if (res) v += rs[u];
-                    mt_store4(yrs, row * M + m, v);
+                    buf_store4(yrs, row * M + m, v);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void b2h_ml_linear_dx(const float* __restrict_
                 for (int r = 0; r < 4; ++r) v[r] = (k4 >> (8 * r)) & 0xff ? v[r] * scale : 0.f;
             }
             if (add) v += *reinterpret_cast<const f32x4*>(add + e0 + k);
-            mt_store4(ors, row * K + k, v);
+            buf_store4(ors, row * K + k, v);
         } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

@@ -3,7 +3,7 @@ row-constant offsets of +-100 from the K bias, stack LayerNorms whose rows have 
 (tests/tpt_stress_ref.py; the CPU side, the fixture and the proofs that the cases see what they are for are in
 tests/test_tpt_stress_cpu.py).  Which kernels a case runs:
 
-  inference, T <= 128, "fp32":   b2h_attn_mfma_f32 / b2h_attn_cross_f32 (attn_core_f32), b2h_tpt_layernorm
+  inference, T <= 128, "fp32":   b2h_attn_f32 (self- and cross-attention), b2h_tpt_layernorm
   inference, T <= 128, "f16x3":  b2h_attn_qkv_h3 / b2h_attn_cross_h3, b2h_tpt_layernorm
   inference, T > 128:            the blocked attention of kernel_attn_long.h in the selected precision for the decoder
                                  (the encoder keeps the short kernels: S <= 128), through forward_fused(..., **OFF)

@@ -78,7 +78,7 @@ def test_hip_matches_reference(name, precision, cuda_device):
 def test_hip_lengths_up_to_128_with_a_longer_positional_table(precision, cuda_device):
     """The C ABI takes max_len up to 128 (b2h_tenc_create); the reference's class hard-codes 100
     (HandPoseModels.py:129) but its PositionalEncoding is a plain module a user can swap.  Lengths 101 ... 128
-    run the eight-tile attention instantiations (b2h_attn_qkv_h3<8> / b2h_attn_mfma_f32<8>), which no other test
+    run the eight-tile attention instantiations (b2h_attn_qkv_h3<8> / b2h_attn_f32<8>), which no other test
     reaches: seven full tiles + a partial one, exactly eight, and the tile edges around them."""
     m, state, _ = _gpu_model(cuda_device, precision)
     m.pos_encoder = hps.PositionalEncoding(24, 0.5, max_len=128).to(cuda_device)
