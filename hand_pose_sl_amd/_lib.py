@@ -29,8 +29,8 @@ PRE_CHEST_DIFF, PRE_NORMALIZE, POST_DENORMALIZE, POST_MASK_TAIL = 1, 2, 4, 8
 PREDICT = {"right_hand": 0, "right_index": 1, "right_3fingers": 2}
 PREDICT_NINP = {58: "right_index", 42: "right_3fingers"}
 
-# enum b2h_train_kernel (b2h_tpt_set_train_kernel, b2h_tpt_set_train_linear), by the names of
-# TextPoseTransformer.set_train_kernels / set_train_linear
+# enum b2h_train_kernel (b2h_tpt_set_train_kernel, b2h_tpt_set_train_linear and their b2h_tenc_* twins), by the names
+# of set_train_kernels / set_train_linear of TextPoseTransformer and TransformerEnc
 TRAIN_KERNELS = {"valu": 0, "mfma": 1}
 
 # enum b2h_status
@@ -92,6 +92,10 @@ SYMBOLS = {
     "b2h_tpt_train_attn_name": (ctypes.c_char_p, [_vp, ctypes.c_int64]),
     "b2h_tpt_set_train_linear": (ctypes.c_int, [_vp, ctypes.c_int]),
     "b2h_tpt_train_linear_name": (ctypes.c_char_p, [_vp]),
+    "b2h_tenc_set_train_kernel": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "b2h_tenc_train_attn_name": (ctypes.c_char_p, [_vp, ctypes.c_int64]),
+    "b2h_tenc_set_train_linear": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "b2h_tenc_train_linear_name": (ctypes.c_char_p, [_vp]),
     "b2h_tpt_train_bytes": (ctypes.c_size_t, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "b2h_tpt_train_forward": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp), ctypes.c_float, _vp,
                                              _vp, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp]),

@@ -108,6 +108,22 @@ class NativeDropout:
         return [masks[k] for k, _ in order]
 
 
+class TrainRoutes:
+    """Mixin of the two transformers: the two opt-in switches of a training step, `train_kernels` (the attentions) and
+    `train_linear` (the Linear layers), each one of `_lib.TRAIN_KERNELS`, "valu" by default.  The models' setters
+    validate through `_choose_train_route`; `_train_route()` hands the values to TrainFn."""
+
+    train_kernels = "valu"
+    train_linear = "valu"
+
+    def _choose_train_route(self, attr, what, name):
+        """self.<attr> = name if it is one of `_lib.TRAIN_KERNELS`, else ValueError and nothing changes; returns self."""
+        if name not in _lib.TRAIN_KERNELS:
+            raise ValueError(f"{what} must be one of {sorted(_lib.TRAIN_KERNELS)}, got {name!r}")
+        setattr(self, attr, name)
+        return self
+
+
 class TrainFn(torch.autograd.Function):
     """y = model(lead, x) of a transformer in training mode with its gradient, through the model's b2h_*_train_forward
     / b2h_*_backward (exact fp32): `apply(model, p, masks, lead, x, *params)`.  `lead` is the model's leading tensor

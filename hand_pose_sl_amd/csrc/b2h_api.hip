@@ -30,6 +30,7 @@
 #include "kernel_train_attn_long.h"
 #include "kernel_train_attn_mfma.h"
 #include "kernel_train_linear_mfma.h"
+#include "kernel_train_attn_whole_mfma.h"
 #include "kernel_tpt_train.h"
 #include "kernel_train.h"
 #include "kernel_valu.h"
@@ -641,6 +642,8 @@ struct b2h_tenc {
     int nlayers = 0, max_len = 0, device = 0;
     bool has_weights = false;
     int kernel = B2H_TENC_F32;
+    int train_kernel = B2H_TRAIN_VALU; // b2h_tenc_set_train_kernel
+    int train_linear = B2H_TRAIN_VALU; // b2h_tenc_set_train_linear
     float w_absmax = 0.f; // largest |parameter| (NaN counts as inf): B2H_TENC_F16X3 needs < 65504
     // floats of the 5 + 12*nlayers tensors in the order of b2h_tenc_load_weights: pe, pose2hidden_projection, the
     // layers, hidden2pose_projection
@@ -795,6 +798,7 @@ int set_tenc_kernel_attributes() {
                 (rc = raise_lds_cap(kAttnLongH3[nt - 1], attn_long_h3_lds_bytes(nt))))
                 return rc;
         if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd))) return rc;
+        if ((rc = raise_lds_cap(b2h_mw_sdpa)) || (rc = raise_lds_cap(b2h_mw_sdpa_bwd))) return rc;
         if ((rc = raise_lds_cap(b2h_lt_sdpa, (int)kLtFwdLds)) || (rc = raise_lds_cap(b2h_lt_sdpa_bwd_kv, (int)kLtBwdKvLds)) ||
             (rc = raise_lds_cap(b2h_lt_sdpa_bwd_q, (int)kLtBwdQLds)))
             return rc;
@@ -1505,7 +1509,7 @@ std::vector<Span> tt_read_only(const float* const* params, const std::vector<siz
 unsigned tt_row_blocks(int64_t N, int rows) { return (unsigned)((N + rows - 1) / rows); }
 
 // Where a training call runs and which Linear trio it launches: kernel_tenc_train.h's on the vector ALU, or
-// kernel_train_linear_mfma.h's on the matrix cores (TextPoseTransformer after b2h_tpt_set_train_linear only).
+// kernel_train_linear_mfma.h's on the matrix cores (after b2h_tpt_set_train_linear / b2h_tenc_set_train_linear only).
 struct TtLin {
     hipStream_t st;
     bool mfma;
@@ -1558,10 +1562,10 @@ void tt_layernorm_bwd(hipStream_t st, const float* dY, const float* X, const flo
 
 float tt_scale(float p) { return p < 1.f ? 1.f / (1.f - p) : 0.f; }
 
-// Which kernels run an attention in training: the whole-matrix pair (kernel_train_attn.h) up to 128 x 128, beyond
-// that the blocked ones, on the vector ALU (kernel_train_attn_long.h) or on the matrix cores
-// (kernel_train_attn_mfma.h).
-enum class TrainAttn { kWhole, kBlockedValu, kBlockedMfma };
+// Which kernels run an attention in training: a whole-matrix pair up to 128 x 128, on the vector ALU
+// (kernel_train_attn.h) or on the matrix cores (kernel_train_attn_whole_mfma.h); beyond that the blocked ones, on the
+// vector ALU (kernel_train_attn_long.h) or on the matrix cores (kernel_train_attn_mfma.h).
+enum class TrainAttn { kWhole, kBlockedValu, kBlockedMfma, kWholeMfma };
 
 // The gradients of self-attention over [Q | K | V] rows (N, 384): [dQ | dK | dV] in the same layout (self_src's counterpart).
 LtGradDst self_dst(float* gQ) { return LtGradDst{gQ, 3 * kTtD, 0, gQ, 3 * kTtD, kTtD, 2 * kTtD}; }
@@ -1574,6 +1578,8 @@ void train_sdpa(hipStream_t st, TrainAttn route, const AttnSrc& src, const uint8
     const dim3 grid(heads, lt_blocks(Tq, kLtQb));
     if (route == TrainAttn::kWhole)
         hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes(Tq, Tk, false), st, src, mask, sc, O, Tq, Tk);
+    else if (route == TrainAttn::kWholeMfma)
+        hipLaunchKernelGGL(b2h_mw_sdpa, dim3(heads), dim3(256), mw_sdpa_lds_bytes(Tq, Tk, false), st, src, mask, sc, O, Tq, Tk);
     else if (route == TrainAttn::kBlockedMfma)
         hipLaunchKernelGGL(b2h_mt_sdpa, grid, dim3(256), kMtFwdLds, st, src, mask, sc, O, lse, Tq, Tk);
     else
@@ -1588,6 +1594,9 @@ void train_sdpa_bwd(hipStream_t st, TrainAttn route, const AttnSrc& src, const f
     if (route == TrainAttn::kWhole) {
         hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3(heads), dim3(256), tt_sdpa_lds_bytes(Tq, Tk, true), st, src, dO, mask, sc, dst,
                            Tq, Tk);
+    } else if (route == TrainAttn::kWholeMfma) {
+        hipLaunchKernelGGL(b2h_mw_sdpa_bwd, dim3(heads), dim3(256), mw_sdpa_lds_bytes(Tq, Tk, true), st, src, dO, mask, sc, dst,
+                           Tq, Tk);
     } else if (route == TrainAttn::kBlockedMfma) {
         hipLaunchKernelGGL(b2h_mt_sdpa_bwd_q, gq, dim3(256), kMtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
         hipLaunchKernelGGL(b2h_mt_sdpa_bwd_kv, gkv, dim3(256), kMtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
@@ -1598,14 +1607,15 @@ void train_sdpa_bwd(hipStream_t st, TrainAttn route, const AttnSrc& src, const f
 }
 
 // One torch.nn.TransformerEncoderLayer (post-norm, ReLU) over N = B * T rows in training mode: H -> L.H2.
-// w: its twelve tensors in state_dict order; mk: its four keep-masks attn, drop1, ff, drop2, or nullptr.
-void tt_enc_layer_forward(const TtLin& ln, const float* const* w, const TtLayer& L, const float* H, int64_t B, int T,
-                          const uint8_t* const* mk, float sc) {
+// w: its twelve tensors in state_dict order; mk: its four keep-masks attn, drop1, ff, drop2, or nullptr; attn: one of
+// the two whole-matrix routes (T <= 128).
+void tt_enc_layer_forward(const TtLin& ln, TrainAttn attn, const float* const* w, const TtLayer& L, const float* H,
+                          int64_t B, int T, const uint8_t* const* mk, float sc) {
     hipStream_t st = ln.st;
     const int64_t N = B * T;
     const auto mask = [&](int i) { return mk ? mk[i] : nullptr; };
     tt_linear(ln, H, w[0], w[1], L.QKV, N, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
-    train_sdpa(st, TrainAttn::kWhole, self_src(L.QKV), mask(0), sc, L.O, nullptr, B, T, T);
+    train_sdpa(st, attn, self_src(L.QKV), mask(0), sc, L.O, nullptr, B, T, T);
     tt_linear(ln, L.O, w[2], w[3], L.R1, N, kTtD, kTtD, 0, mask(1), sc, H);
     hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R1, w[8], w[9], L.H1, L.ST, 4, N);
     tt_linear(ln, L.H1, w[4], w[5], L.F1, N, kTtD, kTtD, 1, mask(2), sc, nullptr);
@@ -1623,8 +1633,8 @@ TtGrad tt_grad(float* scratch, int64_t N) {
 }
 
 // Backward of tt_enc_layer_forward: G.gA = dH2 on entry, = dH_in on return; g: the layer's twelve gradients.
-void tt_enc_layer_backward(const TtLin& ln, const float* const* w, float* const* g, const TtLayer& L, const float* Hin,
-                           const TtGrad& G, int64_t B, int T, const uint8_t* const* mk, float sc) {
+void tt_enc_layer_backward(const TtLin& ln, TrainAttn attn, const float* const* w, float* const* g, const TtLayer& L,
+                           const float* Hin, const TtGrad& G, int64_t B, int T, const uint8_t* const* mk, float sc) {
     hipStream_t st = ln.st;
     const int64_t N = B * T;
     const auto mask = [&](int i) { return mk ? mk[i] : nullptr; };
@@ -1640,14 +1650,46 @@ void tt_enc_layer_backward(const TtLin& ln, const float* const* w, float* const*
     const float* dA = mk ? G.gBm : G.gB;
     tt_linear_dw(ln, dA, L.O, G.slabs, N, kTtD, kTtD, g[2], g[3]);
     tt_linear_dx(ln, dA, w[2], G.gC, N, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);             // gC = dO
-    train_sdpa_bwd(st, TrainAttn::kWhole, self_src(L.QKV), G.gC, nullptr, nullptr, mask(0), sc, self_dst(G.gQ), B, T, T);
+    train_sdpa_bwd(st, attn, self_src(L.QKV), G.gC, nullptr, nullptr, mask(0), sc, self_dst(G.gQ), B, T, T);
     tt_linear_dw(ln, G.gQ, Hin, G.slabs, N, kTtD, 3 * kTtD, g[0], g[1]);
     tt_linear_dx(ln, G.gQ, w[0], G.gA, N, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);          // gA = dH_in
 }
 
+// Which attention pair and which Linear trio TransformerEnc's training calls launch, as b2h_tenc_set_train_kernel and
+// b2h_tenc_set_train_linear chose, at every (B, T): the one place each that decides; the dispatch and the name
+// functions both ask it.
+TrainAttn tenc_train_attn(const b2h_tenc* m) {
+    return m->train_kernel == B2H_TRAIN_MFMA ? TrainAttn::kWholeMfma : TrainAttn::kWhole;
+}
+bool tenc_train_linear_mfma(const b2h_tenc* m) { return m->train_linear == B2H_TRAIN_MFMA; }
+
 } // namespace
 
 extern "C" {
+
+int b2h_tenc_set_train_kernel(b2h_tenc* m, int kernel) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (kernel != B2H_TRAIN_VALU && kernel != B2H_TRAIN_MFMA) return fail(B2H_ERR_INVALID, "unknown training kernel");
+    m->train_kernel = kernel;
+    return B2H_OK;
+}
+
+int b2h_tenc_set_train_linear(b2h_tenc* m, int kernel) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (kernel != B2H_TRAIN_VALU && kernel != B2H_TRAIN_MFMA) return fail(B2H_ERR_INVALID, "unknown training kernel");
+    m->train_linear = kernel;
+    return B2H_OK;
+}
+
+const char* b2h_tenc_train_attn_name(const b2h_tenc* m, int64_t T) {
+    if (!m || tt_shape_refusal(m, 1, T)) return nullptr;
+    return tenc_train_attn(m) == TrainAttn::kWholeMfma ? "b2h_mw_sdpa" : "b2h_tt_sdpa";
+}
+
+const char* b2h_tenc_train_linear_name(const b2h_tenc* m) {
+    if (!m) return nullptr;
+    return tenc_train_linear_mfma(m) ? "b2h_ml_linear" : "b2h_tt_linear";
+}
 
 size_t b2h_tenc_train_bytes(const b2h_tenc* m, int64_t B, int64_t T, int which) {
     if (!m || B < 1 || T < 1 || (which != 0 && which != 1)) return 0;
@@ -1671,7 +1713,8 @@ int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float*
                                tt_read_only(params, m->sizes, masks, tenc_mask_bytes(m, B, T), {{x, (size_t)N * kInCh * 4}})))
         return rc;
     hipStream_t st = (hipStream_t)stream;
-    const TtLin ln{st, false}; // TransformerEnc keeps the Linear kernels of kernel_tenc_train.h
+    const TtLin ln{st, tenc_train_linear_mfma(m)};
+    const TrainAttn attn = tenc_train_attn(m);
     const float sc = tt_scale(p);
     auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
     float* S = static_cast<float*>(saved);
@@ -1683,7 +1726,7 @@ int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float*
     tt_linear(ln, X0, params[1], params[2], H, N, kInCh, kTtD, 0, nullptr, 1.f, nullptr);
     for (int l = 0; l < m->nlayers; ++l) {
         const TtLayer L = tt_layer(Ls, N, l);
-        tt_enc_layer_forward(ln, params + 3 + 12 * l, L, H, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
+        tt_enc_layer_forward(ln, attn, params + 3 + 12 * l, L, H, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
         H = L.H2;
     }
     const float* const* wh = params + 3 + 12 * m->nlayers;
@@ -1722,7 +1765,8 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
         return rc;
 
     hipStream_t st = (hipStream_t)stream;
-    const TtLin ln{st, false}; // TransformerEnc keeps the Linear kernels of kernel_tenc_train.h
+    const TtLin ln{st, tenc_train_linear_mfma(m)};
+    const TrainAttn attn = tenc_train_attn(m);
     const float sc = tt_scale(p);
     auto mk = [&](int i) { return masks ? masks[i] : nullptr; };
     float* S = const_cast<float*>(static_cast<const float*>(saved)); // read only
@@ -1736,7 +1780,7 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
     tt_linear_dw(ln, dy, Hlast, G.slabs, N, kTtD, kOutCh, grads[oh - 1], grads[oh]);
     tt_linear_dx(ln, dy, params[oh], G.gA, N, kTtD, kOutCh, nullptr, nullptr, 1.f, nullptr);
     for (int l = m->nlayers - 1; l >= 0; --l)
-        tt_enc_layer_backward(ln, params + 3 + 12 * l, grads + 2 + 12 * l, tt_layer(Ls, N, l),
+        tt_enc_layer_backward(ln, attn, params + 3 + 12 * l, grads + 2 + 12 * l, tt_layer(Ls, N, l),
                               l ? tt_layer(Ls, N, l - 1).H2 : H0, G, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
     // pose2hidden_projection (:171) and the positional encoding's dropout (:101-103)
     tt_linear_dw(ln, G.gA, X0, G.slabs, N, kInCh, kTtD, grads[0], grads[1]);
@@ -1921,7 +1965,8 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     const float* H = sv.E0;
     for (int l = 0; l < m->n_enc; ++l) {
         const TtLayer L = sv.enc_layer(l);
-        tt_enc_layer_forward(ln, params + 12 * l, L, H, B, (int)S, masks ? masks + 4 * l : nullptr, sc);
+        tt_enc_layer_forward(ln, TrainAttn::kWhole, params + 12 * l, L, H, B, (int)S, masks ? masks + 4 * l : nullptr,
+                             sc);
         H = L.H2;
     }
     const float* const* wn = params + 12 * m->n_enc;
@@ -2057,8 +2102,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     tt_layernorm_bwd(st, dMEM, sv.enc_out(m->n_enc), sv.STm, params[od - 2], G.gA, G.gBm, nullptr, 1.f, G.slabs, Ns,
                      grads[od - 2], grads[od - 1]);
     for (int l = m->n_enc - 1; l >= 0; --l)
-        tt_enc_layer_backward(ln, params + 12 * l, grads + 12 * l, sv.enc_layer(l), l ? sv.enc_layer(l - 1).H2 : sv.E0, G, B,
-                              (int)S, masks ? masks + 4 * l : nullptr, sc);
+        tt_enc_layer_backward(ln, TrainAttn::kWhole, params + 12 * l, grads + 12 * l, sv.enc_layer(l),
+                              l ? sv.enc_layer(l - 1).H2 : sv.E0, G, B, (int)S, masks ? masks + 4 * l : nullptr, sc);
     hipLaunchKernelGGL(b2h_tptt_embed_bwd, dim3((unsigned)m->n_tokens), dim3(128), 0, st, tokens, G.gA, grads[ot], Ns);
     HIP_TRY(hipGetLastError());
     return B2H_OK;

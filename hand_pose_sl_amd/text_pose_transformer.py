@@ -36,11 +36,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import NativeDropout, NativeModule, TrainFn, _ptrs
+from ._native import NativeDropout, NativeModule, TrainFn, TrainRoutes, _ptrs
 from .transformer_enc import TENC_KERNELS, PositionalEncoding
 
 
-class TextPoseTransformer(NativeDropout, NativeModule, nn.Module):
+class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
     """`precision` (not in the reference; keyword only): the constructor accepts only "fp32" = fp32 operands on the
     matrix cores, the default.  `set_precision("f16x3")` switches the inference forward to the f16 hi + lo split
     (fp32-grade results, the same 2e-5 parity bar; needs |weights| and |activations| < 65504, else the forward
@@ -91,10 +91,7 @@ class TextPoseTransformer(NativeDropout, NativeModule, nn.Module):
         (kernel_train_attn_mfma.h): exact fp32 like the default and as deterministic, in another summation order.  Up
         to 128 frames and in the encoder it changes nothing.  A backward runs the route its forward ran, whatever the
         model says by then.  Measurements: DESIGN.md section 17."""
-        if name not in _lib.TRAIN_KERNELS:
-            raise ValueError(f"train kernels must be one of {sorted(_lib.TRAIN_KERNELS)}, got {name!r}")
-        self.train_kernels = name
-        return self
+        return self._choose_train_route("train_kernels", "train kernels", name)
 
     def set_train_linear(self, name):
         """Select the Linear kernels of later training forwards, "valu" (the default) or "mfma"; returns self.  "mfma"
@@ -103,10 +100,7 @@ class TextPoseTransformer(NativeDropout, NativeModule, nn.Module):
         default's summation order per element, as deterministic.  Independent of `set_train_kernels`; LayerNorm, the
         embedding, the attentions and inference are untouched.  A backward runs the Linears its forward ran, whatever
         the model says by then.  Measurements: DESIGN.md section 19."""
-        if name not in _lib.TRAIN_KERNELS:
-            raise ValueError(f"train linear must be one of {sorted(_lib.TRAIN_KERNELS)}, got {name!r}")
-        self.train_linear = name
-        return self
+        return self._choose_train_route("train_linear", "train linear", name)
 
     _NAME, _CREATE, _LOAD, _DESTROY = "TextPoseTransformer", "b2h_tpt_create", "b2h_tpt_load_weights", "b2h_tpt_destroy"
 

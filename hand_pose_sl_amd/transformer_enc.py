@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import NativeDropout, NativeModule, TrainFn, _ptrs
+from ._native import NativeDropout, NativeModule, TrainFn, TrainRoutes, _ptrs
 
 
 class PositionalEncoding(nn.Module):
@@ -48,21 +48,26 @@ class PositionalEncoding(nn.Module):
 TENC_KERNELS = {"fp32": 0, "f16x3": 1}   # b2h_tenc_kernel (include/b2h.h)
 
 
-class TransformerEnc(NativeDropout, NativeModule, nn.Module):
+class TransformerEnc(NativeDropout, TrainRoutes, NativeModule, nn.Module):
     """`precision` (not in the reference; keyword only): "fp32" = fp32 operands on the matrix cores
     (default); "f16x3" = every Linear operand split into f16 hi + lo, three f16 MFMAs per product
     with fp32 accumulation: fp32-grade error at 3/16 of the matrix cycles, for activations and
     weights inside the f16 range (|x| < 65504).
 
-    Training (model.train(), autograd on, a parameter or the input requires grad): always exact fp32 on the
-    vector ALU, whatever `precision` says, with dropout probability `pos_encoder.dropout.p` everywhere as in the
-    reference; gradients as accurate as the reference's own fp32 CPU training (tests/test_tenc_train_gpu.py)."""
+    Training (model.train(), autograd on, a parameter or the input requires grad): always exact fp32, whatever
+    `precision` says, with dropout probability `pos_encoder.dropout.p` everywhere as in the reference; gradients as
+    accurate as the reference's own fp32 CPU training (tests/test_tenc_train_gpu.py).  By default every kernel of a
+    step runs on the vector ALU; `set_train_kernels("mfma")` (attribute `train_kernels`, default "valu") moves the
+    self-attention of every layer, forward and backward, to fp32 MFMA kernels, and `set_train_linear("mfma")`
+    (attribute `train_linear`, default "valu") every Linear layer."""
 
     def __init__(self, ninp, nhead, nhid, nout, nlayers, dropout=0.5, *, precision="fp32"):
         super().__init__()
         if precision not in TENC_KERNELS:
             raise ValueError(f"precision must be one of {sorted(TENC_KERNELS)}, got {precision!r}")
         self.precision = precision
+        self.train_kernels = "valu"
+        self.train_linear = "valu"
         self.model_type = "Transformer"
         self.src_mask = None
         self.pos_encoder = PositionalEncoding(ninp, dropout, max_len=100)
@@ -74,6 +79,21 @@ class TransformerEnc(NativeDropout, NativeModule, nn.Module):
         self.hidden2pose_projection = nn.Linear(nhid, nout)
         self.pose2hidden_projection = nn.Linear(ninp, nhid)
         self._geom = (int(ninp), int(nhead), int(nhid), int(nout), int(nlayers))
+
+    def set_train_kernels(self, name):
+        """Select the attention kernels of later training forwards, "valu" (the default) or "mfma"; returns self.
+        "mfma" runs every layer's self-attention, forward and backward, on v_mfma_f32_16x16x4_f32
+        (kernel_train_attn_whole_mfma.h): exact fp32 and as deterministic as the default; the forward is bitwise equal
+        to the default's, the backward sums one row term in another order.  A backward runs the route its forward ran,
+        whatever the model says by then.  Measurements: DESIGN.md section 25."""
+        return self._choose_train_route("train_kernels", "train kernels", name)
+
+    def set_train_linear(self, name):
+        """Select the Linear kernels of later training forwards, "valu" (the default) or "mfma"; returns self.  "mfma"
+        runs every Linear layer of the step, forward and backward, on v_mfma_f32_16x16x4_f32
+        (kernel_train_linear_mfma.h): bitwise equal to the default.  Independent of `set_train_kernels`; LayerNorm,
+        the positional encoding and inference are untouched.  A backward runs the Linears its forward ran."""
+        return self._choose_train_route("train_linear", "train linear", name)
 
     _NAME, _CREATE, _LOAD, _DESTROY = "TransformerEnc", "b2h_tenc_create", "b2h_tenc_load_weights", "b2h_tenc_destroy"
 
@@ -141,7 +161,8 @@ class TransformerEnc(NativeDropout, NativeModule, nn.Module):
         return TrainFn.apply(self, p, self._checked_masks(masks, p, x.device, x.shape[0], x.shape[1]), tensors[0], x,
                              *tensors[1:])
 
-    # what TrainFn asks of the model: pe travels as params[0] of the entry points and has no gradient
+    # what TrainFn asks of the model: pe travels as params[0] of the entry points and has no gradient; the two routes
+    # travel to the backward
     _TRAIN_FNS = ("b2h_tenc_train_bytes", "b2h_tenc_train_forward", "b2h_tenc_backward")
     _TRAIN_LEAD_IS_PARAM = True
 
@@ -153,7 +174,8 @@ class TransformerEnc(NativeDropout, NativeModule, nn.Module):
         return (_ptrs((pe, *params)),)
 
     def _train_route(self):
-        return ()
+        return (("b2h_tenc_set_train_kernel", _lib.TRAIN_KERNELS[self.train_kernels]),
+                ("b2h_tenc_set_train_linear", _lib.TRAIN_KERNELS[self.train_linear]))
 
     def _run(self, src, flags, factor, n_frames):
         lib = self._ensure_handle()

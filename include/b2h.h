@@ -264,7 +264,9 @@ int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, 
  * model built with dropout = --transformer-dropout.  These entry points are its forward in .train() mode and
  * its backward (HandPoseModels.py:154-178 under autograd: PositionalEncoding :101-103 with its dropout,
  * pose2hidden_projection, torch's post-norm nn.TransformerEncoderLayer with ReLU, hidden2pose_projection).
- * All arithmetic is exact fp32 on the vector ALU, whatever b2h_tenc_set_kernel selected.  The parameters are
+ * All arithmetic is exact fp32, whatever b2h_tenc_set_kernel selected: on the vector ALU by default, the attentions
+ * and the Linear layers on the matrix cores after b2h_tenc_set_train_kernel / b2h_tenc_set_train_linear (declared with
+ * the TextPoseTransformer switches below).  The parameters are
  * read straight from the caller's tensors (b2h_tenc_load_weights is neither needed nor called), so an
  * optimizer may update them in place between launches.
  * b2h_adam_step below is that optimizer: torch.optim.Adam's update of every tensor in one launch.
@@ -499,13 +501,34 @@ const char* b2h_tpt_train_attn_name(const b2h_tpt* m, int64_t T);
  *                   contract and per-element summation order on v_mfma_f32_16x16x4_f32 (exact fp32); as
  *                   deterministic as the default
  * It leaves alone LayerNorm, the embedding, the attentions (b2h_tpt_set_train_kernel), b2h_tpt_train_bytes and every
- * layout, inference, and TransformerEnc, which keeps the vector-ALU trio.  Either backward accepts either forward's
+ * layout, inference, and TransformerEnc, which has switches of its own (below).  Either backward accepts either forward's
  * saved buffer.  Both trios' LDS caps are raised at b2h_tpt_create, so switching between captures is safe.
  * B2H_ERR_INVALID: NULL model, other value (nothing changes). */
 int b2h_tpt_set_train_linear(b2h_tpt* m, int kernel);
 /* Unmangled name of the Linear forward kernel that b2h_tpt_train_forward would launch under the current setting:
  * "b2h_tt_linear" or "b2h_ml_linear"; static storage.  NULL for a NULL model. */
 const char* b2h_tpt_train_linear_name(const b2h_tpt* m);
+/* The same two switches for TransformerEnc's training calls (b2h_tenc_train_forward / b2h_tenc_backward), over the same
+ * enum, independent of each other; B2H_TRAIN_VALU is the default of every new model.
+ *   b2h_tenc_set_train_kernel  the self-attention of every layer (T <= 128 always): b2h_tt_sdpa / _bwd of
+ *     kernel_train_attn.h, or with B2H_TRAIN_MFMA b2h_mw_sdpa / _bwd of kernel_train_attn_whole_mfma.h: the same
+ *     arguments, one workgroup per (sequence, head), no buffer besides the operands, all six products on
+ *     v_mfma_f32_16x16x4_f32 in the default's summation order.  y is bitwise equal to the default's; the backward
+ *     sums rowsum(dSd o S) in its own fixed order, so the gradients are exact fp32 but not bitwise equal.
+ *   b2h_tenc_set_train_linear  every Linear, forward and backward: b2h_tt_linear / _dx / _dw, or b2h_ml_linear /
+ *     _dx / _dw (bitwise equal to the default's).
+ * b2h_tenc_train_bytes and every layout do not depend on either, so either backward accepts either forward's saved
+ * buffer.  All LDS caps are raised at b2h_tenc_create, so switching between captures is safe.
+ * B2H_ERR_INVALID: NULL model, other value (nothing changes). */
+int b2h_tenc_set_train_kernel(b2h_tenc* m, int kernel);
+int b2h_tenc_set_train_linear(b2h_tenc* m, int kernel);
+/* Unmangled name of the attention forward kernel that b2h_tenc_train_forward would launch at T frames under the current
+ * setting: "b2h_tt_sdpa" or "b2h_mw_sdpa"; static storage.  NULL for a NULL model or a T the training calls refuse
+ * (T < 1, T > the model's max_len). */
+const char* b2h_tenc_train_attn_name(const b2h_tenc* m, int64_t T);
+/* Unmangled name of the Linear forward kernel that b2h_tenc_train_forward would launch: "b2h_tt_linear" or
+ * "b2h_ml_linear"; static storage.  NULL for a NULL model. */
+const char* b2h_tenc_train_linear_name(const b2h_tenc* m);
 
 /* Dropout keep-masks ---------------------------------------------------------
  * The masks of b2h_tenc_train_forward / b2h_tpt_train_forward (uint8, 1 = keep with probability 1 - p) from one

@@ -8,8 +8,11 @@ training kernels are plain per-operation fp32 kernels and carry no speed bar.
     modules) on the same GPU;
   * the same step of the tests' torch port (tests/tenc_train_ref.py) on the host CPU.
     python tools/bench_train_tenc.py [B=128] [T=100] [dropout_source=torch|native] [optimizer=torch|native]
+                                     [train_kernels=valu|mfma] [train_linear=valu|mfma]
 The third argument selects model.set_dropout_source, the fourth the optimizer of the library's
-step, torch.optim.Adam or hps.Adam (section 21); each is recorded only when given."""
+step, torch.optim.Adam or hps.Adam (section 21), the fifth and sixth model.set_train_kernels and
+model.set_train_linear (section 25); each is recorded only when given.  With the fifth or sixth given, the record also
+holds `reference_step_ms_repetitions`: five further repetitions of 20 steps each, for a median and a range."""
 import json
 import os
 import sys
@@ -29,6 +32,8 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 DROPOUT_SOURCE = sys.argv[3] if len(sys.argv) > 3 else None    # absent: the model's default, and no key in the record
 OPTIMIZER = sys.argv[4] if len(sys.argv) > 4 else None    # absent: torch.optim.Adam, and no key in the record
+TRAIN_KERNELS = sys.argv[5] if len(sys.argv) > 5 else None    # absent: the model's default, and no key in the record
+TRAIN_LINEAR = sys.argv[6] if len(sys.argv) > 6 else None
 if OPTIMIZER not in (None, "torch", "native"):
     sys.exit(f"optimizer must be torch or native, got {OPTIMIZER!r}")
 L, P, LR = 4, 0.1, 2e-4
@@ -74,6 +79,10 @@ torch.manual_seed(0)
 m = hps.TransformerEnc(24, 4, 128, 42, L, dropout=P).to(dev).train()
 if DROPOUT_SOURCE is not None:
     m.set_dropout_source(DROPOUT_SOURCE, seed=0)
+if TRAIN_KERNELS is not None:
+    m.set_train_kernels(TRAIN_KERNELS)
+if TRAIN_LINEAR is not None:
+    m.set_train_linear(TRAIN_LINEAR)
 g = torch.Generator(device=dev).manual_seed(1)
 lengths = [T - (i * 37) % (T // 2 + 1) for i in range(B)]
 xs = torch.rand((B, T, 12, 2), device=dev, generator=g) - 0.5
@@ -100,7 +109,14 @@ if DROPOUT_SOURCE is not None:
     out["dropout_source"] = DROPOUT_SOURCE
 if OPTIMIZER is not None:
     out["optimizer"] = OPTIMIZER
-out["reference_step_ms"] = events_ms(make_step(m, list(m.parameters()), OPTIMIZER), 20)
+if TRAIN_KERNELS is not None:
+    out["train_kernels"] = TRAIN_KERNELS
+if TRAIN_LINEAR is not None:
+    out["train_linear"] = TRAIN_LINEAR
+reference_step = make_step(m, list(m.parameters()), OPTIMIZER)
+out["reference_step_ms"] = events_ms(reference_step, 20)
+if TRAIN_KERNELS is not None or TRAIN_LINEAR is not None:
+    out["reference_step_ms_repetitions"] = [events_ms(reference_step, 20, warm=0) for _ in range(5)]
 tm = TorchEnc().to(dev).train()
 pe = m.pos_encoder.pe
 out["torch_rocm_nn_transformer_step_ms_context_only"] = events_ms(make_step(lambda x: tm(x, pe), list(tm.parameters())), 20)
