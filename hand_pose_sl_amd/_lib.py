@@ -29,6 +29,9 @@ PRE_CHEST_DIFF, PRE_NORMALIZE, POST_DENORMALIZE, POST_MASK_TAIL = 1, 2, 4, 8
 PREDICT = {"right_hand": 0, "right_index": 1, "right_3fingers": 2}
 PREDICT_NINP = {58: "right_index", 42: "right_3fingers"}
 
+# enum b2h_batch_flags (b2h_build_batch)
+BATCH_DIF_ENCODING, BATCH_NORMALIZE, BATCH_PAD_FRAME0 = 1, 2, 4
+
 # enum b2h_train_kernel (b2h_tpt_set_train_kernel, b2h_tpt_set_train_linear and their b2h_tenc_* twins), by the names
 # of set_train_kernels / set_train_linear of TextPoseTransformer and TransformerEnc
 TRAIN_KERNELS = {"valu": 0, "mfma": 1}
@@ -108,6 +111,9 @@ SYMBOLS = {
     "b2h_tenc_mask_numel": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int64, _i64p, ctypes.c_int]),
     "b2h_adam_step": (ctypes.c_int, [ctypes.POINTER(_vp)] * 4 + [_i64p, ctypes.c_int, ctypes.c_float, _vp, ctypes.c_float,
                                      ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int64, _vp, _vp]),
+    "b2h_build_batch": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp,
+                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp,
+                                       _vp, _vp, _vp, _vp]),
     "b2h_model_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                       ctypes.POINTER(ctypes.c_int)]),
     "b2h_kernel_supported": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -26,6 +26,7 @@
 #include "kernel_tpt.h"
 #include "kernel_attn_long.h"
 #include "kernel_adam.h"
+#include "kernel_build_batch.h"
 #include "kernel_dropout_masks.h"
 #include "kernel_train_attn_long.h"
 #include "kernel_train_attn_mfma.h"
@@ -2243,6 +2244,72 @@ int b2h_adam_step(float* const* params, const float* const* grads, float* const*
         hipLaunchKernelGGL(b2h_adam_step_k, dim3(blocks), dim3(kAdThreads), 0, (hipStream_t)stream, a);
         HIP_TRY(hipGetLastError());
     }
+    return B2H_OK;
+}
+
+} // extern "C"
+
+// ---- the training set on the device (kernel_build_batch.h) -----------------------------------------------------
+extern "C" {
+
+int b2h_build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                    const int64_t* tokens, int64_t S, const int64_t* utt, const int64_t* start, int64_t B, int64_t T,
+                    int predict, int flags, float factor, float* input_kp, float* target_kp, float* target_conf,
+                    int64_t* text_tokens, int64_t* n_frames, void* stream) {
+    if (B < 0 || T < 0 || n_utt < 0 || n_rows < 0) return fail(B2H_ERR_SHAPE, "negative shape");
+    if (n_body != 8 && n_body != 12) return fail(B2H_ERR_INVALID, "n_body must be 8 or 12");
+    if (predict != B2H_PREDICT_RIGHT_HAND && predict != B2H_PREDICT_RIGHT_INDEX && predict != B2H_PREDICT_RIGHT_3FINGERS)
+        return fail(B2H_ERR_INVALID, "predict must be a b2h_predict value");
+    if (predict != B2H_PREDICT_RIGHT_HAND && n_body != 12)
+        return fail(B2H_ERR_INVALID, "right_index and right_3fingers items need n_body = 12 (no model takes 25 or 17 joints)");
+    if (flags & ~(kBbDif | kBbNorm | kBbPadFrame0)) return fail(B2H_ERR_INVALID, "unknown flag bits (only B2H_BATCH_* apply)");
+    if ((flags & kBbNorm) && !(factor > 0.f)) return fail(B2H_ERR_INVALID, "factor must be > 0");
+    if (!tokens != !text_tokens) return fail(B2H_ERR_INVALID, "tokens and text_tokens go together: both or neither");
+    if (tokens && (S < 1 || S > 128)) return fail(B2H_ERR_INVALID, "1 <= S <= 128");
+    if (B * T == 0) return B2H_OK;
+    if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
+    if (n_rows > ((int64_t)1 << 40) || n_utt > ((int64_t)1 << 40)) return fail(B2H_ERR_SHAPE, "store too large");
+    if (!tokens) S = 0;
+    const int J = n_body + 42;
+    const int ni = predict == B2H_PREDICT_RIGHT_HAND ? n_body : predict == B2H_PREDICT_RIGHT_INDEX ? 29 : 21;
+    const int nt = predict == B2H_PREDICT_RIGHT_HAND ? 21 : predict == B2H_PREDICT_RIGHT_INDEX ? 4 : 12;
+    const size_t frames = (size_t)B * T;
+    // every operand: what the message calls it, where, how many bytes, whether the call may leave it out
+    struct Op { const char* name; const void* p; size_t n; bool optional; };
+    const Op read_only[] = {{"rows", rows, (size_t)n_rows * 3 * J * 4, n_rows == 0}, {"offsets", offsets, (size_t)(n_utt + 1) * 8, false},
+                            {"tokens", tokens, (size_t)n_utt * S * 8, true},   {"utt", utt, (size_t)B * 8, false},
+                            {"start", start, (size_t)B * 8, true}};
+    const Op outs[] = {{"input_kp", input_kp, frames * ni * 8, false},       {"target_kp", target_kp, frames * nt * 8, false},
+                       {"target_conf", target_conf, frames * nt * 4, true}, {"text_tokens", text_tokens, (size_t)B * S * 8, true},
+                       {"n_frames", n_frames, (size_t)B * 8, false}};
+    for (const Op* list : {read_only, outs})
+        for (int i = 0; i < 5; ++i) {
+            const Op& o = list[i];
+            if (!o.p && !o.optional) return fail(B2H_ERR_INVALID, std::string(o.name) + " is NULL");
+            if (misaligned(o.p, 8)) return fail(B2H_ERR_INVALID, std::string(o.name) + " must be 8-byte aligned");
+        }
+    std::vector<Span> out_spans, in_spans;
+    for (const Op& o : outs)
+        if (o.p) out_spans.push_back({o.p, o.n});
+    for (const Op& o : read_only)
+        if (o.p) in_spans.push_back({o.p, o.n, o.name});
+    if (int rc = check_overlap(out_spans, in_spans)) return rc;
+    for (const Op* list : {read_only, outs})
+        for (int i = 0; i < 5; ++i)
+            if (list[i].p && list[i].n)
+                if (int rc = check_device_ptr(list[i].p, list[i].name)) return rc;
+    BbArgs a;
+    a.rows = rows; a.offsets = offsets; a.tokens = tokens; a.utt = utt; a.start = start;
+    a.input_kp = input_kp; a.target_kp = target_kp; a.target_conf = target_conf; a.text_tokens = text_tokens;
+    a.n_frames = n_frames;
+    a.n_rows = n_rows; a.n_utt = n_utt; a.B = B; a.T = T; a.S = S;
+    a.n_body = n_body; a.predict = predict; a.flags = flags; a.ni = ni; a.nt = nt; a.factor = factor;
+    const int64_t lanes[5] = {(int64_t)frames * ni, (int64_t)frames * nt, target_conf ? (int64_t)frames * nt : 0, B * S, B};
+    a.first[0] = 0;
+    for (int s = 0; s < 5; ++s) a.first[s + 1] = a.first[s] + (lanes[s] + kBbThreads - 1) / kBbThreads;
+    if (a.first[5] > 0x7fffffff) return fail(B2H_ERR_SHAPE, "shape too large");
+    hipLaunchKernelGGL(b2h_build_batch_k, dim3((unsigned)a.first[5]), dim3(kBbThreads), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
 

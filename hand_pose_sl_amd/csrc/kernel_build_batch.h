@@ -1,0 +1,111 @@
+// A training batch from the device-resident store (b2h_build_batch, include/b2h.h): the reference builds it per
+// utterance on the host -- frame selection, padding and clipping (dataloaders/text_pose_dataset.py:430-476, 652-688),
+// WristDifference, ChestDifference, NormalizeFixedFactor and one Build*Item transform (steps/utils.py:180-277, in
+// run.py:83-104's order) -- and torch's default collate stacks the items.  Here one launch gathers it.
+//
+// Store: rows (N, 3 J) fp32, J = n_body + 42, a row = [x * J | y * J | c * J] with the joints n_body body, 21 left
+// hand, 21 right hand (n_body 8: the reference's HDF5 row); offsets (U + 1) int64, utterance u owns rows
+// offsets[u] .. offsets[u + 1] - 1; tokens (U, S) int64 or none.
+//
+// The grid is five runs of 256-thread blocks, one per output, so a block serves one output and consecutive lanes store
+// to consecutive addresses: input_kp and target_kp one float2 (a joint) per lane, target_conf one float, text_tokens
+// and n_frames one int64.  Every output word is written by exactly one lane; nothing is read outside the rows of
+// utt[b].  An id outside [0, n_utt), or offsets of it outside 0 <= lo <= hi <= n_rows, indexes nothing: that
+// sequence's floats become quiet NaNs, its tokens -1, its n_frames 0.  No LDS, no atomics; indices are 64-bit.
+#pragma once
+#include "b2h_common.h"
+
+namespace b2h {
+
+constexpr int kBbThreads = 256;
+constexpr int kBbDif = 1, kBbNorm = 2, kBbPadFrame0 = 4;   // B2H_BATCH_* of include/b2h.h
+
+struct BbArgs {
+    const float* rows;
+    const int64_t* offsets;
+    const int64_t* tokens;
+    const int64_t* utt;
+    const int64_t* start;     // may be NULL: every window starts at 0
+    float* input_kp;
+    float* target_kp;
+    float* target_conf;       // may be NULL
+    int64_t* text_tokens;     // NULL iff tokens is
+    int64_t* n_frames;
+    int64_t n_rows, n_utt, B, T, S;
+    int64_t first[6];         // first block of input_kp, target_kp, target_conf, text_tokens, n_frames; the block count
+    int n_body, predict, flags, ni, nt;   // ni, nt: joints of an input / a target frame
+    float factor;
+};
+
+// The rows of sequence b: lo = first row of the window, len = rows of the utterance; false for an id the store lacks.
+__device__ __forceinline__ bool bb_window(const BbArgs& a, int64_t b, int64_t& lo, int64_t& len) {
+    const int64_t u = a.utt[b];
+    if (u < 0 || u >= a.n_utt) return false;
+    const int64_t r0 = a.offsets[u], r1 = a.offsets[u + 1];
+    if (r0 < 0 || r1 < r0 || r1 > a.n_rows) return false;
+    len = r1 - r0;
+    int64_t s = 0;
+    if (len > a.T) {          // select_jsons, text_pose_dataset.py:52-68; a shorter utterance starts at 0
+        s = a.start ? a.start[b] : 0;
+        s = s < 0 ? 0 : (s > len - a.T ? len - a.T : s);
+    }
+    lo = r0 + s;
+    return true;
+}
+
+// The store joint (0 .. J-1) behind joint j of an input frame (target = false) or a target frame.
+__device__ __forceinline__ int bb_source(int n_body, int predict, bool target, int j) {
+    const int hand = n_body + 21;                     // right-hand joint 0
+    if (predict == 0) return target ? hand + j : j;                                       // BuildRightHandItem
+    if (predict == 1)                                                                     // BuildIndexItem, n_body 12
+        return target ? hand + 5 + j : (j < 12 ? j : (j < 17 ? hand + j - 12 : hand + j - 8));
+    return target ? hand + 1 + j : (j < 8 ? hand + 13 + j : (j == 8 ? hand : j - 9));     // Build3fingerItem
+}
+
+__global__ __launch_bounds__(kBbThreads) void b2h_build_batch_k(const BbArgs a) {
+    const int64_t blk = blockIdx.x;
+    const int seg = blk < a.first[1] ? 0 : blk < a.first[2] ? 1 : blk < a.first[3] ? 2 : blk < a.first[4] ? 3 : 4;
+    const int64_t i = (blk - a.first[seg]) * kBbThreads + threadIdx.x;
+    const float qnan = __int_as_float(0x7fc00000);
+    if (seg <= 2) {
+        const int nj = seg == 0 ? a.ni : a.nt;
+        if (i >= a.B * a.T * nj) return;
+        const int64_t f = i / nj;
+        const int j = (int)(i - f * nj);
+        const int64_t b = f / a.T, t = f - b * a.T;
+        int64_t lo, len;
+        const bool known = bb_window(a, b, lo, len);
+        // frames at or past the utterance's end: zeros, or (B2H_BATCH_PAD_FRAME0) the window's first frame again
+        const bool live = known && len > 0 && (t < len || (a.flags & kBbPadFrame0));
+        const int64_t row = live ? lo + (t < len ? t : 0) : 0;
+        const int J = a.n_body + 42;
+        const float* r = a.rows + row * (3 * J);
+        const int src = bb_source(a.n_body, a.predict, seg != 0, j);
+        if (seg == 2) {
+            a.target_conf[i] = !known ? qnan : live ? r[2 * J + src] : 0.f;
+            return;
+        }
+        float2 v = make_float2(known ? 0.f : qnan, known ? 0.f : qnan);
+        if (live) {
+            v = make_float2(r[src], r[J + src]);
+            if (a.flags & kBbDif) {     // the hand minus the RAW body wrist (4), the body minus the chest (1)
+                const int ref = src < a.n_body ? 1 : 4;
+                v.x -= r[ref];
+                v.y -= r[J + ref];
+            }
+            if (a.flags & kBbNorm) { v.x = v.x / a.factor; v.y = v.y / a.factor; }
+        }
+        reinterpret_cast<float2*>(seg == 0 ? a.input_kp : a.target_kp)[i] = v;
+    } else if (seg == 3) {
+        if (i >= a.B * a.S) return;
+        const int64_t b = i / a.S, s = i - b * a.S;
+        const int64_t u = a.utt[b];
+        a.text_tokens[i] = (u >= 0 && u < a.n_utt) ? a.tokens[u * a.S + s] : -1;
+    } else {
+        if (i >= a.B) return;
+        int64_t lo, len;
+        a.n_frames[i] = bb_window(a, i, lo, len) ? (len < a.T ? len : a.T) : 0;
+    }
+}
+
+} // namespace b2h

@@ -1,0 +1,207 @@
+"""The training set on the GPU: `DeviceDataset` holds every frame of every utterance in device memory and
+`DeviceLoader` turns "these utterances, these crop offsets" into the reference's batch dict with one HIP kernel
+(b2h_build_batch, kernel_build_batch.h), so an epoch needs no host work per batch.
+
+The reference builds a batch per utterance on the host -- FastTextPoseDataset.__getitem__ / TextPoseH5Dataset.__getitem__
+(dataloaders/text_pose_dataset.py:430-476, 652-688: frame selection, padding, clipping, torch.tensor(list).float()),
+WristDifference, ChestDifference, NormalizeFixedFactor and one Build*Item (steps/utils.py:180-277, run.py:83-104) --
+under a DataLoader without workers (run.py:135-136), then copies it to the device (traintest.py:89-90,106).
+
+Store layout (include/b2h.h): `rows` (N, 3 J) float32, J = n_body + 42, a row = [x * J | y * J | c * J] with the joints
+n_body body, 21 left hand, 21 right hand; `offsets` (U + 1) int64 ascending; `tokens` (U, S) int64 or None.  n_body = 8
+is the reference's HDF5 row (n_frames, 150); n_body = 12 the same rule for utterances read from OpenPose JSON.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, openpose
+
+SELECTIONS = ("randomcrop", "first")
+PADS = ("zeros", "frame0")
+# (input joints, target joints) of each `--predict` choice (run.py:91-102), the input of right_hand being the body
+_JOINTS = {"right_index": (29, 4), "right_3fingers": (21, 12)}
+
+
+def frames_to_rows(frames):
+    """One utterance's frames (OpenPose frame paths, parsed dicts or merged-JSON entries) -> its (n, 162) float32
+    store rows: 12 body (BODY_HEAD_KEYPOINTS), 21 left-hand, 21 right-hand joints as [x * 54 | y * 54 | c * 54], the
+    12-joint counterpart of openpose.item_to_h5_row.  Values are rounded to float32 as torch.tensor(list).float()
+    rounds them (text_pose_dataset.py:536-544)."""
+    out = np.empty((len(frames), 3, 54), np.float32)
+    for i, fr in enumerate(frames):
+        r_kp, r_conf, l_kp, l_conf, b_kp, b_conf = openpose.load_keypoints(fr)
+        kp = np.asarray(b_kp + l_kp + r_kp, dtype=np.float64)
+        if kp.shape != (54, 2):
+            raise ValueError(f"frame {i}: expected 12 + 21 + 21 joints, got {kp.shape[0]}")
+        out[i, 0], out[i, 1], out[i, 2] = kp[:, 0], kp[:, 1], np.asarray(b_conf + l_conf + r_conf, dtype=np.float64)
+    return out.reshape(len(frames), 162)
+
+
+class DeviceDataset:
+    """`DeviceDataset(rows, offsets, n_body, tokens=None, device="cuda")`: validates the store once on the host and
+    moves it to the GPU.  `len(ds)` is the number of utterances, `ds.lengths` their row counts (a host tensor)."""
+
+    def __init__(self, rows, offsets, n_body, tokens=None, device="cuda"):
+        if n_body not in (8, 12):
+            raise ValueError(f"n_body must be 8 (HDF5 rows) or 12 (OpenPose JSON), got {n_body!r}")
+        rows, offsets = torch.as_tensor(rows), torch.as_tensor(offsets)
+        width = 3 * (n_body + 42)
+        if rows.dtype != torch.float32 or offsets.dtype != torch.int64:
+            raise ValueError(f"rows must be float32 and offsets int64, got {rows.dtype} and {offsets.dtype}")
+        if rows.dim() != 2 or rows.shape[1] != width:
+            raise ValueError(f"rows must be (N, {width}) for n_body = {n_body}, got {tuple(rows.shape)}")
+        if offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError(f"offsets must be (U + 1,), got {tuple(offsets.shape)}")
+        host = offsets.cpu()
+        if int(host[0]) != 0 or int(host[-1]) != rows.shape[0] or bool((host[1:] < host[:-1]).any()):
+            raise ValueError(f"offsets must ascend from 0 to the row count {rows.shape[0]}")
+        n_utt = offsets.numel() - 1
+        if tokens is not None:
+            tokens = torch.as_tensor(tokens)
+            if tokens.dtype != torch.int64:
+                raise ValueError(f"tokens must be int64, got {tokens.dtype}")
+            if tokens.dim() != 2 or tokens.shape[0] != n_utt or not 1 <= tokens.shape[1] <= 128:
+                raise ValueError(f"tokens must be ({n_utt}, S) with 1 <= S <= 128, got {tuple(tokens.shape)}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceDataset lives on the GPU (an MI355X); there is no host fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.n_body = n_body
+        self.rows = rows.to(self.device).contiguous()
+        self.offsets = offsets.to(self.device).contiguous()
+        self.tokens = None if tokens is None else tokens.to(self.device).contiguous()
+        self.lengths = host[1:] - host[:-1]
+
+    def __len__(self):
+        return self.offsets.numel() - 1
+
+    @classmethod
+    def _from_utterances(cls, utterances, n_body, tokens, device):
+        width = 3 * (n_body + 42)
+        arrays = [np.ascontiguousarray(u, dtype=np.float32).reshape(-1, width) if np.size(u) else
+                  np.zeros((0, width), np.float32) for u in utterances]
+        offsets = np.zeros(len(arrays) + 1, np.int64)
+        np.cumsum([a.shape[0] for a in arrays], out=offsets[1:])
+        rows = np.concatenate(arrays, axis=0) if arrays else np.zeros((0, width), np.float32)
+        return cls(torch.from_numpy(rows), torch.from_numpy(offsets), n_body, tokens, device)
+
+    @classmethod
+    def from_h5_rows(cls, utterances, tokens=None, device="cuda"):
+        """A list of (n_i, 150) arrays, the datasets of the reference's keypoints HDF5 file (one per utterance)."""
+        for i, u in enumerate(utterances):
+            if np.ndim(u) != 2 or np.shape(u)[1] != 150:
+                raise ValueError(f"utterance {i}: expected an (n_frames, 150) row array, got {np.shape(u)}")
+        return cls._from_utterances(utterances, 8, tokens, device)
+
+    @classmethod
+    def from_frames(cls, utterances, tokens=None, device="cuda"):
+        """A list of utterances, each a list of OpenPose frame dicts, merged-JSON entries or paths in time order."""
+        return cls._from_utterances([frames_to_rows(list(u)) for u in utterances], 12, tokens, device)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class DeviceLoader:
+    """Iterable over the batches of a DeviceDataset, `len()` of them, each the reference's batch dict on the device:
+    "input_kp" (B, T, J_in, 2), "target_kp" (B, T, J_out, 2), "target_conf" (B, T, J_out), "n_frames" (B) int64,
+    "text_tokens" (B, S) when the store has tokens, and for `right_hand` "body_kp", the same tensor as "input_kp".
+
+    The order is sequential like run.py's loaders (`shuffle` draws a torch.randperm, with `generator` if given);
+    "randomcrop" draws the crop starts with torch on the device, so they follow torch.manual_seed; "first" crops at 0.
+    `pad`: "zeros" as TextPoseH5Dataset pads, "frame0" as the JSON datasets do.  `build(utt, start, out)` is the
+    explicit form."""
+
+    def __init__(self, ds, batch_size, max_frames, selection="randomcrop", predict="right_hand", dif_encoding=True,
+                 normalize=True, factor=1280, pad="zeros", shuffle=False, drop_last=False, generator=None):
+        if not isinstance(ds, DeviceDataset):
+            raise TypeError("ds must be a DeviceDataset")
+        if batch_size < 1 or max_frames < 1:
+            raise ValueError("batch_size and max_frames must be >= 1")
+        if selection not in SELECTIONS:
+            raise ValueError(f"selection must be one of {SELECTIONS}, got {selection!r}")
+        if pad not in PADS:
+            raise ValueError(f"pad must be one of {PADS}, got {pad!r}")
+        if predict not in _lib.PREDICT:
+            raise ValueError(f"predict must be one of {sorted(_lib.PREDICT)}, got {predict!r}")
+        if predict != "right_hand" and ds.n_body != 12:
+            raise ValueError(f"--predict {predict} needs a 12-joint body (a store from OpenPose JSON)")
+        if normalize and not factor > 0:
+            raise ValueError("factor must be > 0")
+        self.ds, self.batch_size, self.max_frames = ds, int(batch_size), int(max_frames)
+        self.selection, self.predict, self.shuffle, self.drop_last, self.generator = selection, predict, shuffle, drop_last, generator
+        self.factor = float(factor)
+        self.flags = ((_lib.BATCH_DIF_ENCODING if dif_encoding else 0) | (_lib.BATCH_NORMALIZE if normalize else 0) |
+                      (_lib.BATCH_PAD_FRAME0 if pad == "frame0" else 0))
+        self.joints = (ds.n_body, 21) if predict == "right_hand" else _JOINTS[predict]
+        # the largest start a random crop may draw, per utterance (select_jsons: random.randint(0, len - n))
+        self._room = (ds.lengths - self.max_frames).clamp_(min=0).to(ds.device)
+
+    def __len__(self):
+        n = len(self.ds)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _spec(self, B):
+        """name -> (shape, dtype) of the tensors `build` writes for B sequences."""
+        T, (ji, jt) = self.max_frames, self.joints
+        spec = {"input_kp": ((B, T, ji, 2), torch.float32), "target_kp": ((B, T, jt, 2), torch.float32),
+                "target_conf": ((B, T, jt), torch.float32), "n_frames": ((B,), torch.int64)}
+        if self.ds.tokens is not None:
+            spec["text_tokens"] = ((B, self.ds.tokens.shape[1]), torch.int64)
+        return spec
+
+    def empty_batch(self, B):
+        """Unwritten tensors of one batch of B sequences: what `build` fills and returns."""
+        out = {k: torch.empty(shape, dtype=dtype, device=self.ds.device) for k, (shape, dtype) in self._spec(B).items()}
+        if self.predict == "right_hand":
+            out["body_kp"] = out["input_kp"]
+        return out
+
+    def build(self, utt, start=None, out=None):
+        """The batch of utterances `utt` ((B) int64 on the device; a list or host tensor is copied there) cropped at
+        `start` ((B) int64, None = 0; read only for utterances longer than max_frames, clamped into them).  `out`: a
+        batch returned earlier, written again in place -- with `utt` and `start` device tensors this launches one
+        kernel and nothing else, so a captured graph replays it after the caller refreshes `utt` and `start` in place."""
+        ds, dev = self.ds, self.ds.device
+        utt = torch.as_tensor(utt, dtype=torch.int64).to(dev).contiguous()
+        if utt.dim() != 1:
+            raise ValueError(f"utt must be (B,), got {tuple(utt.shape)}")
+        B = utt.shape[0]
+        if start is not None:
+            start = torch.as_tensor(start, dtype=torch.int64).to(dev).contiguous()
+            if start.shape != utt.shape:
+                raise ValueError(f"start must be ({B},), got {tuple(start.shape)}")
+        if out is None:
+            out = self.empty_batch(B)
+        for k, (shape, dtype) in self._spec(B).items():
+            t = out.get(k)
+            if t is None or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"out[{k!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        tok = ds.tokens
+        with _lib.on_device(dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(_lib.load().b2h_build_batch(
+                _ptr(ds.rows), ds.rows.shape[0], _ptr(ds.offsets), len(ds), ds.n_body, _ptr(tok),
+                0 if tok is None else tok.shape[1], _ptr(utt), _ptr(start), B, self.max_frames, _lib.PREDICT[self.predict],
+                self.flags, self.factor, _ptr(out["input_kp"]), _ptr(out["target_kp"]), _ptr(out["target_conf"]),
+                _ptr(out.get("text_tokens")) if tok is not None else None, _ptr(out["n_frames"]), st))
+        return out
+
+    def draw_starts(self, utt):
+        """Random crop offsets for the utterances `utt` (device int64): uniform in [0, len - max_frames], 0 for an
+        utterance that fits; drawn on the device from torch's generator, without a host synchronisation."""
+        room = self._room[utt]
+        u = torch.rand(room.shape, dtype=torch.float64, device=room.device)
+        return torch.minimum((u * (room + 1).to(torch.float64)).to(torch.int64), room)
+
+    def __iter__(self):
+        n, dev = len(self.ds), self.ds.device
+        order = (torch.randperm(n, generator=self.generator).to(dev) if self.shuffle else
+                 torch.arange(n, dtype=torch.int64, device=dev))
+        for i in range(len(self)):
+            utt = order[i * self.batch_size:(i + 1) * self.batch_size]
+            yield self.build(utt, self.draw_starts(utt) if self.selection == "randomcrop" else None)

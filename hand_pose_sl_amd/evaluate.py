@@ -10,6 +10,10 @@ batches with AverageMeter (steps/utils.py:11-25).  Here the forward is the HIP m
 of the two HIP reductions of `metrics.py`; the tail mask is skipped because neither criterion reads a
 frame at or beyond `n_frames[i]` (it could not change the value).  One host synchronisation per call,
 not per batch: the per-batch losses stay on the device until the end.
+
+`train_epoch(model, train_loader, criterion, optimizer, args)` is the training counterpart, the loop body of
+traintest.py:87-128 under the same dispatch and the same single synchronisation; with a `DeviceLoader` (dataset.py) as
+the loader an epoch does no host work per batch.
 """
 import torch
 
@@ -34,6 +38,57 @@ def _loss_name(criterion, args, loss):
     return {"maskedPoseL1": "L1", "poderatedPoseL1": "confL1"}.get(name, name)
 
 
+def _check_model_name(what, model, args):
+    """traintest.py:93-109 / :183-200 dispatch on args.model; here the model's class does, and a name that is given
+    must agree with it.  Returns whether the model is the text-conditioned one."""
+    text = isinstance(model, TextPoseTransformer)
+    name = getattr(args, "model", None) if args is not None else None
+    if name is not None and (name == "TextPoseTransformer") != text or name not in (None, "Conv", "TransformerEnc",
+                                                                                   "TextPoseTransformer"):
+        raise ValueError(f"{what} runs Conv, TransformerEnc and TextPoseTransformer, each with a model of its "
+                         f"class; got args.model={name!r} with a {type(model).__name__}")
+    return text
+
+
+def train_epoch(model, train_loader, criterion=None, optimizer=None, args=None, *, loss=None):
+    """One epoch of the reference's training loop (steps/traintest.py:80,87-128) for its three models: per batch the
+    forward -- model(batch["body_kp"]) or, for a TextPoseTransformer, model(batch["text_tokens"], batch["input_kp"]) --,
+    the criterion, optimizer.zero_grad(), loss.backward(), optimizer.step().  `criterion`, `args.loss` and `args.model`
+    are read exactly as validate() reads them; mask_output (:111) is skipped for validate()'s reason: neither criterion
+    reads a frame at or beyond n_frames[i], so it changes neither the loss nor a gradient.  `train_loader`: a
+    DeviceLoader, or any iterable of the reference's batch dicts.  Returns the mean of the batch losses as AverageMeter
+    accumulates it (steps/utils.py:11-25: the sum of the `loss.item()` floats over their count), with one host
+    synchronisation per epoch: the per-batch losses stay on the device until the end."""
+    loss = _loss_name(criterion, args, loss)
+    if loss not in LOSSES:
+        raise ValueError(f"train_epoch() trains with --loss L1 or confL1, not {loss!r}")
+    if optimizer is None:
+        raise ValueError("train_epoch() needs the optimizer")
+    text = _check_model_name("train_epoch()", model, args)
+    dev = next(model.parameters()).device
+    model.train()
+    losses = []
+    for batch in train_loader:
+        if text:   # traintest.py:105-107
+            pose = batch["input_kp"] if "input_kp" in batch else batch["body_kp"]
+            prediction = model(batch["text_tokens"].to(dev), pose.to(dev))
+        else:
+            prediction = model(batch["body_kp"].to(dev))
+        target = batch["target_kp"].to(dev)
+        if loss == "L1":
+            value = masked_pose_l1(prediction, target, batch["n_frames"])
+        else:
+            value = weighted_pose_l1(prediction, target, batch["n_frames"], batch["target_conf"])
+        optimizer.zero_grad()
+        value.backward()
+        optimizer.step()
+        losses.append(value.detach())
+    if not losses:
+        raise ZeroDivisionError("empty loader")  # AverageMeter.get_average() divides by its count
+    values = torch.stack(losses).cpu().tolist()
+    return sum(values) / len(values)
+
+
 def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=None, return_pixels=False):
     """`validate(model, val_loader, criterion, device, args)` exactly as steps/traintest.py:136,168 calls it
     -- `criterion` a maskedPoseL1 / poderatedPoseL1 instance (the reference's or `hand_pose_sl_amd`'s: only
@@ -54,12 +109,7 @@ def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=
     if loss not in LOSSES:
         # MSE / huber make the reference's validate() fail with an unbound `loss` (traintest.py:207-211)
         raise ValueError(f"validate() evaluates --loss L1 or confL1, not {loss!r}")
-    text = isinstance(model, TextPoseTransformer)
-    name = getattr(args, "model", None) if args is not None else None
-    if name is not None and (name == "TextPoseTransformer") != text or name not in (None, "Conv", "TransformerEnc",
-                                                                                   "TextPoseTransformer"):
-        raise ValueError(f"validate() runs Conv, TransformerEnc and TextPoseTransformer, each with a model of its "
-                         f"class; got args.model={name!r} with a {type(model).__name__}")
+    text = _check_model_name("validate()", model, args)
     dev = next(model.parameters()).device
     model.eval()
     losses = []

@@ -594,6 +594,46 @@ int b2h_adam_step(float* const* params, const float* const* grads, float* const*
                   const int64_t* numel, int n_tensors, float lr, const float* lr_dev, float beta1, float beta2,
                   float eps, float weight_decay, int64_t step, const int64_t* step_dev, void* stream);
 
+/* The training set on the device: one kernel builds every batch -------------------
+ * What the reference's datasets and transforms do per utterance on the host (FastTextPoseDataset.__getitem__ and
+ * TextPoseH5Dataset.__getitem__, dataloaders/text_pose_dataset.py:430-476, 652-688: frame selection, padding, clipping;
+ * then WristDifference, ChestDifference, NormalizeFixedFactor and one Build*Item of steps/utils.py:180-277 in
+ * run.py:83-104's order) and torch's default collate stacks, from a store that stays on the GPU (kernel_build_batch.h).
+ * Store:
+ *   rows    (n_rows, 3 J) fp32, J = n_body + 42: every frame of every utterance back to back; a row is
+ *           [x * J | y * J | c * J], the joints n_body body, then 21 left hand, then 21 right hand.  n_body = 8 is the
+ *           reference's HDF5 row (n_frames, 150) (array2item, text_pose_dataset.py:587-612); n_body = 12 the same rule,
+ *           162 wide, for utterances loaded from OpenPose JSON (body joints BODY_HEAD_KEYPOINTS, :14).
+ *   offsets (n_utt + 1) int64, ascending, offsets[n_utt] <= n_rows: utterance u owns rows offsets[u] .. offsets[u+1]-1.
+ *   tokens  (n_utt, S) int64 or NULL (then S is ignored); 1 <= S <= 128.  Tokenising stays with the caller.
+ * Batch: utt (B) int64 names the utterances, start (B) int64 or NULL (= 0) the crop offsets.  With len the row count of
+ * utt[b]: n_frames[b] = min(len, T); the window starts at clamp(start[b], 0, len - T) if len > T and at 0 otherwise
+ * (select_jsons, :52-68).  Frames t >= len are zeros put in before any transform (TextPoseH5Dataset.pad, :614-624)
+ * or, with B2H_BATCH_PAD_FRAME0, the window's first frame again, transformed like any frame (the JSON datasets' pad,
+ * :511-519).  An utterance without rows gives zeros and n_frames 0 either way.
+ *   B2H_BATCH_DIF_ENCODING: hand -= raw body wrist (joint 4), then body -= chest (joint 1)   (run.py:85-87)
+ *   B2H_BATCH_NORMALIZE   : body and hand / factor, a true division                           (run.py:89-90)
+ *   predict (enum b2h_predict): RIGHT_HAND input = body (B, T, n_body, 2), target = right hand (B, T, 21, 2);
+ *           RIGHT_INDEX (B, T, 29, 2) / (B, T, 4, 2) and RIGHT_3FINGERS (B, T, 21, 2) / (B, T, 12, 2) in
+ *           b2h_tpt_build_item's joint orders, n_body = 12 only (B2H_ERR_INVALID with 8: no model takes 25 or 17
+ *           joints).  target_conf (B, T, target joints), or NULL: the target joints' confidences.
+ *   text_tokens (B, S) = tokens[utt[b]], NULL exactly when tokens is; n_frames (B) int64.
+ * Every output element is a copy, or one fp32 subtraction and one correctly rounded fp32 division: equal to torch's,
+ * bit for bit.  utt[b] outside [0, n_utt) (or offsets of it outside 0 <= lo <= hi <= n_rows) indexes nothing: every
+ * float of that sequence becomes a quiet NaN, its tokens -1, its n_frames 0 -- the models turn an id outside their
+ * table into a NaN sequence and the losses return NaN: loud, never a neighbour's data.
+ * One launch, no atomics, every output word written once; stream-ordered, asynchronous, allocates nothing and reads
+ * no device memory on the host, so it can be captured.  B2H_ERR_INVALID, before any device work: n_body not 8 or 12,
+ * an unknown predict or flag bit, a finger mode with n_body 8, factor not > 0 with B2H_BATCH_NORMALIZE, S outside
+ * [1, 128] with tokens, tokens without text_tokens or the reverse, a NULL or not 8-byte-aligned pointer, an output
+ * overlapping the store, utt, start or another output, a pointer that is not memory of the current device.
+ * B2H_ERR_SHAPE: B, T, n_utt or n_rows negative, T > 2^24, B > 2^31 - 1.  B * T == 0 is a no-op (B2H_OK). */
+enum b2h_batch_flags { B2H_BATCH_DIF_ENCODING = 1, B2H_BATCH_NORMALIZE = 2, B2H_BATCH_PAD_FRAME0 = 4 };
+int b2h_build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                    const int64_t* tokens, int64_t S, const int64_t* utt, const int64_t* start, int64_t B, int64_t T,
+                    int predict, int flags, float factor, float* input_kp, float* target_kp, float* target_conf,
+                    int64_t* text_tokens, int64_t* n_frames, void* stream);
+
 /* Introspection / measurement -------------------------------------------- */
 
 /* conv_channels, pos_emb and whether weights are loaded. */

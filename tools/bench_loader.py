@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""GPU box: what feeding a TextPoseTransformer training step costs, from the device-resident store (DeviceLoader,
+b2h_build_batch, kernel_build_batch.h) and from the host as the reference feeds it, one JSON line.
+Context only: there is no speed bar; a "faster" is claimed only where the ranges of the alternating runs separate.
+  * build: `iters` back-to-back b2h_build_batch launches into the same tensors between two HIP events, per launch (the
+    launch gaps are in it: a kernel this short is launch-bound), the median, minimum and maximum of `reps` repetitions;
+    the bytes it reads and writes, counted from the shapes;
+  * host path: wall time per batch of tests/batch_ref.py -- the restatement of the reference's __getitem__ and
+    transforms, held to the reference's own batches bit for bit by the tests -- run per item in this process, stacked
+    and copied to the device, ending in a synchronise: what the reference's DataLoader without workers (run.py:135-136)
+    and the `.to(device)` of its loop (traintest.py:89-90,106) do.  It leaves out JSON parsing and tokenising, which the
+    reference also does per item: a lower bound of the reference's host work;
+  * epoch: hps.train_epoch over `steps` batches of the trainer's default model (4 + 4 layers, geometry (8, 42),
+    dropout 0.1, Adam lr 2e-4; MFMA attention and Linears, native dropout masks, native Adam), fed by the DeviceLoader
+    and by the host path, in alternating runs; wall time of the epoch (it ends in a host synchronisation) per step.
+The store is seeded: `utterances` HDF5-style utterances (8 body joints) of T / 2 .. 3 T frames, random crops.
+    python tools/bench_loader.py                 B x S x T = 128 x 40 x 200, the trainer's default batch
+    python tools/bench_loader.py 128 40 100      the datasets' 100 frames
+    python tools/bench_loader.py [B=128] [S=40] [T=200] [reps=5] [steps=8] [out.json]"""
+import json
+import os
+import random
+import sys
+import time
+import warnings
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import batch_ref  # noqa: E402
+import hand_pose_sl_amd as hps  # noqa: E402
+
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
+S = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+T = int(sys.argv[3]) if len(sys.argv) > 3 else 200
+REPS = int(sys.argv[4]) if len(sys.argv) > 4 else 5
+STEPS = int(sys.argv[5]) if len(sys.argv) > 5 else 8
+OUT = sys.argv[6] if len(sys.argv) > 6 else None
+N_TOKENS, L, P, LR, N_BODY, BUILD_ITERS = 1000, 4, 0.1, 2e-4, 8, 200
+if not torch.cuda.is_available():
+    sys.exit("bench_loader.py measures on the GPU; none is visible")
+dev = torch.device("cuda:0")
+
+
+def stats(values):
+    v = sorted(values)
+    return {"median": v[len(v) // 2], "min": v[0], "max": v[-1]}
+
+
+# ---- the store ---------------------------------------------------------------------------------------------------------
+gen = torch.Generator().manual_seed(0)
+U = B * STEPS
+lengths = torch.randint(T // 2, 3 * T + 1, (U,), generator=gen)
+offsets = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(lengths, 0)])
+J = N_BODY + 42
+rows = (torch.rand((int(offsets[-1]), 3, J), generator=gen) * torch.tensor([1280.0, 720.0, 1.0]).view(1, 3, 1)).reshape(-1, 3 * J)
+tokens = torch.randint(0, N_TOKENS, (U, S), generator=gen)
+ds = hps.DeviceDataset(rows, offsets, N_BODY, tokens, device=dev)
+loader = hps.DeviceLoader(ds, B, T, selection="randomcrop")
+out = {"B": B, "S": S, "T": T, "n_body": N_BODY, "reps": REPS, "steps": STEPS, "utterances": U, "store_rows": int(offsets[-1]),
+       "store_MB": rows.numel() * 4 / 1e6, "model": {"n_enc": L, "n_dec": L, "n_tokens": N_TOKENS, "dropout": P}}
+
+
+# ---- the host path -----------------------------------------------------------------------------------------------------
+def host_batches():
+    """The reference's loader over the same store: items in order, a random crop each (select_jsons draws
+    random.randint), stacked per batch; the loop that consumes them copies them to the device."""
+    for i in range(0, U, B):
+        utt = range(i, min(i + B, U))
+        start = [random.randint(0, max(0, int(lengths[u]) - T)) for u in utt]
+        yield batch_ref.batch(rows, offsets, N_BODY, tokens, utt, start, T)
+
+
+# the two paths build the same batch from the same utterances and starts (the tests hold this at small shapes)
+utt0 = torch.arange(B, dtype=torch.int64)
+start0 = torch.tensor([(int(lengths[u]) * 7) % (max(0, int(lengths[u]) - T) + 1) for u in range(B)])
+want = batch_ref.batch(rows, offsets, N_BODY, tokens, utt0.tolist(), start0.tolist(), T)
+got = loader.build(utt0, start0)
+out["paths_agree_bit_for_bit"] = all(batch_ref.same_bits(got[k], want[k]) for k in want)
+assert out["paths_agree_bit_for_bit"]
+
+# ---- 1. the build launch -------------------------------------------------------------------------------------------------
+dutt, dstart = utt0.to(dev), start0.to(dev)
+for _ in range(20):
+    loader.build(dutt, dstart, out=got)
+torch.cuda.synchronize()
+ms = []
+for _ in range(REPS):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(BUILD_ITERS):
+        loader.build(dutt, dstart, out=got)
+    e1.record()
+    e1.synchronize()
+    ms.append(e0.elapsed_time(e1) / BUILD_ITERS)
+n_frames = torch.clamp(lengths[:B], max=T)
+read = int(n_frames.sum()) * (2 * N_BODY + 3 * 21) * 4 + B * S * 8 + 3 * B * 8     # the joints used of the live frames
+written = B * T * (2 * N_BODY + 3 * 21) * 4 + B * S * 8 + B * 8
+out["build"] = {"what": f"{BUILD_ITERS} back-to-back launches between HIP events, ms per launch", "ms": stats(ms),
+                "bytes_read_needed": read, "bytes_written": written,
+                "GB_per_s_at_median": (read + written) / 1e6 / stats(ms)["median"]}
+
+# ---- 2. the host path, per batch -----------------------------------------------------------------------------------------
+def host_pass_ms():
+    t0, n = time.perf_counter(), 0
+    for b in host_batches():
+        moved = {k: v.to(dev) for k, v in b.items()}
+        torch.cuda.synchronize()
+        n += 1
+    del moved
+    return (time.perf_counter() - t0) * 1e3 / n
+
+
+random.seed(0)
+host_pass_ms()                                                # the first pass warms the allocators
+out["host_path"] = {"what": "wall ms per batch: the restatement per item, stacked, copied to the device, synchronised",
+                    "ms": stats([host_pass_ms() for _ in range(REPS)])}
+
+# ---- 3. an epoch fed each way, alternating -------------------------------------------------------------------------------
+torch.manual_seed(0)
+with warnings.catch_warnings():
+    warnings.simplefilter("ignore", UserWarning)
+    m = hps.TextPoseTransformer(N_TOKENS, N_BODY, 2, 4, 128, 42, L, L, dropout=P).to(dev).train()
+m.set_train_kernels("mfma").set_train_linear("mfma").set_dropout_source("native", seed=0)
+opt = hps.Adam(m.parameters(), lr=LR)
+crit = hps.maskedPoseL1()
+
+
+def epoch_ms(feed):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    hps.train_epoch(m, feed, crit, opt)                       # ends in its one host synchronisation
+    return (time.perf_counter() - t0) * 1e3 / STEPS
+
+
+epoch_ms(loader), epoch_ms(host_batches())                    # warm-up of both
+fed = {"device": [], "host": []}
+for _ in range(REPS):
+    fed["device"].append(epoch_ms(loader))
+    fed["host"].append(epoch_ms(host_batches()))
+out["epoch_step_ms"] = {"what": f"wall ms per step of hps.train_epoch over {STEPS} batches, alternating runs",
+                        "device_loader": stats(fed["device"]), "host_path": stats(fed["host"]),
+                        "device_loader_runs": fed["device"], "host_path_runs": fed["host"],
+                        "ranges_separate": max(fed["device"]) < min(fed["host"]) or max(fed["host"]) < min(fed["device"])}
+line = json.dumps(out)
+print(line)
+if OUT:
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    with open(OUT, "w") as f:
+        f.write(line + "\n")
