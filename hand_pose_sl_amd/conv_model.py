@@ -119,7 +119,7 @@ class ConvModel(NativeModule, nn.Module):
             x = self._check_input(inp)
             return _ConvTrainFn.apply(self, x, *self._params())
         lib = self._ensure_handle()
-        x = self._check_input(inp)
+        x = _aligned(self._check_input(inp))     # b2h_forward takes x on the 16-byte grid
         B, T = x.shape[0], x.shape[1]
         y = torch.empty((B, T, 21, 2), dtype=torch.float32, device=x.device)
         with _lib.on_device(x.device):
@@ -140,6 +140,11 @@ class ConvModel(NativeModule, nn.Module):
         for t in (x, y):
             if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError("forward_into needs contiguous float32 tensors on the model's device")
+            if t.data_ptr() % 16:
+                # caller-owned buffers cannot be cloned here; model(x) copies such an input instead
+                raise RuntimeError("forward_into needs x and y to start on a 16-byte boundary (data_ptr() % 16 == 0): the "
+                                   f"kernels move 16-byte vectors; got an offset of {t.data_ptr() % 16} bytes (a "
+                                   "contiguous view into a larger buffer may start anywhere)")
         with _lib.on_device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.b2h_forward(self._handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()),
@@ -156,7 +161,7 @@ class ConvModel(NativeModule, nn.Module):
             raise RuntimeError("ConvModel.forward_fused is inference-only (no gradient): call model.eval() or wrap the "
                                "call in torch.no_grad(); train through model(x), which is differentiable")
         lib = self._ensure_handle()
-        x = self._check_input(body)
+        x = _aligned(self._check_input(body))
         B, T = x.shape[0], x.shape[1]
         flags = ((_lib.PRE_CHEST_DIFF if dif_encoding else 0) | (_lib.PRE_NORMALIZE if normalize else 0) |
                  (_lib.POST_DENORMALIZE if denormalize else 0) | (_lib.POST_MASK_TAIL if mask_tail else 0))

@@ -1961,8 +1961,9 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
 
     // encoder: token_embedding (:206) -> layers -> encoder.norm
     const float* const* wt = params + 4 + 12 * m->n_enc + 18 * m->n_dec; // token_embedding, hidden2pose, pose2hidden
-    hipLaunchKernelGGL(b2h_tpt_embed, dim3((unsigned)((Ns * 32 + 255) / 256)), dim3(256), 0, st, tokens, wt[0], sv.E0, Ns,
-                       m->n_tokens);
+    // the caller's table is promised 4-byte aligned only: float4 reads on the 16-byte grid, dwords off it
+    hipLaunchKernelGGL(misaligned(wt[0], 16) ? b2h_embed_dwords : b2h_tpt_embed,
+                       dim3((unsigned)((Ns * 32 + 255) / 256)), dim3(256), 0, st, tokens, wt[0], sv.E0, Ns, m->n_tokens);
     const float* H = sv.E0;
     for (int l = 0; l < m->n_enc; ++l) {
         const TtLayer L = sv.enc_layer(l);

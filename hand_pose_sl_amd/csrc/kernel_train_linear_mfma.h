@@ -57,6 +57,13 @@ __device__ __forceinline__ void ml_store1(__amdgpu_buffer_rsrc_t rs, int float_o
     asm volatile("s_nop 1" ::: "memory"); // as tt_store: keeps tools/store_war_audit.py at zero, no hardware need
 }
 
+// Four keep-mask bytes as one word.  The training calls state no alignment for their masks (bytes), so the word load
+// is taken only where the address allows it (uniform: `p` is the mask's base plus a multiple of 4).
+__device__ __forceinline__ uint32_t ml_mask4(const uint8_t* p) {
+    if ((reinterpret_cast<uintptr_t>(p) & 3) == 0) return *reinterpret_cast<const uint32_t*>(p);
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
 // W rows r0 .. r0 + 127 -> LDS at `pitch` (a multiple of 4), all 128 columns: zeros for rows >= M and columns >= K.
 // With K a multiple of 4 and W 16-byte aligned a thread moves 16 float4, all requested before the first is written:
 // one memory latency per block; otherwise dwords, eight in flight.
@@ -134,7 +141,7 @@ __global__ __launch_bounds__(256) void b2h_ml_linear(const float* __restrict__ X
                 put[u] = row < rows && m < M;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[u][r] = m + r < M ? bias[m + r] : 0.f;
-                k4[u] = vec && mask && put[u] ? *reinterpret_cast<const uint32_t*>(mask + e0 + m) : 0u;
+                k4[u] = vec && mask && put[u] ? ml_mask4(mask + e0 + m) : 0u;
                 rs[u] = vec && res && put[u] ? *reinterpret_cast<const f32x4*>(res + e0 + m) : mt_zero4();
             }
             const float* a0 = smem_ml + (16 * mt + col) * kMlWf + q;
@@ -234,7 +241,7 @@ __global__ __launch_bounds__(256) void b2h_ml_linear_dx(const float* __restrict_
                 for (int r = 0; r < 4; ++r) v[r] = g4[r] > 0.f ? v[r] * scale : 0.f;
             }
             if (mask) {
-                const uint32_t k4 = *reinterpret_cast<const uint32_t*>(mask + e0 + k);
+                const uint32_t k4 = ml_mask4(mask + e0 + k);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = (k4 >> (8 * r)) & 0xff ? v[r] * scale : 0.f;
             }

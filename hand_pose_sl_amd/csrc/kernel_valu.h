@@ -160,18 +160,19 @@ __global__ __launch_bounds__(256) void b2h_target_transform_kernel(const float* 
                                                                    float* __restrict__ out,
                                                                    int64_t frames, int flags,
                                                                    float factor) {
-    // one thread per (frame, joint): float2
+    // one thread per (frame, joint): two floats, as dwords -- the entry point promises fp32 alignment only
     const int64_t n = frames * 21;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t f = i / 21;
-        float2 v = *reinterpret_cast<const float2*>(hand + i * 2);
+        float2 v = make_float2(hand[i * 2], hand[i * 2 + 1]);
         if (flags & 1) {
-            const float2 w = *reinterpret_cast<const float2*>(body + f * kInCh + 4 * 2);
-            v.x -= w.x; v.y -= w.y;
+            const float* w = body + f * kInCh + 4 * 2;
+            v.x -= w[0]; v.y -= w[1];
         }
         if (flags & 2) { v.x = v.x / factor; v.y = v.y / factor; }
-        *reinterpret_cast<float2*>(out + i * 2) = v;
+        out[i * 2] = v.x;
+        out[i * 2 + 1] = v.y;
     }
 }
 
@@ -193,12 +194,13 @@ __global__ __launch_bounds__(256) void b2h_masked_l1_seq_kernel(const float* __r
     int64_t n = n_frames ? n_frames[b] : T;
     n = n < 0 ? 0 : (n > T ? T : n);
     const int64_t cnt = n * nch;                          // floats of this sequence that count
-    const float2* p = reinterpret_cast<const float2*>(pred + b * (int64_t)T * nch);
-    const float2* t = reinterpret_cast<const float2*>(target + b * (int64_t)T * nch);
+    // pred and target as dwords: the metric entry points promise fp32 alignment only (the same sum, term for term)
+    const float* p = pred + b * (int64_t)T * nch;
+    const float* t = target + b * (int64_t)T * nch;
     const float* sc = WEIGHTED ? scores + b * (int64_t)T * (nch / 2) : nullptr;
     float acc = 0.f;
     for (int64_t i = threadIdx.x; i < cnt / 2; i += 256) { // one (frame, joint) per step
-        const float2 a = p[i], c = t[i];
+        const float2 a = make_float2(p[2 * i], p[2 * i + 1]), c = make_float2(t[2 * i], t[2 * i + 1]);
         if constexpr (WEIGHTED) {
             const float w = sc[i];
             acc += fabsf(__fmul_rn(a.x, w) - __fmul_rn(c.x, w)) + fabsf(__fmul_rn(a.y, w) - __fmul_rn(c.y, w));

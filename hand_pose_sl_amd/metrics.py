@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import _aligned
 
 
 def _l1(prediction, target, lengths, scores, return_per_sequence, what):
@@ -41,7 +42,8 @@ def _l1(prediction, target, lengths, scores, return_per_sequence, what):
     if scores is not None:
         sc = scores.to(device=p.device, dtype=torch.float32).contiguous()   # the reference moves them too (utils.py:439)
     if p.requires_grad and torch.is_grad_enabled():
-        loss, per_seq = _L1Fn.apply(p, t.detach(), nf, None if sc is None else sc.detach())
+        # the gradient kernels take pred and target on the 16-byte grid (the metric kernels read dwords)
+        loss, per_seq = _L1Fn.apply(_aligned(p), _aligned(t.detach()), nf, None if sc is None else sc.detach())
     else:
         loss, per_seq = _l1_forward(p.detach(), t, nf, sc)
     return (loss, per_seq) if return_per_sequence else loss

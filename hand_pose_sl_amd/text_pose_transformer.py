@@ -36,7 +36,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import NativeDropout, NativeModule, TrainFn, TrainRoutes, _ptrs
+from ._native import NativeDropout, NativeModule, TrainFn, TrainRoutes, _aligned, _ptrs
 from .transformer_enc import TENC_KERNELS, PositionalEncoding
 
 
@@ -205,7 +205,8 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
         """The inference kernels: b2h_tpt_forward, or b2h_tpt_forward_fused with fused = (flags, factor, n_frames)."""
         lib, dev = self._ensure_handle()
         tok = input_tokens.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
-        x = input_pose.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        # a composite model's rows are 168 or 232 bytes: pose[1:] of an odd T starts 8 bytes off the 16-byte grid
+        x = _aligned(input_pose.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous())
         B, S, T = tok.shape[0], tok.shape[1], x.shape[1]
         nf = None
         if fused is not None and fused[2] is not None:
@@ -253,8 +254,8 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
         if right_hand.dim() != 4 or tuple(right_hand.shape) != tuple(body.shape[:2]) + (21, 2):
             raise RuntimeError(f"expected right_hand of shape {tuple(body.shape[:2]) + (21, 2)}, got {tuple(right_hand.shape)}")
         lib, dev = self._ensure_handle()
-        b = body.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
-        h = right_hand.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        b = _aligned(body.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous())
+        h = _aligned(right_hand.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous())
         B, T = b.shape[0], b.shape[1]
         item = torch.empty((B, T, self.ninp // 2, 2), dtype=torch.float32, device=dev)
         flags = (_lib.PRE_CHEST_DIFF if dif_encoding else 0) | (_lib.PRE_NORMALIZE if normalize else 0)

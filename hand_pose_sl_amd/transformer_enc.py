@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._native import NativeDropout, NativeModule, TrainFn, TrainRoutes, _ptrs
+from ._native import NativeDropout, NativeModule, TrainFn, TrainRoutes, _aligned, _ptrs
 
 
 class PositionalEncoding(nn.Module):
@@ -182,7 +182,7 @@ class TransformerEnc(NativeDropout, TrainRoutes, NativeModule, nn.Module):
         if src.dim() != 4 or src.shape[2] * src.shape[3] != self.ninp:
             raise RuntimeError(f"expected input of shape (B, T, {self.ninp // 2}, 2), got {tuple(src.shape)}")
         dev = self._modules["pose2hidden_projection"]._parameters["weight"].device
-        x = src.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+        x = _aligned(src.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous())
         B, T = x.shape[0], x.shape[1]
         nf = None
         if flags & _lib.POST_MASK_TAIL:

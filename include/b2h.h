@@ -131,7 +131,7 @@ int b2h_forward_fused(b2h_model* m, const float* body, float* y, int64_t B, int6
 /* Target transform of the training item (right hand relative to the wrist):
  *   hand_out = (hand - body[:, 4]) / factor     WristDifference + Normalize,
  * steps/utils.py:194-201,180-190.  flags: bit0 wrist diff, bit1 normalize.
- *   body (B,T,12,2), hand / hand_out (B,T,21,2), all device fp32. */
+ *   body (B,T,12,2), hand / hand_out (B,T,21,2), all device fp32, no alignment beyond fp32's 4 bytes. */
 int b2h_target_transform(const float* body, const float* hand, float* hand_out, int64_t B,
                          int64_t T, int flags, float factor, void* stream);
 
@@ -139,7 +139,8 @@ int b2h_target_transform(const float* body, const float* hand, float* hand_out, 
  *   loss = mean_i( mean(|pred[i, :n_frames[i]] - target[i, :n_frames[i]]|) ),  i < B.
  * pred, target: device fp32 (B, T, 21, 2); n_frames: device int64 (B) or NULL (= T);
  * per_seq: device fp32 (B) scratch that receives the per-sequence means; loss: device fp32 (1).
- * A sequence with n_frames 0 contributes NaN, as torch's mean of an empty tensor does.
+ * A sequence with n_frames 0 contributes NaN, as torch's mean of an empty tensor does.  The float pointers of the four
+ * metric entry points need no alignment beyond fp32's 4 bytes, n_frames its int64's 8.
  * "Pixel distance" (L12Pixels, steps/utils.py:291-299) is loss / 21 * 1280 on the host. */
 int b2h_masked_l1(const float* pred, const float* target, const int64_t* n_frames, int64_t B,
                   int64_t T, float* per_seq, float* loss, void* stream);
@@ -196,7 +197,8 @@ int b2h_backward(b2h_model* m, const float* const* params, const float* x, const
  *   dpred[i, t < n_i] = (g / B) * sign(pred - target) / (n_i * 42),  0 at t >= n_i,
  * g = *dloss (device fp32 scalar: no host read); n_frames as b2h_masked_l1 (NULL = T, clamped to
  * [0, T] as slicing does); sign(0) = 0 as torch.nn.L1Loss has it.  A sequence with n_i = 0
- * contributes no gradient (its forward loss is NaN). */
+ * contributes no gradient (its forward loss is NaN).  pred, target and dpred of the four gradient entry points must be
+ * 16-byte aligned and dpred must overlap no input (B2H_ERR_INVALID); scores and dloss are fp32 (4 bytes), n_frames int64. */
 int b2h_masked_l1_backward(const float* pred, const float* target, const int64_t* n_frames, int64_t B,
                            int64_t T, const float* dloss, float* dpred, void* stream);
 /* dL/dpred of poderatedPoseL1 (steps/utils.py:431-452): with s = scores[i, t, joint],
@@ -245,7 +247,8 @@ int b2h_tenc_load_weights(b2h_tenc* m, const float* const* tensors, int count, i
 size_t b2h_tenc_workspace_bytes(const b2h_tenc* m, int64_t B, int64_t T);
 /* Replaces TransformerEnc.forward(src) (HandPoseModels.py:152-178): x (B,T,12,2) -> y (B,T,21,2),
  * device fp32.  T <= max_len (the reference's `src + pe[:T]` raises beyond it): B2H_ERR_SHAPE.
- * `workspace`: device memory of at least b2h_tenc_workspace_bytes(m, B, T), 16-byte aligned. */
+ * `workspace`: device memory of at least b2h_tenc_workspace_bytes(m, B, T).  x and the workspace must be 16-byte aligned
+ * (B2H_ERR_INVALID otherwise); y needs no alignment beyond its fp32's 4 bytes (its stores are buffer stores). */
 int b2h_tenc_forward(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, void* workspace,
                      size_t workspace_bytes, void* stream);
 
@@ -280,6 +283,7 @@ int b2h_tenc_forward_fused(b2h_tenc* m, const float* body, float* y, int64_t B, 
  *             pos (B, T, 24); then per layer: attn (B, 4, T, T) on the softmax probabilities,
  *             drop1 (B, T, 128) on out_proj's output, ff (B, T, 128) after linear1's ReLU,
  *             drop2 (B, T, 128) on linear2's output.
+ *           The masks need no alignment (they are bytes); those of b2h_dropout_masks are 16-byte aligned.
  * Like b2h_tenc_forward they are stream-ordered and asynchronous: none synchronises, allocates or reads
  * device memory on the host, so they can be captured into a HIP graph.  1 <= T <= max_len; x, y, dy, dx, the
  * saved buffer and the scratch must be 16-byte aligned and no output may overlap another operand
@@ -436,7 +440,8 @@ int b2h_tpt_build_item(const float* body, const float* right_hand, float* item, 
  *             per encoder layer: attn (B, 4, S, S), drop1, ff, drop2 (B, S, 128 each);
  *             per decoder layer: self_attn (B, 4, T, T), drop1 (B, T, 128), cross_attn (B, 4, T, S),
  *               drop2, ff, drop3 (B, T, 128 each).
- *           There is no embedding or positional mask: the reference never applies its positional encoders.
+ *           There is no embedding or positional mask: the reference never applies its positional encoders.  The
+ *           masks need no alignment (they are bytes).
  * 1 <= S <= 128 and 1 <= T <= B2H_TPT_MAX_FRAMES (B2H_ERR_SHAPE; the reference's trainer pads every item to
  * --max-frames 200, run.py:28).  For T <= 128 each decoder attention is one workgroup per (sequence, head) with the
  * whole score matrix in LDS; for T > 128 the decoder's two attentions and their backwards walk the keys and the
