@@ -114,6 +114,12 @@ SYMBOLS = {
     "b2h_build_batch": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp,
                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp,
                                        _vp, _vp, _vp, _vp]),
+    "b2h_epoch_plan": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                      ctypes.c_uint64, _vp, _vp, _vp]),
+    "b2h_build_batch_planned": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int64,
+                                               _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "b2h_epoch_record": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
     "b2h_model_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                       ctypes.POINTER(ctypes.c_int)]),
     "b2h_kernel_supported": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -28,6 +28,7 @@
 #include "kernel_adam.h"
 #include "kernel_build_batch.h"
 #include "kernel_dropout_masks.h"
+#include "kernel_epoch_plan.h"
 #include "kernel_train_attn_long.h"
 #include "kernel_train_attn_mfma.h"
 #include "kernel_train_linear_mfma.h"
@@ -2251,13 +2252,15 @@ int b2h_adam_step(float* const* params, const float* const* grads, float* const*
 } // extern "C"
 
 // ---- the training set on the device (kernel_build_batch.h) -----------------------------------------------------
-extern "C" {
+namespace {
 
-int b2h_build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
-                    const int64_t* tokens, int64_t S, const int64_t* utt, const int64_t* start, int64_t B, int64_t T,
-                    int predict, int flags, float factor, float* input_kp, float* target_kp, float* target_conf,
-                    int64_t* text_tokens, int64_t* n_frames, void* stream) {
-    if (B < 0 || T < 0 || n_utt < 0 || n_rows < 0) return fail(B2H_ERR_SHAPE, "negative shape");
+// b2h_build_batch (step NULL: utt and start hold B entries) and b2h_build_batch_planned (utt and start hold the n_plan
+// entries of an epoch's plan, *step selects B of them): the same checks in the same order, the same launch.
+int build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body, const int64_t* tokens,
+                int64_t S, const int64_t* utt, const int64_t* start, int64_t n_plan, const int64_t* step, bool planned,
+                int64_t B, int64_t T, int predict, int flags, float factor, float* input_kp, float* target_kp,
+                float* target_conf, int64_t* text_tokens, int64_t* n_frames, void* stream) {
+    if (B < 0 || T < 0 || n_utt < 0 || n_rows < 0 || n_plan < 0) return fail(B2H_ERR_SHAPE, "negative shape");
     if (n_body != 8 && n_body != 12) return fail(B2H_ERR_INVALID, "n_body must be 8 or 12");
     if (predict != B2H_PREDICT_RIGHT_HAND && predict != B2H_PREDICT_RIGHT_INDEX && predict != B2H_PREDICT_RIGHT_3FINGERS)
         return fail(B2H_ERR_INVALID, "predict must be a b2h_predict value");
@@ -2269,8 +2272,10 @@ int b2h_build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, i
     if (tokens && (S < 1 || S > 128)) return fail(B2H_ERR_INVALID, "1 <= S <= 128");
     if (B * T == 0) return B2H_OK;
     if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
-    if (n_rows > ((int64_t)1 << 40) || n_utt > ((int64_t)1 << 40)) return fail(B2H_ERR_SHAPE, "store too large");
+    if (n_rows > ((int64_t)1 << 40) || n_utt > ((int64_t)1 << 40) || n_plan > ((int64_t)1 << 40))
+        return fail(B2H_ERR_SHAPE, "store too large");
     if (!tokens) S = 0;
+    const size_t entries = planned ? (size_t)n_plan : (size_t)B;
     const int J = n_body + 42;
     const int ni = predict == B2H_PREDICT_RIGHT_HAND ? n_body : predict == B2H_PREDICT_RIGHT_INDEX ? 29 : 21;
     const int nt = predict == B2H_PREDICT_RIGHT_HAND ? 21 : predict == B2H_PREDICT_RIGHT_INDEX ? 4 : 12;
@@ -2278,14 +2283,17 @@ int b2h_build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, i
     // every operand: what the message calls it, where, how many bytes, whether the call may leave it out
     struct Op { const char* name; const void* p; size_t n; bool optional; };
     const Op read_only[] = {{"rows", rows, (size_t)n_rows * 3 * J * 4, n_rows == 0}, {"offsets", offsets, (size_t)(n_utt + 1) * 8, false},
-                            {"tokens", tokens, (size_t)n_utt * S * 8, true},   {"utt", utt, (size_t)B * 8, false},
-                            {"start", start, (size_t)B * 8, true}};
+                            {"tokens", tokens, (size_t)n_utt * S * 8, true},
+                            {planned ? "utt_plan" : "utt", utt, entries * 8, planned && n_plan == 0},
+                            {planned ? "start_plan" : "start", start, entries * 8, true},
+                            {"step", step, 8, !planned}};
+    const int n_ops[2] = {6, 5};
     const Op outs[] = {{"input_kp", input_kp, frames * ni * 8, false},       {"target_kp", target_kp, frames * nt * 8, false},
                        {"target_conf", target_conf, frames * nt * 4, true}, {"text_tokens", text_tokens, (size_t)B * S * 8, true},
                        {"n_frames", n_frames, (size_t)B * 8, false}};
-    for (const Op* list : {read_only, outs})
-        for (int i = 0; i < 5; ++i) {
-            const Op& o = list[i];
+    for (int l = 0; l < 2; ++l)
+        for (int i = 0; i < n_ops[l]; ++i) {
+            const Op& o = (l ? outs : read_only)[i];
             if (!o.p && !o.optional) return fail(B2H_ERR_INVALID, std::string(o.name) + " is NULL");
             if (misaligned(o.p, 8)) return fail(B2H_ERR_INVALID, std::string(o.name) + " must be 8-byte aligned");
         }
@@ -2295,21 +2303,104 @@ int b2h_build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, i
     for (const Op& o : read_only)
         if (o.p) in_spans.push_back({o.p, o.n, o.name});
     if (int rc = check_overlap(out_spans, in_spans)) return rc;
-    for (const Op* list : {read_only, outs})
-        for (int i = 0; i < 5; ++i)
-            if (list[i].p && list[i].n)
-                if (int rc = check_device_ptr(list[i].p, list[i].name)) return rc;
+    for (int l = 0; l < 2; ++l)
+        for (int i = 0; i < n_ops[l]; ++i) {
+            const Op& o = (l ? outs : read_only)[i];
+            if (o.p && o.n)
+                if (int rc = check_device_ptr(o.p, o.name)) return rc;
+        }
     BbArgs a;
     a.rows = rows; a.offsets = offsets; a.tokens = tokens; a.utt = utt; a.start = start;
     a.input_kp = input_kp; a.target_kp = target_kp; a.target_conf = target_conf; a.text_tokens = text_tokens;
     a.n_frames = n_frames;
     a.n_rows = n_rows; a.n_utt = n_utt; a.B = B; a.T = T; a.S = S;
     a.n_body = n_body; a.predict = predict; a.flags = flags; a.ni = ni; a.nt = nt; a.factor = factor;
+    a.step = planned ? step : nullptr; a.n_plan = n_plan; a.n_steps = planned ? (n_plan + B - 1) / B : 0;
     const int64_t lanes[5] = {(int64_t)frames * ni, (int64_t)frames * nt, target_conf ? (int64_t)frames * nt : 0, B * S, B};
     a.first[0] = 0;
     for (int s = 0; s < 5; ++s) a.first[s + 1] = a.first[s] + (lanes[s] + kBbThreads - 1) / kBbThreads;
     if (a.first[5] > 0x7fffffff) return fail(B2H_ERR_SHAPE, "shape too large");
     hipLaunchKernelGGL(b2h_build_batch_k, dim3((unsigned)a.first[5]), dim3(kBbThreads), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int b2h_build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                    const int64_t* tokens, int64_t S, const int64_t* utt, const int64_t* start, int64_t B, int64_t T,
+                    int predict, int flags, float factor, float* input_kp, float* target_kp, float* target_conf,
+                    int64_t* text_tokens, int64_t* n_frames, void* stream) {
+    return build_batch(rows, n_rows, offsets, n_utt, n_body, tokens, S, utt, start, 0, nullptr, false, B, T, predict, flags,
+                       factor, input_kp, target_kp, target_conf, text_tokens, n_frames, stream);
+}
+
+int b2h_build_batch_planned(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                            const int64_t* tokens, int64_t S, const int64_t* utt_plan, const int64_t* start_plan,
+                            int64_t n_plan, const int64_t* step, int64_t B, int64_t T, int predict, int flags, float factor,
+                            float* input_kp, float* target_kp, float* target_conf, int64_t* text_tokens, int64_t* n_frames,
+                            void* stream) {
+    return build_batch(rows, n_rows, offsets, n_utt, n_body, tokens, S, utt_plan, start_plan, n_plan, step, true, B, T,
+                       predict, flags, factor, input_kp, target_kp, target_conf, text_tokens, n_frames, stream);
+}
+
+// ---- an epoch's plan and its step word (kernel_epoch_plan.h) ---------------------------------------------------
+int b2h_epoch_plan(const int64_t* offsets, int64_t n_utt, int64_t T, int shuffle, int random_crop, uint64_t seed,
+                   uint64_t epoch, int64_t* utt_plan, int64_t* start_plan, void* stream) {
+    if (n_utt < 0 || T < 0) return fail(B2H_ERR_SHAPE, "negative shape");
+    if (n_utt > ((int64_t)1 << 30)) return fail(B2H_ERR_SHAPE, "store too large (a plan holds at most 2^30 utterances)");
+    if ((shuffle != 0 && shuffle != 1) || (random_crop != 0 && random_crop != 1))
+        return fail(B2H_ERR_INVALID, "shuffle and random_crop must be 0 or 1");
+    if (random_crop && !start_plan) return fail(B2H_ERR_INVALID, "start_plan is NULL (it may be only without random_crop)");
+    if (!utt_plan && n_utt > 0) return fail(B2H_ERR_INVALID, "utt_plan is NULL");
+    if (random_crop && !offsets && n_utt > 0) return fail(B2H_ERR_INVALID, "offsets is NULL");
+    if (!random_crop) offsets = nullptr;   // not read
+    const size_t plan = (size_t)n_utt * 8;
+    const struct { const char* name; const void* p; size_t n; } ops[3] = {
+        {"offsets", offsets, (size_t)(n_utt + 1) * 8}, {"utt_plan", utt_plan, plan}, {"start_plan", start_plan, plan}};
+    for (const auto& o : ops)
+        if (misaligned(o.p, 8)) return fail(B2H_ERR_INVALID, std::string(o.name) + " must be 8-byte aligned");
+    if (n_utt == 0) return B2H_OK;
+    std::vector<Span> out_spans = {{utt_plan, plan}}, in_spans;
+    if (start_plan) out_spans.push_back({start_plan, plan});
+    if (offsets) in_spans.push_back({offsets, ops[0].n, "offsets"});
+    if (int rc = check_overlap(out_spans, in_spans)) return rc;
+    for (const auto& o : ops)
+        if (o.p)
+            if (int rc = check_device_ptr(o.p, o.name)) return rc;
+    EpArgs a;
+    a.offsets = offsets; a.utt_plan = utt_plan; a.start_plan = start_plan;
+    a.n_utt = n_utt; a.T = T;
+    a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32);
+    a.epoch0 = (uint32_t)epoch; a.epoch1 = (uint32_t)(epoch >> 32);
+    a.h = 1;
+    while (((int64_t)1 << (2 * a.h)) < n_utt) ++a.h;
+    a.shuffle = shuffle; a.random_crop = random_crop;
+    const unsigned blocks = (unsigned)((n_utt + kEpThreads - 1) / kEpThreads);
+    hipLaunchKernelGGL(b2h_epoch_plan_k, dim3(blocks), dim3(kEpThreads), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+int b2h_epoch_record(const float* loss, float* losses, int64_t n_losses, int64_t* step, void* stream) {
+    if (n_losses < 0) return fail(B2H_ERR_SHAPE, "negative shape");
+    if (n_losses > ((int64_t)1 << 40)) return fail(B2H_ERR_SHAPE, "n_losses too large");
+    if (!loss) return fail(B2H_ERR_INVALID, "loss is NULL");
+    if (!losses && n_losses > 0) return fail(B2H_ERR_INVALID, "losses is NULL");
+    if (!step) return fail(B2H_ERR_INVALID, "step is NULL");
+    if (misaligned(loss, 4) || misaligned(losses, 4)) return fail(B2H_ERR_INVALID, "loss and losses must be 4-byte aligned");
+    if (misaligned(step, 8)) return fail(B2H_ERR_INVALID, "step must be 8-byte aligned");
+    const size_t bytes = (size_t)n_losses * 4;
+    std::vector<Span> out_spans = {{step, 8}};
+    if (bytes) out_spans.push_back({losses, bytes});
+    if (int rc = check_overlap(out_spans, {{loss, 4, "loss"}})) return rc;
+    if (int rc = check_device_ptr(loss, "loss")) return rc;
+    if (bytes)
+        if (int rc = check_device_ptr(losses, "losses")) return rc;
+    if (int rc = check_device_ptr(step, "step")) return rc;
+    hipLaunchKernelGGL(b2h_epoch_record_k, dim3(1), dim3(1), 0, (hipStream_t)stream, loss, losses, n_losses, step);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }

@@ -12,6 +12,10 @@
 // and n_frames one int64.  Every output word is written by exactly one lane; nothing is read outside the rows of
 // utt[b].  An id outside [0, n_utt), or offsets of it outside 0 <= lo <= hi <= n_rows, indexes nothing: that
 // sequence's floats become quiet NaNs, its tokens -1, its n_frames 0.  No LDS, no atomics; indices are 64-bit.
+//
+// b2h_build_batch_planned launches the same kernel with BbArgs::step set: utt and start are then the plan of a whole
+// epoch (kernel_epoch_plan.h) and sequence b reads entry *step * B + b of it; a step below 0 or an entry at or past
+// n_plan is an unknown utterance, so a replay past the end of the plan is loud.
 #pragma once
 #include "b2h_common.h"
 
@@ -35,18 +39,32 @@ struct BbArgs {
     int64_t first[6];         // first block of input_kp, target_kp, target_conf, text_tokens, n_frames; the block count
     int n_body, predict, flags, ni, nt;   // ni, nt: joints of an input / a target frame
     float factor;
+    // b2h_build_batch_planned: utt and start are an epoch's plan of n_plan entries and sequence b reads entry
+    // *step * B + b.  NULL for b2h_build_batch: entry b.
+    const int64_t* step;
+    int64_t n_plan, n_steps;  // n_steps = ceil(n_plan / B): the steps that have an entry
 };
+
+// The entry of utt / start that sequence b reads, or -1 for a planned build whose step has none for it.
+__device__ __forceinline__ int64_t bb_entry(const BbArgs& a, int64_t b) {
+    if (!a.step) return b;
+    const int64_t s = *a.step;                        // wave-uniform: one 8-byte scalar load
+    if (s < 0 || s >= a.n_steps) return -1;           // before the product: s * B cannot overflow below n_steps
+    const int64_t p = s * a.B + b;
+    return p < a.n_plan ? p : -1;
+}
 
 // The rows of sequence b: lo = first row of the window, len = rows of the utterance; false for an id the store lacks.
 __device__ __forceinline__ bool bb_window(const BbArgs& a, int64_t b, int64_t& lo, int64_t& len) {
-    const int64_t u = a.utt[b];
+    const int64_t e = bb_entry(a, b);
+    const int64_t u = e < 0 ? -1 : a.utt[e];
     if (u < 0 || u >= a.n_utt) return false;
     const int64_t r0 = a.offsets[u], r1 = a.offsets[u + 1];
     if (r0 < 0 || r1 < r0 || r1 > a.n_rows) return false;
     len = r1 - r0;
     int64_t s = 0;
     if (len > a.T) {          // select_jsons, text_pose_dataset.py:52-68; a shorter utterance starts at 0
-        s = a.start ? a.start[b] : 0;
+        s = a.start ? a.start[e] : 0;
         s = s < 0 ? 0 : (s > len - a.T ? len - a.T : s);
     }
     lo = r0 + s;
@@ -99,7 +117,8 @@ __global__ __launch_bounds__(kBbThreads) void b2h_build_batch_k(const BbArgs a) 
     } else if (seg == 3) {
         if (i >= a.B * a.S) return;
         const int64_t b = i / a.S, s = i - b * a.S;
-        const int64_t u = a.utt[b];
+        const int64_t e = bb_entry(a, b);
+        const int64_t u = e < 0 ? -1 : a.utt[e];
         a.text_tokens[i] = (u >= 0 && u < a.n_utt) ? a.tokens[u * a.S + s] : -1;
     } else {
         if (i >= a.B) return;

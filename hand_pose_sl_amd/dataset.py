@@ -20,6 +20,7 @@ from . import _lib, openpose
 
 SELECTIONS = ("randomcrop", "first")
 PADS = ("zeros", "frame0")
+PLAN_SOURCES = ("torch", "native")
 # (input joints, target joints) of each `--predict` choice (run.py:91-102), the input of right_hand being the body
 _JOINTS = {"right_index": (29, 4), "right_3fingers": (21, 12)}
 
@@ -114,12 +115,21 @@ class DeviceLoader:
     The order is sequential like run.py's loaders (`shuffle` draws a torch.randperm, with `generator` if given);
     "randomcrop" draws the crop starts with torch on the device, so they follow torch.manual_seed; "first" crops at 0.
     `pad`: "zeros" as TextPoseH5Dataset pads, "frame0" as the JSON datasets do.  `build(utt, start, out)` is the
-    explicit form."""
+    explicit form.
+
+    `plan_epoch()` returns the order and the crop starts of a whole epoch as two device tensors, and
+    `build_planned(plan, step_word, out)` builds the batch a device step word selects from them: the two halves of an
+    epoch of captured steps (`GraphTrainer`).  `plan_source` "torch" (the default) draws the plan as `__iter__` draws,
+    "native" with b2h_epoch_plan (kernel_epoch_plan.h) from (`seed`, epoch number) alone, and `__iter__` then iterates
+    that plan too; torch's generators are not touched."""
 
     def __init__(self, ds, batch_size, max_frames, selection="randomcrop", predict="right_hand", dif_encoding=True,
-                 normalize=True, factor=1280, pad="zeros", shuffle=False, drop_last=False, generator=None):
+                 normalize=True, factor=1280, pad="zeros", shuffle=False, drop_last=False, generator=None,
+                 plan_source="torch", seed=0):
         if not isinstance(ds, DeviceDataset):
             raise TypeError("ds must be a DeviceDataset")
+        if plan_source not in PLAN_SOURCES:
+            raise ValueError(f"plan_source must be one of {PLAN_SOURCES}, got {plan_source!r}")
         if batch_size < 1 or max_frames < 1:
             raise ValueError("batch_size and max_frames must be >= 1")
         if selection not in SELECTIONS:
@@ -134,8 +144,10 @@ class DeviceLoader:
             raise ValueError("factor must be > 0")
         self.ds, self.batch_size, self.max_frames = ds, int(batch_size), int(max_frames)
         self.selection, self.predict, self.shuffle, self.drop_last, self.generator = selection, predict, shuffle, drop_last, generator
+        self.plan_source, self.seed = plan_source, int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.epochs_planned = 0   # the epoch number of the next native plan
         self.factor = float(factor)
-        self.flags = ((_lib.BATCH_DIF_ENCODING if dif_encoding else 0) | (_lib.BATCH_NORMALIZE if normalize else 0) |
+        self.flags =((_lib.BATCH_DIF_ENCODING if dif_encoding else 0) | (_lib.BATCH_NORMALIZE if normalize else 0) |
                       (_lib.BATCH_PAD_FRAME0 if pad == "frame0" else 0))
         self.joints = (ds.n_body, 21) if predict == "right_hand" else _JOINTS[predict]
         # the largest start a random crop may draw, per utterance (select_jsons: random.randint(0, len - n))
@@ -198,9 +210,75 @@ class DeviceLoader:
         u = torch.rand(room.shape, dtype=torch.float64, device=room.device)
         return torch.minimum((u * (room + 1).to(torch.float64)).to(torch.int64), room)
 
-    def __iter__(self):
-        n, dev = len(self.ds), self.ds.device
+    def plan_epoch(self, epoch=None):
+        """(utt_plan, start_plan) of one epoch: device int64 tensors of len(ds) entries, the utterance and the crop
+        start of every sequence in the order the batches take them; start_plan is None unless the selection is
+        "randomcrop".  "torch": exactly what `__iter__` draws, in its order -- the randperm, then `draw_starts` batch
+        by batch (the entries of a dropped last batch start at 0, undrawn) --, so from one generator state an eager
+        epoch and a planned one see the same batches.  "native": one b2h_epoch_plan launch keyed by (seed, epoch);
+        `epoch` None takes the loader's own count and advances it."""
+        n, dev, B = len(self.ds), self.ds.device, self.batch_size
+        crop = self.selection == "randomcrop"
+        if self.plan_source == "native":
+            if epoch is None:
+                epoch, self.epochs_planned = self.epochs_planned, self.epochs_planned + 1
+            utt = torch.empty(n, dtype=torch.int64, device=dev)
+            start = torch.empty(n, dtype=torch.int64, device=dev) if crop else None
+            with _lib.on_device(dev):
+                st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                _lib.check(_lib.load().b2h_epoch_plan(_ptr(self.ds.offsets), n, self.max_frames, int(bool(self.shuffle)),
+                                                      int(crop), self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF, _ptr(utt),
+                                                      _ptr(start), st))
+            return utt, start
         order = (torch.randperm(n, generator=self.generator).to(dev) if self.shuffle else
+                 torch.arange(n, dtype=torch.int64, device=dev))
+        if not crop:
+            return order, None
+        drawn = [self.draw_starts(order[i * B:(i + 1) * B]) for i in range(len(self))]
+        drawn.append(torch.zeros(n - sum(d.shape[0] for d in drawn), dtype=torch.int64, device=dev))
+        return order, torch.cat(drawn)
+
+    def build_planned(self, plan, step_word, out):
+        """The planned counterpart of `build`: the batch of `out`'s B sequences, entries *step_word * B .. + B - 1 of
+        `plan` = (utt_plan, start_plan or None) (b2h_build_batch_planned); `step_word` is a one-element int64 tensor on
+        the device.  One kernel launch and nothing else, so a captured graph replays it with whatever the step word
+        holds by then; entries past the plan's end come out as unknown utterances (NaN, -1, 0).  Returns `out`."""
+        ds, dev = self.ds, self.ds.device
+        utt, start = plan
+        for name, t in (("utt_plan", utt), ("step_word", step_word)) + ((("start_plan", start),) if start is not None else ()):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != dev or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous 1-d int64 tensor on {dev}")
+        if start is not None and start.shape != utt.shape:
+            raise ValueError(f"start_plan must be ({utt.shape[0]},), got {tuple(start.shape)}")
+        if step_word.numel() != 1:
+            raise ValueError("step_word must hold one element")
+        nf = out.get("n_frames") if isinstance(out, dict) else None
+        if nf is None or nf.dim() != 1:
+            raise ValueError("out must be a batch from empty_batch() or build()")
+        B = nf.shape[0]
+        for k, (shape, dtype) in self._spec(B).items():
+            t = out.get(k)
+            if t is None or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"out[{k!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        tok = ds.tokens
+        with _lib.on_device(dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(_lib.load().b2h_build_batch_planned(
+                _ptr(ds.rows), ds.rows.shape[0], _ptr(ds.offsets), len(ds), ds.n_body, _ptr(tok),
+                0 if tok is None else tok.shape[1], _ptr(utt), _ptr(start), utt.shape[0], _ptr(step_word), B, self.max_frames,
+                _lib.PREDICT[self.predict], self.flags, self.factor, _ptr(out["input_kp"]), _ptr(out["target_kp"]),
+                _ptr(out["target_conf"]), _ptr(out.get("text_tokens")) if tok is not None else None, _ptr(out["n_frames"]), st))
+        return out
+
+    def __iter__(self):
+        if self.plan_source == "native":
+            utt, start = self.plan_epoch()
+            for i in range(len(self)):
+                sl = slice(i * self.batch_size, (i + 1) * self.batch_size)
+                yield self.build(utt[sl], None if start is None else start[sl])
+            return
+        n, dev = len(self.ds), self.ds.device
+        order =(torch.randperm(n, generator=self.generator).to(dev) if self.shuffle else
                  torch.arange(n, dtype=torch.int64, device=dev))
         for i in range(len(self)):
             utt = order[i * self.batch_size:(i + 1) * self.batch_size]

@@ -639,6 +639,56 @@ int b2h_build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, i
                     int predict, int flags, float factor, float* input_kp, float* target_kp, float* target_conf,
                     int64_t* text_tokens, int64_t* n_frames, void* stream);
 
+/* A captured epoch: its plan, the planned batch build and the step word -----------
+ * What torch.randperm and the per-batch crop draws give the eager loop (run.py:135 `shuffle`, select_jsons,
+ * text_pose_dataset.py:52-68), for a whole epoch from one launch (kernel_epoch_plan.h), so that a training step captured
+ * into a HIP graph is replayed through an epoch with no host work in between: b2h_epoch_plan once per epoch, then per
+ * step b2h_build_batch_planned ... b2h_adam_step, b2h_epoch_record.
+ *
+ * b2h_epoch_plan writes utt_plan (n_utt) int64 and start_plan (n_utt) int64 (NULL allowed when random_crop is 0, and
+ * then meaning 0; given without random_crop it is filled with zeros).  Every entry is a pure function of its index:
+ *   utt_plan[i]   = i without shuffle.  With shuffle, perm(i): a 4-round balanced Feistel network over [0, 2^(2h)), h
+ *                   the smallest value >= 1 with 2^(2h) >= n_utt, re-applied while the value is >= n_utt (cycle
+ *                   walking), a permutation of [0, n_utt) for every (seed, epoch).  One pass over x, mask = 2^h - 1:
+ *                   L = x >> h, R = x & mask; four times, r = 0 .. 3: (L, R) = (R, L ^ (P(R, 1 + r) & mask));
+ *                   x = L << h | R.
+ *   start_plan[i] = the crop start of utterance u = utt_plan[i]: with len = offsets[u+1] - offsets[u] and
+ *                   room = max(len - T, 0), floor(P(i, 0) * (room + 1) / 2^32): uniform in [0, room], 0 for an
+ *                   utterance that fits.  The meaning of DeviceLoader.draw_starts, with other bits, as the native
+ *                   dropout masks relate to torch's.
+ *   P(c, tag)     = output word 0 of the Philox4x32-10 block (b2h_dropout_masks' generator) with counter
+ *                   (c, tag, epoch lo, epoch hi) and key (seed lo, seed hi): tags 1 .. 4 are the Feistel rounds, tag 0
+ *                   the crop draws.
+ * offsets is the store's (n_utt + 1) int64 array, read only with random_crop (it may be NULL otherwise).  One launch,
+ * one lane per entry, no sort, no atomics, no LDS; stream-ordered, asynchronous, allocates nothing and reads no device
+ * memory on the host, so it can be captured.  B2H_ERR_INVALID, before any device work: shuffle or random_crop not 0 or
+ * 1, utt_plan NULL, start_plan or offsets NULL with random_crop, a pointer not 8-byte aligned, utt_plan, start_plan and
+ * offsets overlapping, a pointer that is not memory of the current device.  B2H_ERR_SHAPE: n_utt or T negative,
+ * n_utt > 2^30.  n_utt == 0 is a no-op (B2H_OK). */
+int b2h_epoch_plan(const int64_t* offsets, int64_t n_utt, int64_t T, int shuffle, int random_crop, uint64_t seed,
+                   uint64_t epoch, int64_t* utt_plan, int64_t* start_plan, void* stream);
+
+/* b2h_build_batch over a plan: utt_plan and start_plan (n_plan entries each; start_plan NULL = 0) take the place of utt
+ * and start, and sequence b reads entry p = *step * B + b, `step` a device int64 word that is only read.  If *step < 0
+ * or p >= n_plan the sequence is built as an unknown utterance -- quiet NaN floats, tokens -1, n_frames 0 -- so a
+ * replay past the end of the plan is loud, never a stale batch; the last step of a plan that is no multiple of B has
+ * such sequences behind its entries.  Everything else, the launch included (the same kernel, one extra wave-uniform
+ * 8-byte load per thread), is b2h_build_batch's; so are the refusals, which name utt_plan, start_plan and step, plus
+ * B2H_ERR_SHAPE for n_plan < 0 or > 2^40.  utt_plan may be NULL when n_plan is 0. */
+int b2h_build_batch_planned(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                            const int64_t* tokens, int64_t S, const int64_t* utt_plan, const int64_t* start_plan,
+                            int64_t n_plan, const int64_t* step, int64_t B, int64_t T, int predict, int flags, float factor,
+                            float* input_kp, float* target_kp, float* target_conf, int64_t* text_tokens, int64_t* n_frames,
+                            void* stream);
+
+/* The end of a captured step: one work-item reads s = *step, stores *loss to losses[s] if 0 <= s < n_losses, and in
+ * every case stores *step = s + 1.  Stream-ordered after the Adam update it is the only writer of the step word inside
+ * a step (no atomics), and the per-batch losses stay on the device until the epoch's one copy.  loss, losses: device
+ * fp32, 4-byte aligned (losses may be NULL when n_losses is 0); step: device int64, 8-byte aligned.  Allocates nothing,
+ * can be captured.  B2H_ERR_INVALID, before any device work: a NULL or misaligned pointer, step overlapping loss or
+ * losses, loss inside losses, a pointer that is not memory of the current device.  B2H_ERR_SHAPE: n_losses negative. */
+int b2h_epoch_record(const float* loss, float* losses, int64_t n_losses, int64_t* step, void* stream);
+
 /* Introspection / measurement -------------------------------------------- */
 
 /* conv_channels, pos_emb and whether weights are loaded. */

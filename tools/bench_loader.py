@@ -16,7 +16,16 @@ Context only: there is no speed bar; a "faster" is claimed only where the ranges
 The store is seeded: `utterances` HDF5-style utterances (8 body joints) of T / 2 .. 3 T frames, random crops.
     python tools/bench_loader.py                 B x S x T = 128 x 40 x 200, the trainer's default batch
     python tools/bench_loader.py 128 40 100      the datasets' 100 frames
-    python tools/bench_loader.py [B=128] [S=40] [T=200] [reps=5] [steps=8] [out.json]"""
+    python tools/bench_loader.py [B=128] [S=40] [T=200] [reps=5] [steps=8] [out.json] [arm=feed]
+
+The captured arm (`arm` = captured:tpt, captured:tenc or captured:conv) measures something else
+with the same store: hps.train_epoch against hps.GraphTrainer.epoch() over the same loader, model and optimizer, in
+alternating runs of `steps` steps after a warm-up of each (the trainer's eager first step and its capture are in the
+warm-up), wall time per step; tpt is the model above, tenc TransformerEnc(24, 4, 128, 42, 4) with MFMA attention and
+Linears and native masks, conv ConvModel(30), the last two on a 12-joint store.  It also times the plan of an epoch over
+32 768 utterances: one b2h_epoch_plan launch (back-to-back between HIP events, and one `plan_epoch()` call to the
+synchronise) against the torch-drawn plan of the same loader.  `arm` = eager:<model> runs only the eager epochs, for a
+kernel trace of the eager step."""
 import json
 import os
 import random
@@ -37,8 +46,12 @@ S = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 200
 REPS = int(sys.argv[4]) if len(sys.argv) > 4 else 5
 STEPS = int(sys.argv[5]) if len(sys.argv) > 5 else 8
-OUT = sys.argv[6] if len(sys.argv) > 6 else None
-N_TOKENS, L, P, LR, N_BODY, BUILD_ITERS = 1000, 4, 0.1, 2e-4, 8, 200
+OUT = sys.argv[6] if len(sys.argv) > 6 and sys.argv[6] != "-" else None
+ARM, _, MODEL = (sys.argv[7] if len(sys.argv) > 7 else "feed").partition(":")
+if ARM not in ("feed", "captured", "eager") or (ARM != "feed" and MODEL not in ("tpt", "tenc", "conv")):
+    sys.exit("arm must be feed, captured:tpt|tenc|conv or eager:tpt|tenc|conv")
+N_TOKENS, L, P, LR, BUILD_ITERS = 1000, 4, 0.1, 2e-4, 200
+N_BODY = 12 if MODEL in ("tenc", "conv") else 8
 if not torch.cuda.is_available():
     sys.exit("bench_loader.py measures on the GPU; none is visible")
 dev = torch.device("cuda:0")
@@ -61,6 +74,91 @@ ds = hps.DeviceDataset(rows, offsets, N_BODY, tokens, device=dev)
 loader = hps.DeviceLoader(ds, B, T, selection="randomcrop")
 out = {"B": B, "S": S, "T": T, "n_body": N_BODY, "reps": REPS, "steps": STEPS, "utterances": U, "store_rows": int(offsets[-1]),
        "store_MB": rows.numel() * 4 / 1e6, "model": {"n_enc": L, "n_dec": L, "n_tokens": N_TOKENS, "dropout": P}}
+
+
+def finish():
+    line = json.dumps(out)
+    print(line)
+    if OUT:
+        os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+        with open(OUT, "w") as f:
+            f.write(line + "\n")
+
+
+# ---- the captured arm: train_epoch against GraphTrainer.epoch(), alternating --------------------------------------------
+def captured_arm():
+    torch.manual_seed(0)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)
+        if MODEL == "tpt":
+            m = hps.TextPoseTransformer(N_TOKENS, N_BODY, 2, 4, 128, 42, L, L, dropout=P)
+        elif MODEL == "tenc":
+            m = hps.TransformerEnc(24, 4, 128, 42, L, dropout=P)
+        else:
+            m = hps.ConvModel(30, "ReLU", False)
+    m = m.to(dev).train()
+    if MODEL != "conv":
+        m.set_train_kernels("mfma").set_train_linear("mfma").set_dropout_source("native", seed=0)
+    opt = hps.Adam(m.parameters(), lr=LR)
+    crit = hps.maskedPoseL1()
+    trainer = hps.GraphTrainer(m, loader, opt, crit)
+    out["arm"], out["model"] = ARM, {"tpt": out["model"], "tenc": {"nlayers": L, "dropout": P}, "conv": {"conv_channels": 30}}[MODEL]
+    out["model"]["name"] = MODEL
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()                                                  # either epoch ends in its one host synchronisation
+        return (time.perf_counter() - t0) * 1e3 / STEPS
+
+    eager = lambda: hps.train_epoch(m, loader, crit, opt)
+    timed(eager)                                              # warm-up: allocators, the optimizer state
+    if ARM == "eager":
+        out["epoch_step_ms"] = {"what": f"wall ms per step of hps.train_epoch over {STEPS} batches",
+                                "eager": stats([timed(eager) for _ in range(REPS)])}
+        return finish()
+    timed(trainer.epoch), timed(trainer.epoch)                # warm-up: the eager first step, the capture
+    runs = {"eager": [], "captured": []}
+    for _ in range(REPS):
+        runs["eager"].append(timed(eager))
+        runs["captured"].append(timed(trainer.epoch))
+    out["epoch_step_ms"] = {"what": f"wall ms per step over epochs of {STEPS} steps, hps.train_epoch and hps.GraphTrainer.epoch() "
+                                    "in alternating runs, same model, optimizer and loader",
+                            "eager": stats(runs["eager"]), "captured": stats(runs["captured"]), "eager_runs": runs["eager"],
+                            "captured_runs": runs["captured"], "captures": trainer.captures, "replays": trainer.replays,
+                            "ranges_separate": max(runs["captured"]) < min(runs["eager"]) or max(runs["eager"]) < min(runs["captured"])}
+    # the plan of an epoch over 32 768 utterances of 1 .. 3 frames at T = 1: native launch against the torch-drawn plan
+    n = 32768
+    g = torch.Generator().manual_seed(1)
+    lens = torch.randint(1, 4, (n,), generator=g)
+    offs = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(lens, 0)])
+    big = hps.DeviceDataset(torch.zeros((int(offs[-1]), 3 * J)), offs, N_BODY, device=dev)
+    plans = {}
+    for source in ("native", "torch"):
+        ld = hps.DeviceLoader(big, 128, 1, selection="randomcrop", shuffle=True, plan_source=source)
+        ld.plan_epoch()
+        plans[source + "_plan_epoch_wall_ms"] = stats([timed(lambda: (ld.plan_epoch(), torch.cuda.synchronize())) * STEPS for _ in range(max(REPS, 5))])
+        if source == "native":
+            ms = []
+            for _ in range(REPS):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(BUILD_ITERS):
+                    ld.plan_epoch(epoch=0)
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1) / BUILD_ITERS)
+            plans["native_launch_ms"] = stats(ms)
+    plans["what"] = (f"the plan of {n} utterances, shuffled with random crops: wall ms of one plan_epoch() call up to a "
+                     f"synchronise, and {BUILD_ITERS} back-to-back b2h_epoch_plan calls (each with its two torch.empty) "
+                     "between HIP events, ms per call")
+    out["plan"] = plans
+    finish()
+
+
+if ARM != "feed":
+    captured_arm()
+    sys.exit(0)
 
 
 # ---- the host path -----------------------------------------------------------------------------------------------------
@@ -144,9 +242,4 @@ out["epoch_step_ms"] = {"what": f"wall ms per step of hps.train_epoch over {STEP
                         "device_loader": stats(fed["device"]), "host_path": stats(fed["host"]),
                         "device_loader_runs": fed["device"], "host_path_runs": fed["host"],
                         "ranges_separate": max(fed["device"]) < min(fed["host"]) or max(fed["host"]) < min(fed["device"])}
-line = json.dumps(out)
-print(line)
-if OUT:
-    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
-    with open(OUT, "w") as f:
-        f.write(line + "\n")
+finish()
