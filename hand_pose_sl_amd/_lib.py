@@ -32,6 +32,9 @@ PREDICT_NINP = {58: "right_index", 42: "right_3fingers"}
 # enum b2h_batch_flags (b2h_build_batch)
 BATCH_DIF_ENCODING, BATCH_NORMALIZE, BATCH_PAD_FRAME0 = 1, 2, 4
 
+# enum b2h_coverage (b2h_window_plan), by the names of window_plan / predict_dataset
+COVERAGE = {"all": 0, "first": 1}
+
 # enum b2h_train_kernel (b2h_tpt_set_train_kernel, b2h_tpt_set_train_linear and their b2h_tenc_* twins), by the names
 # of set_train_kernels / set_train_linear of TextPoseTransformer and TransformerEnc
 TRAIN_KERNELS = {"valu": 0, "mfma": 1}
@@ -120,6 +123,12 @@ SYMBOLS = {
                                                _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     "b2h_epoch_record": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
+    "b2h_window_plan": (ctypes.c_int64, [_i64p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _i64p, _i64p, _i64p,
+                                         ctypes.c_int64]),
+    "b2h_scatter_rows": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64,
+                                        ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, ctypes.c_float, _vp,
+                                        _vp]),
+    "b2h_joint_error": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "b2h_model_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                       ctypes.POINTER(ctypes.c_int)]),
     "b2h_kernel_supported": (ctypes.c_int, [_vp, ctypes.c_int]),

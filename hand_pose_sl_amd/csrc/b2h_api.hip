@@ -27,6 +27,7 @@
 #include "kernel_attn_long.h"
 #include "kernel_adam.h"
 #include "kernel_build_batch.h"
+#include "kernel_scatter_rows.h"
 #include "kernel_dropout_masks.h"
 #include "kernel_epoch_plan.h"
 #include "kernel_train_attn_long.h"
@@ -2254,12 +2255,9 @@ int b2h_adam_step(float* const* params, const float* const* grads, float* const*
 // ---- the training set on the device (kernel_build_batch.h) -----------------------------------------------------
 namespace {
 
-// b2h_build_batch (step NULL: utt and start hold B entries) and b2h_build_batch_planned (utt and start hold the n_plan
-// entries of an epoch's plan, *step selects B of them): the same checks in the same order, the same launch.
-int build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body, const int64_t* tokens,
-                int64_t S, const int64_t* utt, const int64_t* start, int64_t n_plan, const int64_t* step, bool planned,
-                int64_t B, int64_t T, int predict, int flags, float factor, float* input_kp, float* target_kp,
-                float* target_conf, int64_t* text_tokens, int64_t* n_frames, void* stream) {
+// The store and batch description b2h_build_batch and b2h_scatter_rows share: the first refusals of both, in this order.
+int batch_description_refusal(int64_t n_rows, int64_t n_utt, int n_body, int64_t n_plan, int64_t B, int64_t T, int predict,
+                              int flags, float factor) {
     if (B < 0 || T < 0 || n_utt < 0 || n_rows < 0 || n_plan < 0) return fail(B2H_ERR_SHAPE, "negative shape");
     if (n_body != 8 && n_body != 12) return fail(B2H_ERR_INVALID, "n_body must be 8 or 12");
     if (predict != B2H_PREDICT_RIGHT_HAND && predict != B2H_PREDICT_RIGHT_INDEX && predict != B2H_PREDICT_RIGHT_3FINGERS)
@@ -2268,6 +2266,16 @@ int build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64
         return fail(B2H_ERR_INVALID, "right_index and right_3fingers items need n_body = 12 (no model takes 25 or 17 joints)");
     if (flags & ~(kBbDif | kBbNorm | kBbPadFrame0)) return fail(B2H_ERR_INVALID, "unknown flag bits (only B2H_BATCH_* apply)");
     if ((flags & kBbNorm) && !(factor > 0.f)) return fail(B2H_ERR_INVALID, "factor must be > 0");
+    return B2H_OK;
+}
+
+// b2h_build_batch (step NULL: utt and start hold B entries) and b2h_build_batch_planned (utt and start hold the n_plan
+// entries of an epoch's plan, *step selects B of them): the same checks in the same order, the same launch.
+int build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body, const int64_t* tokens,
+                int64_t S, const int64_t* utt, const int64_t* start, int64_t n_plan, const int64_t* step, bool planned,
+                int64_t B, int64_t T, int predict, int flags, float factor, float* input_kp, float* target_kp,
+                float* target_conf, int64_t* text_tokens, int64_t* n_frames, void* stream) {
+    if (int rc = batch_description_refusal(n_rows, n_utt, n_body, n_plan, B, T, predict, flags, factor)) return rc;
     if (!tokens != !text_tokens) return fail(B2H_ERR_INVALID, "tokens and text_tokens go together: both or neither");
     if (tokens && (S < 1 || S > 128)) return fail(B2H_ERR_INVALID, "1 <= S <= 128");
     if (B * T == 0) return B2H_OK;
@@ -2402,6 +2410,119 @@ int b2h_epoch_record(const float* loss, float* losses, int64_t n_losses, int64_t
     if (int rc = check_device_ptr(step, "step")) return rc;
     hipLaunchKernelGGL(b2h_epoch_record_k, dim3(1), dim3(1), 0, (hipStream_t)stream, loss, losses, n_losses, step);
     HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+// ---- whole-store inference: the window plan, the row write-back, the joint error (kernel_scatter_rows.h) -------
+int64_t b2h_window_plan(const int64_t* offsets, int64_t n_utt, int64_t T, int coverage, int64_t* utt_plan,
+                        int64_t* start_plan, int64_t* skip_plan, int64_t capacity) {
+    const auto refuse = [](const char* why) {
+        (void)fail(B2H_ERR_INVALID, why);
+        return (int64_t)-1;
+    };
+    if (T < 1) return refuse("T must be >= 1");
+    if (n_utt < 0 || capacity < 0) return refuse("negative shape");
+    if (coverage != B2H_COVER_ALL && coverage != B2H_COVER_FIRST) return refuse("coverage must be a b2h_coverage value");
+    if (!offsets && n_utt > 0) return refuse("offsets is NULL");
+    if (n_utt > 0 && offsets[0] < 0) return refuse("offsets must ascend from offsets[0] >= 0");
+    for (int64_t u = 0; u < n_utt; ++u)
+        if (offsets[u + 1] < offsets[u]) return refuse("offsets must ascend from offsets[0] >= 0");
+    int64_t count = 0;
+    for (int64_t u = 0; u < n_utt; ++u) {
+        const int64_t L = offsets[u + 1] - offsets[u];
+        if (L == 0) continue;
+        const int64_t k = (coverage == B2H_COVER_FIRST || L <= T) ? 1 : (L + T - 1) / T;
+        for (int64_t i = 0; i < k; ++i, ++count) {
+            if (count >= capacity) continue;
+            if (!utt_plan || !start_plan || !skip_plan) return refuse("utt_plan, start_plan or skip_plan is NULL");
+            const bool last = k > 1 && i == k - 1;    // a full window that ends with the utterance
+            utt_plan[count] = u;
+            start_plan[count] = last ? L - T : i * T;
+            skip_plan[count] = last ? k * T - L : 0;
+        }
+    }
+    return count;
+}
+
+int b2h_scatter_rows(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                     const int64_t* utt, const int64_t* start, const int64_t* skip, int64_t B, int64_t T, int predict,
+                     int flags, float factor, const float* pred, float conf, float* rows_out, void* stream) {
+    if (int rc = batch_description_refusal(n_rows, n_utt, n_body, 0, B, T, predict, flags, factor)) return rc;
+    if (!std::isfinite(conf)) return fail(B2H_ERR_INVALID, "conf must be finite");
+    if (B * T == 0) return B2H_OK;
+    if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
+    if (n_rows > ((int64_t)1 << 40) || n_utt > ((int64_t)1 << 40)) return fail(B2H_ERR_SHAPE, "store too large");
+    const int J = n_body + 42;
+    const int nt = predict == B2H_PREDICT_RIGHT_HAND ? 21 : predict == B2H_PREDICT_RIGHT_INDEX ? 4 : 12;
+    const size_t store = (size_t)n_rows * 3 * J * 4;
+    struct Op { const char* name; const void* p; size_t n; bool optional, out; };
+    const Op ops[] = {{"rows", rows, store, n_rows == 0, false},  {"offsets", offsets, (size_t)(n_utt + 1) * 8, false, false},
+                      {"utt", utt, (size_t)B * 8, false, false},  {"start", start, (size_t)B * 8, true, false},
+                      {"skip", skip, (size_t)B * 8, true, false}, {"pred", pred, (size_t)B * T * nt * 8, false, false},
+                      {"rows_out", rows_out, store, n_rows == 0, true}};
+    for (const Op& o : ops) {
+        if (!o.p && !o.optional) return fail(B2H_ERR_INVALID, std::string(o.name) + " is NULL");
+        if (misaligned(o.p, 8)) return fail(B2H_ERR_INVALID, std::string(o.name) + " must be 8-byte aligned");
+    }
+    std::vector<Span> out_spans, in_spans;
+    for (const Op& o : ops)
+        if (o.p) (o.out ? out_spans : in_spans).push_back({o.p, o.n, o.name});
+    if (int rc = check_overlap(out_spans, in_spans)) return rc;
+    for (const Op& o : ops)
+        if (o.p && o.n)
+            if (int rc = check_device_ptr(o.p, o.name)) return rc;
+    SrArgs a = {};
+    a.w.rows = rows; a.w.offsets = offsets; a.w.utt = utt; a.w.start = start;
+    a.w.n_rows = n_rows; a.w.n_utt = n_utt; a.w.B = B; a.w.T = T;
+    a.w.n_body = n_body; a.w.predict = predict; a.w.flags = flags; a.w.nt = nt; a.w.factor = factor;
+    a.skip = skip; a.pred = pred; a.rows_out = rows_out; a.conf = conf;
+    const int64_t blocks = (B * T * nt + kBbThreads - 1) / kBbThreads;
+    if (blocks > 0x7fffffff) return fail(B2H_ERR_SHAPE, "shape too large");
+    hipLaunchKernelGGL(b2h_scatter_rows_k, dim3((unsigned)blocks), dim3(kBbThreads), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+int b2h_joint_error(const float* rows_pred, const float* rows_true, int64_t n_rows, const int64_t* offsets, int64_t n_utt,
+                    int n_body, float* utt_sum, int32_t* utt_count, double* total_sum, int64_t* total_count, void* stream) {
+    if (n_rows < 0 || n_utt < 0) return fail(B2H_ERR_SHAPE, "negative shape");
+    if (n_body != 8 && n_body != 12) return fail(B2H_ERR_INVALID, "n_body must be 8 or 12");
+    if (!total_sum != !total_count) return fail(B2H_ERR_INVALID, "total_sum and total_count go together: both or neither");
+    if (n_rows > ((int64_t)1 << 40) || n_utt > ((int64_t)1 << 30)) return fail(B2H_ERR_SHAPE, "store too large");
+    if (n_utt == 0 && !total_sum) return B2H_OK;
+    const size_t store = (size_t)n_rows * 3 * (n_body + 42) * 4, cells = (size_t)n_utt * kJeJoints;
+    struct Op { const char* name; const void* p; size_t n; uintptr_t align; bool optional, out; };
+    const Op ops[] = {{"rows_pred", rows_pred, store, 4, n_rows == 0, false},
+                      {"rows_true", rows_true, store, 4, n_rows == 0, false},
+                      {"offsets", offsets, (size_t)(n_utt + 1) * 8, 8, n_utt == 0, false},
+                      {"utt_sum", utt_sum, cells * 4, 4, n_utt == 0, true},
+                      {"utt_count", utt_count, cells * 4, 4, n_utt == 0, true},
+                      {"total_sum", total_sum, kJeJoints * 8, 8, true, true},
+                      {"total_count", total_count, kJeJoints * 8, 8, true, true}};
+    for (const Op& o : ops) {
+        if (!o.p && !o.optional) return fail(B2H_ERR_INVALID, std::string(o.name) + " is NULL");
+        if (misaligned(o.p, o.align))
+            return fail(B2H_ERR_INVALID, std::string(o.name) + " must be " + std::to_string(o.align) + "-byte aligned");
+    }
+    std::vector<Span> out_spans, in_spans;
+    for (const Op& o : ops)
+        if (o.p && o.n) (o.out ? out_spans : in_spans).push_back({o.p, o.n, o.name});
+    if (int rc = check_overlap(out_spans, in_spans)) return rc;
+    for (const Op& o : ops)
+        if (o.p && o.n)
+            if (int rc = check_device_ptr(o.p, o.name)) return rc;
+    JeArgs a;
+    a.rows_pred = rows_pred; a.rows_true = rows_true; a.offsets = offsets; a.utt_sum = utt_sum; a.utt_count = utt_count;
+    a.total_sum = total_sum; a.total_count = total_count; a.n_rows = n_rows; a.n_utt = n_utt; a.n_body = n_body;
+    if (n_utt > 0) {
+        const unsigned blocks = (unsigned)((cells + kJeThreads - 1) / kJeThreads);
+        hipLaunchKernelGGL(b2h_joint_error_k, dim3(blocks), dim3(kJeThreads), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (total_sum) {
+        hipLaunchKernelGGL(b2h_joint_total_k, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
     return B2H_OK;
 }
 

@@ -102,6 +102,23 @@ class DeviceDataset:
         """A list of utterances, each a list of OpenPose frame dicts, merged-JSON entries or paths in time order."""
         return cls._from_utterances([frames_to_rows(list(u)) for u in utterances], 12, tokens, device)
 
+    def with_rows(self, rows):
+        """A store with this one's offsets, tokens and n_body (shared, not copied) around other `rows`: a contiguous
+        float32 tensor of this store's shape on its device, taken as it is -- no copy, nothing validated again."""
+        if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.shape != self.rows.shape or
+                rows.device != self.device or not rows.is_contiguous()):
+            raise ValueError(f"rows must be a contiguous float32 tensor of shape {tuple(self.rows.shape)} on {self.device}")
+        other = object.__new__(type(self))
+        other.__dict__.update(self.__dict__)
+        other.rows = rows
+        return other
+
+    def utterance_rows(self):
+        """The store as a list of (n_i, 3 J) float32 numpy arrays, one per utterance: the inverse of `from_h5_rows`
+        (for n_body 8 the datasets of the reference's keypoints HDF5 file)."""
+        rows, off = self.rows.cpu().numpy(), self.offsets.cpu().tolist()
+        return [rows[off[u]:off[u + 1]].copy() for u in range(len(self))]
+
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
@@ -121,7 +138,10 @@ class DeviceLoader:
     `build_planned(plan, step_word, out)` builds the batch a device step word selects from them: the two halves of an
     epoch of captured steps (`GraphTrainer`).  `plan_source` "torch" (the default) draws the plan as `__iter__` draws,
     "native" with b2h_epoch_plan (kernel_epoch_plan.h) from (`seed`, epoch number) alone, and `__iter__` then iterates
-    that plan too; torch's generators are not touched."""
+    that plan too; torch's generators are not touched.
+
+    `write_back(prediction, utt, start, skip, rows_out)` is the inverse of `build` for the target: a batch of
+    predictions back into store rows (b2h_scatter_rows), what `predict_dataset` (predict.py) runs per slice."""
 
     def __init__(self, ds, batch_size, max_frames, selection="randomcrop", predict="right_hand", dif_encoding=True,
                  normalize=True, factor=1280, pad="zeros", shuffle=False, drop_last=False, generator=None,
@@ -202,6 +222,38 @@ class DeviceLoader:
                 self.flags, self.factor, _ptr(out["input_kp"]), _ptr(out["target_kp"]), _ptr(out["target_conf"]),
                 _ptr(out.get("text_tokens")) if tok is not None else None, _ptr(out["n_frames"]), st))
         return out
+
+    def write_back(self, prediction, utt, start, skip, rows_out, conf=1.0):
+        """The inverse of `build` for the target: `prediction` ((B, max_frames, J_out, 2) float32 on the device, in the
+        units of "target_kp") written into the store rows `rows_out` (a float32 tensor of the store's shape, normally a
+        clone of `ds.rows`) with one kernel (b2h_scatter_rows): * factor and + the raw wrist as the loader's transforms
+        ask, into the joints `predict` predicts, their confidences set to `conf`.  `utt`, `start` as `build` takes
+        them; `skip` ((B) int64 or None = 0): the leading frames of each window that are left alone.  Frames at or past
+        the utterance's end are never written.  Returns `rows_out`."""
+        ds, dev = self.ds, self.ds.device
+        utt = torch.as_tensor(utt, dtype=torch.int64).to(dev).contiguous()
+        if utt.dim() != 1:
+            raise ValueError(f"utt must be (B,), got {tuple(utt.shape)}")
+        B = utt.shape[0]
+        opt = {}
+        for name, t in (("start", start), ("skip", skip)):
+            if t is not None:
+                t = torch.as_tensor(t, dtype=torch.int64).to(dev).contiguous()
+                if t.shape != utt.shape:
+                    raise ValueError(f"{name} must be ({B},), got {tuple(t.shape)}")
+            opt[name] = t
+        shape = (B, self.max_frames, self.joints[1], 2)
+        for name, t, want in (("prediction", prediction, shape), ("rows_out", rows_out, tuple(ds.rows.shape))):
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != want or t.dtype != torch.float32 or t.device != dev or
+                    not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {want} on {dev}")
+        with _lib.on_device(dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(_lib.load().b2h_scatter_rows(
+                _ptr(ds.rows), ds.rows.shape[0], _ptr(ds.offsets), len(ds), ds.n_body, _ptr(utt), _ptr(opt["start"]),
+                _ptr(opt["skip"]), B, self.max_frames, _lib.PREDICT[self.predict], self.flags, self.factor, _ptr(prediction),
+                float(conf), _ptr(rows_out), st))
+        return rows_out
 
     def draw_starts(self, utt):
         """Random crop offsets for the utterances `utt` (device int64): uniform in [0, len - max_frames], 0 for an

@@ -7,7 +7,7 @@ The working equivalent of the reference's `infer_utterance.py` (:52-111) + `step
         --model-checkpoint best_model.pth --output-folder out/ [--model Conv|TransformerEnc|TextPoseTransformer]
         [--conv-channels 30] [--conv-pos-emb] [--max-frames 200] [--no-normalize] [--dif-encoding]
         [--precision fp32] [--tokens ids.json | --text "..." --tokenizer tokenizer.json]
-        [--predict right_hand|right_index|right_3fingers]
+        [--predict right_hand|right_index|right_3fingers] [--all-frames [--batch-size 128]]
 
 With `--model Conv` (default) transforms, model and de-normalisation run as ONE fused kernel
 (`ConvModel.forward_fused`); with `--model TransformerEnc` (infer_utterance.py:99-101) the item
@@ -26,6 +26,10 @@ the 12 body joints and the right hand without the predicted fingers (29 or 21 jo
 `hand_right_keypoints_2d` are rewritten.
 No torch elementwise kernel runs on any of the three paths.
 Several utterances (sub-folders) are batched into one launch.
+With `--all-frames` every frame of every utterance is predicted, not only the first `--max-frames`: the utterances
+become a device-resident store (`DeviceDataset.from_frames`) and `predict_dataset` runs the model over windows of
+`--max-frames` frames that cover it once; `--dif-encoding` is then the trainer's pair of transforms (the hand relative to
+the raw wrist, the body to the chest) and the wrist is added back to the prediction.
 """
 import argparse
 import glob
@@ -75,6 +79,27 @@ def predict_utterances(model, utterances, max_frames=200, dif_encoding=False, no
         pred = model.forward_fused(*lead, body.to(dev), dif_encoding=dif_encoding, normalize=normalize,
                                    denormalize=normalize, mask_tail=False, **extra)
     return pred.cpu().numpy(), [it["n_frames"] for it in items]
+
+
+def predict_all_frames(model, utterances, max_frames=200, dif_encoding=False, normalize=True, tokens=None,
+                       predict="right_hand", batch_size=128):
+    """`utterances` as predict_utterances takes them, every frame of each predicted (predict_dataset over windows of
+    `max_frames` frames, short utterances padded by repeating frame 0).  Returns one (n_i, J, 2) numpy array per
+    utterance in pixel units, J = 21, or the 4 / 12 predicted finger joints; with `dif_encoding` the loader's transforms
+    are the trainer's and the prediction gets the raw wrist back."""
+    from .dataset import DeviceDataset, DeviceLoader
+    from .predict import predict_dataset
+    if isinstance(model, TextPoseTransformer):
+        if tokens is None or len(tokens) != len(utterances):
+            raise ValueError("a TextPoseTransformer needs `tokens`: one list of token ids per utterance")
+        tokens = torch.tensor([pad_tokens(t) for t in tokens], dtype=torch.int64)
+    elif tokens is not None:
+        raise ValueError("`tokens` is for a TextPoseTransformer")
+    ds = DeviceDataset.from_frames(utterances, tokens=tokens, device=next(model.parameters()).device)
+    loader = DeviceLoader(ds, batch_size, max_frames, selection="first", predict=predict, dif_encoding=dif_encoding,
+                          normalize=normalize, pad="frame0")
+    hand = slice(33 + openpose.PREDICT_TARGET_JOINTS[predict].start, 33 + openpose.PREDICT_TARGET_JOINTS[predict].stop)
+    return [np.stack([r[:, :54][:, hand], r[:, 54:108][:, hand]], axis=2) for r in predict_dataset(model, loader).utterance_rows()]
 
 
 def _tpt_geometry(state):
@@ -134,6 +159,11 @@ def main(argv=None):
     ap.add_argument("--predict", default="right_hand", choices=sorted(PREDICT_GEOMETRY),
                     help="what the model predicts (infer_utterance.py:62-85): the whole right hand, or -- TextPoseTransformer "
                          "only -- its index finger / three fingers from the body and the rest of the hand")
+    ap.add_argument("--all-frames", action="store_true",
+                    help="predict and write EVERY frame of every utterance (windows of --max-frames frames over a "
+                         "device-resident store), not only the first --max-frames; --dif-encoding then means the trainer's "
+                         "pair of transforms (hand minus raw wrist, body minus chest) with the wrist added back to the output")
+    ap.add_argument("--batch-size", type=int, default=128, help="--all-frames: windows per model launch (traintest.py:339)")
     args = ap.parse_args(argv)
     if args.predict != "right_hand" and args.model != "TextPoseTransformer":
         # the reference's ConvModel / TransformerEnc hard-code 12 input and 21 output joints (HandPoseModels.py:28,32)
@@ -173,8 +203,13 @@ def main(argv=None):
         tokens = _utterance_tokens(args, [os.path.basename(os.path.normpath(f)) for f, _ in utts])
     model.load_state_dict(state)
     model = model.to("cuda").eval()
-    pred, n_frames = predict_utterances(model, [u for _, u in utts], args.max_frames, args.dif_encoding,
-                                        args.normalize, tokens=tokens)
+    if args.all_frames:
+        pred = predict_all_frames(model, [u for _, u in utts], args.max_frames, args.dif_encoding, args.normalize,
+                                  tokens=tokens, predict=args.predict, batch_size=args.batch_size)
+        n_frames = [len(p) for p in pred]
+    else:
+        pred, n_frames = predict_utterances(model, [u for _, u in utts], args.max_frames, args.dif_encoding,
+                                            args.normalize, tokens=tokens)
     os.mkdir(args.output_folder)
     for (folder, frames), p, n in zip(utts, pred, n_frames):
         if merged:

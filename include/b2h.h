@@ -689,6 +689,66 @@ int b2h_build_batch_planned(const float* rows, int64_t n_rows, const int64_t* of
  * losses, loss inside losses, a pointer that is not memory of the current device.  B2H_ERR_SHAPE: n_losses negative. */
 int b2h_epoch_record(const float* loss, float* losses, int64_t n_losses, int64_t* step, void* stream);
 
+/* Whole-store inference: window plan, row write-back, per-joint error ---------------
+ * The reference's stream-shaped caller (infer_utterance_h5.py -> steps/traintest.py:332-391) runs a trained model over a
+ * whole keypoint store in batches and writes the predictions out as store rows.  Here: a plan of windows that covers
+ * every frame of every utterance once, b2h_build_batch per slice of the plan, the model, and b2h_scatter_rows, the
+ * inverse of b2h_build_batch's target transform (kernel_scatter_rows.h).
+ *
+ * b2h_window_plan is a HOST function: offsets and the three plan arrays are host memory, nothing touches the GPU.  For
+ * utterance u with L = offsets[u+1] - offsets[u] rows, in ascending order of u, as entries (utt, start, skip):
+ *   L == 0                      no entry
+ *   B2H_COVER_FIRST             (u, 0, 0): the reference's `--frames-selection first`; rows at or past T get no entry
+ *   B2H_COVER_ALL, L <= T       (u, 0, 0)
+ *   B2H_COVER_ALL, L >  T       k = ceil(L / T) entries: (u, i T, 0) for i = 0 .. k-2, then (u, L - T, k T - L)
+ * The last window of a long utterance is a full window that ends with the utterance, so the model sees T real frames
+ * and no start is changed by b2h_build_batch's clamp; skip counts its leading frames that the window before it covers
+ * already, which the write-back drops.  Every row is therefore addressed by exactly one (entry, frame >= skip).
+ * Returns the number of entries and fills the first min(count, capacity) of each array; with capacity 0 the arrays may
+ * be NULL (call once for the count, once to fill).  Returns -1, with the message in b2h_last_error, for T < 1, n_utt or
+ * capacity negative, an unknown coverage, offsets NULL with n_utt > 0, offsets that do not ascend from
+ * offsets[0] >= 0, or a plan array that is NULL where an entry must be stored. */
+enum b2h_coverage { B2H_COVER_ALL = 0, B2H_COVER_FIRST = 1 };
+int64_t b2h_window_plan(const int64_t* offsets, int64_t n_utt, int64_t T, int coverage, int64_t* utt_plan,
+                        int64_t* start_plan, int64_t* skip_plan, int64_t capacity);
+
+/* A batch of predictions written back into store rows.  The store (rows, n_rows, offsets, n_utt, n_body), utt, start,
+ * B, T, predict, flags and factor are b2h_build_batch's and mean the same; skip (B) int64 or NULL (= 0).  pred is
+ * (B, T, nt, 2) fp32 with nt = 21, 4 or 12 target joints of `predict`; rows_out is (n_rows, 3 J) fp32, initialised by
+ * the caller (normally a copy of rows): only the addressed words are written.  With len the row count of utt[b],
+ * n = min(len, T) and the window of b2h_build_batch, frame t of sequence b is written iff utt[b] is known, len > 0 and
+ * max(skip[b], 0) <= t < n, to row (window start + t), joint d = the store joint behind target joint j:
+ *   v = pred[b, t, j];  B2H_BATCH_NORMALIZE: v = fl(v * factor);  B2H_BATCH_DIF_ENCODING: v = fl(v + w), w the RAW body
+ *   wrist (joint 4) of the same row of `rows`;  rows_out[row][d] = v.x, [J + d] = v.y, [2 J + d] = conf.
+ * Each step is one correctly rounded fp32 operation (never a fused multiply-add), so fl(fl(p f) + w) is reproducible
+ * anywhere.  B2H_BATCH_PAD_FRAME0 is accepted and changes nothing: padded frames are never written.  An unknown id (or
+ * offsets of it outside 0 <= lo <= hi <= n_rows) writes nothing.  Two sequences of one launch that address the same word
+ * leave it unspecified; a plan of b2h_window_plan never does.  One launch, one lane per (b, t, j), no atomics;
+ * stream-ordered, asynchronous, allocates nothing, can be captured.  Refusals: b2h_build_batch's for the arguments
+ * they share, in its order; then B2H_ERR_INVALID for conf not finite, a NULL (rows, rows_out only with n_rows > 0;
+ * offsets, utt, pred) or not 8-byte-aligned pointer (pred is read as float2), rows_out overlapping any other operand, a
+ * pointer that is not memory of the current device.  B * T == 0 is a no-op (B2H_OK). */
+int b2h_scatter_rows(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                     const int64_t* utt, const int64_t* start, const int64_t* skip, int64_t B, int64_t T,
+                     int predict, int flags, float factor, const float* pred, float conf,
+                     float* rows_out, void* stream);
+
+/* Per-utterance, per-joint pixel error of the right hand of one store against another of the same shape.  For joint j
+ * of a row: dx = fl(xa - xb), dy likewise, d = sqrt(fl(fl(dx dx) + fl(dy dy))), each step correctly rounded fp32; the
+ * row counts iff the TRUE store's confidence of that joint is > 0 (OpenPose writes 0 for a joint it did not detect).
+ * utt_sum[u][j] is the fp32 sum of d over the counted rows of u in ascending row order, utt_count[u][j] their number;
+ * every word is written, 0 for an utterance without rows (or with offsets outside 0 <= lo <= hi <= n_rows).  With
+ * total_sum and total_count (21 each; both or neither): total_sum[j] = sum over u ascending of (double)utt_sum[u][j],
+ * total_count[j] likewise.  Two launches, no atomics, fixed orders: the same bits on every run and stream.  Rows, utt_sum
+ * and utt_count need 4-byte alignment, offsets, total_sum and total_count 8.  B2H_ERR_INVALID: n_body not 8 or 12, one
+ * total without the other, a NULL (rows only with n_rows > 0, offsets and the per-utterance outputs only with
+ * n_utt > 0) or misaligned pointer, an output overlapping an input or another output, a pointer that is not memory of the
+ * current device.  B2H_ERR_SHAPE: n_rows or n_utt negative, n_rows > 2^40, n_utt > 2^30.  n_utt == 0 zeroes the totals. */
+int b2h_joint_error(const float* rows_pred, const float* rows_true, int64_t n_rows, const int64_t* offsets,
+                    int64_t n_utt, int n_body, float* utt_sum, int32_t* utt_count,
+                    double* total_sum, int64_t* total_count,
+                    void* stream);
+
 /* Introspection / measurement -------------------------------------------- */
 
 /* conv_channels, pos_emb and whether weights are loaded. */
