@@ -35,8 +35,9 @@ BATCH_DIF_ENCODING, BATCH_NORMALIZE, BATCH_PAD_FRAME0 = 1, 2, 4
 # enum b2h_coverage (b2h_window_plan), by the names of window_plan / predict_dataset
 COVERAGE = {"all": 0, "first": 1}
 
-# enum b2h_train_kernel (b2h_tpt_set_train_kernel, b2h_tpt_set_train_linear and their b2h_tenc_* twins), by the names
-# of set_train_kernels / set_train_linear of TextPoseTransformer and TransformerEnc
+# enum b2h_train_kernel (b2h_tpt_set_train_kernel, b2h_tpt_set_train_linear and their b2h_tenc_* twins,
+# b2h_tpt_set_train_whole), by the names of set_train_kernels / set_train_linear of TextPoseTransformer and
+# TransformerEnc and of TextPoseTransformer.set_train_whole
 TRAIN_KERNELS = {"valu": 0, "mfma": 1}
 
 # enum b2h_status
@@ -98,6 +99,8 @@ SYMBOLS = {
     "b2h_tpt_train_attn_name": (ctypes.c_char_p, [_vp, ctypes.c_int64]),
     "b2h_tpt_set_train_linear": (ctypes.c_int, [_vp, ctypes.c_int]),
     "b2h_tpt_train_linear_name": (ctypes.c_char_p, [_vp]),
+    "b2h_tpt_set_train_whole": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "b2h_tpt_train_enc_attn_name": (ctypes.c_char_p, [_vp]),
     "b2h_tenc_set_train_kernel": (ctypes.c_int, [_vp, ctypes.c_int]),
     "b2h_tenc_train_attn_name": (ctypes.c_char_p, [_vp, ctypes.c_int64]),
     "b2h_tenc_set_train_linear": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -110,8 +110,9 @@ class NativeDropout:
 
 class TrainRoutes:
     """Mixin of the two transformers: the two opt-in switches of a training step, `train_kernels` (the attentions) and
-    `train_linear` (the Linear layers), each one of `_lib.TRAIN_KERNELS`, "valu" by default.  The models' setters
-    validate through `_choose_train_route`; `_train_route()` hands the values to TrainFn."""
+    `train_linear` (the Linear layers), each one of `_lib.TRAIN_KERNELS`, "valu" by default; TextPoseTransformer adds a
+    third of the same kind, `train_whole` (its attentions of at most 128 x 128).  The models' setters validate through
+    `_choose_train_route`; `_train_route()` hands the values to TrainFn."""
 
     train_kernels = "valu"
     train_linear = "valu"

@@ -1020,6 +1020,7 @@ struct b2h_tpt {
     int kernel = B2H_TENC_F32;
     int train_kernel = B2H_TRAIN_VALU; // b2h_tpt_set_train_kernel
     int train_linear = B2H_TRAIN_VALU; // b2h_tpt_set_train_linear
+    int train_whole = B2H_TRAIN_VALU;  // b2h_tpt_set_train_whole
     float w_absmax = 0.f; // largest |parameter|, the embedding table included (NaN counts as inf): B2H_TENC_F16X3 needs < 65504
     DevBuf table;               // token_embedding.weight (n_tokens, 128)
     DevBuf enc_norm, dec_norm;  // encoder.norm / decoder.norm: gamma (128), beta (128)
@@ -1157,6 +1158,13 @@ int b2h_tpt_set_train_linear(b2h_tpt* m, int kernel) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
     if (kernel != B2H_TRAIN_VALU && kernel != B2H_TRAIN_MFMA) return fail(B2H_ERR_INVALID, "unknown TextPoseTransformer train Linear kernel");
     m->train_linear = kernel;
+    return B2H_OK;
+}
+
+int b2h_tpt_set_train_whole(b2h_tpt* m, int kernel) {
+    if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
+    if (kernel != B2H_TRAIN_VALU && kernel != B2H_TRAIN_MFMA) return fail(B2H_ERR_INVALID, "unknown TextPoseTransformer whole-matrix train kernel");
+    m->train_whole = kernel;
     return B2H_OK;
 }
 
@@ -1898,12 +1906,18 @@ void tt_layernorm(hipStream_t st, const float* X, const float* gamma, const floa
     hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, X, gamma, beta, Y, stats, 4, N);
 }
 
-// Which kernels run the decoder's two attentions in training: the whole-matrix pair up to 128 frames, beyond them the
-// blocked ones as b2h_tpt_set_train_kernel chose.  The one place that decides: the dispatch and
-// b2h_tpt_train_attn_name both ask it.
+// Which kernels run the decoder's two attentions in training: a whole-matrix pair up to 128 frames, as
+// b2h_tpt_set_train_whole chose, beyond them the blocked ones as b2h_tpt_set_train_kernel chose.  The one place that
+// decides: the dispatch and b2h_tpt_train_attn_name both ask it.
 TrainAttn tpt_train_attn(const b2h_tpt* m, int64_t T) {
-    if (!tpt_long(T)) return TrainAttn::kWhole;
+    if (!tpt_long(T)) return m->train_whole == B2H_TRAIN_MFMA ? TrainAttn::kWholeMfma : TrainAttn::kWhole;
     return m->train_kernel == B2H_TRAIN_MFMA ? TrainAttn::kBlockedMfma : TrainAttn::kBlockedValu;
+}
+
+// Which whole-matrix pair runs the encoder's self-attention (S <= 128 tokens at every T), as b2h_tpt_set_train_whole
+// chose: the dispatch and b2h_tpt_train_enc_attn_name both ask it.
+TrainAttn tpt_train_enc_attn(const b2h_tpt* m) {
+    return m->train_whole == B2H_TRAIN_MFMA ? TrainAttn::kWholeMfma : TrainAttn::kWhole;
 }
 
 // Which Linear trio the training calls launch, as b2h_tpt_set_train_linear chose, at every (B, S, T): the one place
@@ -1921,9 +1935,15 @@ const char* b2h_tpt_train_attn_name(const b2h_tpt* m, int64_t T) {
     if (!m || T < 1) return nullptr;
     switch (tpt_train_attn(m, T)) {
     case TrainAttn::kWhole: return "b2h_tt_sdpa";
+    case TrainAttn::kWholeMfma: return "b2h_mw_sdpa";
     case TrainAttn::kBlockedValu: return "b2h_lt_sdpa";
     default: return "b2h_mt_sdpa";
     }
+}
+
+const char* b2h_tpt_train_enc_attn_name(const b2h_tpt* m) {
+    if (!m) return nullptr;
+    return tpt_train_enc_attn(m) == TrainAttn::kWholeMfma ? "b2h_mw_sdpa" : "b2h_tt_sdpa";
 }
 
 const char* b2h_tpt_train_linear_name(const b2h_tpt* m) {
@@ -1969,7 +1989,7 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     const float* H = sv.E0;
     for (int l = 0; l < m->n_enc; ++l) {
         const TtLayer L = sv.enc_layer(l);
-        tt_enc_layer_forward(ln, TrainAttn::kWhole, params + 12 * l, L, H, B, (int)S, masks ? masks + 4 * l : nullptr,
+        tt_enc_layer_forward(ln, tpt_train_enc_attn(m), params + 12 * l, L, H, B, (int)S, masks ? masks + 4 * l : nullptr,
                              sc);
         H = L.H2;
     }
@@ -2106,7 +2126,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     tt_layernorm_bwd(st, dMEM, sv.enc_out(m->n_enc), sv.STm, params[od - 2], G.gA, G.gBm, nullptr, 1.f, G.slabs, Ns,
                      grads[od - 2], grads[od - 1]);
     for (int l = m->n_enc - 1; l >= 0; --l)
-        tt_enc_layer_backward(ln, TrainAttn::kWhole, params + 12 * l, grads + 12 * l, sv.enc_layer(l),
+        tt_enc_layer_backward(ln, tpt_train_enc_attn(m), params + 12 * l, grads + 12 * l, sv.enc_layer(l),
                               l ? sv.enc_layer(l - 1).H2 : sv.E0, G, B, (int)S, masks ? masks + 4 * l : nullptr, sc);
     hipLaunchKernelGGL(b2h_tptt_embed_bwd, dim3((unsigned)m->n_tokens), dim3(128), 0, st, tokens, G.gA, grads[ot], Ns);
     HIP_TRY(hipGetLastError());

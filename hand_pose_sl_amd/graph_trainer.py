@@ -79,7 +79,8 @@ class GraphTrainer:
         m, ld, ds = self.model, self.loader, self.loader.ds
         g = self.optimizer.param_groups[0]
         drop = m.__dict__.get("_drop_step")
-        return (getattr(m, "train_kernels", None), getattr(m, "train_linear", None), getattr(m, "dropout_source", None),
+        return (getattr(m, "train_kernels", None), getattr(m, "train_linear", None), getattr(m, "train_whole", None),
+                getattr(m, "dropout_source", None),
                 getattr(m, "_drop_seed", None), _dropout_p(m), None if drop is None else drop.data_ptr(),
                 float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                 ld.batch_size, ld.max_frames, ld.predict, ld.flags, ld.factor, ld.drop_last, ld.selection, len(ds), ds.n_body,

@@ -19,7 +19,9 @@ Training: in training mode with autograd enabled and a parameter or `input_pose`
 reference's loop body (steps/traintest.py:105-121) runs unchanged with any torch optimizer, at S <= 128 tokens and
 T <= 1024 frames (the trainer pads to `--max-frames 200`, run.py:28; beyond 128 frames the decoder's two attentions
 run blocked, kernel_train_attn_long.h, or after `model.set_train_kernels("mfma")` on the matrix cores in exact fp32,
-kernel_train_attn_mfma.h).  The dropout keep-masks
+kernel_train_attn_mfma.h; after `model.set_train_whole("mfma")` the encoder's self-attention at every T and the
+decoder's two attentions up to 128 frames run the whole-matrix fp32 MFMA pair b2h_mw_sdpa / _bwd,
+kernel_train_attn_whole_mfma.h).  The dropout keep-masks
 are drawn by torch on the model's device (`_draw_dropout_masks`; they follow torch.manual_seed) and handed to the
 kernels; after `model.set_dropout_source("native", seed)` libb2h draws them itself, all of a step in one launch
 (b2h_dropout_masks, kernel_dropout_masks.h).  Every other call (eval mode or no_grad) runs the inference kernels.
@@ -49,7 +51,9 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
     may touch that test lifts it.  Training is exact fp32 whatever the precision, and takes T <= 1024 frames;
     `set_train_kernels("mfma")` (attribute `train_kernels`, default "valu") moves the decoder's attentions beyond 128
     frames to fp32 MFMA kernels, and `set_train_linear("mfma")` (attribute `train_linear`, default "valu") moves every
-    Linear layer of a training step, forward and backward at every length, to fp32 MFMA kernels.  The
+    Linear layer of a training step, forward and backward at every length, to fp32 MFMA kernels, and
+    `set_train_whole("mfma")` (attribute `train_whole`, default "valu") moves every attention of at most 128 x 128 (the
+    encoder's, and up to 128 frames the decoder's two) to the whole-matrix fp32 MFMA pair.  The
     inference route of `model(tokens, pose)` stops at 128 (`forward_long` / `forward_fused` go to 1024)."""
 
     def __init__(self, n_tokens, n_joints, joints_dim, nhead, nhid, nout, n_enc_layers, n_dec_layers, dropout=0.5, *,
@@ -60,6 +64,7 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
         self.precision = precision
         self.train_kernels = "valu"
         self.train_linear = "valu"
+        self.train_whole = "valu"
         self.model_type = "Transformer"
         self.src_mask = None
         self.token_pos_encoder = PositionalEncoding(nhid, dropout, max_len=40)
@@ -101,6 +106,16 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
         embedding, the attentions and inference are untouched.  A backward runs the Linears its forward ran, whatever
         the model says by then.  Measurements: DESIGN.md section 19."""
         return self._choose_train_route("train_linear", "train linear", name)
+
+    def set_train_whole(self, name):
+        """Select the whole-matrix attention kernels of later training forwards, "valu" (the default) or "mfma";
+        returns self.  "mfma" runs every attention of at most 128 x 128 -- the encoder's self-attention (S x S) at
+        every T, and up to 128 frames the decoder's self-attention (T x T) and cross-attention (T x S) -- forward and
+        backward on v_mfma_f32_16x16x4_f32 (b2h_mw_sdpa / _bwd, kernel_train_attn_whole_mfma.h): exact fp32, y bitwise
+        equal to the default's, the gradients in another fixed summation order.  Independent of `set_train_kernels`
+        (which keeps the decoder beyond 128 frames) and `set_train_linear`.  A backward runs the kernels its forward
+        ran, whatever the model says by then.  Measurements: DESIGN.md section 30."""
+        return self._choose_train_route("train_whole", "train whole", name)
 
     _NAME, _CREATE, _LOAD, _DESTROY = "TextPoseTransformer", "b2h_tpt_create", "b2h_tpt_load_weights", "b2h_tpt_destroy"
 
@@ -186,7 +201,8 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
 
     def _train_route(self):
         return (("b2h_tpt_set_train_kernel", _lib.TRAIN_KERNELS[self.train_kernels]),
-                ("b2h_tpt_set_train_linear", _lib.TRAIN_KERNELS[self.train_linear]))
+                ("b2h_tpt_set_train_linear", _lib.TRAIN_KERNELS[self.train_linear]),
+                ("b2h_tpt_set_train_whole", _lib.TRAIN_KERNELS[self.train_whole]))
 
     def forward(self, input_tokens, input_pose):
         train = self._wants_grad(input_tokens, input_pose) and self._device().type == "cuda"

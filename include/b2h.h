@@ -496,7 +496,8 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
 typedef enum b2h_train_kernel { B2H_TRAIN_VALU = 0, B2H_TRAIN_MFMA = 1 } b2h_train_kernel;
 int b2h_tpt_set_train_kernel(b2h_tpt* m, int kernel);
 /* Unmangled name of the decoder's self-attention forward kernel that b2h_tpt_train_forward would launch at T frames
- * under the current setting: "b2h_tt_sdpa" (T <= 128), "b2h_lt_sdpa" or "b2h_mt_sdpa"; static storage, for tests and
+ * under the current settings: "b2h_tt_sdpa" or, after b2h_tpt_set_train_whole below, "b2h_mw_sdpa" (T <= 128),
+ * "b2h_lt_sdpa" or "b2h_mt_sdpa"; static storage, for tests and
  * for matching rocprofv3 kernel-trace rows.  NULL for a NULL model or T < 1. */
 const char* b2h_tpt_train_attn_name(const b2h_tpt* m, int64_t T);
 /* A second, independent switch (the same enum): which kernels run the Linear layers of the training calls, forward
@@ -513,6 +514,23 @@ int b2h_tpt_set_train_linear(b2h_tpt* m, int kernel);
 /* Unmangled name of the Linear forward kernel that b2h_tpt_train_forward would launch under the current setting:
  * "b2h_tt_linear" or "b2h_ml_linear"; static storage.  NULL for a NULL model. */
 const char* b2h_tpt_train_linear_name(const b2h_tpt* m);
+/* A third, independent switch (the same enum): which whole-matrix pair runs every training attention of at most
+ * 128 x 128 -- the encoder's self-attention (S x S) at every T, and at T <= 128 the decoder's self-attention (T x T)
+ * and cross-attention (T x S):
+ *   B2H_TRAIN_VALU  the default of every new model: b2h_tt_sdpa / _bwd of kernel_train_attn.h
+ *   B2H_TRAIN_MFMA  b2h_mw_sdpa / _bwd of kernel_train_attn_whole_mfma.h: the same arguments, one workgroup per
+ *                   (sequence, head), no buffer besides the operands, all six products on v_mfma_f32_16x16x4_f32 in
+ *                   the default's summation order.  y is bitwise equal to the default's; the backward sums
+ *                   rowsum(dSd o S) in its own fixed order, so the gradients are exact fp32 but not bitwise equal
+ * At T > 128 the decoder's attentions stay with b2h_tpt_set_train_kernel.  b2h_tpt_train_bytes does not depend on the
+ * switch (the pair needs no LSE or D buffer), so either backward accepts either forward's saved buffer.  Both pairs'
+ * LDS caps are raised at b2h_tpt_create, so switching between captures is safe.  B2H_ERR_INVALID: NULL model, other
+ * value (nothing changes). */
+int b2h_tpt_set_train_whole(b2h_tpt* m, int kernel);
+/* Unmangled name of the encoder's self-attention forward kernel that b2h_tpt_train_forward would launch under the
+ * current setting: "b2h_tt_sdpa" or "b2h_mw_sdpa"; static storage.  NULL for a NULL model.  After
+ * b2h_tpt_set_train_whole(m, B2H_TRAIN_MFMA), b2h_tpt_train_attn_name(m, T) is "b2h_mw_sdpa" too at T <= 128. */
+const char* b2h_tpt_train_enc_attn_name(const b2h_tpt* m);
 /* The same two switches for TransformerEnc's training calls (b2h_tenc_train_forward / b2h_tenc_backward), over the same
  * enum, independent of each other; B2H_TRAIN_VALU is the default of every new model.
  *   b2h_tenc_set_train_kernel  the self-attention of every layer (T <= 128 always): b2h_tt_sdpa / _bwd of

@@ -25,7 +25,9 @@ warm-up), wall time per step; tpt is the model above, tenc TransformerEnc(24, 4,
 Linears and native masks, conv ConvModel(30), the last two on a 12-joint store.  It also times the plan of an epoch over
 32 768 utterances: one b2h_epoch_plan launch (back-to-back between HIP events, and one `plan_epoch()` call to the
 synchronise) against the torch-drawn plan of the same loader.  `arm` = eager:<model> runs only the eager epochs, for a
-kernel trace of the eager step."""
+kernel trace of the eager step.  An eighth argument, `train_whole` = valu (default) or mfma, sets
+TextPoseTransformer.set_train_whole in the captured and eager arms; `arm` = whole:tpt runs eager epochs under valu and
+under mfma in alternating runs."""
 import json
 import os
 import random
@@ -48,8 +50,11 @@ REPS = int(sys.argv[4]) if len(sys.argv) > 4 else 5
 STEPS = int(sys.argv[5]) if len(sys.argv) > 5 else 8
 OUT = sys.argv[6] if len(sys.argv) > 6 and sys.argv[6] != "-" else None
 ARM, _, MODEL = (sys.argv[7] if len(sys.argv) > 7 else "feed").partition(":")
-if ARM not in ("feed", "captured", "eager") or (ARM != "feed" and MODEL not in ("tpt", "tenc", "conv")):
-    sys.exit("arm must be feed, captured:tpt|tenc|conv or eager:tpt|tenc|conv")
+WHOLE = sys.argv[8] if len(sys.argv) > 8 else "valu"
+if ARM not in ("feed", "captured", "eager", "whole") or (ARM != "feed" and MODEL not in ("tpt", "tenc", "conv")):
+    sys.exit("arm must be feed, captured:tpt|tenc|conv, eager:tpt|tenc|conv or whole:tpt")
+if WHOLE not in ("valu", "mfma") or (ARM == "whole" and MODEL != "tpt"):
+    sys.exit("train_whole must be valu or mfma; the whole arm is whole:tpt")
 N_TOKENS, L, P, LR, BUILD_ITERS = 1000, 4, 0.1, 2e-4, 200
 N_BODY = 12 if MODEL in ("tenc", "conv") else 8
 if not torch.cuda.is_available():
@@ -99,11 +104,15 @@ def captured_arm():
     m = m.to(dev).train()
     if MODEL != "conv":
         m.set_train_kernels("mfma").set_train_linear("mfma").set_dropout_source("native", seed=0)
+    if MODEL == "tpt":
+        m.set_train_whole(WHOLE)
     opt = hps.Adam(m.parameters(), lr=LR)
     crit = hps.maskedPoseL1()
     trainer = hps.GraphTrainer(m, loader, opt, crit)
     out["arm"], out["model"] = ARM, {"tpt": out["model"], "tenc": {"nlayers": L, "dropout": P}, "conv": {"conv_channels": 30}}[MODEL]
     out["model"]["name"] = MODEL
+    if MODEL == "tpt":
+        out["model"]["train_whole"] = WHOLE
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -116,6 +125,20 @@ def captured_arm():
     if ARM == "eager":
         out["epoch_step_ms"] = {"what": f"wall ms per step of hps.train_epoch over {STEPS} batches",
                                 "eager": stats([timed(eager) for _ in range(REPS)])}
+        return finish()
+    if ARM == "whole":                                        # the third switch: valu against mfma, eager epochs
+        runs = {"valu": [], "mfma": []}
+        timed(lambda: (m.set_train_whole("mfma"), eager()))   # warm-up of the second route
+        for _ in range(REPS):
+            for route in ("valu", "mfma"):
+                m.set_train_whole(route)
+                runs[route].append(timed(eager))
+        out["model"]["train_whole"] = "valu and mfma"
+        out["epoch_step_ms"] = {"what": f"wall ms per step of hps.train_epoch over {STEPS} batches, train_whole valu and mfma in "
+                                        "alternating runs, same model, optimizer and loader",
+                                "valu": stats(runs["valu"]), "mfma": stats(runs["mfma"]), "valu_runs": runs["valu"],
+                                "mfma_runs": runs["mfma"],
+                                "ranges_separate": max(runs["mfma"]) < min(runs["valu"]) or max(runs["valu"]) < min(runs["mfma"])}
         return finish()
     timed(trainer.epoch), timed(trainer.epoch)                # warm-up: the eager first step, the capture
     runs = {"eager": [], "captured": []}
