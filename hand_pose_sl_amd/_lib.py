@@ -40,6 +40,9 @@ COVERAGE = {"all": 0, "first": 1}
 # TransformerEnc and of TextPoseTransformer.set_train_whole
 TRAIN_KERNELS = {"valu": 0, "mfma": 1}
 
+# enum B2H_SCHED_* (b2h_step_prepare), by the names of Adam(schedule=...)
+SCHEDULES = {"none": 0, "linear": 1, "inv_sqrt": 2}
+
 # enum b2h_status
 OK, ERR_INVALID, ERR_SHAPE, ERR_NO_WEIGHTS, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 
@@ -117,6 +120,12 @@ SYMBOLS = {
     "b2h_tenc_mask_numel": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int64, _i64p, ctypes.c_int]),
     "b2h_adam_step": (ctypes.c_int, [ctypes.POINTER(_vp)] * 4 + [_i64p, ctypes.c_int, ctypes.c_float, _vp, ctypes.c_float,
                                      ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int64, _vp, _vp]),
+    "b2h_adam_step_guarded": (ctypes.c_int, [ctypes.POINTER(_vp)] * 4 + [_i64p, ctypes.c_int, ctypes.c_float, _vp, ctypes.c_float,
+                                             ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "b2h_step_prepare_bytes": (ctypes.c_size_t, [_i64p, ctypes.c_int]),
+    "b2h_step_prepare": (ctypes.c_int, [ctypes.POINTER(_vp), _i64p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float,
+                                        _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        ctypes.c_size_t, _vp]),
     "b2h_build_batch": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp,
                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp,
                                        _vp, _vp, _vp, _vp]),

@@ -26,6 +26,7 @@
 #include "kernel_tpt.h"
 #include "kernel_attn_long.h"
 #include "kernel_adam.h"
+#include "kernel_step_control.h"
 #include "kernel_build_batch.h"
 #include "kernel_scatter_rows.h"
 #include "kernel_dropout_masks.h"
@@ -2202,13 +2203,12 @@ double shortest_decimal(float x) {
     }
     return std::strtod(buf, nullptr);
 }
-} // namespace
 
-extern "C" {
-
-int b2h_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                  const int64_t* numel, int n_tensors, float lr, const float* lr_dev, float beta1, float beta2, float eps,
-                  float weight_decay, int64_t step, const int64_t* step_dev, void* stream) {
+// b2h_adam_step (guard == nullptr: b2h_adam_step_k) and b2h_adam_step_guarded (b2h_adam_guarded_k behind the two words
+// of *guard): one list of refusals, one packing of the kernel arguments.
+int adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+              const int64_t* numel, int n_tensors, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+              float weight_decay, int64_t step, const int64_t* step_dev, const AdGuard* guard, void* stream) {
     if (n_tensors < 0) return fail(B2H_ERR_INVALID, "n_tensors must be >= 0");
     if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(B2H_ERR_INVALID, "betas must be in [0, 1)");
     if (!(eps >= 0.f)) return fail(B2H_ERR_INVALID, "eps must be >= 0");
@@ -2217,6 +2217,8 @@ int b2h_adam_step(float* const* params, const float* const* grads, float* const*
     if (step_dev ? step < 0 : step < 1)
         return fail(B2H_ERR_INVALID, "step counts from 1 (from 0 with step_dev: step + *step_dev must be >= 1)");
     if (misaligned(lr_dev, 4) || misaligned(step_dev, 8)) return fail(B2H_ERR_INVALID, "lr_dev / step_dev is misaligned");
+    if (guard && (misaligned(guard->grad_scale_dev, 4) || misaligned(guard->apply_dev, 8)))
+        return fail(B2H_ERR_INVALID, "grad_scale_dev / apply_dev is misaligned");
     if (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel))
         return fail(B2H_ERR_INVALID, "params / grads / exp_avg / exp_avg_sq / numel is NULL");
     for (int i = 0; i < n_tensors; ++i) {
@@ -2234,6 +2236,11 @@ int b2h_adam_step(float* const* params, const float* const* grads, float* const*
             for (int y = x + 1; y < 4; ++y)
                 if (overlaps(ptr[x], bytes, ptr[y], bytes))
                     return fail(B2H_ERR_INVALID, "params, grads, exp_avg and exp_avg_sq of tensor " + at + " overlap");
+        if (guard)
+            for (int x : {0, 2, 3}) // the tensors the kernel writes, against the words it reads
+                if ((guard->grad_scale_dev && overlaps(ptr[x], bytes, guard->grad_scale_dev, 4)) ||
+                    (guard->apply_dev && overlaps(ptr[x], bytes, guard->apply_dev, 8)))
+                    return fail(B2H_ERR_INVALID, "grad_scale_dev / apply_dev lies inside an updated array of tensor " + at);
     }
     AdArgs a;
     a.b1 = shortest_decimal(beta1);
@@ -2264,9 +2271,137 @@ int b2h_adam_step(float* const* params, const float* const* grads, float* const*
         const int64_t chunks = a.first[a.n];
         if (chunks == 0) continue;
         const unsigned blocks = (unsigned)std::min<int64_t>((chunks + kAdThreads - 1) / kAdThreads, kAdMaxBlocks);
-        hipLaunchKernelGGL(b2h_adam_step_k, dim3(blocks), dim3(kAdThreads), 0, (hipStream_t)stream, a);
+        if (guard)
+            hipLaunchKernelGGL(b2h_adam_guarded_k, dim3(blocks), dim3(kAdThreads), 0, (hipStream_t)stream, a, *guard);
+        else
+            hipLaunchKernelGGL(b2h_adam_step_k, dim3(blocks), dim3(kAdThreads), 0, (hipStream_t)stream, a);
         HIP_TRY(hipGetLastError());
     }
+    return B2H_OK;
+}
+} // namespace
+
+extern "C" {
+
+int b2h_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                  const int64_t* numel, int n_tensors, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                  float weight_decay, int64_t step, const int64_t* step_dev, void* stream) {
+    return adam_step(params, grads, exp_avg, exp_avg_sq, numel, n_tensors, lr, lr_dev, beta1, beta2, eps, weight_decay, step,
+                     step_dev, nullptr, stream);
+}
+
+int b2h_adam_step_guarded(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                          const int64_t* numel, int n_tensors, float lr, const float* lr_dev, float beta1, float beta2,
+                          float eps, float weight_decay, int64_t step, const int64_t* step_dev, const float* grad_scale_dev,
+                          const int64_t* apply_dev, void* stream) {
+    const AdGuard guard{grad_scale_dev, apply_dev};
+    return adam_step(params, grads, exp_avg, exp_avg_sq, numel, n_tensors, lr, lr_dev, beta1, beta2, eps, weight_decay, step,
+                     step_dev, &guard, stream);
+}
+
+// ---- between backward and the update: norm, clip, guard, warmup (kernel_step_control.h) ----------------------------
+static_assert(kSchedNone == B2H_SCHED_NONE && kSchedLinear == B2H_SCHED_LINEAR && kSchedInvSqrt == B2H_SCHED_INV_SQRT,
+              "kernel_step_control.h and b2h.h name the same schedules");
+size_t b2h_step_prepare_bytes(const int64_t* numel, int n_tensors) {
+    if (n_tensors <= 0 || !numel) return 0;
+    int64_t chunks = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (numel[i] < 0 || numel[i] > (int64_t)1 << 40) return 0;
+        chunks += (numel[i] + 3) / 4;
+    }
+    return (size_t)((chunks + kScBlockChunks - 1) / kScBlockChunks) * sizeof(double);
+}
+
+int b2h_step_prepare(const float* const* grads, const int64_t* numel, int n_tensors, float max_norm, int guard, float base_lr,
+                     const float* base_lr_dev, int schedule, int64_t warmup_steps, int64_t step, const int64_t* step_dev,
+                     float* norm_out, float* scale_out, int64_t* apply_out, int64_t* skipped, float* lr_out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (n_tensors < 0) return fail(B2H_ERR_INVALID, "n_tensors must be >= 0");
+    if (max_norm != max_norm) return fail(B2H_ERR_INVALID, "max_norm is NaN (<= 0 switches clipping off)");
+    if (schedule != kSchedNone && schedule != kSchedLinear && schedule != kSchedInvSqrt)
+        return fail(B2H_ERR_INVALID, "schedule must be a B2H_SCHED_* value");
+    if (schedule != kSchedNone && warmup_steps < 1) return fail(B2H_ERR_INVALID, "warmup_steps must be >= 1 with a schedule");
+    if (schedule != kSchedNone && (step_dev ? step < 0 : step < 1))
+        return fail(B2H_ERR_INVALID, "step counts from 1 (from 0 with step_dev: step + *step_dev must be >= 1)");
+    if (!base_lr_dev && !(base_lr >= 0.f)) return fail(B2H_ERR_INVALID, "base_lr must be >= 0");
+    if (misaligned(base_lr_dev, 4) || misaligned(step_dev, 8)) return fail(B2H_ERR_INVALID, "base_lr_dev / step_dev is misaligned");
+    if (misaligned(norm_out, 4) || misaligned(scale_out, 4) || misaligned(lr_out, 4))
+        return fail(B2H_ERR_INVALID, "norm_out / scale_out / lr_out must be 4-byte aligned");
+    if (misaligned(apply_out, 8) || misaligned(skipped, 8)) return fail(B2H_ERR_INVALID, "apply_out / skipped must be 8-byte aligned");
+    const bool stage1 = max_norm > 0.f || guard;
+    size_t need = 0;
+    if (stage1 && n_tensors > 0) {
+        if (!grads || !numel) return fail(B2H_ERR_INVALID, "grads / numel is NULL");
+        for (int i = 0; i < n_tensors; ++i) {
+            const std::string at = "[" + std::to_string(i) + "]";
+            if (numel[i] < 0) return fail(B2H_ERR_INVALID, "numel" + at + " is negative");
+            if (numel[i] == 0) continue; // the pointer of an empty tensor is never looked at
+            if (numel[i] > (int64_t)1 << 40) return fail(B2H_ERR_INVALID, "numel" + at + " is too large");
+            if (!grads[i]) return fail(B2H_ERR_INVALID, "grads" + at + " is NULL");
+            if (misaligned(grads[i], 4)) return fail(B2H_ERR_INVALID, "grads" + at + " must be 4-byte aligned");
+        }
+        need = b2h_step_prepare_bytes(numel, n_tensors);
+    }
+    if (need) {
+        if (!workspace) return fail(B2H_ERR_INVALID, "workspace is NULL");
+        if (misaligned(workspace, 16)) return fail(B2H_ERR_INVALID, "workspace must be 16-byte aligned");
+        if (workspace_bytes < need)
+            return fail(B2H_ERR_INVALID, "workspace too small: " + std::to_string(workspace_bytes) + " < " + std::to_string(need) +
+                                             " bytes (b2h_step_prepare_bytes)");
+    }
+    const Span out[6] = {{norm_out, 4, "norm_out"},  {scale_out, 4, "scale_out"}, {apply_out, 8, "apply_out"},
+                         {skipped, 8, "skipped"},    {lr_out, 4, "lr_out"},       {need ? workspace : nullptr, need, "workspace"}};
+    for (int x = 0; x < 6; ++x) {
+        if (!out[x].p) continue;
+        const std::string name = out[x].what;
+        for (int y = x + 1; y < 6; ++y)
+            if (out[y].p && overlaps(out[x].p, out[x].n, out[y].p, out[y].n))
+                return fail(B2H_ERR_INVALID, name + " overlaps " + out[y].what);
+        if ((base_lr_dev && overlaps(out[x].p, out[x].n, base_lr_dev, 4)) || (step_dev && overlaps(out[x].p, out[x].n, step_dev, 8)))
+            return fail(B2H_ERR_INVALID, name + " overlaps base_lr_dev / step_dev");
+        for (int i = 0; need && i < n_tensors; ++i)
+            if (numel[i] > 0 && overlaps(out[x].p, out[x].n, grads[i], (size_t)numel[i] * 4))
+                return fail(B2H_ERR_INVALID, name + " overlaps grads[" + std::to_string(i) + "]");
+    }
+    int64_t base = 0; // chunks of the call's tensors before this launch
+    for (int at = 0; need && at < n_tensors; at += kScMaxTensors) { // at most kScMaxTensors tensors per launch
+        SsArgs a;
+        a.partial = (double*)workspace;
+        a.n = std::min(n_tensors - at, kScMaxTensors);
+        a.first[0] = base;
+        for (int i = 0; i < kScMaxTensors; ++i) {
+            const bool used = i < a.n && numel[at + i] > 0;
+            a.g[i] = used ? grads[at + i] : nullptr;
+            a.numel[i] = used ? numel[at + i] : 0;
+            a.first[i + 1] = a.first[i] + (a.numel[i] + 3) / 4;
+        }
+        const int64_t end = a.first[a.n];
+        if (end == base) continue;
+        const int64_t blocks = (end - 1) / kScBlockChunks - base / kScBlockChunks + 1;
+        hipLaunchKernelGGL(b2h_grad_sumsq_k, dim3((unsigned)std::min<int64_t>(blocks, kScMaxBlocks)), dim3(kScThreads), 0,
+                           (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+        base = end;
+    }
+    ScArgs c;
+    c.partial = (const double*)workspace;
+    c.n_partial = (int64_t)(need / sizeof(double));
+    c.max_norm = (double)max_norm;
+    c.base_lr = (double)base_lr;
+    c.base_lr_dev = base_lr_dev;
+    c.warmup = warmup_steps;
+    c.step = step;
+    c.step_dev = step_dev;
+    c.norm_out = norm_out;
+    c.scale_out = scale_out;
+    c.apply_out = apply_out;
+    c.skipped = skipped;
+    c.lr_out = lr_out;
+    c.guard = guard ? 1 : 0;
+    c.schedule = schedule;
+    if (!norm_out && !scale_out && !apply_out && !skipped && !lr_out) return B2H_OK; // nothing to store
+    hipLaunchKernelGGL(b2h_step_control_k, dim3(1), dim3(kScThreads), 0, (hipStream_t)stream, c);
+    HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
 

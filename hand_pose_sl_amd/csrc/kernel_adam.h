@@ -135,4 +135,78 @@ __global__ void __launch_bounds__(kAdThreads) b2h_adam_step_k(const AdArgs a) {
     }
 }
 
+// b2h_adam_step_guarded: the update above behind the two device words of b2h_step_prepare (kernel_step_control.h).
+//   b2h_adam_guarded_k  the same listing per element through ad_update, after
+//                         g <- g * *grad_scale_dev        one fp32 rounding, as g.mul_(clip_coef) in torch
+//                       and every thread returns before it touches memory when *apply_dev == 0 (a wave-uniform read).
+//                       Either word may be nullptr: no scaling, no guard.
+// A sibling of b2h_adam_step_k with a loop of its own, not an instantiation of one template: the kernel above keeps its
+// source and its listing (tests/test_adam_cpu.py pins both).
+struct AdGuard {
+    const float* grad_scale_dev; // or nullptr
+    const int64_t* apply_dev;    // or nullptr
+};
+static_assert(sizeof(AdArgs) + sizeof(AdGuard) <= 4096, "the kernel arguments of b2h_adam_guarded_k must fit in 4 KB");
+
+__device__ __forceinline__ float ad_scale(float g, float s) {
+#pragma clang fp contract(off) // the product is rounded before ad_update sees it
+    return g * s;
+}
+
+__global__ void __launch_bounds__(kAdThreads) b2h_adam_guarded_k(const AdArgs a, const AdGuard w) {
+    if (w.apply_dev && *w.apply_dev == 0) return;
+    const bool scaled = w.grad_scale_dev != nullptr;
+    const float gs = scaled ? *w.grad_scale_dev : 1.f;
+    const int64_t total = a.first[a.n], stride = (int64_t)gridDim.x * kAdThreads;
+    AdScalars s{a.w1, a.b2f, a.w2, a.eps, a.wd, a.bc2s, -a.step_size};
+    if (a.step_dev || a.lr_dev) {
+        const int64_t t = a.step + (a.step_dev ? *a.step_dev : 0);
+        float step_size;
+        ad_bias(a.b1, a.b2, (double)(a.lr_dev ? *a.lr_dev : a.lr), t, &s.bc2s, &step_size);
+        s.neg_step = -step_size;
+    }
+    for (int64_t c = (int64_t)blockIdx.x * kAdThreads + threadIdx.x; c < total; c += stride) {
+        const int64_t cw = ((int64_t)__builtin_amdgcn_readfirstlane((int)(c >> 32)) << 32) |
+                           (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+        int lo = 0, hi = a.n; // first[lo] <= cw < first[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (a.first[mid] <= cw)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        int i = lo;
+        while (c >= a.first[i + 1]) ++i;
+        const int64_t numel = a.numel[i], e0 = (c - a.first[i]) * 4;
+        float* pp = a.p[i] + e0;
+        const float* gp = a.g[i] + e0;
+        float* mp = a.m[i] + e0;
+        float* vp = a.v[i] + e0;
+        const bool aligned = (((uintptr_t)a.p[i] | (uintptr_t)a.g[i] | (uintptr_t)a.m[i] | (uintptr_t)a.v[i]) & 15) == 0;
+        if (aligned && e0 + 4 <= numel) {
+            float4 g4 = *reinterpret_cast<const float4*>(gp);
+            float4 m4 = *reinterpret_cast<const float4*>(mp), v4 = *reinterpret_cast<const float4*>(vp),
+                   p4 = *reinterpret_cast<const float4*>(pp);
+            if (scaled) g4 = make_float4(ad_scale(g4.x, gs), ad_scale(g4.y, gs), ad_scale(g4.z, gs), ad_scale(g4.w, gs));
+            ad_update(p4.x, g4.x, m4.x, v4.x, s);
+            ad_update(p4.y, g4.y, m4.y, v4.y, s);
+            ad_update(p4.z, g4.z, m4.z, v4.z, s);
+            ad_update(p4.w, g4.w, m4.w, v4.w, s);
+            *reinterpret_cast<float4*>(pp) = p4;
+            *reinterpret_cast<float4*>(mp) = m4;
+            *reinterpret_cast<float4*>(vp) = v4;
+        } else {
+            const int count = (int)(numel - e0 < 4 ? numel - e0 : 4); // 1 .. 4
+            for (int j = 0; j < count; ++j) {
+                float p = pp[j], m = mp[j], v = vp[j];
+                ad_update(p, scaled ? ad_scale(gp[j], gs) : gp[j], m, v, s);
+                pp[j] = p;
+                mp[j] = m;
+                vp[j] = v;
+            }
+        }
+    }
+}
+
 } // namespace b2h

@@ -16,7 +16,8 @@ between.  A final partial batch runs eagerly through the ordinary `build` on the
 per epoch, of the losses.
 
 The graph is captured again (after one more eager step) when something baked into it changes: the models' train-kernel,
-train-linear and dropout switches, Adam's betas, eps and weight_decay, the batch geometry or the store, or the storage
+train-linear and dropout switches, Adam's betas, eps, weight_decay and its four step-control options (max_grad_norm,
+skip_nonfinite, warmup_steps, schedule; the warmup's progress is the step word and is not), the batch geometry or the store, or the storage
 of a parameter.  The learning rate is not baked in: `epoch()` calls `optimizer.sync_hyper()`.
 """
 import ctypes
@@ -83,6 +84,7 @@ class GraphTrainer:
                 getattr(m, "dropout_source", None),
                 getattr(m, "_drop_seed", None), _dropout_p(m), None if drop is None else drop.data_ptr(),
                 float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                self.optimizer.max_grad_norm, self.optimizer.skip_nonfinite, self.optimizer.warmup_steps, self.optimizer.schedule,
                 ld.batch_size, ld.max_frames, ld.predict, ld.flags, ld.factor, ld.drop_last, ld.selection, len(ds), ds.n_body,
                 ds.rows.data_ptr(), ds.offsets.data_ptr(), None if ds.tokens is None else ds.tokens.data_ptr(),
                 tuple(p.data_ptr() for grp in self.optimizer.param_groups for p in grp["params"]))

@@ -617,6 +617,68 @@ int b2h_adam_step(float* const* params, const float* const* grads, float* const*
                   const int64_t* numel, int n_tensors, float lr, const float* lr_dev, float beta1, float beta2,
                   float eps, float weight_decay, int64_t step, const int64_t* step_dev, void* stream);
 
+/* Between backward and the update: gradient clipping, a non-finite guard, warmup ----
+ * What a transformer training loop has between loss.backward() and optimizer.step(), decided on the device and left in
+ * device words, so that a captured step (whose host code never runs again) clips, skips and warms up on every replay:
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm) with the 2-norm, "skip the update when a gradient is not
+ * finite", and a per-step schedule of the learning rate (kernel_step_control.h).  Two stages:
+ *   1. only when max_norm > 0 or guard != 0: partial sums of squares.  One flat index runs over the 16-byte chunks
+ *      (4 floats, the last one of a tensor shorter) of all tensors in the order given; block b of 1024 chunks gives
+ *        partial[b] = sum of fma(x, x, .) over its elements in a fixed order, in double
+ *      (the product of two floats is exact in double, so nothing overflows or underflows for any fp32 gradients, where
+ *      the fp32 norm of torch overflows near 1.8e19); workspace holds the partials.
+ *   2. one workgroup adds the partials in a fixed order and stores, with t = step + *step_dev (without the *step_dev
+ *      term when step_dev is NULL) the 1-based index of the update about to be made, all in double:
+ *        total = sum of partial[]                      0 when stage 1 did not run
+ *        norm  = sqrt(total)
+ *        *norm_out  = (float)norm
+ *        *apply_out = guard ? isfinite(total) : 1
+ *        *skipped  += !apply                            a plain read-modify-write: zero it once before the first step
+ *        *scale_out = apply == 0  ? 0.0f
+ *                   : max_norm > 0 ? (float)(c >= 1 ? 1 : c) with c = max_norm / (norm + 1e-6)
+ *                   : 1.0f                              torch's clamped clip_coef; a NaN norm gives a NaN scale, as
+ *                                                       torch does, when the guard is off
+ *        *lr_out    = (float)(base * f(t))              base = base_lr, or *base_lr_dev when that is not NULL
+ *          B2H_SCHED_NONE      f = 1
+ *          B2H_SCHED_LINEAR    f = t >= W ? 1 : t / W                  from t >= W on, the base rate's own bits
+ *          B2H_SCHED_INV_SQRT  f = t <= W ? t / W : sqrt(W / t)        W = warmup_steps >= 1
+ * The words are a function of the numel list and the values alone: not of the stream, the device, the grid or the
+ * pointers' alignment.  grads is only read; p.grad stays unscaled: b2h_adam_step_guarded applies *scale_out.
+ *   grads, numel: HOST arrays of n_tensors device pointers (fp32, contiguous, 4-byte aligned; a 16-byte aligned tensor
+ *                 is read 16 bytes at a time) and element counts.  Not looked at, and may be NULL, when stage 1 does not
+ *                 run; the pointer of a tensor with numel 0 is not looked at.
+ *   norm_out, scale_out, lr_out (float, 4-byte aligned), apply_out, skipped (int64, 8-byte aligned): device words; any
+ *                 of them may be NULL and is then not stored.  base_lr_dev (4), step_dev (8) are only read.
+ *   workspace   : b2h_step_prepare_bytes(numel, n_tensors) bytes of device memory, 16-byte aligned: 8 bytes per 4096
+ *                 gradient elements; every partial is stored before it is read, so it needs no initialising.  May be
+ *                 NULL when stage 1 does not run or that size is 0.  b2h_step_prepare_bytes is a pure host function
+ *                 (0 for a NULL array, n_tensors <= 0 or a negative size).
+ * One launch per 80 tensors for stage 1, one for stage 2.  Stream-ordered and asynchronous: it does not synchronise,
+ * allocate or read device memory on the host, so it can be captured.  B2H_ERR_INVALID, before anything is launched:
+ * n_tensors < 0, NaN max_norm, a schedule that is no B2H_SCHED_* value, warmup_steps < 1 with a schedule, step < 1 with
+ * a schedule and step_dev NULL (step < 0 otherwise), base_lr < 0 or NaN with base_lr_dev NULL, a misaligned word or
+ * workspace; and when stage 1 runs: a NULL array with n_tensors > 0, numel[i] < 0, a NULL or misaligned gradient with
+ * numel[i] > 0, a NULL or too small workspace; an output overlapping another output, base_lr_dev, step_dev or a
+ * gradient.  n_tensors == 0 is no error: the norm is 0. */
+enum { B2H_SCHED_NONE = 0, B2H_SCHED_LINEAR = 1, B2H_SCHED_INV_SQRT = 2 };
+size_t b2h_step_prepare_bytes(const int64_t* numel, int n_tensors);
+int b2h_step_prepare(const float* const* grads, const int64_t* numel, int n_tensors, float max_norm, int guard,
+                     float base_lr, const float* base_lr_dev, int schedule, int64_t warmup_steps, int64_t step,
+                     const int64_t* step_dev, float* norm_out, float* scale_out, int64_t* apply_out, int64_t* skipped,
+                     float* lr_out, void* workspace, size_t workspace_bytes, void* stream);
+/* b2h_adam_step behind the words of b2h_step_prepare (b2h_adam_guarded_k, kernel_adam.h): per element
+ *   g <- g * *grad_scale_dev                   one fp32 rounding, as g.mul_(clip_coef) in torch; grads is not written
+ * then the listing of b2h_adam_step unchanged; and when *apply_dev == 0 nothing is read or written beyond that word:
+ * params, exp_avg and exp_avg_sq keep their bits (the caller then leaves the step count alone: add *apply_dev to it).
+ * Pass b2h_step_prepare's lr_out as lr_dev for the warmed-up rate.  grad_scale_dev (float, 4-byte aligned) and
+ * apply_dev (int64, 8-byte aligned) are only read; either may be NULL (no scaling; no guard), and with both NULL the
+ * result has the bits of b2h_adam_step's.  Everything else, the refusals included, is b2h_adam_step's; in addition
+ * B2H_ERR_INVALID for a misaligned word and for a word inside an array the call updates. */
+int b2h_adam_step_guarded(float* const* params, const float* const* grads, float* const* exp_avg,
+                          float* const* exp_avg_sq, const int64_t* numel, int n_tensors, float lr, const float* lr_dev,
+                          float beta1, float beta2, float eps, float weight_decay, int64_t step, const int64_t* step_dev,
+                          const float* grad_scale_dev, const int64_t* apply_dev, void* stream);
+
 /* The training set on the device: one kernel builds every batch -------------------
  * What the reference's datasets and transforms do per utterance on the host (FastTextPoseDataset.__getitem__ and
  * TextPoseH5Dataset.__getitem__, dataloaders/text_pose_dataset.py:430-476, 652-688: frame selection, padding, clipping;
