@@ -43,6 +43,13 @@ TRAIN_KERNELS = {"valu": 0, "mfma": 1}
 # enum B2H_SCHED_* (b2h_step_prepare), by the names of Adam(schedule=...)
 SCHEDULES = {"none": 0, "linear": 1, "inv_sqrt": 2}
 
+
+class AugmentStruct(ctypes.Structure):
+    """struct b2h_augment (b2h_build_batch_aug): host memory, read during the call."""
+    _fields_ = [("scale", ctypes.c_float), ("rotate_tan", ctypes.c_float), ("mirror_p", ctypes.c_float),
+                ("jitter", ctypes.c_float)]
+
+
 # enum b2h_status
 OK, ERR_INVALID, ERR_SHAPE, ERR_NO_WEIGHTS, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 
@@ -134,6 +141,10 @@ SYMBOLS = {
     "b2h_build_batch_planned": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int64,
                                                _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "b2h_build_batch_aug": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int64, _vp,
+                                           _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.POINTER(AugmentStruct), _vp,
+                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp,
+                                           _vp, _vp, _vp, _vp, _vp]),
     "b2h_epoch_record": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
     "b2h_window_plan": (ctypes.c_int64, [_i64p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _i64p, _i64p, _i64p,
                                          ctypes.c_int64]),

@@ -28,6 +28,7 @@
 #include "kernel_adam.h"
 #include "kernel_step_control.h"
 #include "kernel_build_batch.h"
+#include "kernel_build_batch_aug.h"
 #include "kernel_scatter_rows.h"
 #include "kernel_dropout_masks.h"
 #include "kernel_epoch_plan.h"
@@ -2424,19 +2425,38 @@ int batch_description_refusal(int64_t n_rows, int64_t n_utt, int n_body, int64_t
     return B2H_OK;
 }
 
+// What b2h_build_batch_aug adds to a build: NULL for the two plain entry points.
+struct BatchAugment {
+    const b2h_augment* aug;
+    const uint64_t* key;
+    int64_t entry0;
+};
+
 // b2h_build_batch (step NULL: utt and start hold B entries) and b2h_build_batch_planned (utt and start hold the n_plan
 // entries of an epoch's plan, *step selects B of them): the same checks in the same order, the same launch.
+// b2h_build_batch_aug (`with` set) is either of them with its own kernel, and its own refusals among theirs.
 int build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body, const int64_t* tokens,
                 int64_t S, const int64_t* utt, const int64_t* start, int64_t n_plan, const int64_t* step, bool planned,
                 int64_t B, int64_t T, int predict, int flags, float factor, float* input_kp, float* target_kp,
-                float* target_conf, int64_t* text_tokens, int64_t* n_frames, void* stream) {
+                float* target_conf, int64_t* text_tokens, int64_t* n_frames, void* stream, const BatchAugment* with = nullptr) {
     if (int rc = batch_description_refusal(n_rows, n_utt, n_body, n_plan, B, T, predict, flags, factor)) return rc;
     if (!tokens != !text_tokens) return fail(B2H_ERR_INVALID, "tokens and text_tokens go together: both or neither");
     if (tokens && (S < 1 || S > 128)) return fail(B2H_ERR_INVALID, "1 <= S <= 128");
+    if (with) {
+        if (!with->aug) return fail(B2H_ERR_INVALID, "aug is NULL");
+        const b2h_augment& g = *with->aug;   // each range written so that a NaN fails it
+        if (!(g.scale >= 0.f && g.scale < 1.f)) return fail(B2H_ERR_INVALID, "aug.scale must be in [0, 1)");
+        if (!(g.rotate_tan >= 0.f && g.rotate_tan <= 1.f)) return fail(B2H_ERR_INVALID, "aug.rotate_tan must be in [0, 1]");
+        if (!(g.mirror_p >= 0.f && g.mirror_p <= 1.f)) return fail(B2H_ERR_INVALID, "aug.mirror_p must be in [0, 1]");
+        if (!(g.jitter >= 0.f && std::isfinite(g.jitter))) return fail(B2H_ERR_INVALID, "aug.jitter must be finite and >= 0");
+    }
     if (B * T == 0) return B2H_OK;
     if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
     if (n_rows > ((int64_t)1 << 40) || n_utt > ((int64_t)1 << 40) || n_plan > ((int64_t)1 << 40))
         return fail(B2H_ERR_SHAPE, "store too large");
+    if (with && n_plan > ((int64_t)1 << 32)) return fail(B2H_ERR_SHAPE, "plan too large (a draw index has 32 bits: n_plan <= 2^32)");
+    if (with && (with->entry0 < 0 || with->entry0 > ((int64_t)1 << 32) - B))
+        return fail(B2H_ERR_SHAPE, "entry0 out of range (a draw index has 32 bits: 0 <= entry0, entry0 + B <= 2^32)");
     if (!tokens) S = 0;
     const size_t entries = planned ? (size_t)n_plan : (size_t)B;
     const int J = n_body + 42;
@@ -2449,8 +2469,9 @@ int build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64
                             {"tokens", tokens, (size_t)n_utt * S * 8, true},
                             {planned ? "utt_plan" : "utt", utt, entries * 8, planned && n_plan == 0},
                             {planned ? "start_plan" : "start", start, entries * 8, true},
-                            {"step", step, 8, !planned}};
-    const int n_ops[2] = {6, 5};
+                            {"step", step, 8, !planned},
+                            {"key", with ? with->key : nullptr, 16, !with}};
+    const int n_ops[2] = {7, 5};
     const Op outs[] = {{"input_kp", input_kp, frames * ni * 8, false},       {"target_kp", target_kp, frames * nt * 8, false},
                        {"target_conf", target_conf, frames * nt * 4, true}, {"text_tokens", text_tokens, (size_t)B * S * 8, true},
                        {"n_frames", n_frames, (size_t)B * 8, false}};
@@ -2483,7 +2504,17 @@ int build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64
     a.first[0] = 0;
     for (int s = 0; s < 5; ++s) a.first[s + 1] = a.first[s] + (lanes[s] + kBbThreads - 1) / kBbThreads;
     if (a.first[5] > 0x7fffffff) return fail(B2H_ERR_SHAPE, "shape too large");
-    hipLaunchKernelGGL(b2h_build_batch_k, dim3((unsigned)a.first[5]), dim3(kBbThreads), 0, (hipStream_t)stream, a);
+    if (with) {
+        BaArgs g;
+        g.b = a;
+        g.key = with->key; g.entry0 = with->entry0;
+        g.scale = with->aug->scale; g.rotate_tan = with->aug->rotate_tan; g.jitter = with->aug->jitter;
+        g.mirror_thr = (uint64_t)std::ceil((double)with->aug->mirror_p * 4294967296.0);   // exact: 24 bits times 2^32
+        g.spin = g.scale != 0.f || g.rotate_tan != 0.f;
+        hipLaunchKernelGGL(b2h_build_batch_aug_k, dim3((unsigned)a.first[5]), dim3(kBbThreads), 0, (hipStream_t)stream, g);
+    } else {
+        hipLaunchKernelGGL(b2h_build_batch_k, dim3((unsigned)a.first[5]), dim3(kBbThreads), 0, (hipStream_t)stream, a);
+    }
     HIP_TRY(hipGetLastError());
     return B2H_OK;
 }
@@ -2507,6 +2538,17 @@ int b2h_build_batch_planned(const float* rows, int64_t n_rows, const int64_t* of
                             void* stream) {
     return build_batch(rows, n_rows, offsets, n_utt, n_body, tokens, S, utt_plan, start_plan, n_plan, step, true, B, T,
                        predict, flags, factor, input_kp, target_kp, target_conf, text_tokens, n_frames, stream);
+}
+
+int b2h_build_batch_aug(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                        const int64_t* tokens, int64_t S, const int64_t* utt, const int64_t* start, int64_t n_plan,
+                        const int64_t* step, int64_t entry0, const b2h_augment* aug, const uint64_t* key, int64_t B, int64_t T,
+                        int predict, int flags, float factor, float* input_kp, float* target_kp, float* target_conf,
+                        int64_t* text_tokens, int64_t* n_frames, void* stream) {
+    const BatchAugment with = {aug, key, entry0};
+    const bool planned = step != nullptr;   // without a step word utt and start hold B entries and n_plan is not looked at
+    return build_batch(rows, n_rows, offsets, n_utt, n_body, tokens, S, utt, start, planned ? n_plan : 0, step, planned, B, T,
+                       predict, flags, factor, input_kp, target_kp, target_conf, text_tokens, n_frames, stream, &with);
 }
 
 // ---- an epoch's plan and its step word (kernel_epoch_plan.h) ---------------------------------------------------

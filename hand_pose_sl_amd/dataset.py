@@ -12,6 +12,7 @@ n_body body, 21 left hand, 21 right hand; `offsets` (U + 1) int64 ascending; `to
 is the reference's HDF5 row (n_frames, 150); n_body = 12 the same rule for utterances read from OpenPose JSON.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -124,6 +125,58 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+class Augment:
+    """`Augment(scale=0.0, rotate_deg=0.0, mirror=0.0, jitter=0.0)`: what `DeviceLoader(..., augment=)` draws per
+    sequence and applies inside the batch build (b2h_build_batch_aug, kernel_build_batch_aug.h), a frozen value.
+
+      scale       the sequence is scaled about its chest by a factor uniform in [1 - scale, 1 + scale]; 0 <= scale < 1
+      rotate_deg  and rotated about it by an angle within +-rotate_deg degrees, 0 <= rotate_deg <= 90: tan(angle / 2) is
+                  drawn uniformly, so `rotate_tan` = tan(radians(rotate_deg) / 2), computed in double and rounded once
+      mirror      the probability of a left/right mirror (hands and body sides swapped), 0 <= mirror <= 1
+      jitter      uniform noise of +-jitter pixels on every input joint, finite and >= 0
+
+    The fields hold the float32 values the kernel receives.  A parameter of 0 switches its stage off; all four 0 build
+    the plain batch, bit for bit."""
+    __slots__ = ("scale", "rotate_deg", "mirror", "jitter", "rotate_tan")
+
+    def __init__(self, scale=0.0, rotate_deg=0.0, mirror=0.0, jitter=0.0):
+        given = {"scale": scale, "rotate_deg": rotate_deg, "mirror": mirror, "jitter": jitter}
+        for name, v in given.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+        with np.errstate(over="ignore"):      # a value past float32's range becomes inf and is refused below
+            f32 = {name: float(np.float32(v)) for name, v in given.items()}
+        if not 0.0 <= f32["scale"] < 1.0:
+            raise ValueError(f"scale must be in [0, 1), got {scale!r}")
+        if not 0.0 <= float(rotate_deg) <= 90.0:
+            raise ValueError(f"rotate_deg must be in [0, 90], got {rotate_deg!r}")
+        if not 0.0 <= f32["mirror"] <= 1.0:
+            raise ValueError(f"mirror must be a probability in [0, 1], got {mirror!r}")
+        if not 0.0 <= f32["jitter"] < math.inf:
+            raise ValueError(f"jitter must be finite and >= 0, got {jitter!r}")
+        f32["rotate_deg"] = float(rotate_deg)
+        f32["rotate_tan"] = float(np.float32(math.tan(math.radians(float(rotate_deg)) / 2.0)))
+        for name, v in f32.items():
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value=None):
+        raise AttributeError("Augment is frozen: make another one")
+
+    __delattr__ = __setattr__
+
+    def _fields(self):
+        return (self.scale, self.rotate_tan, self.mirror, self.jitter)
+
+    def __eq__(self, other):
+        return isinstance(other, Augment) and self._fields() == other._fields()
+
+    def __hash__(self):
+        return hash(self._fields())
+
+    def __repr__(self):
+        return f"Augment(scale={self.scale!r}, rotate_deg={self.rotate_deg!r}, mirror={self.mirror!r}, jitter={self.jitter!r})"
+
+
 class DeviceLoader:
     """Iterable over the batches of a DeviceDataset, `len()` of them, each the reference's batch dict on the device:
     "input_kp" (B, T, J_in, 2), "target_kp" (B, T, J_out, 2), "target_conf" (B, T, J_out), "n_frames" (B) int64,
@@ -140,12 +193,19 @@ class DeviceLoader:
     "native" with b2h_epoch_plan (kernel_epoch_plan.h) from (`seed`, epoch number) alone, and `__iter__` then iterates
     that plan too; torch's generators are not touched.
 
+    `augment`: None (every call is the plain build's), or an `Augment`: `build`, `build_planned` and `__iter__` then go
+    through b2h_build_batch_aug, keyed by two device words {seed, epoch} the loader owns.  The epoch word is the number
+    of the epoch's plan -- for "native" the number b2h_epoch_plan receives, for "torch" a count kept the same way --,
+    stored in place by `plan_epoch()` and `__iter__`; the draw index of a sequence is its position in the epoch
+    (`build(..., entry0=)` names the first one of an explicit batch), so `train_epoch()` and `GraphTrainer.epoch()` see
+    the same batches.
+
     `write_back(prediction, utt, start, skip, rows_out)` is the inverse of `build` for the target: a batch of
     predictions back into store rows (b2h_scatter_rows), what `predict_dataset` (predict.py) runs per slice."""
 
     def __init__(self, ds, batch_size, max_frames, selection="randomcrop", predict="right_hand", dif_encoding=True,
                  normalize=True, factor=1280, pad="zeros", shuffle=False, drop_last=False, generator=None,
-                 plan_source="torch", seed=0):
+                 plan_source="torch", seed=0, augment=None):
         if not isinstance(ds, DeviceDataset):
             raise TypeError("ds must be a DeviceDataset")
         if plan_source not in PLAN_SOURCES:
@@ -165,13 +225,31 @@ class DeviceLoader:
         self.ds, self.batch_size, self.max_frames = ds, int(batch_size), int(max_frames)
         self.selection, self.predict, self.shuffle, self.drop_last, self.generator = selection, predict, shuffle, drop_last, generator
         self.plan_source, self.seed = plan_source, int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.epochs_planned = 0   # the epoch number of the next native plan
+        self.epochs_planned = 0   # the epoch number of the next native plan (with `augment`: of the next plan)
+        self._aug_key = None
+        self.augment = augment
         self.factor = float(factor)
         self.flags =((_lib.BATCH_DIF_ENCODING if dif_encoding else 0) | (_lib.BATCH_NORMALIZE if normalize else 0) |
                       (_lib.BATCH_PAD_FRAME0 if pad == "frame0" else 0))
         self.joints = (ds.n_body, 21) if predict == "right_hand" else _JOINTS[predict]
         # the largest start a random crop may draw, per utterance (select_jsons: random.randint(0, len - n))
         self._room = (ds.lengths - self.max_frames).clamp_(min=0).to(ds.device)
+
+    @property
+    def augment(self):
+        return self._augment
+
+    @augment.setter
+    def augment(self, augment):
+        if augment is not None and not isinstance(augment, Augment):
+            raise TypeError("augment must be None or a hand_pose_sl_amd.Augment")
+        self._augment = augment
+        if augment is None:
+            return
+        self._aug = _lib.AugmentStruct(augment.scale, augment.rotate_tan, augment.mirror, augment.jitter)
+        if self._aug_key is None:     # {seed, epoch} as uint64 words; the epoch word is stored by _epoch_number
+            signed = self.seed - (1 << 64) if self.seed >> 63 else self.seed
+            self._aug_key = torch.tensor([signed, 0], dtype=torch.int64, device=self.ds.device)
 
     def __len__(self):
         n = len(self.ds)
@@ -193,11 +271,43 @@ class DeviceLoader:
             out["body_kp"] = out["input_kp"]
         return out
 
-    def build(self, utt, start=None, out=None):
+    def _epoch_number(self, epoch):
+        """The number of the plan being made (None: the loader's own count, advanced), stored into the augmentation's
+        epoch word in place."""
+        if epoch is None:
+            epoch, self.epochs_planned = self.epochs_planned, self.epochs_planned + 1
+        epoch = int(epoch) & 0xFFFFFFFFFFFFFFFF
+        if self.augment is not None:
+            self._aug_key[1:].fill_(epoch - (1 << 64) if epoch >> 63 else epoch)
+        return epoch
+
+    def _launch(self, utt, start, n_plan, step_word, entry0, B, out):
+        """One kernel: b2h_build_batch (no step word) or b2h_build_batch_planned, with `augment` b2h_build_batch_aug."""
+        ds, dev, tok, lib = self.ds, self.ds.device, self.ds.tokens, _lib.load()
+        store = (_ptr(ds.rows), ds.rows.shape[0], _ptr(ds.offsets), len(ds), ds.n_body, _ptr(tok),
+                 0 if tok is None else tok.shape[1], _ptr(utt), _ptr(start))
+        with _lib.on_device(dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            batch = (B, self.max_frames, _lib.PREDICT[self.predict], self.flags, self.factor, _ptr(out["input_kp"]),
+                     _ptr(out["target_kp"]), _ptr(out["target_conf"]),
+                     _ptr(out.get("text_tokens")) if tok is not None else None, _ptr(out["n_frames"]), st)
+            if self.augment is not None:
+                rc = lib.b2h_build_batch_aug(*store, n_plan, _ptr(step_word), int(entry0), ctypes.byref(self._aug),
+                                             _ptr(self._aug_key), *batch)
+            elif step_word is None:
+                rc = lib.b2h_build_batch(*store, *batch)
+            else:
+                rc = lib.b2h_build_batch_planned(*store, n_plan, _ptr(step_word), *batch)
+            _lib.check(rc)
+        return out
+
+    def build(self, utt, start=None, out=None, entry0=0):
         """The batch of utterances `utt` ((B) int64 on the device; a list or host tensor is copied there) cropped at
         `start` ((B) int64, None = 0; read only for utterances longer than max_frames, clamped into them).  `out`: a
         batch returned earlier, written again in place -- with `utt` and `start` device tensors this launches one
-        kernel and nothing else, so a captured graph replays it after the caller refreshes `utt` and `start` in place."""
+        kernel and nothing else, so a captured graph replays it after the caller refreshes `utt` and `start` in place.
+        `entry0` (read only with `augment`): the position in the epoch of the batch's first sequence, which keys its
+        draws; `__iter__` passes i * batch_size for batch i."""
         ds, dev = self.ds, self.ds.device
         utt = torch.as_tensor(utt, dtype=torch.int64).to(dev).contiguous()
         if utt.dim() != 1:
@@ -213,15 +323,7 @@ class DeviceLoader:
             t = out.get(k)
             if t is None or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
                 raise ValueError(f"out[{k!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        tok = ds.tokens
-        with _lib.on_device(dev):
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(_lib.load().b2h_build_batch(
-                _ptr(ds.rows), ds.rows.shape[0], _ptr(ds.offsets), len(ds), ds.n_body, _ptr(tok),
-                0 if tok is None else tok.shape[1], _ptr(utt), _ptr(start), B, self.max_frames, _lib.PREDICT[self.predict],
-                self.flags, self.factor, _ptr(out["input_kp"]), _ptr(out["target_kp"]), _ptr(out["target_conf"]),
-                _ptr(out.get("text_tokens")) if tok is not None else None, _ptr(out["n_frames"]), st))
-        return out
+        return self._launch(utt, start, 0, None, entry0, B, out)
 
     def write_back(self, prediction, utt, start, skip, rows_out, conf=1.0):
         """The inverse of `build` for the target: `prediction` ((B, max_frames, J_out, 2) float32 on the device, in the
@@ -268,20 +370,21 @@ class DeviceLoader:
         "randomcrop".  "torch": exactly what `__iter__` draws, in its order -- the randperm, then `draw_starts` batch
         by batch (the entries of a dropped last batch start at 0, undrawn) --, so from one generator state an eager
         epoch and a planned one see the same batches.  "native": one b2h_epoch_plan launch keyed by (seed, epoch);
-        `epoch` None takes the loader's own count and advances it."""
+        `epoch` None takes the loader's own count and advances it.  With `augment` both sources store that number into
+        the augmentation's epoch word."""
         n, dev, B = len(self.ds), self.ds.device, self.batch_size
         crop = self.selection == "randomcrop"
         if self.plan_source == "native":
-            if epoch is None:
-                epoch, self.epochs_planned = self.epochs_planned, self.epochs_planned + 1
+            epoch = self._epoch_number(epoch)
             utt = torch.empty(n, dtype=torch.int64, device=dev)
             start = torch.empty(n, dtype=torch.int64, device=dev) if crop else None
             with _lib.on_device(dev):
                 st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
                 _lib.check(_lib.load().b2h_epoch_plan(_ptr(self.ds.offsets), n, self.max_frames, int(bool(self.shuffle)),
-                                                      int(crop), self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF, _ptr(utt),
-                                                      _ptr(start), st))
+                                                      int(crop), self.seed, epoch, _ptr(utt), _ptr(start), st))
             return utt, start
+        if self.augment is not None:
+            self._epoch_number(epoch)
         order = (torch.randperm(n, generator=self.generator).to(dev) if self.shuffle else
                  torch.arange(n, dtype=torch.int64, device=dev))
         if not crop:
@@ -312,26 +415,20 @@ class DeviceLoader:
             t = out.get(k)
             if t is None or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
                 raise ValueError(f"out[{k!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        tok = ds.tokens
-        with _lib.on_device(dev):
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(_lib.load().b2h_build_batch_planned(
-                _ptr(ds.rows), ds.rows.shape[0], _ptr(ds.offsets), len(ds), ds.n_body, _ptr(tok),
-                0 if tok is None else tok.shape[1], _ptr(utt), _ptr(start), utt.shape[0], _ptr(step_word), B, self.max_frames,
-                _lib.PREDICT[self.predict], self.flags, self.factor, _ptr(out["input_kp"]), _ptr(out["target_kp"]),
-                _ptr(out["target_conf"]), _ptr(out.get("text_tokens")) if tok is not None else None, _ptr(out["n_frames"]), st))
-        return out
+        return self._launch(utt, start, utt.shape[0], step_word, 0, B, out)
 
     def __iter__(self):
         if self.plan_source == "native":
             utt, start = self.plan_epoch()
             for i in range(len(self)):
                 sl = slice(i * self.batch_size, (i + 1) * self.batch_size)
-                yield self.build(utt[sl], None if start is None else start[sl])
+                yield self.build(utt[sl], None if start is None else start[sl], entry0=i * self.batch_size)
             return
         n, dev = len(self.ds), self.ds.device
+        if self.augment is not None:
+            self._epoch_number(None)
         order =(torch.randperm(n, generator=self.generator).to(dev) if self.shuffle else
                  torch.arange(n, dtype=torch.int64, device=dev))
         for i in range(len(self)):
             utt = order[i * self.batch_size:(i + 1) * self.batch_size]
-            yield self.build(utt, self.draw_starts(utt) if self.selection == "randomcrop" else None)
+            yield self.build(utt, self.draw_starts(utt) if self.selection == "randomcrop" else None, entry0=i * self.batch_size)

@@ -17,8 +17,9 @@ per epoch, of the losses.
 
 The graph is captured again (after one more eager step) when something baked into it changes: the models' train-kernel,
 train-linear and dropout switches, Adam's betas, eps, weight_decay and its four step-control options (max_grad_norm,
-skip_nonfinite, warmup_steps, schedule; the warmup's progress is the step word and is not), the batch geometry or the store, or the storage
-of a parameter.  The learning rate is not baked in: `epoch()` calls `optimizer.sync_hyper()`.
+skip_nonfinite, warmup_steps, schedule; the warmup's progress is the step word and is not), the batch geometry or the store, the
+loader's `Augment` fields or its key words' storage (the epoch word's value is not: `plan_epoch()` rewrites it in place), or the
+storage of a parameter.  The learning rate is not baked in: `epoch()` calls `optimizer.sync_hyper()`.
 """
 import ctypes
 
@@ -87,6 +88,7 @@ class GraphTrainer:
                 self.optimizer.max_grad_norm, self.optimizer.skip_nonfinite, self.optimizer.warmup_steps, self.optimizer.schedule,
                 ld.batch_size, ld.max_frames, ld.predict, ld.flags, ld.factor, ld.drop_last, ld.selection, len(ds), ds.n_body,
                 ds.rows.data_ptr(), ds.offsets.data_ptr(), None if ds.tokens is None else ds.tokens.data_ptr(),
+                None if ld.augment is None else ld.augment._fields() + (ld._aug_key.data_ptr(),),
                 tuple(p.data_ptr() for grp in self.optimizer.param_groups for p in grp["params"]))
 
     def _reset(self, key):
@@ -163,7 +165,8 @@ class GraphTrainer:
             self.replays += 1
         if tail:
             sl = slice(full * B, n)
-            self._train_on(ld.build(self._utt_plan[sl], None if self._start_plan is None else self._start_plan[sl]))
+            self._train_on(ld.build(self._utt_plan[sl], None if self._start_plan is None else self._start_plan[sl],
+                                    entry0=full * B))
         values = self._losses[:count].cpu().tolist()
         if full:   # replays wrote through raw pointers: tell autograd and the models' packed-weights key
             torch.autograd.graph.increment_version([p for grp in opt.param_groups for p in grp["params"]])

@@ -54,6 +54,9 @@ def _check(model, loader, conf):
     if not isinstance(loader, DeviceLoader):
         raise ValueError("predict_dataset() reads the store through a DeviceLoader: wrap the DeviceDataset in "
                          "DeviceLoader(ds, batch_size, max_frames, ...) with the trainer's transforms")
+    if loader.augment is not None:
+        raise ValueError("predict_dataset() writes predictions back into store coordinates, which a scaled, rotated or "
+                         "mirrored window no longer has: use a DeviceLoader with augment=None")
     if not math.isfinite(conf):
         raise ValueError(f"conf must be a finite confidence for the predicted joints, got {conf!r}")
     ds, T = loader.ds, loader.max_frames

@@ -761,6 +761,62 @@ int b2h_build_batch_planned(const float* rows, int64_t n_rows, const int64_t* of
                             float* input_kp, float* target_kp, float* target_conf, int64_t* text_tokens, int64_t* n_frames,
                             void* stream);
 
+/* The batch build with data augmentation: scale, rotation, mirror, jitter ---------
+ * Every sequence is scaled, rotated and mirrored about its own chest and its input joints are jittered, drawn and
+ * applied inside the build launch (kernel_build_batch_aug.h).  The reference has no augmentation; the definition is this
+ * project's own and tests/augment_ref.py restates it in numpy float32, bit for bit.  b2h_build_batch and
+ * b2h_build_batch_planned are untouched.
+ *
+ * Arguments: the store as b2h_build_batch; utt, start, n_plan, step as b2h_build_batch_planned, except that step may be
+ * NULL; B .. stream as b2h_build_batch.
+ *   step != NULL: sequence b reads plan entry p = *step * B + b under the planned build's rules; p is its draw index.
+ *   step == NULL: sequence b reads utt[b] and start[b] (B entries; n_plan is not looked at) and its draw index is
+ *                 p = entry0 + b, so an eager epoch that passes entry0 = i * B for batch i builds what the replayed
+ *                 step builds.
+ *   key: two device uint64 words {seed, epoch}, only read: a caller rewrites epoch in place between epochs without
+ *        capturing again.
+ * Meaning: "augment the raw frame, then do what b2h_build_batch does".  For a live frame a virtual store row is formed;
+ * selection, padding, B2H_BATCH_DIF_ENCODING, B2H_BATCH_NORMALIZE and the predict gather apply to it unchanged.  Frames
+ * of zero padding stay zeros and get no jitter; B2H_BATCH_PAD_FRAME0 frames are live and their jitter uses their own t.
+ * Draws: Philox4x32-10 (b2h_dropout_masks' generator), key (seed lo, seed hi); d(w) = float(w >> 8) * 2^-24 * 2 - 1, in
+ * [-1, 1) and exact in fp32.  Counter word 1 is a tag: 0 .. 4 belong to b2h_epoch_plan, 16 and 17 are these.
+ *   sequence block, counter (p, 16, epoch lo, epoch hi): word 0 the scale, 1 the rotation, 2 the mirror, 3 unused.
+ *     s = 1 + scale * d(w0);  t = rotate_tan * d(w1);  t2 = t * t;  den = 1 + t2;  c = (1 - t2) / den;
+ *     sn = (t + t) / den -- the rational form of a rotation by theta with tan(theta / 2) = t, without sinf / cosf, whose
+ *     bits would differ between device and host;  mirror = w2 < ceil(double(mirror_p) * 2^32), compared in 64 bits.
+ *   virtual row: joint q reads store joint q' = mirror ? M(q) : q, its confidence copied unchanged.  M swaps the left- and
+ *     the right-hand block joint for joint and the body's sides: [0, 1, 5, 6, 7, 2, 3, 4, 9, 8, 11, 10] for n_body 12
+ *     (BODY_25 joints 0 - 7, 15 - 18), the first eight of those for n_body 8.  With (cx, cy) the frame's raw chest (body
+ *     joint 1, which M fixes):  dx = x - cx;  dy = y - cy;  if (mirror) dx = -dx;  rx = c * dx - sn * dy;
+ *     ry = sn * dx + c * dy;  x' = cx + s * rx;  y' = cy + s * ry.  A joint OpenPose missed (0, 0, conf 0) is transformed
+ *     like any other: the reference's own transforms treat it no differently.
+ *   jitter: on input_kp only, after the difference encoding and before the division by factor.  Input joint j (the index
+ *     in input_kp, not the store joint) of frame t takes words 2 (j & 1) and 2 (j & 1) + 1 of the block with counter
+ *     (p, 17 | t << 8, epoch lo, j >> 1):  v.x = v.x + jitter * d(w_x);  v.y = v.y + jitter * d(w_y).  The epoch enters
+ *     the jitter with its LOW 32 bits only; t < 2^24 by the limit on T.  target_kp, target_conf, text_tokens and n_frames
+ *     never see it.
+ * Each fp32 operation above is one correctly rounded operation, never contracted into a fused multiply-add.  A stage
+ * whose parameters are 0 is not run, so that it changes no bit (cx + (x - cx) is not x in fp32; v + 0 * d turns -0 into
+ * +0): with scale and rotate_tan both 0 the rotation-and-scale stage is skipped (y' = y; x' = x, or cx + dx under a
+ * mirror), with jitter 0 nothing is added.  With all four 0 the outputs are b2h_build_batch's, bit for bit.
+ * One launch on b2h_build_batch's grid, every output word written once, no LDS, no atomics; stream-ordered,
+ * asynchronous, allocates nothing, reads `aug` during the call and no device memory on the host: capturable under
+ * b2h_build_batch's conditions.  Refusals, before any device work: b2h_build_batch_planned's (with step NULL,
+ * b2h_build_batch's), plus B2H_ERR_INVALID for aug NULL, a b2h_augment field outside its range or not finite (the
+ * message names the field), key NULL, not 8-byte aligned, overlapping an output or not memory of the current device;
+ * B2H_ERR_SHAPE for n_plan > 2^32, entry0 < 0 or entry0 + B > 2^32 (a draw index has 32 bits). */
+typedef struct b2h_augment {   /* host memory, read during the call */
+    float scale;       /* s uniform in [1 - scale, 1 + scale];            0 <= scale < 1        */
+    float rotate_tan;  /* t = tan(theta / 2) uniform in [-rotate_tan, rotate_tan]; 0 <= . <= 1  */
+    float mirror_p;    /* probability of a left/right mirror;             0 <= . <= 1           */
+    float jitter;      /* uniform noise of +-jitter pixels on input_kp;   0 <= . , finite       */
+} b2h_augment;
+int b2h_build_batch_aug(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                        const int64_t* tokens, int64_t S, const int64_t* utt, const int64_t* start, int64_t n_plan,
+                        const int64_t* step, int64_t entry0, const b2h_augment* aug, const uint64_t* key, int64_t B, int64_t T,
+                        int predict, int flags, float factor, float* input_kp, float* target_kp, float* target_conf,
+                        int64_t* text_tokens, int64_t* n_frames, void* stream);
+
 /* The end of a captured step: one work-item reads s = *step, stores *loss to losses[s] if 0 <= s < n_losses, and in
  * every case stores *step = s + 1.  Stream-ordered after the Adam update it is the only writer of the step word inside
  * a step (no atomics), and the per-batch losses stay on the device until the epoch's one copy.  loss, losses: device

@@ -27,7 +27,14 @@ Linears and native masks, conv ConvModel(30), the last two on a 12-joint store. 
 synchronise) against the torch-drawn plan of the same loader.  `arm` = eager:<model> runs only the eager epochs, for a
 kernel trace of the eager step.  An eighth argument, `train_whole` = valu (default) or mfma, sets
 TextPoseTransformer.set_train_whole in the captured and eager arms; `arm` = whole:tpt runs eager epochs under valu and
-under mfma in alternating runs."""
+under mfma in alternating runs.
+
+`--augment` (anywhere among the arguments; the arm and train_whole arguments are then not read) measures the augmented
+build of DESIGN.md section 32 against the plain one over the same store, alternating: b2h_build_batch_aug (Augment(scale
+0.2, rotate_deg 15, mirror 0.5, jitter 3)) and b2h_build_batch as `iters` back-to-back launches between HIP events, per
+launch, and hps.GraphTrainer.epoch() of the model above over a loader with and one without `augment=`, wall time per
+step.  It first checks that Augment() -- all four 0 -- builds the plain batch bit for bit at this shape.  Kernel times
+come from running it under `rocprofv3 --kernel-trace --stats`, in a run of its own."""
 import json
 import os
 import random
@@ -43,6 +50,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import batch_ref  # noqa: E402
 import hand_pose_sl_amd as hps  # noqa: E402
 
+AUGMENT = "--augment" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--augment"]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 200
@@ -179,6 +188,74 @@ def captured_arm():
     finish()
 
 
+# ---- the augmented build against the plain one, alternating --------------------------------------------------------------
+def augment_arm():
+    aug = hps.Augment(scale=0.2, rotate_deg=15, mirror=0.5, jitter=3)
+    loaders = {"plain": loader, "augmented": hps.DeviceLoader(ds, B, T, selection="randomcrop", augment=aug)}
+    out["arm"], out["augment"] = "augment", {"scale": aug.scale, "rotate_deg": aug.rotate_deg, "mirror": aug.mirror, "jitter": aug.jitter}
+    utt = torch.arange(B, dtype=torch.int64, device=dev)
+    start = torch.tensor([(int(lengths[u]) * 7) % (max(0, int(lengths[u]) - T) + 1) for u in range(B)], device=dev)
+    want = loader.build(utt, start)
+    zero = hps.DeviceLoader(ds, B, T, selection="randomcrop", augment=hps.Augment()).build(utt, start, entry0=B)
+    out["zero_parameters_agree_bit_for_bit"] = all(batch_ref.same_bits(zero[k], want[k]) for k in want)
+    assert out["zero_parameters_agree_bit_for_bit"]
+    bufs = {k: ld.build(utt, start) for k, ld in loaders.items()}
+    out["augmented_input_differs"] = not torch.equal(bufs["plain"]["input_kp"], bufs["augmented"]["input_kp"])
+
+    def launches(name):
+        ld, buf = loaders[name], bufs[name]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(BUILD_ITERS):
+            ld.build(utt, start, out=buf)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / BUILD_ITERS
+
+    for name in loaders:
+        launches(name)                                        # warm-up of both
+    runs = {"plain": [], "augmented": []}
+    for _ in range(REPS):
+        for name in runs:
+            runs[name].append(launches(name))
+    out["build"] = {"what": f"{BUILD_ITERS} back-to-back launches between HIP events, ms per launch (launch gaps included), "
+                            "b2h_build_batch and b2h_build_batch_aug in alternating runs",
+                    "plain": stats(runs["plain"]), "augmented": stats(runs["augmented"]), "plain_runs": runs["plain"],
+                    "augmented_runs": runs["augmented"],
+                    "ranges_separate": max(runs["plain"]) < min(runs["augmented"]) or max(runs["augmented"]) < min(runs["plain"])}
+
+    trainers = {}
+    for name, ld in loaders.items():
+        torch.manual_seed(0)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            m = hps.TextPoseTransformer(N_TOKENS, N_BODY, 2, 4, 128, 42, L, L, dropout=P).to(dev).train()
+        m.set_train_kernels("mfma").set_train_linear("mfma").set_dropout_source("native", seed=0)
+        trainers[name] = hps.GraphTrainer(m, ld, hps.Adam(m.parameters(), lr=LR), hps.maskedPoseL1())
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()                                                  # the epoch ends in its one host synchronisation
+        return (time.perf_counter() - t0) * 1e3 / STEPS
+
+    for tr in trainers.values():
+        timed(tr.epoch), timed(tr.epoch)                      # warm-up: the eager first step, the capture
+    runs = {"plain": [], "augmented": []}
+    for _ in range(REPS):
+        for name in runs:
+            runs[name].append(timed(trainers[name].epoch))
+    out["epoch_step_ms"] = {"what": f"wall ms per step over hps.GraphTrainer.epoch() of {STEPS} steps, a loader without and one "
+                                    "with augment= in alternating runs, twin models and optimizers",
+                            "plain": stats(runs["plain"]), "augmented": stats(runs["augmented"]), "plain_runs": runs["plain"],
+                            "augmented_runs": runs["augmented"], "captures": {k: t.captures for k, t in trainers.items()},
+                            "ranges_separate": max(runs["plain"]) < min(runs["augmented"]) or max(runs["augmented"]) < min(runs["plain"])}
+    finish()
+
+
+if AUGMENT:
+    augment_arm()
+    sys.exit(0)
 if ARM != "feed":
     captured_arm()
     sys.exit(0)
