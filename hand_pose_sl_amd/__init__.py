@@ -10,6 +10,7 @@ from .evaluate import train_epoch, validate  # noqa: F401
 from .graph_trainer import GraphTrainer  # noqa: F401
 from .metrics import l1_to_pixels, masked_pose_l1, maskedPoseL1, poderatedPoseL1, weighted_pose_l1  # noqa: F401
 from .optim import Adam  # noqa: F401
+from .padding import token_lengths  # noqa: F401
 from .predict import joint_pixel_error, predict_dataset, window_plan  # noqa: F401
 from .text_pose_transformer import TextPoseTransformer  # noqa: F401
 from .transformer_enc import PositionalEncoding, TransformerEnc  # noqa: F401
@@ -17,4 +18,4 @@ from .transformer_enc import PositionalEncoding, TransformerEnc  # noqa: F401
 __all__ = ["ConvModel", "LinearPositionalEmbedding", "target_transform", "masked_pose_l1", "weighted_pose_l1",
            "l1_to_pixels", "maskedPoseL1", "poderatedPoseL1", "validate", "TransformerEnc", "PositionalEncoding",
            "TextPoseTransformer", "Adam", "DeviceDataset", "DeviceLoader", "Augment", "train_epoch",
-           "GraphTrainer", "window_plan", "predict_dataset", "joint_pixel_error"]
+           "GraphTrainer", "window_plan", "predict_dataset", "joint_pixel_error", "token_lengths"]

@@ -102,6 +102,9 @@ SYMBOLS = {
                                        ctypes.c_size_t, _vp]),
     "b2h_tpt_forward_fused": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]),
+    "b2h_tpt_forward_masked": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "b2h_token_lengths": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
     "b2h_tpt_info": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_int)] * 6),
     "b2h_tpt_build_item": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_float, _vp]),
@@ -121,6 +124,12 @@ SYMBOLS = {
     "b2h_tpt_backward": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp), ctypes.c_float, _vp, _vp,
                                         ctypes.c_size_t, _vp, ctypes.POINTER(_vp), _vp, ctypes.c_size_t, ctypes.c_int64,
                                         ctypes.c_int64, ctypes.c_int64, _vp]),
+    "b2h_tpt_train_forward_masked": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp), ctypes.c_float,
+                                                    _vp, _vp, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                    _vp, _vp, _vp]),
+    "b2h_tpt_backward_masked": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp), ctypes.c_float, _vp, _vp,
+                                               ctypes.c_size_t, _vp, ctypes.POINTER(_vp), _vp, ctypes.c_size_t, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp]),
     "b2h_dropout_masks": (ctypes.c_int, [ctypes.POINTER(_vp), _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                          ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
     "b2h_tpt_mask_numel": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _i64p, ctypes.c_int]),

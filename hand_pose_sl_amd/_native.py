@@ -140,7 +140,16 @@ class TrainFn(torch.autograd.Function):
                                     (`pe`), or is an argument of its own that only has to be aligned (the token ids)
         _train_shapes(lead, x)      the batch as the entry points take it, (B, T) or (B, S, T); y's shape; dx's shape
         _train_head(lead, params)   the entry points' arguments between the handle and x (forward) / the masks (backward)
-        _train_route()              (setter entry point, value) pairs that select the kernels of a forward"""
+        _train_route()              (setter entry point, value) pairs that select the kernels of a forward
+
+    Key lengths (TextPoseTransformer's padding masks): `lead` may be a tuple (token ids, text_lengths, frame_lengths),
+    each length an int64 (B,) tensor on the device or None.  They are not differentiable; the context carries them
+    to the backward next to the token ids, and both passes then call the model's `_TRAIN_FNS_MASKED` pair, which
+    takes the two arrays between the batch dimensions and the stream.  A bare tensor makes the calls it always made."""
+
+    @staticmethod
+    def _length_args(lengths):
+        return tuple(ctypes.c_void_p(t.data_ptr()) if t is not None else None for t in lengths)
 
     @staticmethod
     def _set_route(lib, model, route):
@@ -152,23 +161,28 @@ class TrainFn(torch.autograd.Function):
         for t in ((lead,) if model._TRAIN_LEAD_IS_PARAM else ()) + params:
             if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError("training needs contiguous float32 parameters on the input's device")
+        lengths = ()
+        if isinstance(lead, tuple):
+            lead, *lengths = lead
+        fns = model._TRAIN_FNS_MASKED if lengths else model._TRAIN_FNS
         lib, dev = model._ensure_created()
         x = _aligned(x)
         if not model._TRAIN_LEAD_IS_PARAM:
             lead = _aligned(lead)
         dims, yshape, xshape = model._train_shapes(lead, x)
         y = torch.empty(yshape, dtype=torch.float32, device=x.device)
-        nbytes = getattr(lib, model._TRAIN_FNS[0])(model._handle, *dims, 0)
+        nbytes = getattr(lib, fns[0])(model._handle, *dims, 0)
         saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
         route = model._train_route()
         with _lib.on_device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             TrainFn._set_route(lib, model, route)
-            _lib.check(getattr(lib, model._TRAIN_FNS[1])(
+            _lib.check(getattr(lib, fns[1])(
                 model._handle, *model._train_head(lead, params), ctypes.c_void_p(x.data_ptr()),
                 _ptrs(masks) if masks else None, p, ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(saved.data_ptr()), nbytes,
-                *dims, ctypes.c_void_p(st)))
+                *dims, *TrainFn._length_args(lengths), ctypes.c_void_p(st)))
         ctx.model, ctx.p, ctx.masks, ctx.dims, ctx.xshape, ctx.route = model, p, masks, dims, xshape, route
+        ctx.fns, ctx.lengths = fns, tuple(lengths)
         ctx.save_for_backward(saved, lead, *params)
         return y
 
@@ -187,16 +201,16 @@ class TrainFn(torch.autograd.Function):
             dy = _aligned(dy.to(torch.float32).contiguous())   # autograd may hand over an expanded / CopySlices gradient
             grads = [torch.empty_like(t) for t in params]
             dx = torch.empty(ctx.xshape, dtype=torch.float32, device=dev) if need_dx else None
-            nbytes = getattr(lib, model._TRAIN_FNS[0])(model._handle, *dims, 1)
+            nbytes = getattr(lib, ctx.fns[0])(model._handle, *dims, 1)
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             with _lib.on_device(dev):
                 st = torch.cuda.current_stream(dev).cuda_stream
                 TrainFn._set_route(lib, model, ctx.route)
-                _lib.check(getattr(lib, model._TRAIN_FNS[2])(
+                _lib.check(getattr(lib, ctx.fns[2])(
                     model._handle, *model._train_head(lead, params), _ptrs(masks) if masks else None, ctx.p,
                     ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(saved.data_ptr()), saved.numel(),
                     ctypes.c_void_p(dx.data_ptr()) if dx is not None else None, _ptrs(grads), ctypes.c_void_p(ws.data_ptr()),
-                    nbytes, *dims, ctypes.c_void_p(st)))
+                    nbytes, *dims, *TrainFn._length_args(ctx.lengths), ctypes.c_void_p(st)))
         return (None, None, None, None, dx) + tuple(g if ctx.needs_input_grad[5 + i] else None for i, g in enumerate(grads))
 
 

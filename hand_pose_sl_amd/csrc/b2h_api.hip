@@ -32,6 +32,7 @@
 #include "kernel_scatter_rows.h"
 #include "kernel_dropout_masks.h"
 #include "kernel_epoch_plan.h"
+#include "kernel_token_lengths.h"
 #include "kernel_train_attn_long.h"
 #include "kernel_train_attn_mfma.h"
 #include "kernel_train_linear_mfma.h"
@@ -784,6 +785,17 @@ constexpr AttnRowsKernel kAttnF32[2][kAttnMaxTiles] = {
 constexpr AttnRowsKernel kAttnLongF32[kAttnMaxTiles] = {b2h_attn_long_f32<1>, b2h_attn_long_f32<2>, b2h_attn_long_f32<3>,
                                                         b2h_attn_long_f32<4>, b2h_attn_long_f32<5>, b2h_attn_long_f32<6>,
                                                         b2h_attn_long_f32<7>, b2h_attn_long_f32<8>};
+// The two fp32 kernels with a key length per sequence (a key-padding mask): instantiations of
+// their own, so that the ones above stay what they were
+using AttnRowsKlKernel = void (*)(AttnSrc, float*, int, int, const int64_t*);
+constexpr AttnRowsKlKernel kAttnF32Kl[2][kAttnMaxTiles] = {
+    {b2h_attn_klen_f32<1, false>, b2h_attn_klen_f32<2, false>, b2h_attn_klen_f32<3, false>, b2h_attn_klen_f32<4, false>,
+     b2h_attn_klen_f32<5, false>, b2h_attn_klen_f32<6, false>, b2h_attn_klen_f32<7, false>, b2h_attn_klen_f32<8, false>},
+    {b2h_attn_klen_f32<1, true>, b2h_attn_klen_f32<2, true>, b2h_attn_klen_f32<3, true>, b2h_attn_klen_f32<4, true>,
+     b2h_attn_klen_f32<5, true>, b2h_attn_klen_f32<6, true>, b2h_attn_klen_f32<7, true>, b2h_attn_klen_f32<8, true>}};
+constexpr AttnRowsKlKernel kAttnLongF32Kl[kAttnMaxTiles] = {
+    b2h_attn_long_klen_f32<1>, b2h_attn_long_klen_f32<2>, b2h_attn_long_klen_f32<3>, b2h_attn_long_klen_f32<4>,
+    b2h_attn_long_klen_f32<5>, b2h_attn_long_klen_f32<6>, b2h_attn_long_klen_f32<7>, b2h_attn_long_klen_f32<8>};
 constexpr AttnRowsKernel kAttnLongH3[kAttnMaxTiles] = {b2h_attn_long_h3<1>, b2h_attn_long_h3<2>, b2h_attn_long_h3<3>,
                                                        b2h_attn_long_h3<4>, b2h_attn_long_h3<5>, b2h_attn_long_h3<6>,
                                                        b2h_attn_long_h3<7>, b2h_attn_long_h3<8>};
@@ -800,6 +812,7 @@ int set_tenc_kernel_attributes() {
             if ((rc = raise_lds_cap(kAttnQkvH3[nt - 1], attn_qkv_lds_bytes(nt))) ||
                 (rc = raise_lds_cap(kAttnCrossH3[nt - 1], attn_qkv_lds_bytes(nt))) ||
                 (rc = raise_lds_cap(kAttnLongF32[nt - 1], attn_long_f32_lds_bytes(nt))) ||
+                (rc = raise_lds_cap(kAttnLongF32Kl[nt - 1], attn_long_f32_lds_bytes(nt))) ||
                 (rc = raise_lds_cap(kAttnLongH3[nt - 1], attn_long_h3_lds_bytes(nt))))
                 return rc;
         if ((rc = raise_lds_cap(b2h_tt_sdpa)) || (rc = raise_lds_cap(b2h_tt_sdpa_bwd))) return rc;
@@ -839,16 +852,26 @@ AttnSrc cross_src(const float* qc, const float* kv) { return AttnSrc{qc, kTencD,
 // the whole-matrix b2h_attn_f32, one wave per query tile.  That arm is exact fp32 ONLY: f16x3 at T <= 128 keeps its
 // fused kernels (self_attn_h3, b2h_attn_cross_h3) and never gets here.  Beyond, both arithmetics (kernel_attn_long.h):
 // the query tiles are cut into ceil(tiles / 8) blocks of equal tile count (>= 5 for Tq > 128, which the kernels'
-// staging rounds count on), the key tiles likewise into blocks of nk tiles.
-void attn_rows(hipStream_t st, bool h3, const AttnSrc& src, float* out, int64_t B, int Tq, int Tk) {
+// klen: (B) key lengths on the device or nullptr (fp32 only; the caller refuses f16x3 with lengths).  The launch
+// geometry is that of (Tq, Tk) either way.
+void attn_rows(hipStream_t st, bool h3, const AttnSrc& src, float* out, int64_t B, int Tq, int Tk, const int64_t* klen) {
     const int ntq = (Tq + 15) / 16, ntk = (Tk + 15) / 16;
     if (ntq <= kAttnMaxTiles) {
-        hipLaunchKernelGGL(kAttnF32[ntq == ntk][ntk - 1], dim3((unsigned)(B * kTencHeads)), dim3(64 * ntq),
-                           (size_t)attn_f32_lds_bytes(ntk), st, src, out, Tq, Tk);
+        const dim3 grid((unsigned)(B * kTencHeads)), block(64 * ntq);
+        if (klen)
+            hipLaunchKernelGGL(kAttnF32Kl[ntq == ntk][ntk - 1], grid, block, (size_t)attn_f32_lds_bytes(ntk), st, src, out, Tq,
+                               Tk, klen);
+        else
+            hipLaunchKernelGGL(kAttnF32[ntq == ntk][ntk - 1], grid, block, (size_t)attn_f32_lds_bytes(ntk), st, src, out, Tq, Tk);
         return;
     }
     const int nqb = (ntq + kAttnMaxTiles - 1) / kAttnMaxTiles, wpb = (ntq + nqb - 1) / nqb;
     const int nkb = (ntk + kAttnMaxTiles - 1) / kAttnMaxTiles, nk = (ntk + nkb - 1) / nkb;
+    if (klen) {
+        hipLaunchKernelGGL(kAttnLongF32Kl[nk - 1], dim3((unsigned)(B * kTencHeads), (unsigned)nqb), dim3(64 * wpb),
+                           (size_t)attn_long_f32_lds_bytes(nk), st, src, out, Tq, Tk, klen);
+        return;
+    }
     hipLaunchKernelGGL(h3 ? kAttnLongH3[nk - 1] : kAttnLongF32[nk - 1], dim3((unsigned)(B * kTencHeads), (unsigned)nqb),
                        dim3(64 * wpb), (size_t)(h3 ? attn_long_h3_lds_bytes(nk) : attn_long_f32_lds_bytes(nk)), st, src, out,
                        Tq, Tk);
@@ -917,7 +940,7 @@ int tenc_launch(b2h_tenc* m, const float* x, float* y, int64_t B, int64_t T, con
     chain_in(m, x, n, (int)T, fa, ws, st);
     for (int l = 0; l < m->nlayers; ++l) { // torch.nn.TransformerEncoderLayer, post-norm, ReLU
         if (h3) self_attn_h3(m->layers[l].qkv_head, ws.XA, ws.OC, B, (int)T, m->num_cus, st);
-        else attn_rows(st, false, self_src(ws.QKV), ws.OC, B, (int)T, (int)T);
+        else attn_rows(st, false, self_src(ws.QKV), ws.OC, B, (int)T, (int)T, nullptr);
         chain_tail(m, l, y, n, (int)T, fa, ws, st);
     }
     HIP_TRY(hipGetLastError());
@@ -1235,8 +1258,11 @@ size_t b2h_tpt_workspace_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T
 // b2h_tpt_forward_fused.  T <= 128 runs the launches this model has always run, whatever the entry point; T > 128
 // runs the decoder on row sets in both arithmetics -- the chains write Q | K | V, the cross query and the memory's
 // K | V, as the fp32 path always did -- with b2h_attn_long_* for its two attentions (kernel_attn_long.h).
+// text_len / frame_len: (B) key lengths or nullptr, the three key-padding masks of DESIGN.md section 33 (exact fp32
+// only).
 static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* y, int64_t B, int64_t S, int64_t T,
-                      const FusedArgs& fa, int64_t max_frames, void* workspace, size_t workspace_bytes, void* stream) {
+                      const FusedArgs& fa, int64_t max_frames, const int64_t* text_len, const int64_t* frame_len,
+                      void* workspace, size_t workspace_bytes, void* stream) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
     if (!m->has_weights) return fail(B2H_ERR_NO_WEIGHTS, "b2h_tpt_forward before b2h_tpt_load_weights");
     if (B < 0 || S < 1 || T < 1) return fail(B2H_ERR_SHAPE, "expected B >= 0, S >= 1 and T >= 1");
@@ -1251,6 +1277,16 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
     if (misaligned(tokens, 8) || misaligned(x, 16) || misaligned(y, 8) || misaligned(workspace, 16))
         return fail(B2H_ERR_INVALID, "x and workspace must be 16-byte aligned, tokens and y 8-byte aligned");
     if (workspace_bytes < b2h_tpt_workspace_bytes(m, B, S, T)) return fail(B2H_ERR_INVALID, "workspace too small");
+    if (misaligned(text_len, 8) || misaligned(frame_len, 8))
+        return fail(B2H_ERR_INVALID, "text_len and frame_len must be 8-byte aligned int64 arrays");
+    for (const int64_t* len : {text_len, frame_len})
+        if (len && (overlaps(len, (size_t)B * 8, y, (size_t)B * T * m->nout * 4) ||
+                    overlaps(len, (size_t)B * 8, workspace, b2h_tpt_workspace_bytes(m, B, S, T))))
+            return fail(B2H_ERR_INVALID, "y or the workspace overlaps a key length array");
+    if (m->kernel == B2H_TENC_F16X3 && (text_len || frame_len))
+        return fail(B2H_ERR_UNSUPPORTED, "B2H_TENC_F16X3 takes no key lengths (text_len / frame_len): its attention kernels "
+                                         "attend to every row; select exact fp32 with b2h_tpt_set_kernel(fp32), i.e. "
+                                         "b2h_tpt_set_kernel(m, B2H_TENC_F32)");
     const int64_t Ns = B * S, Nt = B * T;
     // grid limits: attention launches B x heads workgroups, the row kernels 8 rows per workgroup, the copy of
     // 42- / 58-float pose rows (b2h_item_pad_rows) 4 rows per workgroup
@@ -1339,7 +1375,7 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
         }
         for (int l = 0; l < m->n_enc; ++l) {
             const EncLayer& L = m->enc[l];
-            attn_rows(st, false, self_src(ws.QKVs), ws.OCs, B, (int)S, (int)S);
+            attn_rows(st, false, self_src(ws.QKVs), ws.OCs, B, (int)S, (int)S, text_len);
             Chain c = tpt_rows(ws.OCs, kTencD, ws.MEM, Ns);
             c.add_layer_tail(L.attn_out, L.ff1, L.ff2, ws.MEM, l + 1 < m->n_enc ? &m->enc[l + 1] : nullptr, ws.QKVs);
             c.launch(m->num_cus, st);
@@ -1368,7 +1404,7 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
     }
     for (int l = 0; l < m->n_dec; ++l) {
         const auto& L = m->dec[l];
-        attn_rows(st, h3, self_src(ws.QKVt), ws.OCt, B, (int)T, (int)T);
+        attn_rows(st, h3, self_src(ws.QKVt), ws.OCt, B, (int)T, (int)T, frame_len);
         {   // self out_proj + x -> norm1 -> X1; the cross-attention query of X1
             Chain c = tpt_rows(ws.OCt, kTencD, ws.XT, Nt, h3);
             c.add(L.attn_out, ST_RESLN_GLOBAL, ws.X1);
@@ -1376,7 +1412,8 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
             c.launch(m->num_cus, st);
         }
         // S <= 128: one key block at any T
-        attn_rows(st, h3, cross_src(ws.QC, ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats), ws.OCt, B, (int)T, (int)S);
+        attn_rows(st, h3, cross_src(ws.QC, ws.MKV + (int64_t)l * Ns * kTptTokenLayerFloats), ws.OCt, B, (int)T, (int)S,
+                  text_len);
         // cross out_proj + X1 -> norm2 -> linear1 ReLU -> linear2 + res -> norm3 -> XT [+ the next layer's Q, K, V]
         Chain c = tpt_rows(ws.OCt, kTencD, ws.X1, Nt, h3);
         c.add_layer_tail(L.cross_out, L.ff1, L.ff2, ws.XT, l + 1 < m->n_dec ? &m->dec[l + 1] : nullptr, ws.QKVt);
@@ -1396,16 +1433,38 @@ static int tpt_launch(b2h_tpt* m, const int64_t* tokens, const float* x, float* 
 int b2h_tpt_forward(b2h_tpt* m, const int64_t* tokens, const float* x, float* y, int64_t B, int64_t S, int64_t T,
                     void* workspace, size_t workspace_bytes, void* stream) {
     const FusedArgs fa{0, 1.0f, nullptr};
-    return tpt_launch(m, tokens, x, y, B, S, T, fa, kTptMaxLen, workspace, workspace_bytes, stream);
+    return tpt_launch(m, tokens, x, y, B, S, T, fa, kTptMaxLen, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+int b2h_tpt_forward_masked(b2h_tpt* m, const int64_t* tokens, const float* body, float* y, int64_t B, int64_t S, int64_t T,
+                           int flags, float factor, const int64_t* n_frames, const int64_t* text_len,
+                           const int64_t* frame_len, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_fused(flags, factor)) return rc;
+    if ((flags & kPostMask) && !n_frames) return fail(B2H_ERR_INVALID, "B2H_POST_MASK_TAIL needs n_frames");
+    const FusedArgs fa{flags, factor, n_frames};
+    return tpt_launch(m, tokens, body, y, B, S, T, fa, B2H_TPT_MAX_FRAMES, text_len, frame_len, workspace, workspace_bytes,
+                      stream);
 }
 
 int b2h_tpt_forward_fused(b2h_tpt* m, const int64_t* tokens, const float* body, float* y, int64_t B, int64_t S, int64_t T,
                           int flags, float factor, const int64_t* n_frames, void* workspace, size_t workspace_bytes,
                           void* stream) {
-    if (int rc = check_fused(flags, factor)) return rc;
-    if ((flags & kPostMask) && !n_frames) return fail(B2H_ERR_INVALID, "B2H_POST_MASK_TAIL needs n_frames");
-    const FusedArgs fa{flags, factor, n_frames};
-    return tpt_launch(m, tokens, body, y, B, S, T, fa, B2H_TPT_MAX_FRAMES, workspace, workspace_bytes, stream);
+    return b2h_tpt_forward_masked(m, tokens, body, y, B, S, T, flags, factor, n_frames, nullptr, nullptr, workspace,
+                                  workspace_bytes, stream);
+}
+
+int b2h_token_lengths(const int64_t* tokens, int64_t B, int64_t S, int64_t pad_id, int64_t* lengths, void* stream) {
+    if (B < 0 || S < 1) return fail(B2H_ERR_SHAPE, "b2h_token_lengths: expected B >= 0 and S >= 1");
+    if (S > 0x7fffffff || (B + 3) / 4 > 0x7fffffff) return fail(B2H_ERR_SHAPE, "b2h_token_lengths: batch too large for one launch");
+    if (B == 0) return B2H_OK;
+    if (!tokens || !lengths) return fail(B2H_ERR_INVALID, "b2h_token_lengths: tokens / lengths is NULL");
+    if (misaligned(tokens, 8) || misaligned(lengths, 8))
+        return fail(B2H_ERR_INVALID, "b2h_token_lengths: tokens and lengths must be 8-byte aligned");
+    if (int rc = check_overlap({{lengths, (size_t)B * 8}}, {{tokens, (size_t)B * S * 8, "tokens"}})) return rc;
+    hipLaunchKernelGGL(b2h_token_lengths_k, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, tokens, B, (int)S,
+                       pad_id, lengths);
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
 }
 
 int b2h_tpt_info(const b2h_tpt* m, int* n_tokens, int* ninp, int* nout, int* n_enc_layers, int* n_dec_layers,
@@ -1585,50 +1644,53 @@ LtGradDst self_dst(float* gQ) { return LtGradDst{gQ, 3 * kTtD, 0, gQ, 3 * kTtD, 
 
 // Attention of B sequences of Tq query rows over Tk key rows in training: O (B*Tq, 128) and, from the blocked kernels
 // only, the rows' log-sum-exp (B, 4, Tq).
+// klen: (B) key lengths or nullptr (tt_key_len).
 void train_sdpa(hipStream_t st, TrainAttn route, const AttnSrc& src, const uint8_t* mask, float sc, float* O, float* lse,
-                int64_t B, int Tq, int Tk) {
+                int64_t B, int Tq, int Tk, const int64_t* klen) {
     const unsigned heads = (unsigned)(B * kTtHeads);
     const dim3 grid(heads, lt_blocks(Tq, kLtQb));
     if (route == TrainAttn::kWhole)
-        hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes(Tq, Tk, false), st, src, mask, sc, O, Tq, Tk);
+        hipLaunchKernelGGL(b2h_tt_sdpa, dim3(heads), dim3(256), tt_sdpa_lds_bytes(Tq, Tk, false), st, src, mask, sc, O, Tq, Tk,
+                           klen);
     else if (route == TrainAttn::kWholeMfma)
-        hipLaunchKernelGGL(b2h_mw_sdpa, dim3(heads), dim3(256), mw_sdpa_lds_bytes(Tq, Tk, false), st, src, mask, sc, O, Tq, Tk);
+        hipLaunchKernelGGL(b2h_mw_sdpa, dim3(heads), dim3(256), mw_sdpa_lds_bytes(Tq, Tk, false), st, src, mask, sc, O, Tq, Tk,
+                           klen);
     else if (route == TrainAttn::kBlockedMfma)
-        hipLaunchKernelGGL(b2h_mt_sdpa, grid, dim3(256), kMtFwdLds, st, src, mask, sc, O, lse, Tq, Tk);
+        hipLaunchKernelGGL(b2h_mt_sdpa, grid, dim3(256), kMtFwdLds, st, src, mask, sc, O, lse, Tq, Tk, klen);
     else
-        hipLaunchKernelGGL(b2h_lt_sdpa, grid, dim3(256), kLtFwdLds, st, src, mask, sc, O, lse, Tq, Tk);
+        hipLaunchKernelGGL(b2h_lt_sdpa, grid, dim3(256), kLtFwdLds, st, src, mask, sc, O, lse, Tq, Tk, klen);
 }
 
 // Its backward.  Blocked: the query owner (dQ, and the row terms D for the key owner), then the key owner (dK, dV).
 void train_sdpa_bwd(hipStream_t st, TrainAttn route, const AttnSrc& src, const float* dO, const float* lse, float* D,
-                    const uint8_t* mask, float sc, const LtGradDst& dst, int64_t B, int Tq, int Tk) {
+                    const uint8_t* mask, float sc, const LtGradDst& dst, int64_t B, int Tq, int Tk, const int64_t* klen) {
     const unsigned heads = (unsigned)(B * kTtHeads);
     const dim3 gq(heads, lt_blocks(Tq, kLtQb)), gkv(heads, lt_blocks(Tk, kLtKb));
     if (route == TrainAttn::kWhole) {
         hipLaunchKernelGGL(b2h_tt_sdpa_bwd, dim3(heads), dim3(256), tt_sdpa_lds_bytes(Tq, Tk, true), st, src, dO, mask, sc, dst,
-                           Tq, Tk);
+                           Tq, Tk, klen);
     } else if (route == TrainAttn::kWholeMfma) {
         hipLaunchKernelGGL(b2h_mw_sdpa_bwd, dim3(heads), dim3(256), mw_sdpa_lds_bytes(Tq, Tk, true), st, src, dO, mask, sc, dst,
-                           Tq, Tk);
+                           Tq, Tk, klen);
     } else if (route == TrainAttn::kBlockedMfma) {
-        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_q, gq, dim3(256), kMtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
-        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_kv, gkv, dim3(256), kMtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_q, gq, dim3(256), kMtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk, klen);
+        hipLaunchKernelGGL(b2h_mt_sdpa_bwd_kv, gkv, dim3(256), kMtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk, klen);
     } else {
-        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_q, gq, dim3(256), kLtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
-        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_kv, gkv, dim3(256), kLtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk);
+        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_q, gq, dim3(256), kLtBwdQLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk, klen);
+        hipLaunchKernelGGL(b2h_lt_sdpa_bwd_kv, gkv, dim3(256), kLtBwdKvLds, st, src, dO, lse, D, mask, sc, dst, Tq, Tk, klen);
     }
 }
 
 // One torch.nn.TransformerEncoderLayer (post-norm, ReLU) over N = B * T rows in training mode: H -> L.H2.
 // w: its twelve tensors in state_dict order; mk: its four keep-masks attn, drop1, ff, drop2, or nullptr; attn: one of
-// the two whole-matrix routes (T <= 128).
+// the two whole-matrix routes (T <= 128); klen: (B) key lengths or nullptr.
 void tt_enc_layer_forward(const TtLin& ln, TrainAttn attn, const float* const* w, const TtLayer& L, const float* H,
-                          int64_t B, int T, const uint8_t* const* mk, float sc) {
+                          int64_t B, int T, const uint8_t* const* mk, float sc, const int64_t* klen) {
     hipStream_t st = ln.st;
     const int64_t N = B * T;
     const auto mask = [&](int i) { return mk ? mk[i] : nullptr; };
     tt_linear(ln, H, w[0], w[1], L.QKV, N, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
-    train_sdpa(st, attn, self_src(L.QKV), mask(0), sc, L.O, nullptr, B, T, T);
+    train_sdpa(st, attn, self_src(L.QKV), mask(0), sc, L.O, nullptr, B, T, T, klen);
     tt_linear(ln, L.O, w[2], w[3], L.R1, N, kTtD, kTtD, 0, mask(1), sc, H);
     hipLaunchKernelGGL(b2h_tt_layernorm, dim3(tt_row_blocks(N, 4)), dim3(256), 0, st, L.R1, w[8], w[9], L.H1, L.ST, 4, N);
     tt_linear(ln, L.H1, w[4], w[5], L.F1, N, kTtD, kTtD, 1, mask(2), sc, nullptr);
@@ -1647,7 +1709,8 @@ TtGrad tt_grad(float* scratch, int64_t N) {
 
 // Backward of tt_enc_layer_forward: G.gA = dH2 on entry, = dH_in on return; g: the layer's twelve gradients.
 void tt_enc_layer_backward(const TtLin& ln, TrainAttn attn, const float* const* w, float* const* g, const TtLayer& L,
-                           const float* Hin, const TtGrad& G, int64_t B, int T, const uint8_t* const* mk, float sc) {
+                           const float* Hin, const TtGrad& G, int64_t B, int T, const uint8_t* const* mk, float sc,
+                           const int64_t* klen) {
     hipStream_t st = ln.st;
     const int64_t N = B * T;
     const auto mask = [&](int i) { return mk ? mk[i] : nullptr; };
@@ -1663,7 +1726,7 @@ void tt_enc_layer_backward(const TtLin& ln, TrainAttn attn, const float* const* 
     const float* dA = mk ? G.gBm : G.gB;
     tt_linear_dw(ln, dA, L.O, G.slabs, N, kTtD, kTtD, g[2], g[3]);
     tt_linear_dx(ln, dA, w[2], G.gC, N, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);             // gC = dO
-    train_sdpa_bwd(st, attn, self_src(L.QKV), G.gC, nullptr, nullptr, mask(0), sc, self_dst(G.gQ), B, T, T);
+    train_sdpa_bwd(st, attn, self_src(L.QKV), G.gC, nullptr, nullptr, mask(0), sc, self_dst(G.gQ), B, T, T, klen);
     tt_linear_dw(ln, G.gQ, Hin, G.slabs, N, kTtD, 3 * kTtD, g[0], g[1]);
     tt_linear_dx(ln, G.gQ, w[0], G.gA, N, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);          // gA = dH_in
 }
@@ -1739,7 +1802,7 @@ int b2h_tenc_train_forward(b2h_tenc* m, const float* const* params, const float*
     tt_linear(ln, X0, params[1], params[2], H, N, kInCh, kTtD, 0, nullptr, 1.f, nullptr);
     for (int l = 0; l < m->nlayers; ++l) {
         const TtLayer L = tt_layer(Ls, N, l);
-        tt_enc_layer_forward(ln, attn, params + 3 + 12 * l, L, H, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
+        tt_enc_layer_forward(ln, attn, params + 3 + 12 * l, L, H, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc, nullptr);
         H = L.H2;
     }
     const float* const* wh = params + 3 + 12 * m->nlayers;
@@ -1794,7 +1857,8 @@ int b2h_tenc_backward(b2h_tenc* m, const float* const* params, const uint8_t* co
     tt_linear_dx(ln, dy, params[oh], G.gA, N, kTtD, kOutCh, nullptr, nullptr, 1.f, nullptr);
     for (int l = m->nlayers - 1; l >= 0; --l)
         tt_enc_layer_backward(ln, attn, params + 3 + 12 * l, grads + 2 + 12 * l, tt_layer(Ls, N, l),
-                              l ? tt_layer(Ls, N, l - 1).H2 : H0, G, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc);
+                              l ? tt_layer(Ls, N, l - 1).H2 : H0, G, B, (int)T, masks ? masks + 1 + 4 * l : nullptr, sc,
+                              nullptr);
     // pose2hidden_projection (:171) and the positional encoding's dropout (:101-103)
     tt_linear_dw(ln, G.gA, X0, G.slabs, N, kInCh, kTtD, grads[0], grads[1]);
     if (dx) tt_linear_dx(ln, G.gA, params[1], dx, N, kInCh, kTtD, nullptr, mk(0), sc, nullptr);
@@ -1894,14 +1958,23 @@ const char* tptt_shape_refusal(int64_t B, int64_t S, int64_t T) {
     return nullptr;
 }
 
-// Checks shared by b2h_tpt_train_forward / b2h_tpt_backward: tt_check's, then the token ids.
+// Checks shared by b2h_tpt_train_forward_masked / b2h_tpt_backward_masked: tt_check's, then the token ids and the key
+// lengths.
 int tptt_check(const b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks, float p,
-               int64_t B, int64_t S, int64_t T) {
+               int64_t B, int64_t S, int64_t T, const int64_t* text_len, const int64_t* frame_len) {
     if (!m) return fail(B2H_ERR_INVALID, "model is NULL");
     if (int rc = tt_check(tptt_shape_refusal(B, S, T), params, tpt_nparams(m), masks, tpt_nmasks(m), p)) return rc;
     if (B > 0 && !tokens) return fail(B2H_ERR_INVALID, "tokens is NULL");
     if (misaligned(tokens, 8)) return fail(B2H_ERR_INVALID, "tokens must be 8-byte aligned");
+    if (misaligned(text_len, 8) || misaligned(frame_len, 8))
+        return fail(B2H_ERR_INVALID, "text_len and frame_len must be 8-byte aligned int64 arrays");
     return B2H_OK;
+}
+
+// The key lengths of a training call among its read-only operands (check_overlap)
+void tptt_add_lengths(std::vector<Span>& ins, const int64_t* text_len, const int64_t* frame_len, int64_t B) {
+    if (text_len) ins.push_back({text_len, (size_t)B * 8, "a key length array"});
+    if (frame_len) ins.push_back({frame_len, (size_t)B * 8, "a key length array"});
 }
 
 void tt_layernorm(hipStream_t st, const float* X, const float* gamma, const float* beta, float* Y, float* stats, int64_t N) {
@@ -1958,10 +2031,10 @@ size_t b2h_tpt_train_bytes(const b2h_tpt* m, int64_t B, int64_t S, int64_t T, in
     return which == 0 ? tpt_saved_bytes(m, B * S, B * T, tpt_long(T)) : tpt_scratch_bytes(B * S, B * T, tpt_long(T));
 }
 
-int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t* tokens, const float* x,
-                          const uint8_t* const* masks, float p, float* y, void* saved, size_t saved_bytes, int64_t B,
-                          int64_t S, int64_t T, void* stream) {
-    if (int rc = tptt_check(m, params, tokens, masks, p, B, S, T)) return rc;
+int b2h_tpt_train_forward_masked(b2h_tpt* m, const float* const* params, const int64_t* tokens, const float* x,
+                                 const uint8_t* const* masks, float p, float* y, void* saved, size_t saved_bytes, int64_t B,
+                                 int64_t S, int64_t T, const int64_t* text_len, const int64_t* frame_len, void* stream) {
+    if (int rc = tptt_check(m, params, tokens, masks, p, B, S, T, text_len, frame_len)) return rc;
     if (B == 0) return B2H_OK;
     if (!x || !y || !saved) return fail(B2H_ERR_INVALID, "NULL pointer");
     if (int rc = check_device(m->device)) return rc;
@@ -1973,10 +2046,10 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     const size_t need = tpt_saved_bytes(m, Ns, Nt, lng);
     if (saved_bytes < need)
         return fail(B2H_ERR_INVALID, "saved buffer smaller than b2h_tpt_train_bytes (" + std::to_string(need) + " B)");
-    if (int rc = check_overlap({{y, (size_t)Nt * m->nout * 4}, {saved, need}},
-                               tt_read_only(params, tpt_param_floats(m), masks, tpt_mask_bytes(m, B, S, T),
-                                            {{tokens, (size_t)Ns * 8}, {x, (size_t)Nt * m->ninp * 4}})))
-        return rc;
+    std::vector<Span> ins = tt_read_only(params, tpt_param_floats(m), masks, tpt_mask_bytes(m, B, S, T),
+                                         {{tokens, (size_t)Ns * 8}, {x, (size_t)Nt * m->ninp * 4}});
+    tptt_add_lengths(ins, text_len, frame_len, B);
+    if (int rc = check_overlap({{y, (size_t)Nt * m->nout * 4}, {saved, need}}, ins)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const TtLin ln{st, tpt_train_linear(m) == TrainLinear::kMfma};
     const float sc = tt_scale(p);
@@ -1992,7 +2065,7 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     for (int l = 0; l < m->n_enc; ++l) {
         const TtLayer L = sv.enc_layer(l);
         tt_enc_layer_forward(ln, tpt_train_enc_attn(m), params + 12 * l, L, H, B, (int)S, masks ? masks + 4 * l : nullptr,
-                             sc);
+                             sc, text_len);
         H = L.H2;
     }
     const float* const* wn = params + 12 * m->n_enc;
@@ -2008,13 +2081,13 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
         const TptDecLayer L = sv.dec_layer(l);
         tt_linear(ln, H, w[0], w[1], L.QKV, Nt, kTtD, 3 * kTtD, 0, nullptr, 1.f, nullptr);
         float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
-        train_sdpa(st, route, self_src(L.QKV), mk(mi), sc, L.O, lse, B, (int)T, (int)T);
+        train_sdpa(st, route, self_src(L.QKV), mk(mi), sc, L.O, lse, B, (int)T, (int)T, frame_len);
         tt_linear(ln, L.O, w[2], w[3], L.R1, Nt, kTtD, kTtD, 0, mk(mi + 1), sc, H);
         tt_layernorm(st, L.R1, w[12], w[13], L.H1, L.ST12, Nt);
         // multihead_attn: the query of H1 (in_proj rows 0..127), [K | V] of the memory (rows 128..383)
         tt_linear(ln, L.H1, w[4], w[5], L.QC, Nt, kTtD, kTtD, 0, nullptr, 1.f, nullptr);
         tt_linear(ln, sv.MEM, w[4] + kDD, w[5] + kTtD, L.KV, Ns, kTtD, 2 * kTtD, 0, nullptr, 1.f, nullptr);
-        train_sdpa(st, route, cross_src(L.QC, L.KV), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S);
+        train_sdpa(st, route, cross_src(L.QC, L.KV), mk(mi + 2), sc, L.OC, lse + Nt * kTtHeads, B, (int)T, (int)S, text_len);
         tt_linear(ln, L.OC, w[6], w[7], L.R2, Nt, kTtD, kTtD, 0, mk(mi + 3), sc, L.H1);
         tt_layernorm(st, L.R2, w[14], w[15], L.H2, L.ST12 + 2, Nt);
         tt_linear(ln, L.H2, w[8], w[9], L.F1, Nt, kTtD, kTtD, 1, mk(mi + 4), sc, nullptr);
@@ -2029,10 +2102,18 @@ int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t*
     return B2H_OK;
 }
 
-int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks, float p,
-                     const float* dy, const void* saved, size_t saved_bytes, float* dx, float* const* grads, void* scratch,
-                     size_t scratch_bytes, int64_t B, int64_t S, int64_t T, void* stream) {
-    if (int rc = tptt_check(m, params, tokens, masks, p, B, S, T)) return rc;
+int b2h_tpt_train_forward(b2h_tpt* m, const float* const* params, const int64_t* tokens, const float* x,
+                          const uint8_t* const* masks, float p, float* y, void* saved, size_t saved_bytes, int64_t B,
+                          int64_t S, int64_t T, void* stream) {
+    return b2h_tpt_train_forward_masked(m, params, tokens, x, masks, p, y, saved, saved_bytes, B, S, T, nullptr, nullptr,
+                                        stream);
+}
+
+int b2h_tpt_backward_masked(b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks,
+                            float p, const float* dy, const void* saved, size_t saved_bytes, float* dx, float* const* grads,
+                            void* scratch, size_t scratch_bytes, int64_t B, int64_t S, int64_t T, const int64_t* text_len,
+                            const int64_t* frame_len, void* stream) {
+    if (int rc = tptt_check(m, params, tokens, masks, p, B, S, T, text_len, frame_len)) return rc;
     if (B == 0) return fail(B2H_ERR_SHAPE, "b2h_tpt_backward needs B >= 1 (the gradients of an empty batch are not defined here)");
     if (!dy || !saved || !scratch) return fail(B2H_ERR_INVALID, "dy / saved / scratch is NULL");
     if (!grads) return fail(B2H_ERR_INVALID, "grads is NULL");
@@ -2055,9 +2136,10 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
     }
     if (dx) outs.push_back({dx, (size_t)Nt * m->ninp * 4});
     outs.push_back({scratch, need});
-    if (int rc = check_overlap(outs, tt_read_only(params, sizes, masks, tpt_mask_bytes(m, B, S, T),
-                                                  {{tokens, (size_t)Ns * 8}, {dy, (size_t)Nt * m->nout * 4}, {saved, need_saved}})))
-        return rc;
+    std::vector<Span> ins = tt_read_only(params, sizes, masks, tpt_mask_bytes(m, B, S, T),
+                                         {{tokens, (size_t)Ns * 8}, {dy, (size_t)Nt * m->nout * 4}, {saved, need_saved}});
+    tptt_add_lengths(ins, text_len, frame_len, B);
+    if (int rc = check_overlap(outs, ins)) return rc;
 
     hipStream_t st = (hipStream_t)stream;
     const TtLin ln{st, tpt_train_linear(m) == TrainLinear::kMfma};
@@ -2099,7 +2181,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         tt_linear_dx(ln, dC, w[6], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dOC
         const float* lse = sv.LSE + (int64_t)l * Nt * kTptSavedFrameLong; // long T only
         train_sdpa_bwd(st, route, cross_src(L.QC, L.KV), G.gC, lse + Nt * kTtHeads, Drow, mk(mi + 2), sc,
-                       LtGradDst{G.gA, kTtD, 0, dKV, 2 * kTtD, 0, kTtD}, B, (int)T, (int)S);          // gA = dQC, dKV
+                       LtGradDst{G.gA, kTtD, 0, dKV, 2 * kTtD, 0, kTtD}, B, (int)T, (int)S, text_len); // gA = dQC, dKV
         // multihead_attn.in_proj: rows 0..127 from (dQC, H1) over the frames, rows 128..383 from ([dK | dV], MEM)
         // over the tokens, each with the slab count of its own row set
         tt_linear_dw(ln, G.gA, L.H1, G.slabs, Nt, kTtD, kTtD, g[4], g[5]);
@@ -2113,7 +2195,7 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
         const float* dA = masks ? G.gBm : G.gB;
         tt_linear_dw(ln, dA, L.O, G.slabs, Nt, kTtD, kTtD, g[2], g[3]);
         tt_linear_dx(ln, dA, w[2], G.gC, Nt, kTtD, kTtD, nullptr, nullptr, 1.f, nullptr);            // gC = dO
-        train_sdpa_bwd(st, route, self_src(L.QKV), G.gC, lse, Drow, mk(mi), sc, self_dst(G.gQ), B, (int)T, (int)T);
+        train_sdpa_bwd(st, route, self_src(L.QKV), G.gC, lse, Drow, mk(mi), sc, self_dst(G.gQ), B, (int)T, (int)T, frame_len);
         tt_linear_dw(ln, G.gQ, Hin, G.slabs, Nt, kTtD, 3 * kTtD, g[0], g[1]);
         tt_linear_dx(ln, G.gQ, w[0], G.gA, Nt, kTtD, 3 * kTtD, nullptr, nullptr, 1.f, G.gB);         // gA = dH_in
     }
@@ -2129,10 +2211,17 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
                      grads[od - 2], grads[od - 1]);
     for (int l = m->n_enc - 1; l >= 0; --l)
         tt_enc_layer_backward(ln, tpt_train_enc_attn(m), params + 12 * l, grads + 12 * l, sv.enc_layer(l),
-                              l ? sv.enc_layer(l - 1).H2 : sv.E0, G, B, (int)S, masks ? masks + 4 * l : nullptr, sc);
+                              l ? sv.enc_layer(l - 1).H2 : sv.E0, G, B, (int)S, masks ? masks + 4 * l : nullptr, sc, text_len);
     hipLaunchKernelGGL(b2h_tptt_embed_bwd, dim3((unsigned)m->n_tokens), dim3(128), 0, st, tokens, G.gA, grads[ot], Ns);
     HIP_TRY(hipGetLastError());
     return B2H_OK;
+}
+
+int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks, float p,
+                     const float* dy, const void* saved, size_t saved_bytes, float* dx, float* const* grads, void* scratch,
+                     size_t scratch_bytes, int64_t B, int64_t S, int64_t T, void* stream) {
+    return b2h_tpt_backward_masked(m, params, tokens, masks, p, dy, saved, saved_bytes, dx, grads, scratch, scratch_bytes, B, S,
+                                   T, nullptr, nullptr, stream);
 }
 
 } // extern "C"

@@ -36,22 +36,24 @@ constexpr int kLongMinWaves = 5; // waves per workgroup the staging rounds below
 constexpr int attn_long_f32_lds_bytes(int nk) { return 2 * attn_f32_lds_bytes(nk); }
 constexpr int attn_long_h3_lds_bytes(int nk) { return 2 * attn_kv_bytes(nk); }
 
+// attn_long_f32_body is the kernel; kl is the number of key rows attended, as in attn_f32_body (kernel_tenc.h): Tk in
+// b2h_attn_long_f32, the sequence's key length in b2h_attn_long_klen_f32, where the key descriptor and the walk end at
+// row kl, so a key block wholly beyond it is never staged.
 template <int NK>
-__global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(AttnSrc src, float* __restrict__ out, int Tq,
-                                                                        int Tk) {
+__device__ __forceinline__ void attn_long_f32_body(AttnSrc src, float* __restrict__ out, int Tq, int Tk, int kl) {
     extern __shared__ __attribute__((aligned(16))) char smem_al[];
     constexpr int kBuf = attn_f32_lds_bytes(NK);      // K, then V of one key block
     constexpr int kChunks = NK * 16 * 8;              // float4 of a block's K (and of its V)
     constexpr int R = (kChunks + 64 * kLongMinWaves - 1) / (64 * kLongMinWaves); // staging rounds: <= 4
     const int b = blockIdx.x / kTencHeads, h = blockIdx.x % kTencHeads;
-    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + (int64_t)b * Tk * src.ldkv, Tk * src.ldkv * 4);
+    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + (int64_t)b * Tk * src.ldkv, kl * src.ldkv * 4);
     const __amdgpu_buffer_rsrc_t qrs = make_rsrc(src.q + (int64_t)b * Tq * src.ldq, Tq * src.ldq * 4);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nthreads = __builtin_amdgcn_readfirstlane(blockDim.x);
     const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
     const int tq = (int)blockIdx.y * (nthreads >> 2) + wave * 16 + col; // 16 queries per wave
-    const int nkb = (Tk + 16 * NK - 1) / (16 * NK);
-    // key block jb -> registers: rows >= Tk (and chunks past the block) read 0
+    const int nkb = (kl + 16 * NK - 1) / (16 * NK);
+    // key block jb -> registers: rows >= kl (and chunks past the block) read 0
     auto fetch = [&](int jb, f32x4 (&k4)[R], f32x4 (&v4)[R]) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -87,10 +89,10 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(AttnSrc 
 #pragma unroll 1
     for (int jb = 0; jb < nkb; ++jb) {
         const bool more = jb + 1 < nkb;
-        fetch(jb + 1, kr, vr); // past the last block every row is >= Tk: zeros, no memory traffic
+        fetch(jb + 1, kr, vr); // past the last block every row is >= kl: zeros, no memory traffic
         const float* Ks = reinterpret_cast<const float*>(smem_al + (jb & 1) * kBuf);
         const float* Vs = reinterpret_cast<const float*>(smem_al + (jb & 1) * kBuf + kBuf / 2);
-        const int left = more ? 16 * NK : Tk - jb * 16 * NK; // valid keys of this block (>= 1)
+        const int left = more ? 16 * NK : kl - jb * 16 * NK; // valid keys of this block (>= 1)
         f32x4 sc[NK];
         float bm = -INFINITY;
 #pragma unroll
@@ -125,6 +127,19 @@ __global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(AttnSrc 
         }
     }
     attn_store_out(out, b, Tq, tq, h, o, l);
+}
+
+template <int NK>
+__global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_f32(AttnSrc src, float* __restrict__ out, int Tq,
+                                                                        int Tk) {
+    attn_long_f32_body<NK>(src, out, Tq, Tk, Tk);
+}
+
+// b2h_attn_long_f32 with a key-padding mask: klen (B) int64 as in b2h_attn_klen_f32
+template <int NK>
+__global__ __launch_bounds__(64 * kAttnMaxTiles) void b2h_attn_long_klen_f32(AttnSrc src, float* __restrict__ out, int Tq,
+                                                                           int Tk, const int64_t* __restrict__ klen) {
+    attn_long_f32_body<NK>(src, out, Tq, Tk, attn_key_len(klen, blockIdx.x / kTencHeads, Tk));
 }
 
 template <int NK>

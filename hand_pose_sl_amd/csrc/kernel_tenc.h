@@ -137,14 +137,21 @@ __device__ __forceinline__ void attn_store_out(float* out, int64_t b, int Tq, in
 // instructions over the sequence's rows: key rows >= Tk read 0 and are masked to -inf, query rows >= Tq read 0 (a
 // uniform softmax over the valid keys, finite) and their stores are dropped by the range check; nothing is
 // predicated and all loads of a staging round are in flight together.
+// attn_f32_body is the kernel; kl is the number of key rows attended: Tk in b2h_attn_f32, the sequence's key length in
+// b2h_attn_klen_f32, where the key descriptor ends at row kl, so that the rows kl .. Tk - 1 are
+// what the rows past Tk are: zeros, masked to -inf.  Tk stays the stride between two sequences' key rows.
+__device__ __forceinline__ int attn_key_len(const int64_t* __restrict__ klen, int b, int Tk) {
+    const int64_t n = klen[b];
+    return n < 1 ? 1 : n > Tk ? Tk : (int)n;
+}
+
 template <int NK, bool SQ>
-__global__ __launch_bounds__(SQ ? 64 * NK : 64 * kAttnMaxTiles) void b2h_attn_f32(AttnSrc src, float* __restrict__ out,
-                                                                                   int Tq, int Tk) {
+__device__ __forceinline__ void attn_f32_body(AttnSrc src, float* __restrict__ out, int Tq, int Tk, int kl) {
     extern __shared__ __attribute__((aligned(16))) char smem_attn[];
     float* Ks = reinterpret_cast<float*>(smem_attn);
     float* Vs = reinterpret_cast<float*>(smem_attn + attn_f32_lds_bytes(NK) / 2);
     const int b = blockIdx.x / kTencHeads, h = blockIdx.x % kTencHeads;
-    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + (int64_t)b * Tk * src.ldkv, Tk * src.ldkv * 4);
+    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + (int64_t)b * Tk * src.ldkv, kl * src.ldkv * 4);
     const __amdgpu_buffer_rsrc_t qrs = make_rsrc(src.q + (int64_t)b * Tq * src.ldq, Tq * src.ldq * 4);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nthreads = SQ ? 64 * NK : __builtin_amdgcn_readfirstlane(blockDim.x);
@@ -186,11 +193,11 @@ __global__ __launch_bounds__(SQ ? 64 * NK : 64 * kAttnMaxTiles) void b2h_attn_f3
         sc[kt] = tile_rows_dot(Ks, kt, qb, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
         for (int r = 0; r < 4; ++r) { // D row 4q + r = key index within the tile
-            if (kt * 16 + 4 * q + r >= Tk) sc[kt][r] = -INFINITY;
+            if (kt * 16 + 4 * q + r >= kl) sc[kt][r] = -INFINITY;
             mx = fmaxf(mx, sc[kt][r]);
         }
     }
-    mx = quad_max(mx); // finite: key 0 exists (Tk >= 1)
+    mx = quad_max(mx); // finite: key 0 exists (kl >= 1)
     float l = 0.f;
 #pragma unroll
     for (int kt = 0; kt < NK; ++kt)
@@ -204,6 +211,20 @@ __global__ __launch_bounds__(SQ ? 64 * NK : 64 * kAttnMaxTiles) void b2h_attn_f3
 #pragma unroll
     for (int kt = 0; kt < NK; ++kt) tile_cols_acc(Vs, kt, sc[kt], o);
     attn_store_out(out, b, Tq, tq, h, o, l);
+}
+
+template <int NK, bool SQ>
+__global__ __launch_bounds__(SQ ? 64 * NK : 64 * kAttnMaxTiles) void b2h_attn_f32(AttnSrc src, float* __restrict__ out,
+                                                                                   int Tq, int Tk) {
+    attn_f32_body<NK, SQ>(src, out, Tq, Tk, Tk);
+}
+
+// b2h_attn_f32 with a key-padding mask: klen (B) int64, sequence b attends to its first clamp(klen[b], 1, Tk) key rows
+template <int NK, bool SQ>
+__global__ __launch_bounds__(SQ ? 64 * NK : 64 * kAttnMaxTiles) void b2h_attn_klen_f32(AttnSrc src, float* __restrict__ out,
+                                                                                      int Tq, int Tk,
+                                                                                      const int64_t* __restrict__ klen) {
+    attn_f32_body<NK, SQ>(src, out, Tq, Tk, attn_key_len(klen, blockIdx.x / kTencHeads, Tk));
 }
 
 // ---- per-frame chain ---------------------------------------------------------------------

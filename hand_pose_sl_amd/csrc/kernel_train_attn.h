@@ -26,6 +26,14 @@ struct LtGradDst {
     int lddkv, coldk, coldv;
 };
 
+// Key-padding mask as a key length: sequence b attends to its key rows 0 .. kl - 1 only, with
+// kl = klen[b] clamped to [1, Tk], or Tk without klen.  Tk stays the stride of the rows and of the keep-masks.
+__device__ inline int tt_key_len(const int64_t* __restrict__ klen, int64_t b, int Tk) {
+    if (!klen) return Tk;
+    const int64_t n = klen[b];
+    return n < 1 ? 1 : n > Tk ? Tk : (int)n;
+}
+
 __host__ __device__ inline int tt_ps(int Tk) { return Tk | 1; } // LDS row stride of the (Tq, Tk) probabilities
 
 // Dynamic LDS of the pair: Q (and dO) at stride 33 over Tq rows, K and V at stride 33 over Tk rows, the (Tq, Tk)
@@ -43,8 +51,9 @@ __device__ inline void tt_load_head(const float* __restrict__ src, int ld, float
 }
 
 // P[i][j] = softmax_j(Q_i . K_j / sqrt(32)), i < Tq, j < Tk <= 128, one wave per row (a lane: keys lane and
-// lane + 64), PRE-dropout.
-__device__ inline void tt_softmax_rows(const float* Q, const float* K, float* P, int Tq, int Tk) {
+// lane + 64), PRE-dropout.  The softmax runs over the keys j < kl <= Tk; P[i][j] is written as +0 for kl <= j < Tk, so
+// that every sum over the Tk keys downstream adds true zeros for them.
+__device__ inline void tt_softmax_rows(const float* Q, const float* K, float* P, int Tq, int Tk, int kl) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6, ps = tt_ps(Tk);
     for (int i = w; i < Tq; i += nw) {
         float s[2];
@@ -52,23 +61,25 @@ __device__ inline void tt_softmax_rows(const float* Q, const float* K, float* P,
         for (int u = 0; u < 2; ++u) {
             const int j = lane + 64 * u;
             float a = 0.f;
-            if (j < Tk)
+            if (j < kl)
 #pragma unroll
                 for (int d = 0; d < kTtHd; ++d) a = fmaf(Q[i * kTtQs + d], K[j * kTtQs + d], a);
-            s[u] = j < Tk ? a * kTtQkScale : -INFINITY;
+            s[u] = j < kl ? a * kTtQkScale : -INFINITY;
         }
         const float mx = tt_wave_max(fmaxf(s[0], s[1]));
-        const float e0 = expf(s[0] - mx), e1 = lane + 64 < Tk ? expf(s[1] - mx) : 0.f; // lane 0 < Tk always; e0 = 0 past Tk
-        const float sum = tt_wave_sum((lane < Tk ? e0 : 0.f) + e1);
+        const float e0 = expf(s[0] - mx), e1 = lane + 64 < kl ? expf(s[1] - mx) : 0.f; // lane 0 < kl always; e0 = 0 past kl
+        const float sum = tt_wave_sum((lane < kl ? e0 : 0.f) + e1);
         if (lane < Tk) P[i * ps + lane] = e0 / sum;
-        if (lane + 64 < Tk) P[i * ps + lane + 64] = e1 / sum;
+        if (lane + 64 < Tk) P[i * ps + lane + 64] = e1 / sum; // 0 / sum = +0 from kl on
     }
 }
 
 // O[i][32 h + d] = sum_j drop(P)[i][j] V[j][d], O (B*Tq, 128); mask (B, 4, Tq, Tk).
-// grid B * 4, 256 threads, tt_sdpa_lds_bytes(Tq, Tk, false) of dynamic LDS.  1 <= Tq, Tk <= 128.
+// grid B * 4, 256 threads, tt_sdpa_lds_bytes(Tq, Tk, false) of dynamic LDS.  1 <= Tq, Tk <= 128.  klen: (B) key lengths
+// or NULL (tt_key_len).
 __global__ __launch_bounds__(256) void b2h_tt_sdpa(AttnSrc src, const uint8_t* __restrict__ mask, float scale,
-                                                   float* __restrict__ O, int Tq, int Tk) {
+                                                   float* __restrict__ O, int Tq, int Tk,
+                                                   const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) float smem_tt[];
     float* Q = smem_tt;
     float* K = Q + Tq * kTtQs;
@@ -81,7 +92,7 @@ __global__ __launch_bounds__(256) void b2h_tt_sdpa(AttnSrc src, const uint8_t* _
     tt_load_head(kv + src.colk, src.ldkv, K, Tk);
     tt_load_head(kv + src.colv, src.ldkv, V, Tk);
     __syncthreads();
-    tt_softmax_rows(Q, K, P, Tq, Tk);
+    tt_softmax_rows(Q, K, P, Tq, Tk, tt_key_len(klen, b, Tk));
     __syncthreads();
     if (mask) {
         const uint8_t* mk = mask + (int64_t)blockIdx.x * Tq * Tk;
@@ -103,10 +114,11 @@ __global__ __launch_bounds__(256) void b2h_tt_sdpa(AttnSrc src, const uint8_t* _
 //   dV[j] = sum_i Pd[i][j] dO[i];  dP = dO V^T;  dSd = keep ? dP * scale : 0;  dZ = S o (dSd - rowsum(dSd o S));
 //   dQ[i] = sum_j dZ[i][j] K[j] / sqrt(32);  dK[j] = sum_i dZ[i][j] Q[i] / sqrt(32).
 // dO (B*Tq, 128) is the gradient of the concatenated heads.  tt_sdpa_lds_bytes(Tq, Tk, true) of dynamic LDS: Q, dO,
-// K, V, the (Tq, Tk) matrix and the mask bytes.
+// K, V, the (Tq, Tk) matrix and the mask bytes.  With klen the rows kl .. Tk - 1 of dK and dV are written as +0: their
+// columns of S and of dZ are +-0, and a sum that starts at +0 and adds +-0 stays +0.
 __global__ __launch_bounds__(256) void b2h_tt_sdpa_bwd(AttnSrc src, const float* __restrict__ dO,
                                                        const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
-                                                       int Tq, int Tk) {
+                                                       int Tq, int Tk, const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) float smem_tt[];
     float* Q = smem_tt;
     float* G = Q + Tq * kTtQs;
@@ -126,7 +138,7 @@ __global__ __launch_bounds__(256) void b2h_tt_sdpa_bwd(AttnSrc src, const float*
         for (int e = threadIdx.x; e < Tq * Tk; e += 256) Mk[e] = mk[e];
     }
     __syncthreads();
-    tt_softmax_rows(Q, K, P, Tq, Tk);
+    tt_softmax_rows(Q, K, P, Tq, Tk, tt_key_len(klen, b, Tk));
     __syncthreads();
     float* outq = dst.dq + b * Tq * dst.lddq + dst.coldq + h * kTtHd;
     float* outkv = dst.dkv + b * Tk * dst.lddkv + h * kTtHd;

@@ -17,8 +17,13 @@
 // dZ = P o (dSd - D):  dV_j = sum_i Pd_ij dO_i,  dK_j = sum_i dZ_ij Q_i / sqrt(32),  dQ_i = sum_j dZ_ij K_j / sqrt(32).
 //
 // Determinism: a workgroup belongs to one (sequence, head); every output element has one owner thread, which adds
-// its terms in registers in ascending block and row order, an order fixed by (Tq, Tk) alone.  No atomics, no
-// handoff between workgroups, nothing read from another sequence.
+// its terms in registers in ascending block and row order, an order fixed by (Tq, Tk) and the sequence's key length
+// alone.  No atomics, no handoff between workgroups, nothing read from another sequence.
+//
+// Key lengths (klen, tt_key_len): the forward and the query owner end their key walk at
+// kl <= Tk, so every walked block still holds a valid key 0 and the keys from kl on are never read; the key owner
+// treats its block's keys from kl on as it treats keys past Tk, stores +0 for them, and a block wholly beyond kl
+// stores its zeros without walking the queries.
 #pragma once
 #include "kernel_train_attn.h"
 
@@ -50,7 +55,8 @@ __device__ inline float lt_dot(const float* a, const float* b) {
 // rows tid / 32 + 8 r for the output.  The row state lives in LDS: running maximum, running sum and the factor
 // alpha = exp(m_old - m_new) of the current key block (0 on the first block, where m_old is not formed).
 __global__ __launch_bounds__(256) void b2h_lt_sdpa(AttnSrc src, const uint8_t* __restrict__ mask, float scale,
-                                                   float* __restrict__ O, float* __restrict__ lse, int Tq, int Tk) {
+                                                   float* __restrict__ O, float* __restrict__ lse, int Tq, int Tk,
+                                                   const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) float smem_lt[];
     float* Q = smem_lt;
     float* K = Q + kLtQb * kTtQs;
@@ -70,8 +76,9 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa(AttnSrc src, const uint8_t* _
     float acc[kLtQb / 8];
 #pragma unroll
     for (int r = 0; r < kLtQb / 8; ++r) acc[r] = 0.f;
-    for (int j0 = 0; j0 < Tk; j0 += kLtKb) {
-        const int nk = min(kLtKb, Tk - j0); // < 128 only in the last block
+    const int kl = tt_key_len(klen, b, Tk);
+    for (int j0 = 0; j0 < kl; j0 += kLtKb) {
+        const int nk = min(kLtKb, kl - j0); // < 128 only in the last block
         __syncthreads();                    // the previous block is done with K, V, P
         tt_load_head(kv + (int64_t)j0 * src.ldkv + src.colk, src.ldkv, K, nk);
         tt_load_head(kv + (int64_t)j0 * src.ldkv + src.colv, src.ldkv, V, nk);
@@ -152,7 +159,7 @@ __device__ inline void lt_bwd_terms(const float* q, const float* g, const float*
 __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_kv(AttnSrc src, const float* __restrict__ dO,
                                                           const float* __restrict__ lse, const float* __restrict__ D,
                                                           const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
-                                                          int Tq, int Tk) {
+                                                          int Tq, int Tk, const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) float smem_lt[];
     float* Q = smem_lt;
     float* G = Q + kLtQb * kTtQs;
@@ -162,7 +169,8 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_kv(AttnSrc src, const flo
     float* dZ = Pd + kLtQb * kLtPs;
     const int64_t b = blockIdx.x / kTtHeads;
     const int h = blockIdx.x % kTtHeads;
-    const int j0 = blockIdx.y * kLtKb, nk = min(kLtKb, Tk - j0);
+    // nst rows are stored; the first nk of them are attended keys, the others get the +0 their sums start from
+    const int j0 = blockIdx.y * kLtKb, nst = min(kLtKb, Tk - j0), nk = min(nst, tt_key_len(klen, b, Tk) - j0);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, d = threadIdx.x & 31, r0 = threadIdx.x >> 5;
     const float* kv = src.kv + (b * Tk + j0) * src.ldkv + h * kTtHd;
     tt_load_head(kv + src.colk, src.ldkv, K, nk);
@@ -170,7 +178,8 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_kv(AttnSrc src, const flo
     float av[kLtKb / 8], ak[kLtKb / 8];
 #pragma unroll
     for (int r = 0; r < kLtKb / 8; ++r) av[r] = ak[r] = 0.f;
-    for (int i0 = 0; i0 < Tq; i0 += kLtQb) {
+    const int tqw = nk > 0 ? Tq : 0; // (workgroup-uniform) a block with no attended key walks no query: it stores its +0
+    for (int i0 = 0; i0 < tqw; i0 += kLtQb) {
         const int nq = min(kLtQb, Tq - i0);
         __syncthreads(); // the previous block is done with Q, G, Pd, dZ
         tt_load_head(src.q + (b * Tq + i0) * src.ldq + src.colq + h * kTtHd, src.ldq, Q, nq);
@@ -202,7 +211,7 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_kv(AttnSrc src, const flo
 #pragma unroll
     for (int r = 0; r < kLtKb / 8; ++r) {
         const int j = r0 + 8 * r;
-        if (j < nk) {
+        if (j < nst) {
             tt_store(out + (int64_t)j * dst.lddkv + dst.coldk, ak[r]);
             tt_store(out + (int64_t)j * dst.lddkv + dst.coldv, av[r]);
         }
@@ -226,7 +235,7 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_kv(AttnSrc src, const flo
 __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_q(AttnSrc src, const float* __restrict__ dO,
                                                          const float* __restrict__ lse, float* __restrict__ D,
                                                          const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
-                                                         int Tq, int Tk) {
+                                                         int Tq, int Tk, const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) float smem_lt[];
     float* Q = smem_lt;
     float* G = Q + kLtQb * kTtQs;
@@ -246,11 +255,12 @@ __global__ __launch_bounds__(256) void b2h_lt_sdpa_bwd_q(AttnSrc src, const floa
     float aq[kLtQb / 8];
 #pragma unroll
     for (int r = 0; r < kLtQb / 8; ++r) aq[r] = 0.f;
+    const int kl = tt_key_len(klen, b, Tk);
     for (int walk = 0; walk < 2; ++walk)
-        for (int j0 = 0; j0 < Tk; j0 += kLtKb) {
-            const int nk = min(kLtKb, Tk - j0);
+        for (int j0 = 0; j0 < kl; j0 += kLtKb) {
+            const int nk = min(kLtKb, kl - j0);
             __syncthreads(); // the previous block is done with K, V, dZ; the first walk's Ds is complete
-            if (walk == 0 || Tk > kLtKb) { // a single key block is still there
+            if (walk == 0 || kl > kLtKb) { // a single key block is still there
                 tt_load_head(kv + (int64_t)j0 * src.ldkv + src.colk, src.ldkv, K, nk);
                 tt_load_head(kv + (int64_t)j0 * src.ldkv + src.colv, src.ldkv, V, nk);
                 __syncthreads();

@@ -33,6 +33,11 @@
 // forward and the query owner, keys of the key owner) only produce columns that the stores' range check drops.  The
 // mask is read inside [0, Tq) x [0, Tk) only; stores are buffer stores over the sequence's rows.
 //
+// Key lengths (klen, tt_key_len), as in kernel_train_attn_long.h: the forward and the query owner
+// put the end of their key descriptor and of their walk at kl <= Tk, so the keys from kl on are what the keys past Tk
+// were, zeros that are never attended; the key owner forces Pd and dZ of its keys in [kl, Tk) to 0, as it does for the
+// queries >= Tq, and stores the +0 its sums start from for every key tile below Tk that it did not walk.
+//
 // Determinism as in kernel_train_attn_long.h: one (sequence, head) per workgroup, one owner lane per output element,
 // blocks and tiles added in ascending order, inside a tile the k-steps r = 0 .. 3 over the rows 4 q + r, q ascending.
 // No atomics, no handoff between workgroups, nothing read from another sequence.
@@ -78,7 +83,8 @@ __device__ __forceinline__ void mt_put_kv(char* buf, const MtRows& x) {
 // lse_i = m_i + log l_i.  grid (B * 4, ceil(Tq / 64)), 256 threads, kMtFwdLds.  Wave w owns the queries i0 + 16 w ..;
 // the row state (m, l) lives in the registers of the four lanes of a column.
 __global__ __launch_bounds__(256) void b2h_mt_sdpa(AttnSrc src, const uint8_t* __restrict__ mask, float scale,
-                                                   float* __restrict__ O, float* __restrict__ lse, int Tq, int Tk) {
+                                                   float* __restrict__ O, float* __restrict__ lse, int Tq, int Tk,
+                                                   const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) char smem_mt[];
     const int64_t b = blockIdx.x / kTtHeads;
     const int h = blockIdx.x % kTtHeads;
@@ -86,8 +92,9 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa(AttnSrc src, const uint8_t* _
     const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
     const int t0 = blockIdx.y * kMtQb + wave * 16, tq = t0 + col;
     const bool live = t0 < Tq; // wave-uniform: a wave past the end only stages
-    const int nkb = lt_blocks(Tk, kMtKb);
-    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + b * Tk * src.ldkv, Tk * src.ldkv * 4);
+    const int kl = tt_key_len(klen, b, Tk); // the keys walked; Tk stays the stride of the rows and of the mask
+    const int nkb = lt_blocks(kl, kMtKb);
+    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + b * Tk * src.ldkv, kl * src.ldkv * 4);
     const __amdgpu_buffer_rsrc_t qrs = make_rsrc(src.q + b * Tq * src.ldq, Tq * src.ldq * 4);
     const uint8_t* mrow = mask && tq < Tq ? mask + ((int64_t)blockIdx.x * Tq + tq) * Tk : nullptr;
     MtRows nx;
@@ -105,7 +112,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa(AttnSrc src, const uint8_t* _
         if (more) mt_fetch_kv(krs, src, h, (jb + 1) * kMtKb, nx);
         const float* Ks = reinterpret_cast<const float*>(smem_mt + (jb & 1) * kMtKvBuf);
         const float* Vs = Ks + kMtKb * kAttnRow;
-        const int left = min(kMtKb, Tk - jb * kMtKb); // valid keys of this block (>= 1)
+        const int left = min(kMtKb, kl - jb * kMtKb); // valid keys of this block (>= 1)
         if (live) {
             f32x4 sc[kMtKb / 16];
             float bm = -INFINITY;
@@ -131,7 +138,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa(AttnSrc src, const uint8_t* _
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int j = kt * 16 + 4 * q + r;
-                        float e = expf(sc[kt][r] - mn); // keys >= Tk: exp(-inf) = 0
+                        float e = expf(sc[kt][r] - mn); // keys >= kl: exp(-inf) = 0
                         ls += e;
                         if (mask) e = mrow && j < left && mrow[jb * kMtKb + j] ? e * scale : 0.f;
                         sc[kt][r] = e;
@@ -168,7 +175,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa(AttnSrc src, const uint8_t* _
 __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(AttnSrc src, const float* __restrict__ dO,
                                                          const float* __restrict__ lse, float* __restrict__ D,
                                                          const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
-                                                         int Tq, int Tk) {
+                                                         int Tq, int Tk, const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) char smem_mt[];
     const int64_t b = blockIdx.x / kTtHeads;
     const int h = blockIdx.x % kTtHeads;
@@ -176,8 +183,9 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(AttnSrc src, const floa
     const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
     const int t0 = blockIdx.y * kMtQb + wave * 16, tq = t0 + col;
     const bool live = t0 < Tq;
-    const int nkb = lt_blocks(Tk, kMtKb);
-    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + b * Tk * src.ldkv, Tk * src.ldkv * 4);
+    const int kl = tt_key_len(klen, b, Tk);
+    const int nkb = lt_blocks(kl, kMtKb);
+    const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + b * Tk * src.ldkv, kl * src.ldkv * 4);
     const __amdgpu_buffer_rsrc_t qrs = make_rsrc(src.q + b * Tq * src.ldq, Tq * src.ldq * 4);
     const __amdgpu_buffer_rsrc_t grs = make_rsrc(dO + b * Tq * kTtD, Tq * kTtD * 4);
     const int64_t row = (int64_t)blockIdx.x * Tq + tq;
@@ -202,7 +210,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(AttnSrc src, const floa
         if (more) mt_fetch_kv(krs, src, h, (jb + 1 == nkb ? 0 : jb + 1) * kMtKb, nx);
         const float* Ks = reinterpret_cast<const float*>(smem_mt + (nkb > 1 ? t & 1 : 0) * kMtKvBuf);
         const float* Vs = Ks + kMtKb * kAttnRow;
-        const int left = min(kMtKb, Tk - jb * kMtKb);
+        const int left = min(kMtKb, kl - jb * kMtKb);
         if (live) {
             if (t == nkb) { // the first walk's sums are complete
                 sigma = Sg;
@@ -217,7 +225,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(AttnSrc src, const floa
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int j = kt * 16 + 4 * q + r;
-                        // keys >= Tk: P = 0; their V rows are 0, so is dP
+                        // keys >= kl: P = 0; their V rows are 0, so is dP
                         const float p = j < left ? expf(s[r] * kTtQkScale - lse_i) / sigma : 0.f;
                         float dsd = dp[r];
                         if (mask) dsd = mrow && j < left && mrow[jb * kMtKb + j] ? dsd * scale : 0.f;
@@ -258,14 +266,17 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_q(AttnSrc src, const floa
 __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(AttnSrc src, const float* __restrict__ dO,
                                                           const float* __restrict__ lse, const float* __restrict__ D,
                                                           const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
-                                                          int Tq, int Tk) {
+                                                          int Tq, int Tk, const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) char smem_mt[];
     const int64_t b = blockIdx.x / kTtHeads;
     const int h = blockIdx.x % kTtHeads;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
-    const int j0 = blockIdx.y * kMtKb, left = min(kMtKb, Tk - j0);
-    const int nqb = lt_blocks(Tq, kMtQb);
+    const int kl = tt_key_len(klen, b, Tk);
+    // the block's key tiles below `left` are walked, those below `nst` are stored (+0 where not walked)
+    const int j0 = blockIdx.y * kMtKb, nst = min(kMtKb, Tk - j0), left = min(kMtKb, kl - j0);
+    // a block wholly beyond kl (left <= 0) walks no query block: it only stores its zeros, and meets no barrier
+    const int nqb = left > 0 ? lt_blocks(Tq, kMtQb) : 0;
     const __amdgpu_buffer_rsrc_t krs = make_rsrc(src.kv + b * Tk * src.ldkv, Tk * src.ldkv * 4);
     const __amdgpu_buffer_rsrc_t qrs = make_rsrc(src.q + b * Tq * src.ldq, Tq * src.ldq * 4);
     const __amdgpu_buffer_rsrc_t grs = make_rsrc(dO + b * Tq * kTtD, Tq * kTtD * 4);
@@ -342,12 +353,12 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(AttnSrc src, const flo
                             const float p = expf(s[r] * kTtQkScale - ls4[r]) / s4[r];
                             float w = p, dsd = dp[r];
                             if (mask) {
-                                const bool keep = i < nq && j < Tk && mask[(row0 + i0 + i) * Tk + j] != 0;
+                                const bool keep = i < nq && j < kl && mask[(row0 + i0 + i) * Tk + j] != 0;
                                 w = keep ? p * scale : 0.f;
                                 dsd = keep ? dsd * scale : 0.f;
                             }
-                            pd[r] = i < nq ? w : 0.f;
-                            dz[r] = i < nq ? p * (dsd - d4[r]) * kTtQkScale : 0.f;
+                            pd[r] = i < nq && j < kl ? w : 0.f; // a key in [kl, Tk) is stored, so it must sum zeros
+                            dz[r] = i < nq && j < kl ? p * (dsd - d4[r]) * kTtQkScale : 0.f;
                         }
                         tile_cols_acc(Gs, qt, pd, av[u]);
                         tile_cols_acc(Qs, qt, dz, ak[u]);
@@ -365,7 +376,7 @@ __global__ __launch_bounds__(256) void b2h_mt_sdpa_bwd_kv(AttnSrc src, const flo
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int kt = wave + 4 * u, off = (j0 + kt * 16 + col) * dst.lddkv + h * kTtHd + 4 * q;
-        if (kt * 16 < left) {
+        if (kt * 16 < nst) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
                 buf_store4(ors, off + dst.coldk + 16 * mt, ak[u][mt]);

@@ -36,7 +36,7 @@
 // for queries in [Tq, 16 ceil(Tq / 16)); the mask is read inside [0, Tq) x [0, Tk) only; stores go through descriptors
 // over the sequence's rows, which drop rows past the end.
 //
-// Determinism: a function of (Tq, Tk) alone.  No atomics, nothing read from another sequence.
+// Determinism: a function of (Tq, Tk) and the sequence's key length alone.  No atomics, nothing read from another sequence.
 #pragma once
 #include "kernel_train_attn.h"
 #include "kernel_train_linear_mfma.h" // ml_load1, mt_zero4
@@ -99,17 +99,19 @@ __device__ __forceinline__ void mw_rows_dot(const float* X, int nkt, const float
 
 // The rows i0 .. i0 + 15 of P hold Q_i . K_j for j < mw_pad(Tk): replaced by drop(softmax_j(. / sqrt(32))), with the
 // reductions of tt_softmax_rows (one wave per row, a lane holds the keys lane and lane + 64).  mk: the keep-mask
-// (Tq, Tk) of this (sequence, head) or NULL.  Keys in [Tk, mw_pad(Tk)) and rows >= Tq are written as 0.
-__device__ __forceinline__ void mw_softmax_tile(float* P, int ps, int i0, int Tq, int Tk, const uint8_t* mk, float scale) {
+// (Tq, Tk) of this (sequence, head) or NULL.  Keys in [kl, mw_pad(Tk)) and rows >= Tq are written as 0: kl <= Tk is the
+// sequence's key length (tt_key_len), the softmax runs over the keys below it.
+__device__ __forceinline__ void mw_softmax_tile(float* P, int ps, int i0, int Tq, int Tk, int kl, const uint8_t* mk,
+                                                float scale) {
     const int lane = threadIdx.x & 63, tkp = mw_pad(Tk);
-    const bool in0 = lane < Tk, in1 = lane + 64 < Tk;
+    const bool in0 = lane < kl, in1 = lane + 64 < kl;
     for (int i = i0; i < i0 + 16; ++i) {
         float* row = P + i * ps;
         float p0 = 0.f, p1 = 0.f;
         if (i < Tq) { // (uniform)
             const float s0 = in0 ? row[lane] * kTtQkScale : -INFINITY, s1 = in1 ? row[lane + 64] * kTtQkScale : -INFINITY;
             const float mx = tt_wave_max(fmaxf(s0, s1));
-            const float e0 = expf(s0 - mx), e1 = in1 ? expf(s1 - mx) : 0.f; // e0 = 0 past Tk
+            const float e0 = expf(s0 - mx), e1 = in1 ? expf(s1 - mx) : 0.f; // e0 = 0 past kl
             const float sum = tt_wave_sum((in0 ? e0 : 0.f) + e1);
             p0 = e0 / sum;
             p1 = e1 / sum;
@@ -198,7 +200,8 @@ __device__ __forceinline__ void mw_store(__amdgpu_buffer_rsrc_t rs, int ld, int 
 
 // S^T tiles of the wave's query tiles -> P, then their rows' softmax (and dropout, under mk)
 __device__ __forceinline__ void mw_probs(const float* K, float* P, int ps, const int (&i0)[2], bool two,
-                                         const float (&qf)[2][kTtHd / 4], int Tq, int Tk, const uint8_t* mk, float scale) {
+                                         const float (&qf)[2][kTtHd / 4], int Tq, int Tk, int kl, const uint8_t* mk,
+                                         float scale) {
     const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
     mw_rows_dot(K, mw_pad(Tk) >> 4, qf[0], qf[1], two, [&](int kt, f32x4 c0, f32x4 c1) {
         // c_u[r] = S[i0_u + col][16 kt + 4 q + r]
@@ -212,15 +215,16 @@ __device__ __forceinline__ void mw_probs(const float* K, float* P, int ps, const
         }
     });
     __builtin_amdgcn_wave_barrier(); // the rows are read back across the wave's lanes (LDS serves a wave in order)
-    mw_softmax_tile(P, ps, i0[0], Tq, Tk, mk, scale);
-    if (two) mw_softmax_tile(P, ps, i0[1], Tq, Tk, mk, scale);
+    mw_softmax_tile(P, ps, i0[0], Tq, Tk, kl, mk, scale);
+    if (two) mw_softmax_tile(P, ps, i0[1], Tq, Tk, kl, mk, scale);
     __builtin_amdgcn_wave_barrier();
 }
 
 // O[i][32 h + d] = sum_j drop(P)[i][j] V[j][d]: b2h_tt_sdpa.  grid B * 4, 256 threads,
-// mw_sdpa_lds_bytes(Tq, Tk, false) of dynamic LDS.  1 <= Tq, Tk <= 128.
+// mw_sdpa_lds_bytes(Tq, Tk, false) of dynamic LDS.  1 <= Tq, Tk <= 128.  klen: (B) key lengths or NULL (tt_key_len).
 __global__ __launch_bounds__(256) void b2h_mw_sdpa(AttnSrc src, const uint8_t* __restrict__ mask, float scale,
-                                                   float* __restrict__ O, int Tq, int Tk) {
+                                                   float* __restrict__ O, int Tq, int Tk,
+                                                   const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) float smem_mw[];
     float* K = smem_mw;
     float* V = K + mw_pad(Tk) * kMwRow;
@@ -240,7 +244,8 @@ __global__ __launch_bounds__(256) void b2h_mw_sdpa(AttnSrc src, const uint8_t* _
     for (int u = 0; u < 2; ++u) mw_frag(qrs, (i0[u] + col) * src.ldq + src.colq + h * kTtHd + q, qf[u]);
     __syncthreads();
     if (i0[0] >= Tq) return; // (uniform) no query tile for this wave; no barrier follows
-    mw_probs(K, P, ps, i0, two, qf, Tq, Tk, mask ? mask + (int64_t)blockIdx.x * Tq * Tk : nullptr, scale);
+    mw_probs(K, P, ps, i0, two, qf, Tq, Tk, tt_key_len(klen, b, Tk), mask ? mask + (int64_t)blockIdx.x * Tq * Tk : nullptr,
+             scale);
     f32x4 o[2][2];
     mw_zero(o);
     mw_acc_over_cols(V, P, ps, i0, two, (Tk + 3) >> 2, o);
@@ -249,10 +254,11 @@ __global__ __launch_bounds__(256) void b2h_mw_sdpa(AttnSrc src, const uint8_t* _
 
 // Backward of b2h_mw_sdpa for one (sequence, head): b2h_tt_sdpa_bwd.  grid B * 4, 256 threads,
 // mw_sdpa_lds_bytes(Tq, Tk, true) of dynamic LDS: Q, dO, K, V, the (Tq, Tk) matrix (S, then dZ / sqrt(32)) and the
-// mask bytes.
+// mask bytes.  With klen the columns kl .. Tk - 1 of S and of dZ are +-0, so the rows kl .. Tk - 1 of dK and dV, sums
+// from +0, are written as +0.
 __global__ __launch_bounds__(256) void b2h_mw_sdpa_bwd(AttnSrc src, const float* __restrict__ dO,
                                                        const uint8_t* __restrict__ mask, float scale, LtGradDst dst,
-                                                       int Tq, int Tk) {
+                                                       int Tq, int Tk, const int64_t* __restrict__ klen) {
     extern __shared__ __attribute__((aligned(16))) float smem_mw[];
     float* Q = smem_mw;
     float* G = Q + mw_pad(Tq) * kMwRow;
@@ -284,7 +290,7 @@ __global__ __launch_bounds__(256) void b2h_mw_sdpa_bwd(AttnSrc src, const float*
         mw_frag(grs, (t0[u] + col) * kTtD + h * kTtHd + q, gf[u]);
     }
     __syncthreads();
-    if (qone) mw_probs(K, P, ps, t0, qtwo, qf, Tq, Tk, nullptr, 1.f); // P = S
+    if (qone) mw_probs(K, P, ps, t0, qtwo, qf, Tq, Tk, tt_key_len(klen, b, Tk), nullptr, 1.f); // P = S
     __syncthreads();
     const __amdgpu_buffer_rsrc_t okv = make_rsrc(dst.dkv + b * Tk * dst.lddkv, Tk * dst.lddkv * 4);
     f32x4 o[2][2];

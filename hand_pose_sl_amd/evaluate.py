@@ -18,6 +18,7 @@ the loader an epoch does no host work per batch.
 import torch
 
 from .metrics import l1_to_pixels, masked_pose_l1, weighted_pose_l1
+from .padding import check_mask_padding, padding_lengths
 from .text_pose_transformer import TextPoseTransformer
 
 LOSSES = ("L1", "confL1")  # the two `--loss` choices validate() can evaluate (traintest.py:207-210)
@@ -50,7 +51,7 @@ def _check_model_name(what, model, args):
     return text
 
 
-def train_epoch(model, train_loader, criterion=None, optimizer=None, args=None, *, loss=None):
+def train_epoch(model, train_loader, criterion=None, optimizer=None, args=None, *, loss=None, mask_padding=False):
     """One epoch of the reference's training loop (steps/traintest.py:80,87-128) for its three models: per batch the
     forward -- model(batch["body_kp"]) or, for a TextPoseTransformer, model(batch["text_tokens"], batch["input_kp"]) --,
     the criterion, optimizer.zero_grad(), loss.backward(), optimizer.step().  `criterion`, `args.loss` and `args.model`
@@ -58,7 +59,13 @@ def train_epoch(model, train_loader, criterion=None, optimizer=None, args=None, 
     reads a frame at or beyond n_frames[i], so it changes neither the loss nor a gradient.  `train_loader`: a
     DeviceLoader, or any iterable of the reference's batch dicts.  Returns the mean of the batch losses as AverageMeter
     accumulates it (steps/utils.py:11-25: the sum of the `loss.item()` floats over their count), with one host
-    synchronisation per epoch: the per-batch losses stay on the device until the end."""
+    synchronisation per epoch: the per-batch losses stay on the device until the end.
+
+    mask_padding (not in the reference; TextPoseTransformer only, else ValueError): the model gets the key-padding
+    masks of the batch, text_lengths = token_lengths(batch["text_tokens"]) (one more tiny launch per step) and
+    frame_lengths = batch["n_frames"], so padded token ids and padded frames are not attended.  A model trained
+    with masks must be validated and run with masks."""
+    mask_padding = check_mask_padding("train_epoch()", model, mask_padding)
     loss = _loss_name(criterion, args, loss)
     if loss not in LOSSES:
         raise ValueError(f"train_epoch() trains with --loss L1 or confL1, not {loss!r}")
@@ -71,7 +78,8 @@ def train_epoch(model, train_loader, criterion=None, optimizer=None, args=None, 
     for batch in train_loader:
         if text:   # traintest.py:105-107
             pose = batch["input_kp"] if "input_kp" in batch else batch["body_kp"]
-            prediction = model(batch["text_tokens"].to(dev), pose.to(dev))
+            lengths = padding_lengths(batch, dev) if mask_padding else {}
+            prediction = model(batch["text_tokens"].to(dev), pose.to(dev), **lengths)
         else:
             prediction = model(batch["body_kp"].to(dev))
         target = batch["target_kp"].to(dev)
@@ -89,7 +97,8 @@ def train_epoch(model, train_loader, criterion=None, optimizer=None, args=None, 
     return sum(values) / len(values)
 
 
-def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=None, return_pixels=False):
+def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=None, return_pixels=False,
+             mask_padding=False):
     """`validate(model, val_loader, criterion, device, args)` exactly as steps/traintest.py:136,168 calls it
     -- `criterion` a maskedPoseL1 / poderatedPoseL1 instance (the reference's or `hand_pose_sl_amd`'s: only
     its class name is read, the HIP reduction of that name computes it), `device` ignored (the model's device
@@ -104,7 +113,8 @@ def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=
     for confL1), tensors on the host or the device as the reference's loader yields them.
     Returns the mean over batches of the batch losses (a float), like the reference; with
     return_pixels also L12Pixels(J, 1280) of it with J the prediction's joint count -- 21, or 4 / 12 for a model of
-    `--predict right_index` / `right_3fingers` (traintest.py:21-28,139)."""
+    `--predict right_index` / `right_3fingers` (traintest.py:21-28,139).  mask_padding: as for train_epoch()."""
+    mask_padding = check_mask_padding("validate()", model, mask_padding)
     loss = _loss_name(criterion, args, loss)
     if loss not in LOSSES:
         # MSE / huber make the reference's validate() fail with an unbound `loss` (traintest.py:207-211)
@@ -117,10 +127,11 @@ def validate(model, val_loader, criterion=None, device=None, args=None, *, loss=
         for batch in val_loader:
             if text:   # traintest.py:193-195
                 pose = batch["input_kp"] if "input_kp" in batch else batch["body_kp"]
+                lengths = padding_lengths(batch, dev) if mask_padding else {}
                 if pose.shape[1] > 128:   # model(tokens, pose) keeps its 128-frame limit: the long path, no transforms
-                    prediction = model.forward_long(batch["text_tokens"], pose)
+                    prediction = model.forward_long(batch["text_tokens"], pose, **lengths)
                 else:
-                    prediction = model(batch["text_tokens"], pose)
+                    prediction = model(batch["text_tokens"], pose, **lengths)
             else:
                 prediction = model(batch["body_kp"])
             target = batch["target_kp"].to(dev)

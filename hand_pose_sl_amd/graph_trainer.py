@@ -19,7 +19,11 @@ The graph is captured again (after one more eager step) when something baked int
 train-linear and dropout switches, Adam's betas, eps, weight_decay and its four step-control options (max_grad_norm,
 skip_nonfinite, warmup_steps, schedule; the warmup's progress is the step word and is not), the batch geometry or the store, the
 loader's `Augment` fields or its key words' storage (the epoch word's value is not: `plan_epoch()` rewrites it in place), or the
-storage of a parameter.  The learning rate is not baked in: `epoch()` calls `optimizer.sync_hyper()`.
+storage of a parameter, or `mask_padding`.  The learning rate is not baked in: `epoch()` calls `optimizer.sync_hyper()`.
+
+`mask_padding=True` (TextPoseTransformer only) is train_epoch()'s: the step hands the model the batch's key-padding masks.
+The b2h_token_lengths launch that makes text_lengths is part of the captured step and reads the capture's own batch
+buffers, as the forward reads n_frames from them.
 """
 import ctypes
 
@@ -30,6 +34,7 @@ from .dataset import DeviceLoader
 from .evaluate import LOSSES, _loss_name
 from .metrics import masked_pose_l1, weighted_pose_l1
 from .optim import Adam
+from .padding import check_mask_padding, padding_lengths
 from .text_pose_transformer import TextPoseTransformer
 
 
@@ -47,7 +52,8 @@ class GraphTrainer:
     and `replays` count the graph captures and replays made so far.  Refuses at construction, before any GPU work,
     what a captured step cannot contain; each message names the remedy."""
 
-    def __init__(self, model, loader, optimizer, criterion=None, *, loss=None):
+    def __init__(self, model, loader, optimizer, criterion=None, *, loss=None, mask_padding=False):
+        self.mask_padding = check_mask_padding("GraphTrainer", model, mask_padding)
         if not isinstance(loader, DeviceLoader):
             raise ValueError("GraphTrainer replays steps that build their batch on the device: put the training set into a "
                              "hand_pose_sl_amd.DeviceDataset and pass a hand_pose_sl_amd.DeviceLoader over it (or use "
@@ -82,7 +88,7 @@ class GraphTrainer:
         g = self.optimizer.param_groups[0]
         drop = m.__dict__.get("_drop_step")
         return (getattr(m, "train_kernels", None), getattr(m, "train_linear", None), getattr(m, "train_whole", None),
-                getattr(m, "dropout_source", None),
+                getattr(m, "dropout_source", None), bool(self.mask_padding),
                 getattr(m, "_drop_seed", None), _dropout_p(m), None if drop is None else drop.data_ptr(),
                 float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                 self.optimizer.max_grad_norm, self.optimizer.skip_nonfinite, self.optimizer.warmup_steps, self.optimizer.schedule,
@@ -106,7 +112,11 @@ class GraphTrainer:
     def _train_on(self, batch):
         """forward, loss, backward, Adam and the record of one batch, in train_epoch()'s order; returns the loss."""
         m, opt, dev = self.model, self.optimizer, self.loader.ds.device
-        prediction = m(batch["text_tokens"], batch["input_kp"]) if self._text else m(batch["body_kp"])
+        if self._text:
+            lengths = padding_lengths(batch, dev) if self.mask_padding else {}
+            prediction = m(batch["text_tokens"], batch["input_kp"], **lengths)
+        else:
+            prediction = m(batch["body_kp"])
         if self.loss == "L1":
             value = masked_pose_l1(prediction, batch["target_kp"], batch["n_frames"])
         else:

@@ -42,6 +42,7 @@ import torch
 
 from . import openpose
 from .conv_model import ConvModel
+from .padding import check_mask_padding, token_lengths
 from .text_pose_transformer import TextPoseTransformer
 from .transformer_enc import TransformerEnc
 
@@ -57,12 +58,16 @@ def pad_tokens(ids, n=N_TOKENS_PER_UTTERANCE):
     return ids + [0] * (n - len(ids))
 
 
-def predict_utterances(model, utterances, max_frames=200, dif_encoding=False, normalize=True, tokens=None):
+def predict_utterances(model, utterances, max_frames=200, dif_encoding=False, normalize=True, tokens=None,
+                       mask_padding=False):
     """`utterances`: list of frame lists (paths or dicts).  Returns (pred_px (U, max_frames, J, 2)
     numpy in pixel units, list of n_frames), J = 21, or the 4 / 12 finger joints of a composite TextPoseTransformer,
     which also reads the utterances' right hands.  Same staging as the reference's dataset (first
     `max_frames` frames, short utterances padded by repeating frame 0).  `tokens`: for a
-    TextPoseTransformer, one list of token ids per utterance (staged with `pad_tokens`)."""
+    TextPoseTransformer, one list of token ids per utterance (staged with `pad_tokens`).  `mask_padding`
+    (TextPoseTransformer only): run with the key-padding masks of the padded ids and frames, as a model trained with
+    train_epoch(mask_padding=True) needs."""
+    mask_padding = check_mask_padding("predict_utterances()", model, mask_padding)
     items = [openpose.load_utterance(u, max_frames) for u in utterances]
     body = torch.from_numpy(np.stack([it["body_kp"] for it in items]))
     dev = next(model.parameters()).device
@@ -73,6 +78,8 @@ def predict_utterances(model, utterances, max_frames=200, dif_encoding=False, no
         lead = (torch.tensor([pad_tokens(t) for t in tokens], dtype=torch.int64),)
         if model.ninp in (42, 58):   # `--predict right_3fingers` / `right_index`
             extra = {"right_hand": torch.from_numpy(np.stack([it["right_hand_kp"] for it in items])).to(dev)}
+        if mask_padding:
+            extra.update(text_lengths=token_lengths(lead[0].to(dev)), frame_lengths=[it["n_frames"] for it in items])
     elif tokens is not None:
         raise ValueError("`tokens` is for a TextPoseTransformer")
     with torch.no_grad():   # steps/utils.py:180-210 and traintest.py:270-271 fused into the model's kernels
@@ -82,11 +89,11 @@ def predict_utterances(model, utterances, max_frames=200, dif_encoding=False, no
 
 
 def predict_all_frames(model, utterances, max_frames=200, dif_encoding=False, normalize=True, tokens=None,
-                       predict="right_hand", batch_size=128):
+                       predict="right_hand", batch_size=128, mask_padding=False):
     """`utterances` as predict_utterances takes them, every frame of each predicted (predict_dataset over windows of
     `max_frames` frames, short utterances padded by repeating frame 0).  Returns one (n_i, J, 2) numpy array per
     utterance in pixel units, J = 21, or the 4 / 12 predicted finger joints; with `dif_encoding` the loader's transforms
-    are the trainer's and the prediction gets the raw wrist back."""
+    are the trainer's and the prediction gets the raw wrist back.  `mask_padding`: predict_dataset's."""
     from .dataset import DeviceDataset, DeviceLoader
     from .predict import predict_dataset
     if isinstance(model, TextPoseTransformer):
@@ -99,7 +106,7 @@ def predict_all_frames(model, utterances, max_frames=200, dif_encoding=False, no
     loader = DeviceLoader(ds, batch_size, max_frames, selection="first", predict=predict, dif_encoding=dif_encoding,
                           normalize=normalize, pad="frame0")
     hand = slice(33 + openpose.PREDICT_TARGET_JOINTS[predict].start, 33 + openpose.PREDICT_TARGET_JOINTS[predict].stop)
-    return [np.stack([r[:, :54][:, hand], r[:, 54:108][:, hand]], axis=2) for r in predict_dataset(model, loader).utterance_rows()]
+    return [np.stack([r[:, :54][:, hand], r[:, 54:108][:, hand]], axis=2) for r in predict_dataset(model, loader, mask_padding=mask_padding).utterance_rows()]
 
 
 def _tpt_geometry(state):
@@ -164,10 +171,17 @@ def main(argv=None):
                          "device-resident store), not only the first --max-frames; --dif-encoding then means the trainer's "
                          "pair of transforms (hand minus raw wrist, body minus chest) with the wrist added back to the output")
     ap.add_argument("--batch-size", type=int, default=128, help="--all-frames: windows per model launch (traintest.py:339)")
+    ap.add_argument("--mask-padding", action="store_true",
+                    help="TextPoseTransformer, --precision fp32: key-padding masks for the padded token ids and frames; "
+                         "required for a checkpoint trained with mask_padding=True, wrong for one trained without")
     args = ap.parse_args(argv)
     if args.predict != "right_hand" and args.model != "TextPoseTransformer":
         # the reference's ConvModel / TransformerEnc hard-code 12 input and 21 output joints (HandPoseModels.py:28,32)
         raise SystemExit(f"--predict {args.predict} needs --model TextPoseTransformer")
+    if args.mask_padding and args.model != "TextPoseTransformer":
+        raise SystemExit("--mask-padding needs --model TextPoseTransformer")
+    if args.mask_padding and args.precision != "fp32":
+        raise SystemExit("--mask-padding runs with --precision fp32 (the f16x3 attention kernels take no key lengths)")
     if args.model == "TextPoseTransformer":
         if not args.tokens and not (args.text is not None and args.tokenizer):
             _utterance_tokens(args, [])   # raises SystemExit with the message
@@ -205,11 +219,12 @@ def main(argv=None):
     model = model.to("cuda").eval()
     if args.all_frames:
         pred = predict_all_frames(model, [u for _, u in utts], args.max_frames, args.dif_encoding, args.normalize,
-                                  tokens=tokens, predict=args.predict, batch_size=args.batch_size)
+                                  tokens=tokens, predict=args.predict, batch_size=args.batch_size,
+                                  mask_padding=args.mask_padding)
         n_frames = [len(p) for p in pred]
     else:
         pred, n_frames = predict_utterances(model, [u for _, u in utts], args.max_frames, args.dif_encoding,
-                                            args.normalize, tokens=tokens)
+                                            args.normalize, tokens=tokens, mask_padding=args.mask_padding)
     os.mkdir(args.output_folder)
     for (folder, frames), p, n in zip(utts, pred, n_frames):
         if merged:

@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from .conv_model import ConvModel
 from .dataset import DeviceDataset, DeviceLoader, _ptr
+from .padding import check_mask_padding, padding_lengths
 from .text_pose_transformer import TextPoseTransformer
 from .transformer_enc import TransformerEnc
 
@@ -81,14 +82,17 @@ def _check(model, loader, conf):
     return False
 
 
-def predict_dataset(model, loader, coverage="all", conf=1.0):
+def predict_dataset(model, loader, coverage="all", conf=1.0, mask_padding=False):
     """Run `model` over the whole store of `loader` (a DeviceLoader: it supplies the store, batch_size, max_frames,
     predict, the transforms, the factor and the pad; its selection and shuffle are not used) and return a DeviceDataset
     with the same offsets, tokens and n_body whose predicted right-hand joints hold the predictions in store units --
     * factor, + the raw wrist under dif_encoding -- with confidence `conf`; every other word is the input store's.
     coverage "all" predicts every frame (`window_plan`), "first" the first max_frames of each utterance.  The model
     runs in eval mode under no_grad in the precision it is set to (its mode is restored), dispatched as validate()
-    dispatches; the loop does no host synchronisation."""
+    dispatches; the loop does no host synchronisation.  mask_padding (TextPoseTransformer only, else ValueError):
+    every window runs with its key-padding masks, text_lengths = token_lengths(tokens) and frame_lengths = the window's
+    n_frames, as train_epoch(mask_padding=True) trains; a model trained with masks must be run with them."""
+    mask_padding = check_mask_padding("predict_dataset()", model, mask_padding)
     text = _check(model, loader, conf)
     ds, B = loader.ds, loader.batch_size
     utt, start, skip = (t.to(ds.device) for t in window_plan(ds, loader.max_frames, coverage))
@@ -106,9 +110,11 @@ def predict_dataset(model, loader, coverage="all", conf=1.0):
                 if not text:
                     prediction = model(batch["body_kp"])
                 elif loader.max_frames > 128:   # model(tokens, pose) keeps its 128-frame limit: the long path
-                    prediction = model.forward_long(batch["text_tokens"], batch["input_kp"])
+                    lengths = padding_lengths(batch, ds.device) if mask_padding else {}
+                    prediction = model.forward_long(batch["text_tokens"], batch["input_kp"], **lengths)
                 else:
-                    prediction = model(batch["text_tokens"], batch["input_kp"])
+                    lengths = padding_lengths(batch, ds.device) if mask_padding else {}
+                    prediction = model(batch["text_tokens"], batch["input_kp"], **lengths)
                 loader.write_back(prediction.contiguous(), u, s, k, rows_out, conf)
     finally:
         model.train(was_training)

@@ -10,8 +10,15 @@ with the caller, as in the reference (traintest.py:105-107).  The geometries are
 (n_joints, nout) = (12, 42) (infer_utterance.py:79-80), (8, 42) (run.py:100-101, the trainer's default), (29, 8)
 (`--predict right_index`, run.py:92-93) and (21, 24) (`right_3fingers`, :96-97), and any other pairing of those
 values (n_joints * joints_dim in {16, 24, 42, 58}, nout in {8, 24, 42}).  The torch containers only hold parameters: the forward runs
-through the C ABI (`b2h_tpt_forward`).  Like the reference, the model passes no mask (padded token id 0 is attended
-like any other id) and never applies its two positional encodings, which exist only as `pe` buffers.
+through the C ABI (`b2h_tpt_forward`).  Like the reference, the model by default passes no mask (padded token id 0 is
+attended like any other id) and never applies its two positional encodings, which exist only as `pe` buffers.
+
+Key-padding masks (not in the reference): `text_lengths` and `frame_lengths`, keywords of
+`forward`, `forward_long`, `forward_fused` and `_forward_train`, each a tensor or sequence of shape (B,) or None.  Padding
+is a suffix, so torch's src / memory key-padding masks are `text_lengths` (`token_lengths(tokens)`) and its tgt
+key-padding mask is `frame_lengths` (the loader's `n_frames`): key j of sequence b is attended iff
+j < clamp(length[b], 1, rows).  A length of 0 counts as 1, where torch returns NaN.  Exact fp32 only: with
+`set_precision("f16x3")` a length is refused.  A model trained with masks must be run with masks.
 
 Training: in training mode with autograd enabled and a parameter or `input_pose` requiring a gradient,
 `model(input_tokens, input_pose)` runs `_native.TrainFn` -- an exact-fp32 HIP forward and backward
@@ -178,18 +185,39 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
             if lo < 0 or hi >= self.n_tokens:
                 raise IndexError("index out of range in self")  # nn.Embedding's message
 
-    def _forward_train(self, input_tokens, input_pose, masks):
-        """The differentiable forward (`_native.TrainFn`) with the given keep-masks (`_draw_dropout_masks`)."""
+    def _key_lengths(self, lengths, name, B, dev):
+        """A key-length argument as the int64 (B,) tensor on `dev` the entry points read, or None."""
+        if lengths is None:
+            return None
+        t = torch.as_tensor(lengths).detach().to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+        if t.shape != (B,):
+            raise RuntimeError(f"expected {name} of shape ({B},), got {tuple(t.shape)}")
+        return t
+
+    @staticmethod
+    def _check_lengths(B, text_lengths, frame_lengths):
+        """The shape refusal of `_key_lengths`, where nothing has been moved to a device yet."""
+        for lengths, name in ((text_lengths, "text_lengths"), (frame_lengths, "frame_lengths")):
+            if lengths is not None and tuple(torch.as_tensor(lengths).shape) != (B,):
+                raise RuntimeError(f"expected {name} of shape ({B},), got {tuple(torch.as_tensor(lengths).shape)}")
+
+    def _forward_train(self, input_tokens, input_pose, masks, text_lengths=None, frame_lengths=None):
+        """The differentiable forward (`_native.TrainFn`) with the given keep-masks (`_draw_dropout_masks`) and key
+        lengths, which travel to the backward next to the token ids."""
         self._check_inputs(input_tokens, input_pose)
         dev = self._device()
         tok = input_tokens.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
         x = input_pose.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
         p = self._dropout_p
         masks = self._checked_masks(masks, p, x.device, tok.shape[0], tok.shape[1], x.shape[1])
-        return TrainFn.apply(self, p, masks, tok, x, *self._tensors())
+        tl = self._key_lengths(text_lengths, "text_lengths", tok.shape[0], dev)
+        fl = self._key_lengths(frame_lengths, "frame_lengths", tok.shape[0], dev)
+        lead = tok if tl is None and fl is None else (tok, tl, fl)
+        return TrainFn.apply(self, p, masks, lead, x, *self._tensors())
 
     # what TrainFn asks of the model: the token ids are an argument of their own; the two routes travel to the backward
     _TRAIN_FNS = ("b2h_tpt_train_bytes", "b2h_tpt_train_forward", "b2h_tpt_backward")
+    _TRAIN_FNS_MASKED = ("b2h_tpt_train_bytes", "b2h_tpt_train_forward_masked", "b2h_tpt_backward_masked")
     _TRAIN_LEAD_IS_PARAM = False
 
     def _train_shapes(self, tok, x):
@@ -204,7 +232,7 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
                 ("b2h_tpt_set_train_linear", _lib.TRAIN_KERNELS[self.train_linear]),
                 ("b2h_tpt_set_train_whole", _lib.TRAIN_KERNELS[self.train_whole]))
 
-    def forward(self, input_tokens, input_pose):
+    def forward(self, input_tokens, input_pose, text_lengths=None, frame_lengths=None):
         train = self._wants_grad(input_tokens, input_pose) and self._device().type == "cuda"
         if not train and self.training and self._dropout_p > 0.0:
             raise RuntimeError("hand_pose_sl_amd.TextPoseTransformer: this call runs the inference kernels (autograd is "
@@ -213,12 +241,29 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
                                "and this path has none; call model.eval()")
         self._check_inputs(input_tokens, input_pose)
         if train:
+            # the lengths are validated before the masks are drawn, so a refusal does not advance a generator
+            self._check_lengths(input_tokens.shape[0], text_lengths, frame_lengths)
             return self._forward_train(input_tokens, input_pose, self._draw_dropout_masks(
-                input_tokens.shape[0], input_tokens.shape[1], input_pose.shape[1]))
-        return self._run(input_tokens, input_pose, None)
+                input_tokens.shape[0], input_tokens.shape[1], input_pose.shape[1]), text_lengths, frame_lengths)
+        if text_lengths is None and frame_lengths is None:
+            return self._run(input_tokens, input_pose, None)
+        return self._run(input_tokens, input_pose, (0, 1.0, None), text_lengths, frame_lengths, max_frames=128)
 
-    def _run(self, input_tokens, input_pose, fused):
-        """The inference kernels: b2h_tpt_forward, or b2h_tpt_forward_fused with fused = (flags, factor, n_frames)."""
+    def _run(self, input_tokens, input_pose, fused, text_lengths=None, frame_lengths=None, max_frames=None):
+        """The inference kernels: b2h_tpt_forward, or b2h_tpt_forward_fused with fused = (flags, factor, n_frames), or
+        with a key length b2h_tpt_forward_masked (`max_frames`: the limit of `forward`, which that entry point does not
+        have)."""
+        masked = text_lengths is not None or frame_lengths is not None
+        if masked:
+            self._check_lengths(input_tokens.shape[0], text_lengths, frame_lengths)
+            if self.precision == "f16x3":
+                # b2h_tpt_forward_masked's own refusal (B2H_ERR_UNSUPPORTED), raised here before any launch
+                raise RuntimeError("libb2h: B2H_TENC_F16X3 takes no key lengths (text_lengths / frame_lengths): its attention "
+                                   "kernels attend to every row; select exact fp32 with b2h_tpt_set_kernel(fp32), i.e. "
+                                   "model.set_precision(\"fp32\") (status -6)")
+            if max_frames is not None and input_pose.dim() == 4 and input_pose.shape[1] > max_frames:
+                raise RuntimeError("libb2h: TextPoseTransformer: S and T are limited to 128 in model(tokens, pose); "
+                                   "forward_long and forward_fused take T <= 1024 (status -2)")
         lib, dev = self._ensure_handle()
         tok = input_tokens.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
         # a composite model's rows are 168 or 232 bytes: pose[1:] of an odd T starts 8 bytes off the 16-byte grid
@@ -240,13 +285,21 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
                     ctypes.c_void_p(y.data_ptr()), B, S, T)
             if fused is None:
                 _lib.check(lib.b2h_tpt_forward(*head, *args, ctypes.c_void_p(st)))
+            elif masked:
+                tl = self._key_lengths(text_lengths, "text_lengths", B, dev)
+                fl = self._key_lengths(frame_lengths, "frame_lengths", B, dev)
+                _lib.check(lib.b2h_tpt_forward_masked(*head, fused[0], fused[1],
+                                                      ctypes.c_void_p(nf.data_ptr()) if nf is not None else None,
+                                                      ctypes.c_void_p(tl.data_ptr()) if tl is not None else None,
+                                                      ctypes.c_void_p(fl.data_ptr()) if fl is not None else None, *args,
+                                                      ctypes.c_void_p(st)))
             else:
                 _lib.check(lib.b2h_tpt_forward_fused(*head, fused[0], fused[1],
                                                      ctypes.c_void_p(nf.data_ptr()) if nf is not None else None, *args,
                                                      ctypes.c_void_p(st)))
         return y
 
-    def forward_long(self, input_tokens, input_pose):
+    def forward_long(self, input_tokens, input_pose, text_lengths=None, frame_lengths=None):
         """`model(input_tokens, input_pose)` in inference for 1 <= T <= 1024 frames, in any geometry: the long path on
         rows that are already the model's input (for a composite model the (B, T, 21 | 29, 2) rows of `build_item` or of
         the reference's dataset), no transform on either side.  Equal to `model(tokens, pose)` bit for bit at T <= 128."""
@@ -254,7 +307,7 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
             raise RuntimeError("TextPoseTransformer.forward_long is inference-only (no gradient, no dropout): call "
                                "model.eval() or wrap the call in torch.no_grad(); train through model(tokens, pose)")
         self._check_inputs(input_tokens, input_pose)
-        return self._run(input_tokens, input_pose, (0, 1.0, None))
+        return self._run(input_tokens, input_pose, (0, 1.0, None), text_lengths, frame_lengths)
 
     def build_item(self, body, right_hand, dif_encoding=True, normalize=True, factor=1280.0):
         """The (B, T, n_joints, 2) input rows of a composite model (`--predict right_index`: 29 joints, `right_3fingers`:
@@ -283,7 +336,7 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
         return item
 
     def forward_fused(self, input_tokens, body, n_frames=None, dif_encoding=True, normalize=True, denormalize=True,
-                      mask_tail=False, factor=1280.0, right_hand=None):
+                      mask_tail=False, factor=1280.0, right_hand=None, text_lengths=None, frame_lengths=None):
         """Token ids and raw-pixel body keypoints in, pixel-space hand keypoints out, with the item transforms inside
         the model's own kernels (b2h_tpt_forward_fused): ChestDifference + /factor (steps/utils.py:180-210) on the pose
         rows as they enter pose2hidden_projection -> the model -> x factor (traintest.py:270-271) and the optional
@@ -300,7 +353,10 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
         `right_hand` (B, T, 21, 2), raw pixels: required exactly when the model takes a composite input (n_joints 21 or
         29, `--predict right_3fingers` / `right_index`).  `body` is then the 12 body joints, the input rows are made by
         `build_item` (where `dif_encoding` and `normalize` then apply) and the model runs with its own pre-transforms
-        off; the output side is as for the body-only models."""
+        off; the output side is as for the body-only models.
+
+        `text_lengths`, `frame_lengths`: the key-padding masks (module docstring), through b2h_tpt_forward_masked;
+        `n_frames` stays the tail mask's own argument, usually the same tensor as `frame_lengths`."""
         composite = self.ninp in _lib.PREDICT_NINP
         if composite != (right_hand is not None):
             raise ValueError(f"right_hand must be given exactly when the model takes a composite input (n_joints 21 or 29); "
@@ -320,7 +376,8 @@ class TextPoseTransformer(NativeDropout, TrainRoutes, NativeModule, nn.Module):
         self._check_inputs(input_tokens, body)
         flags = ((_lib.PRE_CHEST_DIFF if dif_encoding else 0) | (_lib.PRE_NORMALIZE if normalize else 0) |
                  (_lib.POST_DENORMALIZE if denormalize else 0) | (_lib.POST_MASK_TAIL if mask_tail else 0))
-        return self._run(input_tokens, body, (flags, float(factor), n_frames if mask_tail else None))
+        return self._run(input_tokens, body, (flags, float(factor), n_frames if mask_tail else None), text_lengths,
+                         frame_lengths)
 
 
 _TptTrainFn = TrainFn   # the name earlier documents and tests' docstrings use

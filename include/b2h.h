@@ -404,6 +404,32 @@ int b2h_tpt_forward_fused(b2h_tpt* m, const int64_t* tokens, const float* body, 
  * A model with ninp 42 or 58 answers them with B2H_ERR_INVALID: its rows are made by b2h_tpt_build_item, which
  * applies them, and enter b2h_tpt_forward_fused with the B2H_POST_* flags only. */
 
+/* Key-padding masks as key lengths.  The reference pads every sentence to 40 ids with 0 and every utterance to
+ * --max-frames with zero rows and calls nn.Transformer without a mask, so the padding is attended.  Padding here is
+ * always a suffix, so torch's three boolean masks are one length per sequence: for an attention over Tk key rows and a
+ * device array klen (int64 (B), 8-byte aligned) sequence b attends to its key rows 0 .. kl - 1 only, with
+ *   kl = clamp(klen[b], 1, Tk)        -- torch's key_padding_mask[b][j] = (j >= kl).
+ * Keys from kl on have probability exactly 0 and are not read; all query rows are computed, padded ones included
+ * (finite, as in torch).  One deviation from torch: a length of 0 counts as 1 (torch gives NaN for a row with every key
+ * masked); a length above Tk counts as Tk.
+ *   text_len  : the encoder's self-attention (src_key_padding_mask) and the decoder's cross-attention
+ *               (memory_key_padding_mask);  frame_len: the decoder's self-attention (tgt_key_padding_mask).
+ * Either may be NULL on its own; with both NULL every entry point below is its parent, launch for launch and bit
+ * for bit.  A model trained with masks must be run with masks.
+ *
+ * lengths[b] = 1 + (last s with tokens[b][s] != pad_id), 1 if every id is pad_id: the text_len of token rows padded
+ * at the end with pad_id (0 in the reference, which is also its tokenizer's <unk>: a sentence that really ends in
+ * <unk> loses those tokens).  tokens (B, S) and lengths (B): device int64, 8-byte aligned, not overlapping
+ * (B2H_ERR_INVALID); B >= 0, S >= 1 (B2H_ERR_SHAPE); B == 0 is a no-op.  One launch, capturable. */
+int b2h_token_lengths(const int64_t* tokens, int64_t B, int64_t S, int64_t pad_id, int64_t* lengths, void* stream);
+/* b2h_tpt_forward_fused with key lengths; n_frames (B2H_POST_MASK_TAIL) stays an argument of its own, usually the same
+ * array as frame_len.  Exact fp32 only: with B2H_TENC_F16X3 selected and a non-NULL length it returns
+ * B2H_ERR_UNSUPPORTED -- call b2h_tpt_set_kernel(m, B2H_TENC_F32).  Neither y nor the workspace may overlap a length
+ * array (B2H_ERR_INVALID).  A sequence's output is the same bits alone and inside any batch, as without lengths. */
+int b2h_tpt_forward_masked(b2h_tpt* m, const int64_t* tokens, const float* body, float* y, int64_t B, int64_t S,
+                           int64_t T, int flags, float factor, const int64_t* n_frames, const int64_t* text_len,
+                           const int64_t* frame_len, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The geometry of a model and whether weights are loaded; any output pointer may be NULL. */
 int b2h_tpt_info(const b2h_tpt* m, int* n_tokens, int* ninp, int* nout, int* n_enc_layers, int* n_dec_layers,
                  int* has_weights);
@@ -483,6 +509,20 @@ int b2h_tpt_backward(b2h_tpt* m, const float* const* params, const int64_t* toke
                      float p, const float* dy, const void* saved, size_t saved_bytes, float* dx,
                      float* const* grads, void* scratch, size_t scratch_bytes, int64_t B, int64_t S, int64_t T,
                      void* stream);
+/* The pair with key lengths (see b2h_token_lengths above): text_len and frame_len are device int64 (B), 8-byte
+ * aligned, read-only operands that no output may overlap (B2H_ERR_INVALID), each NULL or not on its own; pass the
+ * backward what the forward got.  In the backward the rows kl .. Tk - 1 of every attention's dK and dV are written
+ * as +0, so the gradient of a padded frame row is exactly 0 when dy is 0 there.  All four training attention routes
+ * take them; the summation order of a sequence is a function of (S, T) and its own two lengths.  Capturable like their
+ * parents; b2h_tpt_train_bytes is unchanged.  b2h_tpt_train_forward / b2h_tpt_backward are these with NULL, NULL. */
+int b2h_tpt_train_forward_masked(b2h_tpt* m, const float* const* params, const int64_t* tokens, const float* x,
+                                 const uint8_t* const* masks, float p, float* y, void* saved, size_t saved_bytes,
+                                 int64_t B, int64_t S, int64_t T, const int64_t* text_len, const int64_t* frame_len,
+                                 void* stream);
+int b2h_tpt_backward_masked(b2h_tpt* m, const float* const* params, const int64_t* tokens, const uint8_t* const* masks,
+                            float p, const float* dy, const void* saved, size_t saved_bytes, float* dx,
+                            float* const* grads, void* scratch, size_t scratch_bytes, int64_t B, int64_t S, int64_t T,
+                            const int64_t* text_len, const int64_t* frame_len, void* stream);
 /* Which kernels the training calls use where there is a choice.  This switch covers the decoder's two attentions at
  * T > 128 (the Linear layers have a switch of their own, b2h_tpt_set_train_linear below):
  *   B2H_TRAIN_VALU  the default of every new model: kernel_train_attn_long.h, fp32 FMAs on the vector ALU

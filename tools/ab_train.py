@@ -2,7 +2,7 @@
 """GPU box: same-process, interleaved A/B of two or more builds of libb2h.so on one training step (train-forward +
 backward) of TransformerEnc or TextPoseTransformer through the C ABI, after tools/ab_lib.py and tools/ab_tpt.py.
     python tools/ab_train.py <libA.so> <libB.so> [...] --model tpt --shape 128 40 200 --layers 4 --p 0.1 \
-        [--attn valu|mfma] [--linear valu|mfma] [--geometry 8 42] [--rounds 7] [--iters 10] [--host-calls 0] \
+        [--attn valu|mfma] [--linear valu|mfma] [--whole valu|mfma] [--geometry 8 42] [--rounds 7] [--iters 10] [--host-calls 0] \
         [--refused-calls 0] [--max-len 100]
 Each library is loaded under its own ctypes handle (only the symbols it has are typed) and gets its own model handle;
 all of them run on the same inputs, parameters, masks and the same output, saved and scratch buffers.  Naming the same
@@ -28,6 +28,7 @@ ap.add_argument("--layers", type=int, default=4, help="encoder layers; a tpt mod
 ap.add_argument("--p", type=float, default=0.1)
 ap.add_argument("--attn", choices=sorted(_lib.TRAIN_KERNELS), default="valu")
 ap.add_argument("--linear", choices=sorted(_lib.TRAIN_KERNELS), default="valu")
+ap.add_argument("--whole", choices=sorted(_lib.TRAIN_KERNELS), default="valu", help="tpt only: b2h_tpt_set_train_whole")
 ap.add_argument("--geometry", type=int, nargs=2, default=(8, 42), metavar=("N_JOINTS", "NOUT"), help="tpt only")
 ap.add_argument("--max-len", type=int, default=100, help="tenc only: rows of the positional table (T <= max_len)")
 ap.add_argument("--rounds", type=int, default=7)
@@ -84,6 +85,8 @@ for path in a.libs:
     if tpt:
         assert lib.b2h_tpt_set_train_kernel(h, _lib.TRAIN_KERNELS[a.attn]) == 0, lib.b2h_last_error()
         assert lib.b2h_tpt_set_train_linear(h, _lib.TRAIN_KERNELS[a.linear]) == 0, lib.b2h_last_error()
+        if a.whole != "valu":   # (a library older than the switch keeps its only route)
+            assert lib.b2h_tpt_set_train_whole(h, _lib.TRAIN_KERNELS[a.whole]) == 0, lib.b2h_last_error()
     libs.append((lib, h))
 nbytes = getattr(libs[0][0], f"b2h_{a.model}_train_bytes")
 nsaved, nscratch = nbytes(libs[0][1], *dims, 0), nbytes(libs[0][1], *dims, 1)
