@@ -35,6 +35,9 @@ BATCH_DIF_ENCODING, BATCH_NORMALIZE, BATCH_PAD_FRAME0 = 1, 2, 4
 # enum b2h_coverage (b2h_window_plan), by the names of window_plan / predict_dataset
 COVERAGE = {"all": 0, "first": 1}
 
+# enum b2h_blend (b2h_scatter_rows_blend), by the names of write_back_blend / predict_dataset
+BLEND = {"linear": 0, "centre": 1}
+
 # enum b2h_train_kernel (b2h_tpt_set_train_kernel, b2h_tpt_set_train_linear and their b2h_tenc_* twins,
 # b2h_tpt_set_train_whole), by the names of set_train_kernels / set_train_linear of TextPoseTransformer and
 # TransformerEnc and of TextPoseTransformer.set_train_whole
@@ -160,6 +163,11 @@ SYMBOLS = {
     "b2h_scatter_rows": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64,
                                         ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, ctypes.c_float, _vp,
                                         _vp]),
+    "b2h_window_plan_overlap": (ctypes.c_int64, [_i64p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _i64p, _i64p, _i64p,
+                                                 ctypes.c_int64]),
+    "b2h_scatter_rows_blend": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp,
+                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_float, _vp, _vp, ctypes.c_int, ctypes.c_float, _vp, _vp]),
     "b2h_joint_error": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "b2h_model_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                       ctypes.POINTER(ctypes.c_int)]),

@@ -2608,6 +2608,110 @@ int build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64
     return B2H_OK;
 }
 
+// What b2h_scatter_rows_blend adds to a write-back: NULL for b2h_scatter_rows.
+struct RowsBlend {
+    int64_t n_plan, entry0;
+    const float* pred_before;
+    int blend;
+};
+
+// b2h_scatter_rows (utt, start and skip hold B entries) and b2h_scatter_rows_blend (`with` set: they hold the n_plan
+// entries of a plan, of which the batch is entry0 .. entry0 + B - 1): the same checks in the same order, and the
+// second's own among them.
+int scatter_rows(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body, const int64_t* utt,
+                 const int64_t* start, const int64_t* skip, int64_t B, int64_t T, int predict, int flags, float factor,
+                 const float* pred, float conf, float* rows_out, void* stream, const RowsBlend* with = nullptr) {
+    if (int rc = batch_description_refusal(n_rows, n_utt, n_body, with ? with->n_plan : 0, B, T, predict, flags, factor)) return rc;
+    if (!std::isfinite(conf)) return fail(B2H_ERR_INVALID, "conf must be finite");
+    if (with) {
+        if (with->blend != B2H_BLEND_LINEAR && with->blend != B2H_BLEND_CENTRE)
+            return fail(B2H_ERR_INVALID, "blend must be a b2h_blend value");
+        if (with->entry0 < 0 || with->entry0 > with->n_plan - B)
+            return fail(B2H_ERR_INVALID, "entry0 out of range (0 <= entry0, entry0 + B <= n_plan): entry0 " +
+                                             std::to_string(with->entry0) + ", B " + std::to_string(B) + ", n_plan " +
+                                             std::to_string(with->n_plan));
+    }
+    if (B * T == 0) return B2H_OK;
+    if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
+    if (n_rows > ((int64_t)1 << 40) || n_utt > ((int64_t)1 << 40)) return fail(B2H_ERR_SHAPE, "store too large");
+    if (with && with->n_plan > ((int64_t)1 << 40)) return fail(B2H_ERR_SHAPE, "plan too large");
+    const int J = n_body + 42;
+    const int nt = predict == B2H_PREDICT_RIGHT_HAND ? 21 : predict == B2H_PREDICT_RIGHT_INDEX ? 4 : 12;
+    const size_t store = (size_t)n_rows * 3 * J * 4, entries = (size_t)(with ? with->n_plan : B) * 8;
+    struct Op { const char* name; const void* p; size_t n; bool optional, out; };
+    const Op ops[] = {{"rows", rows, store, n_rows == 0, false},
+                      {"offsets", offsets, (size_t)(n_utt + 1) * 8, false, false},
+                      {with ? "utt_plan" : "utt", utt, entries, false, false},
+                      {with ? "start_plan" : "start", start, entries, !with, false},
+                      {with ? "skip_plan" : "skip", skip, entries, !with, false},
+                      {"pred", pred, (size_t)B * T * nt * 8, false, false},
+                      {"pred_before", with ? with->pred_before : nullptr, (size_t)T * nt * 8, true, false},
+                      {"rows_out", rows_out, store, n_rows == 0, true}};
+    for (const Op& o : ops) {
+        if (!o.p && !o.optional) return fail(B2H_ERR_INVALID, std::string(o.name) + " is NULL");
+        if (misaligned(o.p, 8)) return fail(B2H_ERR_INVALID, std::string(o.name) + " must be 8-byte aligned");
+    }
+    std::vector<Span> out_spans, in_spans;
+    for (const Op& o : ops)
+        if (o.p) (o.out ? out_spans : in_spans).push_back({o.p, o.n, o.name});
+    if (int rc = check_overlap(out_spans, in_spans)) return rc;
+    for (const Op& o : ops)
+        if (o.p && o.n)
+            if (int rc = check_device_ptr(o.p, o.name)) return rc;
+    SbArgs g = {};
+    SrArgs& a = g.s;
+    a.w.rows = rows; a.w.offsets = offsets; a.w.utt = utt; a.w.start = start;
+    a.w.n_rows = n_rows; a.w.n_utt = n_utt; a.w.B = B; a.w.T = T;
+    a.w.n_body = n_body; a.w.predict = predict; a.w.flags = flags; a.w.nt = nt; a.w.factor = factor;
+    a.skip = skip; a.pred = pred; a.rows_out = rows_out; a.conf = conf;
+    const int64_t blocks = (B * T * nt + kBbThreads - 1) / kBbThreads;
+    if (blocks > 0x7fffffff) return fail(B2H_ERR_SHAPE, "shape too large");
+    if (with) {
+        g.before = with->pred_before; g.entry0 = with->entry0; g.n_plan = with->n_plan; g.blend = with->blend;
+        hipLaunchKernelGGL(b2h_scatter_rows_blend_k, dim3((unsigned)blocks), dim3(kBbThreads), 0, (hipStream_t)stream, g);
+    } else {
+        hipLaunchKernelGGL(b2h_scatter_rows_k, dim3((unsigned)blocks), dim3(kBbThreads), 0, (hipStream_t)stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return B2H_OK;
+}
+
+// b2h_window_plan (overlap 0) and b2h_window_plan_overlap: windows at stride T - overlap, the last a full window that
+// ends with the utterance.  With overlap 0 that is ceil(L / T) windows at i T and (L - T, k T - L).
+int64_t window_plan(const int64_t* offsets, int64_t n_utt, int64_t T, int coverage, int64_t overlap, int64_t* utt_plan,
+                    int64_t* start_plan, int64_t* skip_plan, int64_t capacity) {
+    const auto refuse = [](const std::string& why) {
+        (void)fail(B2H_ERR_INVALID, why);
+        return (int64_t)-1;
+    };
+    if (T < 1) return refuse("T must be >= 1");
+    if (n_utt < 0 || capacity < 0) return refuse("negative shape");
+    if (coverage != B2H_COVER_ALL && coverage != B2H_COVER_FIRST) return refuse("coverage must be a b2h_coverage value");
+    if (!offsets && n_utt > 0) return refuse("offsets is NULL");
+    if (n_utt > 0 && offsets[0] < 0) return refuse("offsets must ascend from offsets[0] >= 0");
+    for (int64_t u = 0; u < n_utt; ++u)
+        if (offsets[u + 1] < offsets[u]) return refuse("offsets must ascend from offsets[0] >= 0");
+    if (overlap < 0 || overlap > T / 2)
+        return refuse("overlap must be in 0 .. T / 2 (a frame is predicted by at most two windows): overlap " +
+                      std::to_string(overlap) + ", T " + std::to_string(T));
+    const int64_t stride = T - overlap;               // >= 1
+    int64_t count = 0;
+    for (int64_t u = 0; u < n_utt; ++u) {
+        const int64_t L = offsets[u + 1] - offsets[u];
+        if (L == 0) continue;
+        const int64_t k = (coverage == B2H_COVER_FIRST || L <= T) ? 1 : (L - T + stride - 1) / stride + 1;
+        for (int64_t i = 0; i < k; ++i, ++count) {
+            if (count >= capacity) continue;
+            if (!utt_plan || !start_plan || !skip_plan) return refuse("utt_plan, start_plan or skip_plan is NULL");
+            const bool last = k > 1 && i == k - 1;    // a full window that ends with the utterance
+            utt_plan[count] = u;
+            start_plan[count] = last ? L - T : i * stride;
+            skip_plan[count] = last ? i * stride - (L - T) : 0;
+        }
+    }
+    return count;
+}
+
 } // namespace
 
 extern "C" {
@@ -2702,71 +2806,28 @@ int b2h_epoch_record(const float* loss, float* losses, int64_t n_losses, int64_t
 // ---- whole-store inference: the window plan, the row write-back, the joint error (kernel_scatter_rows.h) -------
 int64_t b2h_window_plan(const int64_t* offsets, int64_t n_utt, int64_t T, int coverage, int64_t* utt_plan,
                         int64_t* start_plan, int64_t* skip_plan, int64_t capacity) {
-    const auto refuse = [](const char* why) {
-        (void)fail(B2H_ERR_INVALID, why);
-        return (int64_t)-1;
-    };
-    if (T < 1) return refuse("T must be >= 1");
-    if (n_utt < 0 || capacity < 0) return refuse("negative shape");
-    if (coverage != B2H_COVER_ALL && coverage != B2H_COVER_FIRST) return refuse("coverage must be a b2h_coverage value");
-    if (!offsets && n_utt > 0) return refuse("offsets is NULL");
-    if (n_utt > 0 && offsets[0] < 0) return refuse("offsets must ascend from offsets[0] >= 0");
-    for (int64_t u = 0; u < n_utt; ++u)
-        if (offsets[u + 1] < offsets[u]) return refuse("offsets must ascend from offsets[0] >= 0");
-    int64_t count = 0;
-    for (int64_t u = 0; u < n_utt; ++u) {
-        const int64_t L = offsets[u + 1] - offsets[u];
-        if (L == 0) continue;
-        const int64_t k = (coverage == B2H_COVER_FIRST || L <= T) ? 1 : (L + T - 1) / T;
-        for (int64_t i = 0; i < k; ++i, ++count) {
-            if (count >= capacity) continue;
-            if (!utt_plan || !start_plan || !skip_plan) return refuse("utt_plan, start_plan or skip_plan is NULL");
-            const bool last = k > 1 && i == k - 1;    // a full window that ends with the utterance
-            utt_plan[count] = u;
-            start_plan[count] = last ? L - T : i * T;
-            skip_plan[count] = last ? k * T - L : 0;
-        }
-    }
-    return count;
+    return window_plan(offsets, n_utt, T, coverage, 0, utt_plan, start_plan, skip_plan, capacity);
+}
+
+int64_t b2h_window_plan_overlap(const int64_t* offsets, int64_t n_utt, int64_t T, int64_t overlap, int64_t* utt_plan,
+                                int64_t* start_plan, int64_t* skip_plan, int64_t capacity) {
+    return window_plan(offsets, n_utt, T, B2H_COVER_ALL, overlap, utt_plan, start_plan, skip_plan, capacity);
 }
 
 int b2h_scatter_rows(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
                      const int64_t* utt, const int64_t* start, const int64_t* skip, int64_t B, int64_t T, int predict,
                      int flags, float factor, const float* pred, float conf, float* rows_out, void* stream) {
-    if (int rc = batch_description_refusal(n_rows, n_utt, n_body, 0, B, T, predict, flags, factor)) return rc;
-    if (!std::isfinite(conf)) return fail(B2H_ERR_INVALID, "conf must be finite");
-    if (B * T == 0) return B2H_OK;
-    if (B > 0x7fffffff || T > (1 << 24)) return fail(B2H_ERR_SHAPE, "shape too large");
-    if (n_rows > ((int64_t)1 << 40) || n_utt > ((int64_t)1 << 40)) return fail(B2H_ERR_SHAPE, "store too large");
-    const int J = n_body + 42;
-    const int nt = predict == B2H_PREDICT_RIGHT_HAND ? 21 : predict == B2H_PREDICT_RIGHT_INDEX ? 4 : 12;
-    const size_t store = (size_t)n_rows * 3 * J * 4;
-    struct Op { const char* name; const void* p; size_t n; bool optional, out; };
-    const Op ops[] = {{"rows", rows, store, n_rows == 0, false},  {"offsets", offsets, (size_t)(n_utt + 1) * 8, false, false},
-                      {"utt", utt, (size_t)B * 8, false, false},  {"start", start, (size_t)B * 8, true, false},
-                      {"skip", skip, (size_t)B * 8, true, false}, {"pred", pred, (size_t)B * T * nt * 8, false, false},
-                      {"rows_out", rows_out, store, n_rows == 0, true}};
-    for (const Op& o : ops) {
-        if (!o.p && !o.optional) return fail(B2H_ERR_INVALID, std::string(o.name) + " is NULL");
-        if (misaligned(o.p, 8)) return fail(B2H_ERR_INVALID, std::string(o.name) + " must be 8-byte aligned");
-    }
-    std::vector<Span> out_spans, in_spans;
-    for (const Op& o : ops)
-        if (o.p) (o.out ? out_spans : in_spans).push_back({o.p, o.n, o.name});
-    if (int rc = check_overlap(out_spans, in_spans)) return rc;
-    for (const Op& o : ops)
-        if (o.p && o.n)
-            if (int rc = check_device_ptr(o.p, o.name)) return rc;
-    SrArgs a = {};
-    a.w.rows = rows; a.w.offsets = offsets; a.w.utt = utt; a.w.start = start;
-    a.w.n_rows = n_rows; a.w.n_utt = n_utt; a.w.B = B; a.w.T = T;
-    a.w.n_body = n_body; a.w.predict = predict; a.w.flags = flags; a.w.nt = nt; a.w.factor = factor;
-    a.skip = skip; a.pred = pred; a.rows_out = rows_out; a.conf = conf;
-    const int64_t blocks = (B * T * nt + kBbThreads - 1) / kBbThreads;
-    if (blocks > 0x7fffffff) return fail(B2H_ERR_SHAPE, "shape too large");
-    hipLaunchKernelGGL(b2h_scatter_rows_k, dim3((unsigned)blocks), dim3(kBbThreads), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return B2H_OK;
+    return scatter_rows(rows, n_rows, offsets, n_utt, n_body, utt, start, skip, B, T, predict, flags, factor, pred, conf,
+                        rows_out, stream);
+}
+
+int b2h_scatter_rows_blend(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                           const int64_t* utt_plan, const int64_t* start_plan, const int64_t* skip_plan, int64_t n_plan,
+                           int64_t entry0, int64_t B, int64_t T, int predict, int flags, float factor, const float* pred,
+                           const float* pred_before, int blend, float conf, float* rows_out, void* stream) {
+    const RowsBlend with = {n_plan, entry0, pred_before, blend};
+    return scatter_rows(rows, n_rows, offsets, n_utt, n_body, utt_plan, start_plan, skip_plan, B, T, predict, flags, factor,
+                        pred, conf, rows_out, stream, &with);
 }
 
 int b2h_joint_error(const float* rows_pred, const float* rows_true, int64_t n_rows, const int64_t* offsets, int64_t n_utt,

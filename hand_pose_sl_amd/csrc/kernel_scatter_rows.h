@@ -1,6 +1,6 @@
-// The inference half of the device-resident store (b2h_scatter_rows, b2h_joint_error, include/b2h.h): the reference's
-// whole-store caller (infer_utterance_h5.py -> steps/traintest.py:332-391) runs a model over every utterance and writes
-// the predictions out as store rows; it multiplies by the factor only and leaves "add the wrist back" as a TODO
+// The inference half of the device-resident store (b2h_scatter_rows, b2h_scatter_rows_blend, b2h_joint_error,
+// include/b2h.h): the reference's whole-store caller (infer_utterance_h5.py -> steps/traintest.py:332-391) runs a
+// model over every utterance and writes the predictions out as store rows; it multiplies by the factor only and leaves "add the wrist back" as a TODO
 // (traintest.py:275-279).  Here one launch writes a batch of predictions back into rows, the inverse of
 // b2h_build_batch_k's target transform, and two small launches give the per-utterance, per-joint pixel error of one store
 // against another.
@@ -11,13 +11,16 @@
 // utterance is known, len > 0 and max(skip[b], 0) <= t < min(len, T): padded frames, frames an earlier window of the plan
 // covered and unknown utterances write nothing.  v = pred, * factor (B2H_BATCH_NORMALIZE), + the raw wrist of the same row
 // of `rows` (B2H_BATCH_DIF_ENCODING), each a separate correctly rounded fp32 operation (no contraction to an fma); three
-// dword stores x, y, conf.  No LDS, no atomics; indices are 64-bit.
+// dword stores x, y, conf.  No LDS, no atomics; indices are 64-bit.  b2h_scatter_rows_blend_k (below) is the same
+// write-back for a plan of overlapping windows.
 //
 // The arithmetic of both kernels is stated as float32 operations that numpy repeats bit for bit.  hipcc's __fmul_rn,
 // __fadd_rn and __fsub_rn are plain * + - here (its headers give the rounded OCML forms only under
 // OCML_BASIC_ROUNDED_OPERATIONS), which -ffp-contract's default may still fuse, and its __fsqrt_rn is the native
 // square root, one ulp off in places.  So each kernel body switches contraction off with the pragma -- that is what
-// keeps the named intrinsics apart -- and the square root is sqrtf, which hipcc rounds correctly by default
+// keeps the named intrinsics apart in the kernels' shared tail and in b2h_joint_error_k; the blend's
+// fl(fl(wa pa) + fl(wb pb)) still came out as a packed fma with them, so it is written with plain operators, which the
+// pragma covers lexically -- and the square root is sqrtf, which hipcc rounds correctly by default
 // (-fhip-fp32-correctly-rounded-divide-sqrt, as kernel_build_batch.h relies on for its division).
 //
 // b2h_joint_error_k: one lane per (utterance, right-hand joint), the 21 joints of an utterance on neighbouring lanes
@@ -36,6 +39,26 @@ struct SrArgs {
     float conf;
 };
 
+// The tail both write-back kernels share: value v of target joint j into row `row` of rows_out.
+__device__ __forceinline__ void sr_store(const SrArgs& a, int64_t row, int j, float2 v) {
+#pragma clang fp contract(off)
+    const int J = a.w.n_body + 42;
+    const int d = bb_source(a.w.n_body, a.w.predict, true, j);
+    if (a.w.flags & kBbNorm) {
+        v.x = __fmul_rn(v.x, a.w.factor);
+        v.y = __fmul_rn(v.y, a.w.factor);
+    }
+    if (a.w.flags & kBbDif) {                         // the RAW body wrist (4) that b2h_build_batch_k subtracted
+        const float* r = a.w.rows + row * (3 * J);
+        v.x = __fadd_rn(v.x, r[4]);
+        v.y = __fadd_rn(v.y, r[J + 4]);
+    }
+    float* o = a.rows_out + row * (3 * J);
+    o[d] = v.x;
+    o[J + d] = v.y;
+    o[2 * J + d] = a.conf;
+}
+
 __global__ __launch_bounds__(kBbThreads) void b2h_scatter_rows_k(const SrArgs a) {
 #pragma clang fp contract(off)
     const int64_t i = (int64_t)blockIdx.x * kBbThreads + threadIdx.x;
@@ -50,23 +73,71 @@ __global__ __launch_bounds__(kBbThreads) void b2h_scatter_rows_k(const SrArgs a)
     int64_t first = a.skip ? a.skip[b] : 0;
     first = first < 0 ? 0 : first;
     if (len <= 0 || t < first || t >= n) return;
-    const int J = a.w.n_body + 42;
-    const int64_t row = lo + t;                       // < offsets[u + 1] <= n_rows: lo + T <= the utterance's end if len > T
-    const int d = bb_source(a.w.n_body, a.w.predict, true, j);
-    float2 v = reinterpret_cast<const float2*>(a.pred)[i];
-    if (a.w.flags & kBbNorm) {
-        v.x = __fmul_rn(v.x, a.w.factor);
-        v.y = __fmul_rn(v.y, a.w.factor);
+    // row lo + t < offsets[u + 1] <= n_rows: lo + T <= the utterance's end if len > T
+    sr_store(a, lo + t, j, reinterpret_cast<const float2*>(a.pred)[i]);
+}
+
+// b2h_scatter_rows_blend_k: the write-back of a plan whose windows overlap (b2h_window_plan_overlap).  The batch holds
+// entries entry0 .. entry0 + B - 1 of the plan in s.w.utt / s.w.start / s.skip (n_plan entries each); one lane per
+// (b, t, j) as above.  Entry e's predecessor is e - 1 if it has the same utterance, its successor e + 1 likewise; their
+// windows come from bb_window too, so every start is the clamped one.  A lane writes iff skip[e] <= t < end, end =
+// min(len, T) without a successor, else the frame at which the successor's used frames begin: the tail that the
+// successor blends is the successor's, so every row has one writer in one launch and the launches may run in any order.
+// The first w = (predecessor's window end) - (first used row) used frames are the blend region: there the lane reads
+// the predecessor's value of the same row, a second float2 stream at the fixed offset (start[e] - start[e-1] - T) frames
+// in `pred`, or `before` (the predecessor's (T, nt, 2) block) for b == 0.  LINEAR: wb = fl((p + 1) / (w + 1)),
+// wa = fl(1 - wb), v = fl(fl(wa pa) + fl(wb pb)); CENTRE: v = 2 p >= w ? pb : pa.  `before` NULL: entry0 is written as
+// if it had no predecessor (nothing is read through it).
+struct SbArgs {
+    SrArgs s;
+    const float* before;      // may be NULL
+    int64_t entry0, n_plan;
+    int blend;                // 0 linear, 1 centre
+};
+
+__global__ __launch_bounds__(kBbThreads) void b2h_scatter_rows_blend_k(const SbArgs a) {
+#pragma clang fp contract(off)
+    const BbArgs& w = a.s.w;
+    const int64_t i = (int64_t)blockIdx.x * kBbThreads + threadIdx.x;
+    const int nt = w.nt;
+    if (i >= w.B * w.T * nt) return;
+    const int64_t f = i / nt;
+    const int j = (int)(i - f * nt);
+    const int64_t b = f / w.T, t = f - b * w.T;
+    const int64_t e = a.entry0 + b;                   // < n_plan: the host checked entry0 + B <= n_plan
+    int64_t lo, len;
+    if (!bb_window(w, e, lo, len)) return;
+    const int64_t n = len < w.T ? len : w.T;
+    int64_t first = a.s.skip[e];
+    first = first < 0 ? 0 : first;
+    if (len <= 0 || t < first || t >= n) return;
+    const int64_t u = w.utt[e];
+    int64_t lo2, len2;
+    if (e + 1 < a.n_plan && w.utt[e + 1] == u && bb_window(w, e + 1, lo2, len2)) {
+        const int64_t skip2 = a.s.skip[e + 1];
+        if (t >= lo2 + (skip2 < 0 ? 0 : skip2) - lo) return;      // the successor's frame
     }
-    if (a.w.flags & kBbDif) {                         // the RAW body wrist (4) that b2h_build_batch_k subtracted
-        const float* r = a.w.rows + row * (3 * J);
-        v.x = __fadd_rn(v.x, r[4]);
-        v.y = __fadd_rn(v.y, r[J + 4]);
+    float2 v = reinterpret_cast<const float2*>(a.s.pred)[i];
+    if (e > 0 && (b > 0 || a.before) && w.utt[e - 1] == u && bb_window(w, e - 1, lo2, len2)) {
+        const int64_t ta = t + (lo - lo2);            // this row's frame in the predecessor's window
+        const int64_t width = lo2 + w.T - (lo + first), p = t - first;
+        if (p < width && ta >= 0) {                   // p < width is ta < T
+            const float2 pa = b > 0 ? reinterpret_cast<const float2*>(a.s.pred)[i + (lo - lo2 - w.T) * nt]
+                                    : reinterpret_cast<const float2*>(a.before)[ta * nt + j];
+            if (a.blend == 0) {
+                // plain operators, which the pragma above covers: the __f*_rn functions are inlined from a header
+                // it does not reach, and a product and a sum that both come from there fuse into one fma
+                const float wb = (float)(p + 1) / (float)(width + 1);
+                const float wa = 1.f - wb;
+                const float ax = wa * pa.x, ay = wa * pa.y, bx = wb * v.x, by = wb * v.y;
+                v.x = ax + bx;
+                v.y = ay + by;
+            } else if (2 * p < width) {
+                v = pa;
+            }
+        }
     }
-    float* o = a.rows_out + row * (3 * J);
-    o[d] = v.x;
-    o[J + d] = v.y;
-    o[2 * J + d] = a.conf;
+    sr_store(a.s, lo + t, j, v);
 }
 
 constexpr int kJeThreads = 256;

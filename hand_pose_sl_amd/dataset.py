@@ -201,7 +201,8 @@ class DeviceLoader:
     the same batches.
 
     `write_back(prediction, utt, start, skip, rows_out)` is the inverse of `build` for the target: a batch of
-    predictions back into store rows (b2h_scatter_rows), what `predict_dataset` (predict.py) runs per slice."""
+    predictions back into store rows (b2h_scatter_rows), what `predict_dataset` (predict.py) runs per slice;
+    `write_back_blend` is the same for a plan of overlapping windows (b2h_scatter_rows_blend)."""
 
     def __init__(self, ds, batch_size, max_frames, selection="randomcrop", predict="right_hand", dif_encoding=True,
                  normalize=True, factor=1280, pad="zeros", shuffle=False, drop_last=False, generator=None,
@@ -355,6 +356,47 @@ class DeviceLoader:
                 _ptr(ds.rows), ds.rows.shape[0], _ptr(ds.offsets), len(ds), ds.n_body, _ptr(utt), _ptr(opt["start"]),
                 _ptr(opt["skip"]), B, self.max_frames, _lib.PREDICT[self.predict], self.flags, self.factor, _ptr(prediction),
                 float(conf), _ptr(rows_out), st))
+        return rows_out
+
+    def write_back_blend(self, prediction, plan, entry0, rows_out, prediction_before=None, blend="linear", conf=1.0):
+        """`write_back` for a plan of overlapping windows (`window_plan(..., overlap=K)`), one kernel
+        (b2h_scatter_rows_blend).  `plan`: the WHOLE plan (utt, start, skip) as device int64 tensors (host tensors or
+        lists are copied there); `prediction` ((B, max_frames, J_out, 2)) holds entries entry0 .. entry0 + B - 1 of
+        it and `prediction_before` ((max_frames, J_out, 2), required when entry0 > 0) entry entry0 - 1, the last block
+        of the batch before.  A window writes its used frames up to where the next window of the utterance begins
+        its own, and the first K of them are blended with the window before: "linear" weights (p + 1) / (K + 1) for
+        the later window, "centre" takes each frame from the window whose centre is nearer.  Every row is written by
+        one call over the plan, so the calls may come in any order.  Returns `rows_out`."""
+        ds, dev = self.ds, self.ds.device
+        if blend not in _lib.BLEND:
+            raise ValueError(f"blend must be one of {sorted(_lib.BLEND)}, got {blend!r}")
+        if len(plan) != 3:
+            raise ValueError("plan must be (utt, start, skip), as window_plan returns it")
+        plan = [torch.as_tensor(t, dtype=torch.int64).to(dev).contiguous() for t in plan]
+        if plan[0].dim() != 1 or any(t.shape != plan[0].shape for t in plan):
+            raise ValueError(f"plan must be three (n_plan,) tensors, got {[tuple(t.shape) for t in plan]}")
+        n_plan, entry0 = plan[0].shape[0], int(entry0)
+        block = (self.max_frames, self.joints[1], 2)
+        if not isinstance(prediction, torch.Tensor) or prediction.dim() != 4:
+            raise ValueError(f"prediction must be a contiguous float32 tensor of shape (B, {', '.join(map(str, block))}) on {dev}")
+        B = prediction.shape[0]
+        if entry0 < 0 or entry0 + B > n_plan:
+            raise ValueError(f"entries {entry0} .. {entry0 + B - 1} are not in a plan of {n_plan}")
+        if entry0 > 0 and prediction_before is None:
+            raise ValueError("prediction_before (the prediction of plan entry entry0 - 1) is needed when entry0 > 0")
+        for name, t, want in (("prediction", prediction, (B,) + block), ("prediction_before", prediction_before, block),
+                              ("rows_out", rows_out, tuple(ds.rows.shape))):
+            if t is None and name == "prediction_before":
+                continue
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != want or t.dtype != torch.float32 or t.device != dev or
+                    not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {want} on {dev}")
+        with _lib.on_device(dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(_lib.load().b2h_scatter_rows_blend(
+                _ptr(ds.rows), ds.rows.shape[0], _ptr(ds.offsets), len(ds), ds.n_body, *[_ptr(t) for t in plan], n_plan,
+                entry0, B, self.max_frames, _lib.PREDICT[self.predict], self.flags, self.factor, _ptr(prediction),
+                _ptr(prediction_before), _lib.BLEND[blend], float(conf), _ptr(rows_out), st))
         return rows_out
 
     def draw_starts(self, utt):

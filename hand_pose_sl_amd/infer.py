@@ -7,7 +7,8 @@ The working equivalent of the reference's `infer_utterance.py` (:52-111) + `step
         --model-checkpoint best_model.pth --output-folder out/ [--model Conv|TransformerEnc|TextPoseTransformer]
         [--conv-channels 30] [--conv-pos-emb] [--max-frames 200] [--no-normalize] [--dif-encoding]
         [--precision fp32] [--tokens ids.json | --text "..." --tokenizer tokenizer.json]
-        [--predict right_hand|right_index|right_3fingers] [--all-frames [--batch-size 128]]
+        [--predict right_hand|right_index|right_3fingers]
+        [--all-frames [--batch-size 128] [--overlap K [--blend linear|centre]]]
 
 With `--model Conv` (default) transforms, model and de-normalisation run as ONE fused kernel
 (`ConvModel.forward_fused`); with `--model TransformerEnc` (infer_utterance.py:99-101) the item
@@ -29,7 +30,8 @@ Several utterances (sub-folders) are batched into one launch.
 With `--all-frames` every frame of every utterance is predicted, not only the first `--max-frames`: the utterances
 become a device-resident store (`DeviceDataset.from_frames`) and `predict_dataset` runs the model over windows of
 `--max-frames` frames that cover it once; `--dif-encoding` is then the trainer's pair of transforms (the hand relative to
-the raw wrist, the body to the chest) and the wrist is added back to the prediction.
+the raw wrist, the body to the chest) and the wrist is added back to the prediction.  `--overlap K` makes those
+windows overlap by K frames and blends the two predictions of the shared frames (`predict_dataset(overlap=, blend=)`).
 """
 import argparse
 import glob
@@ -89,11 +91,11 @@ def predict_utterances(model, utterances, max_frames=200, dif_encoding=False, no
 
 
 def predict_all_frames(model, utterances, max_frames=200, dif_encoding=False, normalize=True, tokens=None,
-                       predict="right_hand", batch_size=128, mask_padding=False):
+                       predict="right_hand", batch_size=128, mask_padding=False, overlap=0, blend="linear"):
     """`utterances` as predict_utterances takes them, every frame of each predicted (predict_dataset over windows of
     `max_frames` frames, short utterances padded by repeating frame 0).  Returns one (n_i, J, 2) numpy array per
     utterance in pixel units, J = 21, or the 4 / 12 predicted finger joints; with `dif_encoding` the loader's transforms
-    are the trainer's and the prediction gets the raw wrist back.  `mask_padding`: predict_dataset's."""
+    are the trainer's and the prediction gets the raw wrist back.  `mask_padding`, `overlap`, `blend`: predict_dataset's."""
     from .dataset import DeviceDataset, DeviceLoader
     from .predict import predict_dataset
     if isinstance(model, TextPoseTransformer):
@@ -106,7 +108,8 @@ def predict_all_frames(model, utterances, max_frames=200, dif_encoding=False, no
     loader = DeviceLoader(ds, batch_size, max_frames, selection="first", predict=predict, dif_encoding=dif_encoding,
                           normalize=normalize, pad="frame0")
     hand = slice(33 + openpose.PREDICT_TARGET_JOINTS[predict].start, 33 + openpose.PREDICT_TARGET_JOINTS[predict].stop)
-    return [np.stack([r[:, :54][:, hand], r[:, 54:108][:, hand]], axis=2) for r in predict_dataset(model, loader, mask_padding=mask_padding).utterance_rows()]
+    out = predict_dataset(model, loader, mask_padding=mask_padding, overlap=overlap, blend=blend)
+    return [np.stack([r[:, :54][:, hand], r[:, 54:108][:, hand]], axis=2) for r in out.utterance_rows()]
 
 
 def _tpt_geometry(state):
@@ -171,6 +174,13 @@ def main(argv=None):
                          "device-resident store), not only the first --max-frames; --dif-encoding then means the trainer's "
                          "pair of transforms (hand minus raw wrist, body minus chest) with the wrist added back to the output")
     ap.add_argument("--batch-size", type=int, default=128, help="--all-frames: windows per model launch (traintest.py:339)")
+    ap.add_argument("--overlap", type=int, default=0,
+                    help="--all-frames: the windows of an utterance longer than --max-frames overlap by this many frames "
+                         "(0 .. max-frames // 2) and the two predictions of those frames are blended (--blend), so no frame "
+                         "next to a window boundary is predicted from one side only")
+    ap.add_argument("--blend", default="linear", choices=["linear", "centre"],
+                    help="--overlap: cross-fade the two windows (linear), or take each frame from the window whose centre is "
+                         "nearer (centre)")
     ap.add_argument("--mask-padding", action="store_true",
                     help="TextPoseTransformer, --precision fp32: key-padding masks for the padded token ids and frames; "
                          "required for a checkpoint trained with mask_padding=True, wrong for one trained without")
@@ -178,6 +188,10 @@ def main(argv=None):
     if args.predict != "right_hand" and args.model != "TextPoseTransformer":
         # the reference's ConvModel / TransformerEnc hard-code 12 input and 21 output joints (HandPoseModels.py:28,32)
         raise SystemExit(f"--predict {args.predict} needs --model TextPoseTransformer")
+    if args.overlap and not args.all_frames:
+        raise SystemExit("--overlap needs --all-frames (without it only the first --max-frames frames are predicted, by one window)")
+    if not 0 <= args.overlap <= args.max_frames // 2:
+        raise SystemExit(f"--overlap must be in 0 .. --max-frames // 2 = {args.max_frames // 2}")
     if args.mask_padding and args.model != "TextPoseTransformer":
         raise SystemExit("--mask-padding needs --model TextPoseTransformer")
     if args.mask_padding and args.precision != "fp32":
@@ -220,7 +234,7 @@ def main(argv=None):
     if args.all_frames:
         pred = predict_all_frames(model, [u for _, u in utts], args.max_frames, args.dif_encoding, args.normalize,
                                   tokens=tokens, predict=args.predict, batch_size=args.batch_size,
-                                  mask_padding=args.mask_padding)
+                                  mask_padding=args.mask_padding, overlap=args.overlap, blend=args.blend)
         n_frames = [len(p) for p in pred]
     else:
         pred, n_frames = predict_utterances(model, [u for _, u in utts], args.max_frames, args.dif_encoding,

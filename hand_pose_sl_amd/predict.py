@@ -4,7 +4,8 @@ steps/traintest.py:332-391, which runs the model over the store in batches and w
   window_plan(...)       windows of `max_frames` frames that cover every frame of every utterance exactly once
                          (b2h_window_plan, a host function)
   predict_dataset(...)   plan -> DeviceLoader.build -> model -> DeviceLoader.write_back (b2h_scatter_rows), slice by
-                         slice of the plan; returns a new DeviceDataset
+                         slice of the plan; returns a new DeviceDataset.  overlap=K: windows that overlap by K frames
+                         (b2h_window_plan_overlap), blended in the write-back (b2h_scatter_rows_blend)
   joint_pixel_error(...) per-utterance, per-joint Euclidean pixel error of one store's right hands against another's
                          (b2h_joint_error), deterministic
 
@@ -26,14 +27,20 @@ from .text_pose_transformer import TextPoseTransformer
 from .transformer_enc import TransformerEnc
 
 
-def window_plan(offsets_or_dataset, max_frames, coverage="all"):
+def window_plan(offsets_or_dataset, max_frames, coverage="all", overlap=0):
     """(utt, start, skip) host int64 tensors: the windows of `max_frames` frames that predict a store.  "all": every row
     is addressed by exactly one (entry, frame >= skip) -- an utterance longer than max_frames gets ceil(len / max_frames)
     windows, the last a full one ending with the utterance whose first `skip` frames the one before it covers;
     "first": one window at 0 per utterance (the reference's `--frames-selection first`).  Empty utterances get none.
-    `offsets_or_dataset`: a DeviceDataset, or its (U + 1) ascending int64 offsets."""
+    `overlap` K > 0 ("all" only, K <= max_frames // 2; b2h_window_plan_overlap): the windows of a long utterance lie
+    max_frames - K apart, so each begins its used frames K rows before the one before it ends -- the rows that
+    `DeviceLoader.write_back_blend` blends.  `offsets_or_dataset`: a DeviceDataset, or its (U + 1) ascending int64
+    offsets."""
     if coverage not in _lib.COVERAGE:
         raise ValueError(f"coverage must be one of {sorted(_lib.COVERAGE)}, got {coverage!r}")
+    overlap = int(overlap)
+    if overlap and coverage != "all":
+        raise ValueError(f"overlap={overlap} needs coverage='all': with coverage={coverage!r} an utterance has one window")
     src = offsets_or_dataset.offsets if isinstance(offsets_or_dataset, DeviceDataset) else offsets_or_dataset
     off = torch.as_tensor(src).detach().cpu().contiguous()
     if off.dtype != torch.int64 or off.dim() != 1 or off.numel() < 1:
@@ -41,11 +48,15 @@ def window_plan(offsets_or_dataset, max_frames, coverage="all"):
     i64p = ctypes.POINTER(ctypes.c_int64)
     lib, n_utt = _lib.load(), off.numel() - 1
     host = lambda t: ctypes.cast(t.data_ptr(), i64p) if t.numel() else None
-    count = lib.b2h_window_plan(host(off), n_utt, int(max_frames), _lib.COVERAGE[coverage], None, None, None, 0)
+    if overlap:
+        fill = lambda *out: lib.b2h_window_plan_overlap(host(off), n_utt, int(max_frames), overlap, *out)
+    else:
+        fill = lambda *out: lib.b2h_window_plan(host(off), n_utt, int(max_frames), _lib.COVERAGE[coverage], *out)
+    count = fill(None, None, None, 0)
     if count < 0:
         raise ValueError(_lib.last_error())
     plan = [torch.empty(count, dtype=torch.int64) for _ in range(3)]
-    if lib.b2h_window_plan(host(off), n_utt, int(max_frames), _lib.COVERAGE[coverage], *[host(t) for t in plan], count) != count:
+    if fill(*[host(t) for t in plan], count) != count:
         raise RuntimeError(f"libb2h: {_lib.last_error()}")
     return tuple(plan)
 
@@ -82,7 +93,7 @@ def _check(model, loader, conf):
     return False
 
 
-def predict_dataset(model, loader, coverage="all", conf=1.0, mask_padding=False):
+def predict_dataset(model, loader, coverage="all", conf=1.0, mask_padding=False, overlap=0, blend="linear"):
     """Run `model` over the whole store of `loader` (a DeviceLoader: it supplies the store, batch_size, max_frames,
     predict, the transforms, the factor and the pad; its selection and shuffle are not used) and return a DeviceDataset
     with the same offsets, tokens and n_body whose predicted right-hand joints hold the predictions in store units --
@@ -91,11 +102,23 @@ def predict_dataset(model, loader, coverage="all", conf=1.0, mask_padding=False)
     runs in eval mode under no_grad in the precision it is set to (its mode is restored), dispatched as validate()
     dispatches; the loop does no host synchronisation.  mask_padding (TextPoseTransformer only, else ValueError):
     every window runs with its key-padding masks, text_lengths = token_lengths(tokens) and frame_lengths = the window's
-    n_frames, as train_epoch(mask_padding=True) trains; a model trained with masks must be run with them."""
+    n_frames, as train_epoch(mask_padding=True) trains; a model trained with masks must be run with them.
+    overlap K (0 .. max_frames // 2, coverage "all"): the windows of an utterance longer than max_frames overlap by K
+    frames (`window_plan(..., overlap=K)`) and `DeviceLoader.write_back_blend` blends the two predictions of those
+    frames -- blend "linear": a cross-fade, "centre": each frame from the window whose centre is nearer --, so no frame
+    next to a window boundary is predicted with context on one side only.  With K = 0 the calls and the result are
+    exactly those of a call without it."""
     mask_padding = check_mask_padding("predict_dataset()", model, mask_padding)
     text = _check(model, loader, conf)
+    overlap = int(overlap)
+    if not 0 <= overlap <= loader.max_frames // 2:
+        raise ValueError(f"overlap must be in 0 .. max_frames // 2 = {loader.max_frames // 2} (a frame is predicted by at "
+                         f"most two windows), got {overlap}")
+    if blend not in _lib.BLEND:
+        raise ValueError(f"blend must be one of {sorted(_lib.BLEND)}, got {blend!r}")
     ds, B = loader.ds, loader.batch_size
-    utt, start, skip = (t.to(ds.device) for t in window_plan(ds, loader.max_frames, coverage))
+    plan = utt, start, skip = [t.to(ds.device) for t in window_plan(ds, loader.max_frames, coverage, overlap)]
+    before = None    # overlap > 0: the prediction of the plan entry before the batch, a view that keeps its batch alive
     rows_out = ds.rows.clone()
     was_training = model.training
     model.eval()
@@ -115,7 +138,12 @@ def predict_dataset(model, loader, coverage="all", conf=1.0, mask_padding=False)
                 else:
                     lengths = padding_lengths(batch, ds.device) if mask_padding else {}
                     prediction = model(batch["text_tokens"], batch["input_kp"], **lengths)
-                loader.write_back(prediction.contiguous(), u, s, k, rows_out, conf)
+                prediction = prediction.contiguous()
+                if overlap:
+                    loader.write_back_blend(prediction, plan, i, rows_out, before, blend, conf)
+                    before = prediction[-1]
+                else:
+                    loader.write_back(prediction, u, s, k, rows_out, conf)
     finally:
         model.train(was_training)
     return ds.with_rows(rows_out)

@@ -909,6 +909,51 @@ int b2h_scatter_rows(const float* rows, int64_t n_rows, const int64_t* offsets, 
                      int predict, int flags, float factor, const float* pred, float conf,
                      float* rows_out, void* stream);
 
+/* Overlapping windows, blended in the write-back.  A frame at the edge of a window is predicted with context on one
+ * side only, so windows that merely touch can make the trajectory jump at every boundary.  b2h_window_plan_overlap is
+ * b2h_window_plan with B2H_COVER_ALL for windows that overlap by `overlap` = K frames (a HOST function, the same
+ * protocol and arrays).  With stride s = T - K, for utterance u of L rows:
+ *   L == 0     no entry
+ *   L <= T     (u, 0, 0)
+ *   L >  T     n = ceil((L - T) / s) + 1 entries: (u, i s, 0) for i = 0 .. n-2, then (u, L - T, (n-1) s - (L - T))
+ * The last window is again a full one that ends with the utterance; skip counts its leading frames that lie before
+ * row (n-1) s.  Every window after an utterance's first therefore begins its used frames (start + skip) exactly K rows
+ * before the end of the window before it, K <= T / 2 keeps a window's first K and last K frames apart, and with K = 0
+ * the plan is b2h_window_plan's, entry for entry.  Returns -1 as b2h_window_plan does, and for overlap < 0 or
+ * 2 overlap > T (the message names both numbers). */
+int64_t b2h_window_plan_overlap(const int64_t* offsets, int64_t n_utt, int64_t T, int64_t overlap, int64_t* utt_plan,
+                                int64_t* start_plan, int64_t* skip_plan, int64_t capacity);
+
+/* b2h_scatter_rows for such a plan.  utt_plan, start_plan and skip_plan are the WHOLE plan (n_plan entries each) in
+ * device memory; pred (B, T, nt, 2) holds the predictions of entries entry0 .. entry0 + B - 1 and pred_before
+ * (T, nt, 2) those of entry entry0 - 1.  For entry e, e - 1 is its predecessor if it exists and has the same utt, e + 1
+ * its successor likewise; windows are b2h_build_batch's (the clamped start), skips below 0 count as 0, and with
+ * w = max(start[e-1] + T - (start[e] + skip[e]), 0), or 0 without a predecessor:
+ *   frame t of entry e is written iff utt is known, len > 0 and skip[e] <= t < end, where end = min(len, T) without a
+ *   successor, else min(that, start[e+1] + skip[e+1] - start[e]): the tail a successor blends is left to the successor;
+ *   for p = t - skip[e] < w (the blend region) with pa the predecessor's value of the same row -- its frame
+ *   t + start[e] - start[e-1], read from pred (b > 0) or pred_before (b == 0) -- and pb the entry's own:
+ *     B2H_BLEND_LINEAR   wb = fl((float)(p + 1) / (float)(w + 1)), wa = fl(1 - wb), v = fl(fl(wa pa) + fl(wb pb))
+ *     B2H_BLEND_CENTRE   v = 2 p >= w ? pb : pa   (a select: each window keeps the frames nearer to its centre)
+ *   elsewhere v = pb; then * factor, + wrist and the three stores exactly as b2h_scatter_rows.
+ * (In a plan not made by b2h_window_plan_overlap a predecessor's frame before its frame 0 does not exist: v = pb.)
+ * Every addressed word is written by one lane of one launch over the plan -- no read-modify-write, no atomics, no
+ * dependence on the order of the launches -- and with K = 0 the result is b2h_scatter_rows's, bit for bit.
+ * pred_before may be NULL when entry0 == 0 or entry entry0 - 1 belongs to another utterance.  Which of the two holds is
+ * in device memory, which no host check reads: a caller passes it whenever entry0 > 0.  With NULL nothing is read
+ * through it and entry entry0 is written as if it had no predecessor.  It may alias pred.  Stream-ordered,
+ * asynchronous, allocates nothing, can be captured; one launch, 64-bit indices.  Refusals: b2h_scatter_rows's scalar
+ * checks in its order (n_plan negative is a negative shape), then B2H_ERR_INVALID for an unknown blend and for
+ * entry0 < 0 or entry0 + B > n_plan; B * T == 0 is then a no-op; then the size limits (n_plan <= 2^40), a NULL
+ * (utt_plan, start_plan and skip_plan are all required) or not 8-byte-aligned pointer, pred_before included, rows_out
+ * overlapping any other operand, pred_before included, a pointer that is not memory of the current device. */
+enum b2h_blend { B2H_BLEND_LINEAR = 0, B2H_BLEND_CENTRE = 1 };
+int b2h_scatter_rows_blend(const float* rows, int64_t n_rows, const int64_t* offsets, int64_t n_utt, int n_body,
+                           const int64_t* utt_plan, const int64_t* start_plan, const int64_t* skip_plan, int64_t n_plan,
+                           int64_t entry0, int64_t B, int64_t T, int predict, int flags, float factor,
+                           const float* pred, const float* pred_before, int blend, float conf,
+                           float* rows_out, void* stream);
+
 /* Per-utterance, per-joint pixel error of the right hand of one store against another of the same shape.  For joint j
  * of a row: dx = fl(xa - xb), dy likewise, d = sqrt(fl(fl(dx dx) + fl(dy dy))), each step correctly rounded fp32; the
  * row counts iff the TRUE store's confidence of that joint is > 0 (OpenPose writes 0 for a joint it did not detect).

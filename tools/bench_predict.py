@@ -10,8 +10,14 @@ result against the store (hps.joint_pixel_error), one JSON line.  Context only: 
 The store is tools/bench_loader.py's: seeded, `utterances` HDF5-style utterances (8 body joints) of T / 2 .. 3 T frames;
 the model the trainer's default geometry (4 + 4 layers, (8, 42)).
     python tools/bench_predict.py [B=128] [S=40] [T=200] [reps=5] [utterances=1024] [out.json] [once]
+                                  [--overlap K [--blend linear|centre]]
 `once`: one predict_dataset per precision and one joint_pixel_error, nothing else -- the run to put under
-`rocprofv3 --kernel-trace --stats` for the per-kernel times."""
+`rocprofv3 --kernel-trace --stats` for the per-kernel times.
+`--overlap K` adds, per precision, an "overlap" record: predict_dataset with windows that overlap by K frames
+(b2h_window_plan_overlap, b2h_scatter_rows_blend) against overlap 0, `reps` runs of each ALTERNATING in this one process
+after a warm-up of both, median and range; both plan lengths and their ratio, which is what the time ratio should be
+(the model's work grows with the number of windows); and write_back_blend_ms, one b2h_scatter_rows_blend launch of a full
+batch timed as write_back_ms is.  With `once` the one predict_dataset per precision runs with the overlap."""
 import json
 import os
 import sys
@@ -24,6 +30,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import hand_pose_sl_amd as hps  # noqa: E402
 
+OVERLAP, BLEND = 0, "linear"
+for flag in ("--overlap", "--blend"):          # the two options, wherever they stand; what is left is positional
+    if flag in sys.argv:
+        at = sys.argv.index(flag)
+        if at + 1 >= len(sys.argv):
+            sys.exit(f"{flag} needs a value")
+        value = sys.argv[at + 1]
+        del sys.argv[at:at + 2]
+        if flag == "--overlap":
+            OVERLAP = int(value)
+        else:
+            BLEND = value
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 200
@@ -86,7 +104,7 @@ for precision in ("fp32", "f16x3"):
     model.set_precision(precision)
     res = {}
     if ONCE:
-        pred = hps.predict_dataset(model, loader)
+        pred = hps.predict_dataset(model, loader, overlap=OVERLAP, blend=BLEND)
     else:
         wall_ms(lambda: hps.predict_dataset(model, loader))          # warm-up: allocators, workspaces
         ms = stats([wall_ms(lambda: hps.predict_dataset(model, loader)) for _ in range(REPS)])
@@ -101,7 +119,23 @@ for precision in ("fp32", "f16x3"):
             res["forward_ms"] = launch_ms(lambda: model.forward_long(batch["text_tokens"], batch["input_kp"]))
             res["write_back_ms"] = launch_ms(lambda: loader.write_back(y, u, s, k, rows_out))
         res["build_plus_write_back_over_forward"] = (res["build_ms"]["median"] + res["write_back_ms"]["median"]) / res["forward_ms"]["median"]
-        pred = hps.predict_dataset(model, loader)
+        if OVERLAP:
+            wide = [t.to(dev) for t in hps.window_plan(ds, T, overlap=OVERLAP)]
+            runs = {0: lambda: hps.predict_dataset(model, loader), OVERLAP: lambda: hps.predict_dataset(
+                model, loader, overlap=OVERLAP, blend=BLEND)}
+            ms = {k: [] for k in runs}
+            wall_ms(runs[OVERLAP])                                       # warm-up: this plan's last batch has another size
+            for _ in range(REPS):
+                for k, fn in runs.items():
+                    ms[k].append(wall_ms(fn))
+            with torch.no_grad():
+                blend_ms = launch_ms(lambda: loader.write_back_blend(y, wide, B, rows_out, y[-1], BLEND))
+            res["overlap"] = {"overlap": OVERLAP, "blend": BLEND, "windows": wide[0].numel(), "windows_without": plan[0].numel(),
+                              "windows_ratio": wide[0].numel() / plan[0].numel(), "predict_ms": stats(ms[OVERLAP]),
+                              "predict_ms_without": stats(ms[0]),
+                              "time_ratio_at_median": stats(ms[OVERLAP])["median"] / stats(ms[0])["median"],
+                              "write_back_blend_ms": blend_ms}
+        pred = hps.predict_dataset(model, loader, overlap=OVERLAP, blend=BLEND)
     out[precision] = res
 err = hps.joint_pixel_error(pred, ds)
 if not ONCE:
