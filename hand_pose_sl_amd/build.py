@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libb2h.so")
 SOURCES = ["b2h_api.hip"]
-HEADERS = [os.path.join("dev", "b2h_dev.h"), os.path.join("dev", "b2h_dev_exports.h"), "b2h_common.h", "f16_split.h", "kernel_adam.h", "kernel_attn_long.h", "kernel_build_batch.h", "kernel_build_batch_aug.h", "kernel_dropout_masks.h", "kernel_epoch_plan.h", "kernel_mfma.h", "kernel_mfma16.h", "kernel_mfma16w.h", "kernel_mfma3.h", "kernel_mfma3w.h", "kernel_scatter_rows.h", "kernel_step_control.h", "kernel_tenc.h", "kernel_tenc_train.h", "kernel_token_lengths.h", "kernel_tpt.h", "kernel_tpt_train.h", "kernel_train.h", "kernel_train_attn.h", "kernel_train_attn_long.h", "kernel_train_attn_mfma.h", "kernel_train_attn_whole_mfma.h", "kernel_train_linear_mfma.h", "kernel_valu.h", os.path.join("..", "..", "include", "b2h.h")]
+HEADERS = [os.path.join("dev", "b2h_dev.h"), os.path.join("dev", "b2h_dev_exports.h"), "b2h_common.h", "chunk_locator.h", "f16_split.h", "kernel_adam.h", "kernel_attn_long.h", "kernel_build_batch.h", "kernel_build_batch_aug.h", "kernel_dropout_masks.h", "kernel_epoch_plan.h", "kernel_mfma.h", "kernel_mfma16.h", "kernel_mfma16w.h", "kernel_mfma3.h", "kernel_mfma3w.h", "kernel_scatter_rows.h", "kernel_step_control.h", "kernel_tenc.h", "kernel_tenc_train.h", "kernel_token_lengths.h", "kernel_tpt.h", "kernel_tpt_train.h", "kernel_train.h", "kernel_train_attn.h", "kernel_train_attn_long.h", "kernel_train_attn_mfma.h", "kernel_train_attn_whole_mfma.h", "kernel_train_linear_mfma.h", "kernel_valu.h", os.path.join("..", "..", "include", "b2h.h")]
 ARCH = "gfx950"
 
 

@@ -159,6 +159,46 @@ int check_overlap(const std::vector<Span>& outs, const std::vector<Span>& read_o
     return B2H_OK;
 }
 
+// An operand of a data-path entry point (build_batch, scatter_rows, b2h_epoch_plan, b2h_joint_error): what a message
+// calls it, where it lies, its bytes, the alignment the call promises, whether the call may leave it out, whether it is
+// written.  A table of them is checked in its own order, so the read-only operands stand before the outputs.
+struct Op {
+    const char* name;
+    const void* p;
+    size_t n;
+    uintptr_t align;
+    bool optional, out;
+};
+
+// Operand by operand: a missing one that is not optional, then a misaligned one.
+int check_ops_given(const Op* ops, size_t count) {
+    for (const Op* o = ops; o < ops + count; ++o) {
+        if (!o->p && !o->optional) return fail(B2H_ERR_INVALID, std::string(o->name) + " is NULL");
+        if (misaligned(o->p, o->align))
+            return fail(B2H_ERR_INVALID, std::string(o->name) + " must be " + std::to_string(o->align) + "-byte aligned");
+    }
+    return B2H_OK;
+}
+
+// check_overlap over the operands that are given, then check_device_ptr on those that have bytes.  An operand of zero
+// bytes takes part in the overlap check only with `empty_overlaps` (it then collides with a span it lies strictly
+// inside): the entry points differ in this and callers can see it.
+int check_ops_memory(const Op* ops, size_t count, bool empty_overlaps) {
+    std::vector<Span> out_spans, in_spans;
+    for (const Op* o = ops; o < ops + count; ++o)
+        if (o->p && (o->n || empty_overlaps)) (o->out ? out_spans : in_spans).push_back({o->p, o->n, o->name});
+    if (int rc = check_overlap(out_spans, in_spans)) return rc;
+    for (const Op* o = ops; o < ops + count; ++o)
+        if (o->p && o->n)
+            if (int rc = check_device_ptr(o->p, o->name)) return rc;
+    return B2H_OK;
+}
+
+template <size_t N> int check_ops(const Op (&ops)[N], bool empty_overlaps) {
+    if (int rc = check_ops_given(ops, N)) return rc;
+    return check_ops_memory(ops, N, empty_overlaps);
+}
+
 // Host copies of a model's fp32 tensors (non-NULL; host memory, or memory of the current device) of the given
 // sizes in floats.  Returns after the device is idle: no launch may still read the old packed buffers.
 int fetch_tensors(const float* const* tensors, const std::vector<size_t>& sizes, int on_device,
@@ -2552,36 +2592,19 @@ int build_batch(const float* rows, int64_t n_rows, const int64_t* offsets, int64
     const int ni = predict == B2H_PREDICT_RIGHT_HAND ? n_body : predict == B2H_PREDICT_RIGHT_INDEX ? 29 : 21;
     const int nt = predict == B2H_PREDICT_RIGHT_HAND ? 21 : predict == B2H_PREDICT_RIGHT_INDEX ? 4 : 12;
     const size_t frames = (size_t)B * T;
-    // every operand: what the message calls it, where, how many bytes, whether the call may leave it out
-    struct Op { const char* name; const void* p; size_t n; bool optional; };
-    const Op read_only[] = {{"rows", rows, (size_t)n_rows * 3 * J * 4, n_rows == 0}, {"offsets", offsets, (size_t)(n_utt + 1) * 8, false},
-                            {"tokens", tokens, (size_t)n_utt * S * 8, true},
-                            {planned ? "utt_plan" : "utt", utt, entries * 8, planned && n_plan == 0},
-                            {planned ? "start_plan" : "start", start, entries * 8, true},
-                            {"step", step, 8, !planned},
-                            {"key", with ? with->key : nullptr, 16, !with}};
-    const int n_ops[2] = {7, 5};
-    const Op outs[] = {{"input_kp", input_kp, frames * ni * 8, false},       {"target_kp", target_kp, frames * nt * 8, false},
-                       {"target_conf", target_conf, frames * nt * 4, true}, {"text_tokens", text_tokens, (size_t)B * S * 8, true},
-                       {"n_frames", n_frames, (size_t)B * 8, false}};
-    for (int l = 0; l < 2; ++l)
-        for (int i = 0; i < n_ops[l]; ++i) {
-            const Op& o = (l ? outs : read_only)[i];
-            if (!o.p && !o.optional) return fail(B2H_ERR_INVALID, std::string(o.name) + " is NULL");
-            if (misaligned(o.p, 8)) return fail(B2H_ERR_INVALID, std::string(o.name) + " must be 8-byte aligned");
-        }
-    std::vector<Span> out_spans, in_spans;
-    for (const Op& o : outs)
-        if (o.p) out_spans.push_back({o.p, o.n});
-    for (const Op& o : read_only)
-        if (o.p) in_spans.push_back({o.p, o.n, o.name});
-    if (int rc = check_overlap(out_spans, in_spans)) return rc;
-    for (int l = 0; l < 2; ++l)
-        for (int i = 0; i < n_ops[l]; ++i) {
-            const Op& o = (l ? outs : read_only)[i];
-            if (o.p && o.n)
-                if (int rc = check_device_ptr(o.p, o.name)) return rc;
-        }
+    const Op ops[] = {{"rows", rows, (size_t)n_rows * 3 * J * 4, 8, n_rows == 0, false},
+                      {"offsets", offsets, (size_t)(n_utt + 1) * 8, 8, false, false},
+                      {"tokens", tokens, (size_t)n_utt * S * 8, 8, true, false},
+                      {planned ? "utt_plan" : "utt", utt, entries * 8, 8, planned && n_plan == 0, false},
+                      {planned ? "start_plan" : "start", start, entries * 8, 8, true, false},
+                      {"step", step, 8, 8, !planned, false},
+                      {"key", with ? with->key : nullptr, 16, 8, !with, false},
+                      {"input_kp", input_kp, frames * ni * 8, 8, false, true},
+                      {"target_kp", target_kp, frames * nt * 8, 8, false, true},
+                      {"target_conf", target_conf, frames * nt * 4, 8, true, true},
+                      {"text_tokens", text_tokens, (size_t)B * S * 8, 8, true, true},
+                      {"n_frames", n_frames, (size_t)B * 8, 8, false, true}};
+    if (int rc = check_ops(ops, true)) return rc;
     BbArgs a;
     a.rows = rows; a.offsets = offsets; a.tokens = tokens; a.utt = utt; a.start = start;
     a.input_kp = input_kp; a.target_kp = target_kp; a.target_conf = target_conf; a.text_tokens = text_tokens;
@@ -2638,26 +2661,15 @@ int scatter_rows(const float* rows, int64_t n_rows, const int64_t* offsets, int6
     const int J = n_body + 42;
     const int nt = predict == B2H_PREDICT_RIGHT_HAND ? 21 : predict == B2H_PREDICT_RIGHT_INDEX ? 4 : 12;
     const size_t store = (size_t)n_rows * 3 * J * 4, entries = (size_t)(with ? with->n_plan : B) * 8;
-    struct Op { const char* name; const void* p; size_t n; bool optional, out; };
-    const Op ops[] = {{"rows", rows, store, n_rows == 0, false},
-                      {"offsets", offsets, (size_t)(n_utt + 1) * 8, false, false},
-                      {with ? "utt_plan" : "utt", utt, entries, false, false},
-                      {with ? "start_plan" : "start", start, entries, !with, false},
-                      {with ? "skip_plan" : "skip", skip, entries, !with, false},
-                      {"pred", pred, (size_t)B * T * nt * 8, false, false},
-                      {"pred_before", with ? with->pred_before : nullptr, (size_t)T * nt * 8, true, false},
-                      {"rows_out", rows_out, store, n_rows == 0, true}};
-    for (const Op& o : ops) {
-        if (!o.p && !o.optional) return fail(B2H_ERR_INVALID, std::string(o.name) + " is NULL");
-        if (misaligned(o.p, 8)) return fail(B2H_ERR_INVALID, std::string(o.name) + " must be 8-byte aligned");
-    }
-    std::vector<Span> out_spans, in_spans;
-    for (const Op& o : ops)
-        if (o.p) (o.out ? out_spans : in_spans).push_back({o.p, o.n, o.name});
-    if (int rc = check_overlap(out_spans, in_spans)) return rc;
-    for (const Op& o : ops)
-        if (o.p && o.n)
-            if (int rc = check_device_ptr(o.p, o.name)) return rc;
+    const Op ops[] = {{"rows", rows, store, 8, n_rows == 0, false},
+                      {"offsets", offsets, (size_t)(n_utt + 1) * 8, 8, false, false},
+                      {with ? "utt_plan" : "utt", utt, entries, 8, false, false},
+                      {with ? "start_plan" : "start", start, entries, 8, !with, false},
+                      {with ? "skip_plan" : "skip", skip, entries, 8, !with, false},
+                      {"pred", pred, (size_t)B * T * nt * 8, 8, false, false},
+                      {"pred_before", with ? with->pred_before : nullptr, (size_t)T * nt * 8, 8, true, false},
+                      {"rows_out", rows_out, store, 8, n_rows == 0, true}};
+    if (int rc = check_ops(ops, true)) return rc;
     SbArgs g = {};
     SrArgs& a = g.s;
     a.w.rows = rows; a.w.offsets = offsets; a.w.utt = utt; a.w.start = start;
@@ -2756,18 +2768,13 @@ int b2h_epoch_plan(const int64_t* offsets, int64_t n_utt, int64_t T, int shuffle
     if (random_crop && !offsets && n_utt > 0) return fail(B2H_ERR_INVALID, "offsets is NULL");
     if (!random_crop) offsets = nullptr;   // not read
     const size_t plan = (size_t)n_utt * 8;
-    const struct { const char* name; const void* p; size_t n; } ops[3] = {
-        {"offsets", offsets, (size_t)(n_utt + 1) * 8}, {"utt_plan", utt_plan, plan}, {"start_plan", start_plan, plan}};
-    for (const auto& o : ops)
-        if (misaligned(o.p, 8)) return fail(B2H_ERR_INVALID, std::string(o.name) + " must be 8-byte aligned");
+    // every operand optional: what may be NULL was settled above, with messages of this entry point's own
+    const Op ops[] = {{"offsets", offsets, (size_t)(n_utt + 1) * 8, 8, true, false},
+                      {"utt_plan", utt_plan, plan, 8, true, true},
+                      {"start_plan", start_plan, plan, 8, true, true}};
+    if (int rc = check_ops_given(ops, 3)) return rc;
     if (n_utt == 0) return B2H_OK;
-    std::vector<Span> out_spans = {{utt_plan, plan}}, in_spans;
-    if (start_plan) out_spans.push_back({start_plan, plan});
-    if (offsets) in_spans.push_back({offsets, ops[0].n, "offsets"});
-    if (int rc = check_overlap(out_spans, in_spans)) return rc;
-    for (const auto& o : ops)
-        if (o.p)
-            if (int rc = check_device_ptr(o.p, o.name)) return rc;
+    if (int rc = check_ops_memory(ops, 3, true)) return rc;
     EpArgs a;
     a.offsets = offsets; a.utt_plan = utt_plan; a.start_plan = start_plan;
     a.n_utt = n_utt; a.T = T;
@@ -2838,7 +2845,6 @@ int b2h_joint_error(const float* rows_pred, const float* rows_true, int64_t n_ro
     if (n_rows > ((int64_t)1 << 40) || n_utt > ((int64_t)1 << 30)) return fail(B2H_ERR_SHAPE, "store too large");
     if (n_utt == 0 && !total_sum) return B2H_OK;
     const size_t store = (size_t)n_rows * 3 * (n_body + 42) * 4, cells = (size_t)n_utt * kJeJoints;
-    struct Op { const char* name; const void* p; size_t n; uintptr_t align; bool optional, out; };
     const Op ops[] = {{"rows_pred", rows_pred, store, 4, n_rows == 0, false},
                       {"rows_true", rows_true, store, 4, n_rows == 0, false},
                       {"offsets", offsets, (size_t)(n_utt + 1) * 8, 8, n_utt == 0, false},
@@ -2846,18 +2852,7 @@ int b2h_joint_error(const float* rows_pred, const float* rows_true, int64_t n_ro
                       {"utt_count", utt_count, cells * 4, 4, n_utt == 0, true},
                       {"total_sum", total_sum, kJeJoints * 8, 8, true, true},
                       {"total_count", total_count, kJeJoints * 8, 8, true, true}};
-    for (const Op& o : ops) {
-        if (!o.p && !o.optional) return fail(B2H_ERR_INVALID, std::string(o.name) + " is NULL");
-        if (misaligned(o.p, o.align))
-            return fail(B2H_ERR_INVALID, std::string(o.name) + " must be " + std::to_string(o.align) + "-byte aligned");
-    }
-    std::vector<Span> out_spans, in_spans;
-    for (const Op& o : ops)
-        if (o.p && o.n) (o.out ? out_spans : in_spans).push_back({o.p, o.n, o.name});
-    if (int rc = check_overlap(out_spans, in_spans)) return rc;
-    for (const Op& o : ops)
-        if (o.p && o.n)
-            if (int rc = check_device_ptr(o.p, o.name)) return rc;
+    if (int rc = check_ops(ops, false)) return rc;
     JeArgs a;
     a.rows_pred = rows_pred; a.rows_true = rows_true; a.offsets = offsets; a.utt_sum = utt_sum; a.utt_count = utt_count;
     a.total_sum = total_sum; a.total_count = total_count; a.n_rows = n_rows; a.n_utt = n_utt; a.n_body = n_body;

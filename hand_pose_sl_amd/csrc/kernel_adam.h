@@ -17,10 +17,12 @@
 // partial chunk of a tensor, and every chunk of a tensor one of whose four pointers is not 16-byte aligned, goes
 // element by element, never past numel.  One launch serves up to kAdMaxTensors tensors whose pointers, sizes and
 // chunk-count prefix travel by value in the kernel arguments (no device table, no copy: capture-safe), and the grid
-// walks ONE flat chunk index over all of them, as b2h_dropout_masks_k does.  No LDS, no atomics.
+// walks ONE flat chunk index over all of them, as b2h_dropout_masks_k does; chunk_tensor (chunk_locator.h) finds the
+// tensor of a chunk.  No LDS, no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "chunk_locator.h"
 
 namespace b2h {
 
@@ -81,67 +83,11 @@ __device__ __forceinline__ void ad_update(float& p, float g, float& m, float& v,
     p = __builtin_fmaf(s.neg_step, u, p);
 }
 
-__global__ void __launch_bounds__(kAdThreads) b2h_adam_step_k(const AdArgs a) {
-    const int64_t total = a.first[a.n], stride = (int64_t)gridDim.x * kAdThreads;
-    AdScalars s{a.w1, a.b2f, a.w2, a.eps, a.wd, a.bc2s, -a.step_size};
-    if (a.step_dev || a.lr_dev) { // wave-uniform reads of the two words
-        const int64_t t = a.step + (a.step_dev ? *a.step_dev : 0);
-        float step_size;
-        ad_bias(a.b1, a.b2, (double)(a.lr_dev ? *a.lr_dev : a.lr), t, &s.bc2s, &step_size);
-        s.neg_step = -step_size;
-    }
-    for (int64_t c = (int64_t)blockIdx.x * kAdThreads + threadIdx.x; c < total; c += stride) {
-        // the tensor of chunk c: the last i with first[i] <= c.  The wave's lowest chunk (its first active lane) is
-        // searched with wave-uniform reads, then each lane steps past the few tensor ends inside the wave's 64 chunks.
-        const int64_t cw = ((int64_t)__builtin_amdgcn_readfirstlane((int)(c >> 32)) << 32) |
-                           (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        int lo = 0, hi = a.n; // first[lo] <= cw < first[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (a.first[mid] <= cw)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        int i = lo;
-        while (c >= a.first[i + 1]) ++i; // c < total = first[n]: ends at i <= n - 1
-        const int64_t numel = a.numel[i], e0 = (c - a.first[i]) * 4; // e0 < numel: a chunk exists only where elements do
-        float* pp = a.p[i] + e0;
-        const float* gp = a.g[i] + e0;
-        float* mp = a.m[i] + e0;
-        float* vp = a.v[i] + e0;
-        const bool aligned = (((uintptr_t)a.p[i] | (uintptr_t)a.g[i] | (uintptr_t)a.m[i] | (uintptr_t)a.v[i]) & 15) == 0;
-        if (aligned && e0 + 4 <= numel) {
-            const float4 g4 = *reinterpret_cast<const float4*>(gp);
-            float4 m4 = *reinterpret_cast<const float4*>(mp), v4 = *reinterpret_cast<const float4*>(vp),
-                   p4 = *reinterpret_cast<const float4*>(pp);
-            ad_update(p4.x, g4.x, m4.x, v4.x, s);
-            ad_update(p4.y, g4.y, m4.y, v4.y, s);
-            ad_update(p4.z, g4.z, m4.z, v4.z, s);
-            ad_update(p4.w, g4.w, m4.w, v4.w, s);
-            *reinterpret_cast<float4*>(pp) = p4;
-            *reinterpret_cast<float4*>(mp) = m4;
-            *reinterpret_cast<float4*>(vp) = v4;
-        } else {
-            const int count = (int)(numel - e0 < 4 ? numel - e0 : 4); // 1 .. 4
-            for (int j = 0; j < count; ++j) {
-                float p = pp[j], m = mp[j], v = vp[j];
-                ad_update(p, gp[j], m, v, s);
-                pp[j] = p;
-                mp[j] = m;
-                vp[j] = v;
-            }
-        }
-    }
-}
-
 // b2h_adam_step_guarded: the update above behind the two device words of b2h_step_prepare (kernel_step_control.h).
 //   b2h_adam_guarded_k  the same listing per element through ad_update, after
 //                         g <- g * *grad_scale_dev        one fp32 rounding, as g.mul_(clip_coef) in torch
 //                       and every thread returns before it touches memory when *apply_dev == 0 (a wave-uniform read).
 //                       Either word may be nullptr: no scaling, no guard.
-// A sibling of b2h_adam_step_k with a loop of its own, not an instantiation of one template: the kernel above keeps its
-// source and its listing (tests/test_adam_cpu.py pins both).
 struct AdGuard {
     const float* grad_scale_dev; // or nullptr
     const int64_t* apply_dev;    // or nullptr
@@ -153,32 +99,24 @@ __device__ __forceinline__ float ad_scale(float g, float s) {
     return g * s;
 }
 
-__global__ void __launch_bounds__(kAdThreads) b2h_adam_guarded_k(const AdArgs a, const AdGuard w) {
-    if (w.apply_dev && *w.apply_dev == 0) return;
-    const bool scaled = w.grad_scale_dev != nullptr;
-    const float gs = scaled ? *w.grad_scale_dev : 1.f;
+// The loop of both kernels.  kMayScale is the compile-time half of "is the gradient scaled": false for
+// b2h_adam_step_k, whose instantiation has no scale, no test of one and no multiply; true for b2h_adam_guarded_k, where
+// `scaled` (is there a scale word) and gs (its value) are the run-time half.  Force-inlined into two __global__
+// functions that keep their names: the tests and tools find them by mangled name, and a listing per entry point is what
+// tests/test_adam_cpu.py and tests/test_step_control_cpu.py count loads, stores and divisions in.  `a` by value, as the
+// kernels hold it: no copy is made (the table stays in the kernel arguments) and hipcc's prologue stays what it was.
+template <bool kMayScale> __device__ __forceinline__ void ad_run(const AdArgs a, bool scaled, float gs) {
     const int64_t total = a.first[a.n], stride = (int64_t)gridDim.x * kAdThreads;
     AdScalars s{a.w1, a.b2f, a.w2, a.eps, a.wd, a.bc2s, -a.step_size};
-    if (a.step_dev || a.lr_dev) {
+    if (a.step_dev || a.lr_dev) { // wave-uniform reads of the two words
         const int64_t t = a.step + (a.step_dev ? *a.step_dev : 0);
         float step_size;
         ad_bias(a.b1, a.b2, (double)(a.lr_dev ? *a.lr_dev : a.lr), t, &s.bc2s, &step_size);
         s.neg_step = -step_size;
     }
     for (int64_t c = (int64_t)blockIdx.x * kAdThreads + threadIdx.x; c < total; c += stride) {
-        const int64_t cw = ((int64_t)__builtin_amdgcn_readfirstlane((int)(c >> 32)) << 32) |
-                           (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        int lo = 0, hi = a.n; // first[lo] <= cw < first[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (a.first[mid] <= cw)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        int i = lo;
-        while (c >= a.first[i + 1]) ++i;
-        const int64_t numel = a.numel[i], e0 = (c - a.first[i]) * 4;
+        const int i = chunk_tensor(a.first, a.n, c);
+        const int64_t numel = a.numel[i], e0 = (c - a.first[i]) * 4; // e0 < numel: a chunk exists only where elements do
         float* pp = a.p[i] + e0;
         const float* gp = a.g[i] + e0;
         float* mp = a.m[i] + e0;
@@ -188,7 +126,8 @@ __global__ void __launch_bounds__(kAdThreads) b2h_adam_guarded_k(const AdArgs a,
             float4 g4 = *reinterpret_cast<const float4*>(gp);
             float4 m4 = *reinterpret_cast<const float4*>(mp), v4 = *reinterpret_cast<const float4*>(vp),
                    p4 = *reinterpret_cast<const float4*>(pp);
-            if (scaled) g4 = make_float4(ad_scale(g4.x, gs), ad_scale(g4.y, gs), ad_scale(g4.z, gs), ad_scale(g4.w, gs));
+            if (kMayScale && scaled)
+                g4 = make_float4(ad_scale(g4.x, gs), ad_scale(g4.y, gs), ad_scale(g4.z, gs), ad_scale(g4.w, gs));
             ad_update(p4.x, g4.x, m4.x, v4.x, s);
             ad_update(p4.y, g4.y, m4.y, v4.y, s);
             ad_update(p4.z, g4.z, m4.z, v4.z, s);
@@ -200,13 +139,21 @@ __global__ void __launch_bounds__(kAdThreads) b2h_adam_guarded_k(const AdArgs a,
             const int count = (int)(numel - e0 < 4 ? numel - e0 : 4); // 1 .. 4
             for (int j = 0; j < count; ++j) {
                 float p = pp[j], m = mp[j], v = vp[j];
-                ad_update(p, scaled ? ad_scale(gp[j], gs) : gp[j], m, v, s);
+                ad_update(p, kMayScale && scaled ? ad_scale(gp[j], gs) : gp[j], m, v, s);
                 pp[j] = p;
                 mp[j] = m;
                 vp[j] = v;
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(kAdThreads) b2h_adam_step_k(const AdArgs a) { ad_run<false>(a, false, 1.f); }
+
+__global__ void __launch_bounds__(kAdThreads) b2h_adam_guarded_k(const AdArgs a, const AdGuard w) {
+    if (w.apply_dev && *w.apply_dev == 0) return;
+    const bool scaled = w.grad_scale_dev != nullptr;
+    ad_run<true>(a, scaled, scaled ? *w.grad_scale_dev : 1.f);
 }
 
 } // namespace b2h

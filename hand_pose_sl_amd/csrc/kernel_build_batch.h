@@ -12,6 +12,7 @@
 // and n_frames one int64.  Every output word is written by exactly one lane; nothing is read outside the rows of
 // utt[b].  An id outside [0, n_utt), or offsets of it outside 0 <= lo <= hi <= n_rows, indexes nothing: that
 // sequence's floats become quiet NaNs, its tokens -1, its n_frames 0.  No LDS, no atomics; indices are 64-bit.
+// The body is bb_run below, which b2h_build_batch_aug_k (kernel_build_batch_aug.h) runs too, with a Lane of its own.
 //
 // b2h_build_batch_planned launches the same kernel with BbArgs::step set: utt and start are then the plan of a whole
 // epoch (kernel_epoch_plan.h) and sequence b reads entry *step * B + b of it; a step below 0 or an entry at or past
@@ -80,7 +81,27 @@ __device__ __forceinline__ int bb_source(int n_body, int predict, bool target, i
     return target ? hand + 1 + j : (j < 8 ? hand + 13 + j : (j == 8 ? hand : j - 9));     // Build3fingerItem
 }
 
-__global__ __launch_bounds__(kBbThreads) void b2h_build_batch_k(const BbArgs a) {
+// What b2h_build_batch_k and b2h_build_batch_aug_k (kernel_build_batch_aug.h) differ in, as the `Lane` of bb_run: the
+// value of a live joint, the joint whose confidence is copied, and the jitter.  This one reads the store row as it is.
+struct BbPlainLane {
+    __device__ __forceinline__ void draw(const BbArgs&, int64_t, bool) {}
+    __device__ __forceinline__ int conf_joint(const BbArgs&, int src) const { return src; }
+    __device__ __forceinline__ float2 joint(const BbArgs&, const float* r, int J, int q) const {
+        return make_float2(r[q], r[J + q]);
+    }
+    __device__ __forceinline__ void jitter(float2&, int64_t, int) const {}
+};
+
+// The body of both build kernels: the five block runs, the frame decomposition, padding, the difference encoding, the
+// division and the text_tokens and n_frames runs.  Force-inlined into each __global__ entry point, which keeps its name.
+// Contraction is off for the whole body because the augmented build's every operation is one rounding
+// (kernel_build_batch_aug.h); the plain build has a subtraction and a division here and nothing that could fuse, with
+// the pragma or without.  The pragma is lexical: a Lane's own arithmetic needs its own.
+// `Args` is `const BbArgs` or `const BbArgs&`: each kernel hands its arguments over the way its body held them before
+// the two were folded (the plain kernel by value, the augmented one as the `b` inside its BaArgs), which keeps hipcc's
+// listing of the plain kernel the one it was (profiles/datapath_refactor/).
+template <class Args, class Lane> __device__ __forceinline__ void bb_run(Args a, Lane lane) {
+#pragma clang fp contract(off)
     const int64_t blk = blockIdx.x;
     const int seg = blk < a.first[1] ? 0 : blk < a.first[2] ? 1 : blk < a.first[3] ? 2 : blk < a.first[4] ? 3 : 4;
     const int64_t i = (blk - a.first[seg]) * kBbThreads + threadIdx.x;
@@ -99,18 +120,20 @@ __global__ __launch_bounds__(kBbThreads) void b2h_build_batch_k(const BbArgs a) 
         const int J = a.n_body + 42;
         const float* r = a.rows + row * (3 * J);
         const int src = bb_source(a.n_body, a.predict, seg != 0, j);
+        lane.draw(a, b, live);
         if (seg == 2) {
-            a.target_conf[i] = !known ? qnan : live ? r[2 * J + src] : 0.f;
+            a.target_conf[i] = !known ? qnan : live ? r[2 * J + lane.conf_joint(a, src)] : 0.f;
             return;
         }
         float2 v = make_float2(known ? 0.f : qnan, known ? 0.f : qnan);
         if (live) {
-            v = make_float2(r[src], r[J + src]);
+            v = lane.joint(a, r, J, src);
             if (a.flags & kBbDif) {     // the hand minus the RAW body wrist (4), the body minus the chest (1)
-                const int ref = src < a.n_body ? 1 : 4;
-                v.x -= r[ref];
-                v.y -= r[J + ref];
+                const float2 ref = lane.joint(a, r, J, src < a.n_body ? 1 : 4);
+                v.x = v.x - ref.x;
+                v.y = v.y - ref.y;
             }
+            if (seg == 0) lane.jitter(v, t, j);
             if (a.flags & kBbNorm) { v.x = v.x / a.factor; v.y = v.y / a.factor; }
         }
         reinterpret_cast<float2*>(seg == 0 ? a.input_kp : a.target_kp)[i] = v;
@@ -126,5 +149,7 @@ __global__ __launch_bounds__(kBbThreads) void b2h_build_batch_k(const BbArgs a) 
         a.n_frames[i] = bb_window(a, i, lo, len) ? (len < a.T ? len : a.T) : 0;
     }
 }
+
+__global__ __launch_bounds__(kBbThreads) void b2h_build_batch_k(const BbArgs a) { bb_run<const BbArgs>(a, BbPlainLane{}); }
 
 } // namespace b2h

@@ -36,9 +36,11 @@
 // default contraction, and inlined here their product and sum fuse into one v_fma_f32 whatever pragma the caller has --
 // and / is the correctly rounded division hipcc gives by default, as in kernel_build_batch.h.
 //
-// The grid is b2h_build_batch_k's: five block runs, one float2 per lane, every output word written exactly once.  The
-// sequence block is recomputed per lane (one Philox block and about ten operations), the jitter block only on the
-// input_kp run.  No LDS, no atomics, no scratch; ordinary vector stores.
+// The kernel is bb_run of kernel_build_batch.h, the body it shares with b2h_build_batch_k -- the grid's five block runs,
+// one float2 per lane, every output word written exactly once, padding, the difference encoding, the division -- with
+// BaLane below for the three things that differ: the value of a live joint, the joint whose confidence is copied, and
+// the jitter.  The sequence block is recomputed per lane (one Philox block and about ten operations), the jitter block
+// only on the input_kp run.  No LDS, no atomics, no scratch; ordinary vector stores.
 #pragma once
 #include "kernel_build_batch.h"
 #include "kernel_dropout_masks.h"
@@ -102,65 +104,38 @@ __device__ __forceinline__ float2 ba_joint(const BaArgs& g, const BaSeq& d, cons
     return make_float2(cx + d.s * rx, cy + d.s * ry);
 }
 
-__global__ __launch_bounds__(kBbThreads) void b2h_build_batch_aug_k(const BaArgs g) {
-#pragma clang fp contract(off)
-    const BbArgs& a = g.b;
-    const int64_t blk = blockIdx.x;
-    const int seg = blk < a.first[1] ? 0 : blk < a.first[2] ? 1 : blk < a.first[3] ? 2 : blk < a.first[4] ? 3 : 4;
-    const int64_t i = (blk - a.first[seg]) * kBbThreads + threadIdx.x;
-    const float qnan = __int_as_float(0x7fc00000);
-    if (seg <= 2) {
-        const int nj = seg == 0 ? a.ni : a.nt;
-        if (i >= a.B * a.T * nj) return;
-        const int64_t f = i / nj;
-        const int j = (int)(i - f * nj);
-        const int64_t b = f / a.T, t = f - b * a.T;
-        int64_t lo, len;
-        const bool known = bb_window(a, b, lo, len);
-        const bool live = known && len > 0 && (t < len || (a.flags & kBbPadFrame0));
-        const int64_t row = live ? lo + (t < len ? t : 0) : 0;
-        const int J = a.n_body + 42;
-        const float* r = a.rows + row * (3 * J);
-        const int src = bb_source(a.n_body, a.predict, seg != 0, j);
-        // the draw index: the plan entry, or entry0 + b; below 2^32 by the host's shape rule
-        const uint32_t p = (uint32_t)(a.step ? bb_entry(a, b) : g.entry0 + b);
-        const uint64_t seed = g.key[0], epoch = g.key[1];         // wave-uniform: two 8-byte scalar loads
-        BaSeq d = {1.f, 1.f, 0.f, false};
+// The Lane of bb_run (kernel_build_batch.h) for the augmented build: the sequence's draws, the virtual row's joints,
+// the mirrored confidence and the jitter.
+struct BaLane {
+    const BaArgs& g;
+    uint32_t p;               // the draw index: the plan entry, or entry0 + b; below 2^32 by the host's shape rule
+    uint64_t seed, epoch;
+    BaSeq d;
+
+    __device__ __forceinline__ void draw(const BbArgs& a, int64_t b, bool live) {
+        p = (uint32_t)(a.step ? bb_entry(a, b) : g.entry0 + b);
+        seed = g.key[0], epoch = g.key[1];                         // wave-uniform: two 8-byte scalar loads
+        d = {1.f, 1.f, 0.f, false};
         if (live && (g.spin || g.mirror_thr)) d = ba_sequence(g, p, seed, epoch);
-        if (seg == 2) {
-            a.target_conf[i] = !known ? qnan : live ? r[2 * J + (d.mirror ? ba_mirrored(a.n_body, src) : src)] : 0.f;
-            return;
-        }
-        float2 v = make_float2(known ? 0.f : qnan, known ? 0.f : qnan);
-        if (live) {
-            v = ba_joint(g, d, r, J, src);
-            if (a.flags & kBbDif) {     // the hand minus the virtual row's body wrist (4), the body minus its chest (1)
-                const float2 ref = ba_joint(g, d, r, J, src < a.n_body ? 1 : 4);
-                v.x = v.x - ref.x;
-                v.y = v.y - ref.y;
-            }
-            if (seg == 0 && g.jitter != 0.f) {
-                uint32_t w[4];
-                dm_philox(p, kBaTagJitter | (uint32_t)t << 8, (uint32_t)epoch, (uint32_t)(j >> 1), (uint32_t)seed,
-                          (uint32_t)(seed >> 32), w);
-                const uint32_t wx = (j & 1) ? w[2] : w[0], wy = (j & 1) ? w[3] : w[1];
-                v.x = v.x + g.jitter * ba_unit(wx);
-                v.y = v.y + g.jitter * ba_unit(wy);
-            }
-            if (a.flags & kBbNorm) { v.x = v.x / a.factor; v.y = v.y / a.factor; }
-        }
-        reinterpret_cast<float2*>(seg == 0 ? a.input_kp : a.target_kp)[i] = v;
-    } else if (seg == 3) {
-        if (i >= a.B * a.S) return;
-        const int64_t b = i / a.S, s = i - b * a.S;
-        const int64_t e = bb_entry(a, b);
-        const int64_t u = e < 0 ? -1 : a.utt[e];
-        a.text_tokens[i] = (u >= 0 && u < a.n_utt) ? a.tokens[u * a.S + s] : -1;
-    } else {
-        if (i >= a.B) return;
-        int64_t lo, len;
-        a.n_frames[i] = bb_window(a, i, lo, len) ? (len < a.T ? len : a.T) : 0;
     }
-}
+    __device__ __forceinline__ int conf_joint(const BbArgs& a, int src) const {
+        return d.mirror ? ba_mirrored(a.n_body, src) : src;
+    }
+    __device__ __forceinline__ float2 joint(const BbArgs&, const float* r, int J, int q) const {
+        return ba_joint(g, d, r, J, q);
+    }
+    __device__ __forceinline__ void jitter(float2& v, int64_t t, int j) const {
+#pragma clang fp contract(off)
+        if (g.jitter == 0.f) return;
+        uint32_t w[4];
+        dm_philox(p, kBaTagJitter | (uint32_t)t << 8, (uint32_t)epoch, (uint32_t)(j >> 1), (uint32_t)seed,
+                  (uint32_t)(seed >> 32), w);
+        const uint32_t wx = (j & 1) ? w[2] : w[0], wy = (j & 1) ? w[3] : w[1];
+        v.x = v.x + g.jitter * ba_unit(wx);
+        v.y = v.y + g.jitter * ba_unit(wy);
+    }
+};
+
+__global__ __launch_bounds__(kBbThreads) void b2h_build_batch_aug_k(const BaArgs g) { bb_run<const BbArgs&>(g.b, BaLane{g}); }
 
 } // namespace b2h

@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "chunk_locator.h"
 
 namespace b2h {
 
@@ -56,20 +57,7 @@ __global__ void __launch_bounds__(kDmThreads) b2h_dropout_masks_k(const DmArgs a
     const int64_t total = a.first[a.n], stride = (int64_t)gridDim.x * kDmThreads;
     const uint32_t s = (uint32_t)(a.step + (a.step_dev ? *a.step_dev : 0));
     for (int64_t c = (int64_t)blockIdx.x * kDmThreads + threadIdx.x; c < total; c += stride) {
-        // the mask of chunk c: the last i with first[i] <= c.  The wave's lowest chunk (its first active lane) is
-        // searched with wave-uniform reads, then each lane steps past the few mask ends inside the wave's 64 chunks.
-        const int64_t cw = ((int64_t)__builtin_amdgcn_readfirstlane((int)(c >> 32)) << 32) |
-                           (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        int lo = 0, hi = a.n; // first[lo] <= cw < first[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (a.first[mid] <= cw)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        int i = lo;
-        while (c >= a.first[i + 1]) ++i; // c < total = first[n]: ends at i <= n - 1
+        const int i = chunk_tensor(a.first, a.n, c); // the mask of chunk c
         const int64_t numel = a.numel[i], e0 = (c - a.first[i]) * 16;
         uint8_t* dst = a.ptr[i] + e0;
         const uint32_t number = a.number0 + (uint32_t)i;

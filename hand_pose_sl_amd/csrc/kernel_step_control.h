@@ -24,6 +24,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "chunk_locator.h"
 
 namespace b2h {
 
@@ -79,20 +80,7 @@ __global__ void __launch_bounds__(kScThreads) b2h_grad_sumsq_k(const SsArgs a) {
         for (int k = 0; k < kScBlockChunks / kScThreads; ++k) {
             const int64_t c = b * kScBlockChunks + k * kScThreads + threadIdx.x;
             if (c < lo || c >= hi) continue;
-            // the tensor of chunk c, as b2h_adam_step_k finds it: the wave's lowest chunk by wave-uniform reads, then
-            // each lane past the few tensor ends inside the wave's 64 chunks
-            const int64_t cw = ((int64_t)__builtin_amdgcn_readfirstlane((int)(c >> 32)) << 32) |
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-            int l = 0, h = a.n; // first[l] <= cw < first[h]
-            while (h - l > 1) {
-                const int mid = (l + h) >> 1;
-                if (a.first[mid] <= cw)
-                    l = mid;
-                else
-                    h = mid;
-            }
-            int i = l;
-            while (c >= a.first[i + 1]) ++i; // c < hi = first[n]: ends at i <= n - 1
+            const int i = chunk_tensor(a.first, a.n, c); // lo = first[0] <= c < hi = first[n]
             const int64_t numel = a.numel[i], e0 = (c - a.first[i]) * 4; // e0 < numel
             const float* gp = a.g[i] + e0;
             if (((uintptr_t)a.g[i] & 15) == 0 && e0 + 4 <= numel) {

@@ -264,6 +264,23 @@ def test_guarded_update_against_the_plain_one(cuda_device):
             assert _same_bits(before, _adam(dev, tensors, lr, wd, t, mode, True, apply=0))
 
 
+def test_guarded_update_over_two_launches_against_the_plain_one(cuda_device):
+    """81 tensors: one more than a launch holds, so the guarded kernel's second launch and its chunk locator are met.
+    Sizes (37 i) % 53 (0 at i = 0 and 53), two raised past a wave's 64 chunks; the last tensor is the second launch."""
+    dev, sizes = cuda_device, [(37 * i) % 53 for i in range(81)]
+    sizes[20], sizes[80] = 257, 1025
+    assert len(sizes) == 81 and sizes.count(0) >= 1
+    t, k, wd, lr = adam_ref.cases()[5]
+    p, g, m, v = adam_ref.inputs(sum(sizes), t, k, wd, 340)
+    tensors = _split((p, g, m, v), sizes)
+    before = [(x[0], x[2], x[3]) for x in tensors]
+    for mode in ("aligned", "offset"):
+        plain = _adam(dev, tensors, lr, wd, t, mode, False)
+        assert not _same_bits(plain, before), "the plain update changed nothing: the comparison below would be empty"
+        assert _same_bits(plain, _adam(dev, tensors, lr, wd, t, mode, True, scale=1.0, apply=1)), mode
+        assert _same_bits(before, _adam(dev, tensors, lr, wd, t, mode, True, scale=1.0, apply=0)), "apply 0 wrote"
+
+
 def test_clipped_update_within_the_bar_of_torch_on_this_gpu(cuda_device):
     """clip_grad_norm_ + torch.optim.Adam(foreach=False) on this GPU against the float64 truth gives the bar (2 x its
     largest error + 1 ulp, adam_ref.bar); b2h_step_prepare + b2h_adam_step_guarded must be within it."""
